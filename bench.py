@@ -8,12 +8,17 @@ resident in HBM before timing starts. A step = the full hot path: SHA-512 challe
 decompression, key grouping, ChaCha z + scalar coefficients, Pippenger MSM, [8]/identity.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1048576] [--keys 150] [--msg-len 120]
+  Such a plain run does what the headline needs and no more: set-up, warmup, the K timed steps,
+  one JSON line. --dump-outputs DIR also writes what the last timed step returned (DIR/*.npy,
+  see dump_outputs). --full adds, after the timed steps, everything else this script measures: the
+  instrumented batches (phases_ms, the rooflines), the host-buffer calls (host_api), the CPU
+  baseline with its openssl anchor and, multi-rank, the other scaling shape.
   multi-GPU: python bench.py --gpus N ... starts N ranks itself (torch.distributed.run as a child
   process, before anything touches the GPU); under an outer torch.distributed.run it is one rank.
   At N > 1 the headline is the metric's shape, strong scaling: every step is ONE batch of --n
   (2^20) signatures split over the N ranks; each rank reduces its contiguous shard to one partial
   point and the ranks all-gather the 129-byte records over RCCL and combine them. The weak shape
-  (--n per rank) is reported beside it as `scaling_other_shape`.
+  (--n per rank) is reported beside it as `scaling_other_shape` under --full.
 """
 import argparse
 import ctypes
@@ -214,6 +219,46 @@ def openssl_anchor(seconds=2, cores=1):
             "sample": f"{' '.join(cmd[1:])} ({ver})"}
 
 
+def dump_outputs(out_dir, codes, last):
+    """--dump-outputs: what the timed path handed its caller, one float64 array per file, so that
+    two builds run with the same arguments can be compared output for output (the inputs are
+    seeded, identical from run to run):
+      verdicts.npy         the verdict of every timed step, in order (0 = the batch verified)
+      launch_verdicts.npy  --multi only: the last launch's verdict per batch
+      check_point.npy      last step: the batch's check point as affine x || y, 64 bytes
+                           little-endian reduced mod 2^255 - 19, one value per byte. The wait returns
+                           it as X || Y || Z || T, and which projective representative that is
+                           depends on the order the accumulation's atomics landed in (it differs from
+                           run to run); the affine form does not. A valid whole batch gives the
+                           identity (0, 1). Not written if Z = 0, which is no point at all (only a
+                           --lib probe build that is wrong by design returns that)
+      bad.npy              last step: the reject flag that goes with the point
+    In a multi-rank run the verdicts are the combined ones every rank's caller receives, but the
+    point and flag are rank 0's own shard partial, what its wait returned before the exchange:
+    they are named shard0_check_point.npy and shard0_bad.npy there.
+    A --multi launch returns verdicts only (asking it for partials would rerun it batch by batch)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def put(name, values):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(list(values), dtype=np.float64))
+
+    put("verdicts", codes)
+    if last["verdicts"] is not None:
+        put("launch_verdicts", last["verdicts"])
+        return
+    if last["rank_partial"] is not None:
+        (part, bad), prefix = last["rank_partial"], "shard0_"
+    else:
+        part, bad, prefix = last["partial"].raw, last["bad_int"].value, ""
+    put(prefix + "bad", [bad])
+    p = 2 ** 255 - 19
+    x, y, z = (int.from_bytes(part[32 * i:32 * i + 32], "little") % p for i in range(3))
+    if z:
+        zi = pow(z, p - 2, p)
+        put(prefix + "check_point", (x * zi % p).to_bytes(32, "little") + (y * zi % p).to_bytes(32, "little"))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -278,11 +323,15 @@ def main(argv=None):
                          "whose own parser takes --n for an abbreviation of its options)")
     ap.add_argument("--keys", type=int, default=None, help="validators (0 = distinct keys; default: the config's)")
     ap.add_argument("--msg-len", type=int, default=None, help="message bytes (-1 = uniform 0..1024)")
-    ap.add_argument("--cpu-sample", type=int, default=1 << 20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-sample", type=int, default=1 << 20,
+                    help="with --full: signatures of the workload the CPU baseline verifies (no effect without --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and its openssl anchor (a run without --full has none)")
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the host-buffer (PCIe-inclusive) synchronous calls reported after the timed region")
-    ap.add_argument("--profile-steps", type=int, default=3, help="extra instrumented steps for per-phase timings")
+                    help="with --full: skip the host-buffer (PCIe-inclusive) synchronous calls reported after the "
+                         "timed region (a run without --full has none)")
+    ap.add_argument("--profile-steps", type=int, default=3,
+                    help="with --full: extra instrumented steps for per-phase timings (no effect without --full)")
     ap.add_argument("--inflight", type=int, default=0,
                     help="batches in flight per GPU (submit/wait pipelining, <= the context's 16 slots); "
                          "0 = 6 from 2^20 signatures per GPU up, 7 from 2^19, 16 below (small shards need "
@@ -316,9 +365,20 @@ def main(argv=None):
                          "milliseconds (rank-local), so that the timed steps meet the GPU at its sustained "
                          "rate and not on its way up from idle (0 = none; reported as `spinup` in the line)")
     ap.add_argument("--lib", default=None, help="tools/ab_variants.sh only: load this A/B build of libedc.so")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the instrumented batches "
+                         "(phases_ms, the rooflines, batch_latency_ms), the host-buffer calls (host_api), the CPU "
+                         "baseline with its openssl anchor and, multi-rank, the other scaling shape. Without it the "
+                         "run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returned as DIR/<name>.npy (float64): "
+                         "verdicts (one per timed step), and of the last step the batch's check point (affine) "
+                         "and its bad flag")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(sys.argv[1:] if argv is None else argv, args.gpus)
     c_n, c_keys, c_len, c_desc = CONFIGS[args.config]
@@ -429,6 +489,11 @@ def main(argv=None):
                                  device_combine=eng if backend != "gloo" else None, group=args.exchange_group)
             if dist else None)
     xstat = {"post": 0.0, "pop": 0.0, "combine": 0.0}
+    # what the most recent wait returned beside its verdict (filled only for --dump-outputs)
+    last = {"partial": None, "bad": None, "bad_int": ctypes.c_int(0), "verdicts": None, "rank_partial": None}
+    if args.dump_outputs:
+        last["partial"] = ctypes.create_string_buffer(128)
+        last["bad"] = ctypes.byref(last["bad_int"])
 
     def timed_ring_op(f, name):
         def g(*a):
@@ -459,8 +524,11 @@ def main(argv=None):
             assert dist is None, "--multi runs on one process per node"
             v = (ctypes.c_int * nmb)()
             rc = eng._check(lib.edc_batch_wait_multi(eng.ctx, pending.pop(0), nmb, v, None, None, None))
+            last["verdicts"] = list(v)
             return lambda: rc
-        rc = eng._check(lib.edc_batch_wait(eng.ctx, pending.pop(0), None, None, None))
+        # --dump-outputs: the wait also hands over the batch's check point and bad flag (a 128-byte
+        # copy out of the slot's result record, no device work)
+        rc = eng._check(lib.edc_batch_wait(eng.ctx, pending.pop(0), None, last["partial"], last["bad"]))
         return lambda: rc
 
     tail = {"t_wait": 0.0, "split": None}    # multi-rank: where the timed region's tail goes
@@ -471,6 +539,7 @@ def main(argv=None):
         bad = ctypes.c_int(0)
         eng._check(lib.edc_batch_wait(eng.ctx, t, None, part, ctypes.byref(bad)))
         tail["t_wait"] = time.perf_counter()
+        last["rank_partial"] = (part.raw, bad.value)
         return part.raw, bad.value
 
     def submit_ticket():
@@ -559,6 +628,8 @@ def main(argv=None):
         xstat[key] = 0.0
     elapsed, codes = timed(args.steps)
     exchange_us = {key: round(v / max(1, args.steps) * 1e6, 1) for key, v in xstat.items()}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, codes, last)
     # diagnostic only (EDC_TIMED_REPEATS=r): the same timed region r - 1 more times right after
     # the first, reported beside it; `value` is always the first
     again = []
@@ -567,7 +638,7 @@ def main(argv=None):
         assert all(c == 0 for c in codes_r) or args.lib, f"valid synthetic batch rejected: {codes_r}"
         again.append(round(n * nmb * world * args.steps / el_r, 1))
     other = None
-    if dist and nmb == 1 and not args.prehashed:
+    if args.full and dist and nmb == 1 and not args.prehashed:
         # multi-rank: the other scaling shape beside the headline one, on the same ranks and data
         # (strong: the ranks split one --n batch; weak: every rank verifies --n of its own), so a
         # SCALE record carries both; items are a prefix of this rank's slice, z at global indices
@@ -602,57 +673,58 @@ def main(argv=None):
     # report its verdicts instead of stopping; the product library must verify the batch
     assert verdict_ok or args.lib, f"valid synthetic batch rejected: {codes}"
 
-    # instrumented steps (outside the timed region): per-phase HIP-event timings on the
-    # context stream, for the roofline of the dominant kernel
-    lib.edc_set_timing(eng.ctx, 1)
-    names = [lib.edc_timing_name(i).decode() for i in range(7)]
-    acc = [0.0] * 7
-    acc_ms, acc_entries = [], []      # k_msm_accum_dma alone (edc_last_msm_accum)
-    for _ in range(max(1, args.profile_steps)):
-        rc = lib.edc_batch_verify_device(eng.ctx, n, vk.data_ptr(), sig.data_ptr(), msg.data_ptr(),
-                                         off.data_ptr(), zseed, base, None, None)
-        eng._check(rc)
-        buf = (ctypes.c_float * 7)()
-        lib.edc_last_timings(eng.ctx, buf, 7)
-        for i in range(7):
-            acc[i] += buf[i] / max(1, args.profile_steps)
-        if hasattr(lib, "edc_last_msm_accum"):
-            a_ms, a_ent = ctypes.c_float(0), ctypes.c_uint64(0)
-            if lib.edc_last_msm_accum(eng.ctx, ctypes.byref(a_ms), ctypes.byref(a_ent)) == 0:
-                acc_ms.append(a_ms.value)
-                acc_entries.append(a_ent.value)
-    # the same in-flight loop once more with HIP events on (still outside the timed region): the
-    # dominant kernel's duration while it shares the GPU with the other in-flight batches (this is
-    # what a kernel trace of the default command averages; no collectives, every rank alike)
-    i_dec = names.index("decompress_R")
-    pipe_ms, pend = [], []
+    def instrumented():
+        """--full, every rank: the instrumented steps (outside the timed region), per-phase
+        HIP-event timings on the context stream, for the roofline of the dominant kernel"""
+        lib.edc_set_timing(eng.ctx, 1)
+        names = [lib.edc_timing_name(i).decode() for i in range(7)]
+        acc = [0.0] * 7
+        acc_ms, acc_entries = [], []      # k_msm_accum_dma alone (edc_last_msm_accum)
+        for _ in range(max(1, args.profile_steps)):
+            rc = lib.edc_batch_verify_device(eng.ctx, n, vk.data_ptr(), sig.data_ptr(), msg.data_ptr(),
+                                             off.data_ptr(), zseed, base, None, None)
+            eng._check(rc)
+            buf = (ctypes.c_float * 7)()
+            lib.edc_last_timings(eng.ctx, buf, 7)
+            for i in range(7):
+                acc[i] += buf[i] / max(1, args.profile_steps)
+            if hasattr(lib, "edc_last_msm_accum"):
+                a_ms, a_ent = ctypes.c_float(0), ctypes.c_uint64(0)
+                if lib.edc_last_msm_accum(eng.ctx, ctypes.byref(a_ms), ctypes.byref(a_ent)) == 0:
+                    acc_ms.append(a_ms.value)
+                    acc_entries.append(a_ent.value)
+        # the same in-flight loop once more with HIP events on (still outside the timed region): the
+        # dominant kernel's duration while it shares the GPU with the other in-flight batches (this is
+        # what a kernel trace of the default command averages; no collectives, every rank alike)
+        i_dec = names.index("decompress_R")
+        pipe_ms, pend = [], []
 
-    def wait_timed():
-        eng._check(lib.edc_batch_wait(eng.ctx, pend.pop(0), None, None, None))
-        buf = (ctypes.c_float * 7)()
-        lib.edc_last_timings(eng.ctx, buf, 7)
-        pipe_ms.append(buf[i_dec])
+        def wait_timed():
+            eng._check(lib.edc_batch_wait(eng.ctx, pend.pop(0), None, None, None))
+            buf = (ctypes.c_float * 7)()
+            lib.edc_last_timings(eng.ctx, buf, 7)
+            pipe_ms.append(buf[i_dec])
 
-    for _ in range(3 * max(4, args.inflight)):
-        if len(pend) >= max(1, args.inflight):
+        for _ in range(3 * max(4, args.inflight)):
+            if len(pend) >= max(1, args.inflight):
+                wait_timed()
+            t = lib.edc_batch_submit_device(eng.ctx, n, vk.data_ptr(), sig.data_ptr(), msg.data_ptr(),
+                                            off.data_ptr(), zseed, base, None, 0)
+            eng._check(t)
+            pend.append(t)
+        while pend:
             wait_timed()
-        t = lib.edc_batch_submit_device(eng.ctx, n, vk.data_ptr(), sig.data_ptr(), msg.data_ptr(), off.data_ptr(),
-                                        zseed, base, None, 0)
-        eng._check(t)
-        pend.append(t)
-    while pend:
-        wait_timed()
-    lib.edc_set_timing(eng.ctx, 0)
-    pipe_dec_ms = sum(pipe_ms[max(4, args.inflight):]) / max(1, len(pipe_ms) - max(4, args.inflight))
-    phases = {names[i]: round(acc[i], 4) for i in range(7)}
-    # SHA-512 blocks of the instrumented batch (R || A || M, 17 bytes of padding + length)
-    lens = (off[1:n + 1] - off[:n]).to(torch.int64)
-    sha_blocks = int(((64 + lens + 17 + 127) // 128).sum().item())
+        lib.edc_set_timing(eng.ctx, 0)
+        pipe_dec_ms = sum(pipe_ms[max(4, args.inflight):]) / max(1, len(pipe_ms) - max(4, args.inflight))
+        phases = {names[i]: round(acc[i], 4) for i in range(7)}
+        # SHA-512 blocks of the instrumented batch (R || A || M, 17 bytes of padding + length)
+        lens = (off[1:n + 1] - off[:n]).to(torch.int64)
+        sha_blocks = int(((64 + lens + 17 + 127) // 128).sum().item())
+        return phases, pipe_dec_ms, sha_blocks, acc_ms, acc_entries
 
-    if rank == 0:
-        total = n * nmb * world * args.steps    # strong scaling: n * world == --n
-        value = total / elapsed
-        ms_per_step = elapsed / args.steps * 1e3
+    def full_fields(value, phases, pipe_dec_ms, sha_blocks, acc_ms, acc_entries):
+        """--full, rank 0: the rooflines from the instrumented steps, the host-buffer calls and the
+        CPU baseline, as the keys they add to the line"""
         dom_ms = phases["decompress_R"]
         units = n                      # one launch decodes the R_i of every signature
         achieved = units * ALG_MAD_DECOMP / (dom_ms * 1e-3) / 1e12
@@ -687,39 +759,7 @@ def main(argv=None):
             if isinstance(cpu, dict):
                 cpu["openssl_anchor"] = openssl_anchor()
         alg_sig = ALG_MAD_PER_SIG_REPEATED if args.keys > 0 else ALG_MAD_PER_SIG_DISTINCT
-        line = {
-            "metric": "Ed25519 batch-verified signatures/sec (whole node) at 2^20 sigs",
-            "value": round(value, 1),
-            "unit": "sigs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "u32/u64 integer (GF(2^255-19), radix 2^29 limbs)",
-            "data": "synthetic (ChaCha20-seeded keys/messages, signed on GPU)",
-            "config": {"workload": c_desc,
-                       "sigs_per_gpu": n, "validators": args.keys or "distinct", "msg_len": args.msg_len,
-                       "inflight": args.inflight, "keycache": bool(args.keycache and args.keys > 0),
-                       "prehashed": bool(args.prehashed), "batches_per_launch": nmb,
-                       "multi_union_first": bool(nmb > 1 and not args.multi_exact),
-                       "parallelism": f"shard{world}" if world > 1 else "single"},
-            # the process group the ranks actually formed (None: one process, no collectives)
-            "comm": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(),
-                      "exchange_lag": args.exchange_lag, "exchange_group": args.exchange_group,
-                      "exchange_us": exchange_us, "timed_tail_us": tail["split"],
-                      "exchange_note": "host time per batch inside the timed loop: posting the all-gather, "
-                                       "completing it (waits for the collective), combining the partials; timed_tail_us: the "
-                                       "headline region's end after the last batch's partial"}
-                     if dist else None),
-            "scaling_other_shape": other,
-            "timed_repeats": again or None,
-            # device set-up before the warmup steps (--spinup-ms): batches of this workload, untimed
-            "spinup": {"ms": spin["ms"], "batches": spin["batches"],
-                       "note": "untimed batches of this workload before the warmup steps: from idle the GPU needs "
-                               "~50 ms of load to reach its sustained rate (profiles/r06/r06zr_spinup_sweep.log)"},
+        return {
             "roofline": {"bound": "valu_int", "kernel": "k_decompress (R_i)",
                          "achieved": round(achieved, 3), "peak": round(PEAK_TMAD, 2),
                          "unit": "T v_mad_u64_u32/s", "frac": round(achieved / PEAK_TMAD, 4),
@@ -774,8 +814,53 @@ def main(argv=None):
             # the host-buffer synchronous calls of the Rust shim (PCIe included), NOT `value`
             "host_api": host_api,
             "cpu_baseline": cpu,
+        }
+
+    measured = instrumented() if args.full else None
+    if rank == 0:
+        total = n * nmb * world * args.steps    # strong scaling: n * world == --n
+        value = total / elapsed
+        ms_per_step = elapsed / args.steps * 1e3
+        line = {
+            "metric": "Ed25519 batch-verified signatures/sec (whole node) at 2^20 sigs",
+            "value": round(value, 1),
+            "unit": "sigs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "u32/u64 integer (GF(2^255-19), radix 2^29 limbs)",
+            "data": "synthetic (ChaCha20-seeded keys/messages, signed on GPU)",
+            "config": {"workload": c_desc,
+                       "sigs_per_gpu": n, "validators": args.keys or "distinct", "msg_len": args.msg_len,
+                       "inflight": args.inflight, "keycache": bool(args.keycache and args.keys > 0),
+                       "prehashed": bool(args.prehashed), "batches_per_launch": nmb,
+                       "multi_union_first": bool(nmb > 1 and not args.multi_exact),
+                       "parallelism": f"shard{world}" if world > 1 else "single"},
+            # the process group the ranks actually formed (None: one process, no collectives)
+            "comm": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(),
+                      "exchange_lag": args.exchange_lag, "exchange_group": args.exchange_group,
+                      "exchange_us": exchange_us, "timed_tail_us": tail["split"],
+                      "exchange_note": "host time per batch inside the timed loop: posting the all-gather, "
+                                       "completing it (waits for the collective), combining the partials; timed_tail_us: the "
+                                       "headline region's end after the last batch's partial"}
+                     if dist else None),
+            "timed_repeats": again or None,
+            # device set-up before the warmup steps (--spinup-ms): batches of this workload, untimed
+            "spinup": {"ms": spin["ms"], "batches": spin["batches"],
+                       "note": "untimed batches of this workload before the warmup steps: from idle the GPU needs "
+                               "~50 ms of load to reach its sustained rate (profiles/r06/r06zr_spinup_sweep.log)"},
+            # False: the headline only; the keys that --full measures are then absent
+            "full": bool(args.full),
+            "dump_outputs": args.dump_outputs,
             "gen_s": round(t_gen, 2),
         }
+        line["scaling_other_shape"] = other       # measured only with --full on several ranks, else None
+        if args.full:
+            line.update(full_fields(value, *measured))
         if args.lib:
             line["ab_lib"] = {"path": args.lib, "verdict_ok": verdict_ok}
         print(json.dumps(line), flush=True)

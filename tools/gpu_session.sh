@@ -57,7 +57,7 @@ EOF
 
 bench_step() {   # bench_step <name> <args...>
   local name=$1; shift
-  run "$name" 400 python3 -u bench.py "$@"
+  run "$name" 400 python3 -u bench.py --full "$@"   # summ reads the rooflines and phases_ms
   summ "$(log "$name")" "$name" | tee -a "gpurun_out/${tag}_summary.log"
 }
 
@@ -102,11 +102,11 @@ for step in "$@"; do
       done ;;
     rccl1) run rccl1 300 env EDC_FORCE_DIST=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --steps 40 --warmup 5 --no-cpu-baseline ;;
     gloo2)
-      run gloo2_weak 300 env EDC_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --scaling weak --steps 20 --warmup 3 --no-cpu-baseline
-      run gloo2_strong 300 env EDC_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus 2 --scaling strong --steps 20 --warmup 3 --no-cpu-baseline ;;
+      run gloo2_weak 300 env EDC_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --scaling weak --steps 20 --warmup 3 --no-cpu-baseline
+      run gloo2_strong 300 env EDC_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 bench.py --full --gpus 2 --scaling strong --steps 20 --warmup 3 --no-cpu-baseline ;;
     lat) run lat 300 python3 -u tools/latency_probe.py --sizes c3,n17,c2,n150 ;;
     lat=*) v=${step#lat=}; run lat_$v 300 python3 -u tools/latency_probe.py --sizes c3,n17,c2,n150 --lib "$PWD/$D/libedc_$v.so" ;;
-    gloo4) run gloo4 300 env EDC_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29514 bench.py --gpus 4 --steps 20 --warmup 3 --no-cpu-baseline ;;
+    gloo4) run gloo4 300 env EDC_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29514 bench.py --full --gpus 4 --steps 20 --warmup 3 --no-cpu-baseline ;;
     # bench.py's own launcher (no outer torch.distributed.run): two gloo ranks sharing the GPU
     # must run and report n_gpus 2 / comm.world_size 2; two RCCL ranks on a one-GPU box must
     # refuse within seconds (non-zero exit, expected)
@@ -123,11 +123,11 @@ for step in "$@"; do
     n18x80) bench_step n18x80 --n 262144 --steps 80 --warmup 5 --no-cpu-baseline --no-host-api ;;
     n17x20) bench_step n17x20 --n 131072 --steps 20 --warmup 5 --no-cpu-baseline --no-host-api ;;
     # host-buffer synchronous calls (bench.py's host_api leg): chunked (default) and one piece
-    hapi) run hapi 300 python3 -u bench.py --steps 10 --warmup 3 --no-cpu-baseline
+    hapi) run hapi 300 python3 -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
           python3 -c "import json,sys; d=json.loads(open('$(log hapi)').read().strip().splitlines()[-1]); print('hapi', json.dumps(d['host_api']))" | tee -a "gpurun_out/${tag}_summary.log" ;;
-    hapi=*) v=${step#hapi=}; run hapi_$v 300 env EDC_HOST_BODY_CHUNKS=$v python3 -u bench.py --steps 10 --warmup 3 --no-cpu-baseline
+    hapi=*) v=${step#hapi=}; run hapi_$v 300 env EDC_HOST_BODY_CHUNKS=$v python3 -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
           python3 -c "import json,sys; d=json.loads(open('$(log hapi_$v)').read().strip().splitlines()[-1]); print('hapi=$v', json.dumps(d['host_api']))" | tee -a "gpurun_out/${tag}_summary.log" ;;
-    hapi0) run hapi0 300 env EDC_HOST_CHUNKS=0 python3 -u bench.py --steps 10 --warmup 3 --no-cpu-baseline
+    hapi0) run hapi0 300 env EDC_HOST_CHUNKS=0 python3 -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
           python3 -c "import json,sys; d=json.loads(open('$(log hapi0)').read().strip().splitlines()[-1]); print('hapi0', json.dumps(d['host_api']))" | tee -a "gpurun_out/${tag}_summary.log" ;;
     # copies and kernels of one synchronous host-buffer call on one time axis (tools/host_timeline.py)
     htrace)
@@ -144,7 +144,7 @@ for step in "$@"; do
               c3) a="--steps 40";; c2) a="--config c2 --steps 40";; c5) a="--config c5 --steps 12";;
               n17) a="--n 131072 --steps 40";; n17x20) a="--n 131072 --steps 20";; driver) a="--steps 20";; *) a="$c";;
             esac
-            run ab 300 python3 -u bench.py $a --warmup 5 --no-cpu-baseline --profile-steps 1 --lib "$PWD/$lib"
+            run ab 300 python3 -u bench.py --full $a --warmup 5 --no-cpu-baseline --profile-steps 1 --lib "$PWD/$lib"
             summ "$(log ab)" "$c-$v" | tee -a "gpurun_out/${tag}_ab_summary.log"
           done
         done
