@@ -14,7 +14,8 @@ reference:
     VerificationKeyBytes (src/verification_key.rs:32-87)      VerificationKeyBytes
     VerificationKey::try_from / verify (:160-258)            VerificationKey
     batch::Item, Item::verify_single (src/batch.rs:75-107)   batch.Item
-    batch::Verifier::{new, queue, verify} (:110-217)         batch.Verifier
+    batch::Verifier::{new, queue, verify} (:110-217)         batch.Verifier (everything at verify),
+                                                             batch.StreamVerifier (per-item work at queue)
     SigningKey (src/signing_key.rs; test-data source)        SigningKey
 
 All arithmetic runs in hand-written gfx950 kernels. There is NO CPU fallback: importing works
@@ -26,6 +27,7 @@ import os
 import secrets
 import sys
 import threading
+import weakref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libedc.so")
@@ -52,6 +54,9 @@ ABI_SYMBOLS = [
     "edc_batch_submit_prehashed_device", "edc_batch_verify_prehashed_fallback",
     "edc_batch_verify_prehashed_fallback_device", "edc_multi_route", "edc_multi_debug_force_staged",
     "edc_batch_submit_multi_device", "edc_batch_wait_multi", "edc_combine_records_device", "edc_debug_sc_reduce_wide",
+    "edc_verifier_create", "edc_verifier_destroy", "edc_verifier_queue", "edc_verifier_queue_prehashed",
+    "edc_verifier_queue_device", "edc_verifier_size", "edc_verifier_verify", "edc_verifier_verify_fallback",
+    "edc_verifier_reset",
 ]
 
 
@@ -208,6 +213,19 @@ def load_library(path=None):
         lib.edc_keycache_size.argtypes = [c_vp]
         lib.edc_set_key_grouping.argtypes = [c_vp, ctypes.c_int]
         lib.edc_set_key_split.argtypes = [c_vp, ctypes.c_int]
+        if hasattr(lib, "edc_verifier_create"):              # absent from older A/B builds (tools/)
+            lib.edc_verifier_create.restype = c_vp
+            lib.edc_verifier_create.argtypes = [c_vp, c_sz]
+            lib.edc_verifier_destroy.restype = None
+            lib.edc_verifier_destroy.argtypes = [c_vp]
+            lib.edc_verifier_queue.argtypes = [c_vp, c_sz, c_u8p, c_u8p, c_u8p, c_u64p]
+            lib.edc_verifier_queue_prehashed.argtypes = [c_vp, c_sz, c_u8p, c_u8p, c_u8p]
+            lib.edc_verifier_queue_device.argtypes = [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]
+            lib.edc_verifier_size.restype = c_sz
+            lib.edc_verifier_size.argtypes = [c_vp]
+            lib.edc_verifier_verify.argtypes = [c_vp, c_u8p, c_u8p, c_vp]
+            lib.edc_verifier_verify_fallback.argtypes = [c_vp, c_u8p, c_vp, ctypes.POINTER(ctypes.c_int), c_vp]
+            lib.edc_verifier_reset.argtypes = [c_vp]
         if path is None:
             _lib = lib
         return lib
@@ -254,9 +272,12 @@ class Engine:
         self._lock = threading.Lock()
         self._kc_keys = set()          # host mirror of the key cache's key bytes (keycache_missing)
         self._host_inflight = {}        # ticket -> host buffers borrowed by edc_batch_submit
+        self._verifiers = weakref.WeakSet()   # open batch.StreamVerifier objects (destroyed before the context)
 
     def close(self):
         if self.ctx:
+            for sv in list(getattr(self, "_verifiers", [])):
+                sv.close()
             self.lib.edc_destroy(self.ctx)
             self.ctx = None
 
@@ -915,3 +936,130 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             code, _ = self.verify_detailed(rng)
             if code != EDC_OK:
                 raise InvalidSignature()
+
+    class StreamVerifier:
+        """reference src/batch.rs:110-217 with the reference's division of work: queue() does the
+        per-item work on the GPU as items arrive (copy, SHA-512 -> k, ZIP215 decode of R, key
+        grouping, decode of new keys; edc_verifier_queue*), and verify(rng) only evaluates the
+        equation (edc_verifier_verify). Results equal batch.Verifier's on the same items and z.
+        The queue survives verify(); reset() starts the next block with the same allocations."""
+
+        def __init__(self, engine=None, capacity=0):
+            self._engine = engine or default_engine()
+            self._v = self._engine.lib.edc_verifier_create(self._engine.ctx, int(capacity))
+            if not self._v:
+                raise EngineError("edc_verifier_create failed: "
+                                  + self._engine.lib.edc_last_error(self._engine.ctx).decode())
+            self._engine._verifiers.add(self)
+
+        @classmethod
+        def new(cls, engine=None, capacity=0):
+            return cls(engine, capacity)
+
+        def close(self):
+            if getattr(self, "_v", None):
+                if self._engine.ctx:
+                    self._engine.lib.edc_verifier_destroy(self._v)
+                self._v = None
+                self._engine._verifiers.discard(self)
+
+        def __del__(self):
+            try:
+                self.close()
+            except Exception:
+                pass
+
+        def _handle(self):
+            if not self._v:
+                raise EngineError("StreamVerifier is closed")
+            return self._v
+
+        @property
+        def batch_size(self):
+            return int(self._engine.lib.edc_verifier_size(self._handle()))
+
+        def queue(self, item, sig=None, msg=None):
+            """Verifier::queue: a batch.Item or a (vk, sig, msg) tuple."""
+            if sig is not None:
+                item = batch.Item(item, sig, msg)
+            elif isinstance(item, tuple):
+                item = batch.Item(*item)
+            vk, sg = item.vk_bytes.to_bytes(), item.sig.to_bytes()
+            if item.k is not None:
+                self.queue_many([vk], [sg], ks=[item.k])
+            else:
+                self.queue_many([vk], [sg], msgs=[item._msg])
+
+        def queue_many(self, vks, sigs, msgs=None, ks=None):
+            """Append len(vks) items in order: with their messages, or prehashed with their k."""
+            n = len(vks)
+            if (msgs is None) == (ks is None):
+                raise ValueError("queue_many takes either msgs or ks")
+            if len(sigs) != n or len(msgs if ks is None else ks) != n:
+                raise ValueError("queue_many: lists of different lengths")
+            if not n:
+                return
+            eng, v = self._engine, self._handle()
+            vkb = b"".join(_as_bytes(x, 32) for x in vks)
+            sgb = b"".join(_as_bytes(x, 64) for x in sigs)
+            with eng._lock:
+                if ks is not None:
+                    rc = eng.lib.edc_verifier_queue_prehashed(v, n, vkb, sgb, b"".join(_as_bytes(x, 32) for x in ks))
+                else:
+                    arena, offs = _arena(msgs)
+                    rc = eng.lib.edc_verifier_queue(v, n, vkb, sgb, arena, offs)
+            eng._check(rc)
+
+        def queue_device(self, n, d_vk, d_sig, d_msg=None, d_msg_off=None, d_k=None):
+            """Append n items already in this GPU's memory (device pointers; d_k or the messages)."""
+            eng = self._engine
+            with eng._lock:
+                rc = eng.lib.edc_verifier_queue_device(self._handle(), n, d_vk, d_sig, d_msg, d_msg_off, d_k)
+            eng._check(rc)
+
+        def verify_detailed(self, rng=None):
+            """(code, check8) as batch.Verifier.verify_detailed: rng is a 32-byte ChaCha20 seed, an
+            object with fill_bytes(n) / token_bytes(n) (z drawn per item in queue order,
+            src/batch.rs:64-68), or None (fresh OS randomness)."""
+            eng, v = self._engine, self._handle()
+            n = self.batch_size
+            seed = z = None
+            if isinstance(rng, (bytes, bytearray)) and len(rng) == 32:
+                seed = bytes(rng)
+            elif rng is None:
+                seed = secrets.token_bytes(32)
+            else:
+                draw = rng.fill_bytes if hasattr(rng, "fill_bytes") else rng.token_bytes
+                z = b"".join(bytes(draw(16)) for _ in range(n)) or b"\0"
+            check8 = ctypes.create_string_buffer(32)
+            with eng._lock:
+                rc = eng.lib.edc_verifier_verify(v, seed, z, check8)
+            eng._check(rc)
+            return rc, check8.raw
+
+        def verify(self, rng=None):
+            """Verifier::verify: returns None on success, raises InvalidSignature otherwise."""
+            code, _ = self.verify_detailed(rng)
+            if code != EDC_OK:
+                raise InvalidSignature()
+
+        def verify_with_fallback(self, z_seed):
+            """(code, per-item Item::verify_single codes, check8): verify and, when it fails, the
+            grouped fallback on the retained k, points and grouping. z_seed must be fresh and
+            secret (include/edc.h, edc_find_invalid_device)."""
+            eng, v = self._engine, self._handle()
+            n = self.batch_size
+            verdicts = ctypes.create_string_buffer(max(n, 1))
+            cnt = ctypes.c_int(0)
+            check8 = ctypes.create_string_buffer(32)
+            with eng._lock:
+                rc = eng.lib.edc_verifier_verify_fallback(v, bytes(z_seed), verdicts, ctypes.byref(cnt), check8)
+            eng._check(rc)
+            return rc, list(verdicts.raw[:n]), check8.raw
+
+        def reset(self):
+            """Forget the queued items, keep the allocations."""
+            eng = self._engine
+            with eng._lock:
+                rc = eng.lib.edc_verifier_reset(self._handle())
+            eng._check(rc)

@@ -189,11 +189,35 @@ struct edc_ctx {
   // chunk (+ the keys / offsets piece), created on first use
   hipStream_t hcs = nullptr, hcs2 = nullptr;
   hipEvent_t hev[9] = {}, hev2[9] = {};   // piece 0 + signature chunks / k or message chunks
+  // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
+  // with the slots' whenever the key cache they read is rebuilt
+  std::vector<struct edc_verifier*> verifiers;
   hipStream_t st() const { return slot[0].st; }
   KeyCacheView kc() const {
     if (!kc_m) return KeyCacheView{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0};
     return KeyCacheView{kc_table, kc_keys, kc_ok, kc_comb, kc_tmask, kc_m, bcomb, kc_s0, kc_s1};
   }
+};
+
+// Incremental batch verifier (include/edc.h, edc_verifier_*): the reference's Verifier as an
+// object (src/batch.rs:110-217). Its own workspace slot and streams, the retained bytes of the
+// queued items (vk, sig, k) and the z-independent per-item results (R rows of s.pts, key grouping,
+// decoded keys in the key area, failure bits, flags) persist from queue to queue.
+struct edc_verifier {
+  edc_ctx* ctx = nullptr;
+  Slot s;                       // never the context's slot 0: other calls keep working between queues
+  hipStream_t cs = nullptr;     // copy stream: an append's copies overlap the previous append's kernels
+  hipEvent_t ev_copy = nullptr, ev_chal = nullptr;
+  size_t n = 0, cap = 0;        // queued items / items the retained arrays and the key table are sized for
+  uint8_t *vk = nullptr, *sig = nullptr, *zexp = nullptr;
+  uint32_t* k = nullptr;
+  uint8_t* msg = nullptr;       // one append's message arena and offsets (dead once its k exists)
+  uint64_t* off = nullptr;
+  size_t cap_msg = 0, cap_off = 0;
+  bool chal_pending = false;    // ev_chal guards msg / off against the next append's copies
+  uint32_t T = 0;               // key table slots in use (a power of two, <= s.cap_T)
+  uint32_t salt[2] = {0, 0};    // fixed until reset
+  std::vector<uint64_t> rebased;
 };
 
 // A failed HIP call also leaves the thread's last-error state set; it is cleared here, so that a
@@ -1377,6 +1401,10 @@ static void free_keycache(edc_ctx* ctx) {
 static int sync_all(edc_ctx* ctx) {
   for (Slot& s : ctx->slot)
     if (s.st) CK(hipStreamSynchronize(s.st));
+  for (edc_verifier* v : ctx->verifiers) {
+    if (v->cs) CK(hipStreamSynchronize(v->cs));
+    if (v->s.st) CK(hipStreamSynchronize(v->s.st));
+  }
   return 0;
 }
 
@@ -2397,6 +2425,355 @@ int edc_synchronize(edc_ctx* ctx) {
   for (Slot& s : ctx->slot)
     if (s.st) CK(hipStreamSynchronize(s.st));
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- incremental verifier
+// Verifier::queue does the per-item work (src/batch.rs:82-94, :127-137) and Verifier::verify(rng)
+// only evaluates the equation (:149-217). Here every queue call enqueues, for the appended range
+// alone, the copies, SHA-512 -> k, the ZIP215 decode of R_i into its final row 1 + i, the key
+// find-or-insert against the persistent table and the decode of the keys first seen in the range.
+// verify then runs what depends on z: coefficients, binning, sort, accumulation, reduction, window
+// combine and Horner.
+// Point layout: the batch layout puts key j at row 1 + n + j, and n is only known at verify. Keys
+// are decoded at queue time into a key area (rows 2 + 2 cap_n .. of the slot's point table, which
+// the unsplit verifier never uses otherwise) and k_verifier_place_keys moves the m rows into place
+// at verify: 128 bytes per distinct key, and the MSM then runs the very batch path (same terms,
+// same plan, same kernels) as edc_batch_verify_device, so results are bit-identical by construction.
+// The listed-terms path would need no move but changes the term order and drops the sub-bin split.
+static uint32_t* verifier_kpts(edc_verifier* v) { return v->s.pts + (2 + 2 * v->s.cap_n) * NIELS_WORDS; }
+
+static uint32_t verifier_table_size(size_t cap) { return (uint32_t)next_pow2(2 * (cap < 128 ? 128 : cap)); }
+
+// flags, key table and the R bits of a verifier with nothing queued
+static int verifier_clear(edc_verifier* v) {
+  edc_ctx* ctx = v->ctx;
+  Slot& s = v->s;
+  v->T = verifier_table_size(v->cap);
+  if (v->T > s.cap_T) { ctx->err = "hash table capacity"; return EDC_ERR_ARG; }
+  const uint64_t h = splitmix64(ctx->secret ^ splitmix64(ctx->nbatches++));
+  v->salt[0] = (uint32_t)h;
+  v->salt[1] = (uint32_t)(h >> 32);
+  launch_init_batch(s.st, s.flags, -1, s.u_acc, s.d_out, s.table, v->T, nullptr, 0);
+  CK(hipGetLastError());
+  return 0;
+}
+
+// Enqueue the z-independent work of items [n0, n0 + m), whose vk / sig / k are in place (or land
+// before the slot stream's next event wait): R decode, key find-or-insert, decode of new keys.
+static int verifier_enqueue_range(edc_verifier* v, size_t n0, size_t m) {
+  edc_ctx* ctx = v->ctx;
+  Slot& s = v->s;
+  if (!m) return 0;
+  launch_decompress_range(s.st, (uint32_t)(n0 + m), (uint32_t)n0, (uint32_t)m, 0, v->sig, v->vk, s.key_rep, false, s.pts,
+                          s.itembad + s.cap_n, s.keybad, s.flags, ctx->kc(), false);
+  launch_keys_range(s.st, (uint32_t)n0, (uint32_t)m, v->vk, s.table, v->T - 1, v->salt,
+                    ctx->key_grouping == 2 || ctx->key_grouping == 3, n0 == 0, s.slot_key, s.key_slot, s.key_rep,
+                    s.key_index, s.key_acc, verifier_kpts(v), s.keybad, s.flags, ctx->kc());
+  CK(hipGetLastError());
+  return 0;
+}
+
+// Room for `need` items. Growing copies the retained bytes, resizes the key table and redoes the
+// z-independent work of everything queued (R rows, grouping, key decode) in the new workspace:
+// the same kernels over the same bytes, so growth never changes a result.
+static int verifier_reserve(edc_verifier* v, size_t need) {
+  edc_ctx* ctx = v->ctx;
+  Slot& s = v->s;
+  if (need <= v->cap && v->vk) return 0;
+  if (need >= (1ull << 28)) { ctx->err = "batch too large for one verifier (max 2^28 items)"; return EDC_ERR_ARG; }
+  if (s.st) CK(hipStreamSynchronize(s.st));
+  if (v->cs) CK(hipStreamSynchronize(v->cs));
+  size_t cap = v->cap * 2 > need ? v->cap * 2 : need;
+  if (cap < 1) cap = 1;
+  uint8_t *nvk = nullptr, *nsig = nullptr, *nz = nullptr;
+  uint32_t* nk = nullptr;
+  CK(dalloc(&nvk, cap * 32));
+  CK(dalloc(&nsig, cap * 64));
+  CK(dalloc(&nz, cap * 16));
+  CK(dalloc(&nk, cap * 8));
+  if (v->n) {
+    CK(hipMemcpy(nvk, v->vk, v->n * 32, hipMemcpyDeviceToDevice));
+    CK(hipMemcpy(nsig, v->sig, v->n * 64, hipMemcpyDeviceToDevice));
+    CK(hipMemcpy(nk, v->k, v->n * 32, hipMemcpyDeviceToDevice));
+  }
+  for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k})
+    if (p) (void)hipFree(p);
+  v->vk = nvk;
+  v->sig = nsig;
+  v->zexp = nz;
+  v->k = nk;
+  v->cap = cap;
+  int rc = ensure_slot(ctx, s, cap);
+  if (rc) return rc;
+  s.kin = v->k;
+  rc = verifier_clear(v);
+  if (rc) return rc;
+  return verifier_enqueue_range(v, 0, v->n);
+}
+
+// The message arena of one append: reused by the next one once its SHA-512 pass has run.
+static int verifier_msg_room(edc_verifier* v, size_t m, size_t mbytes) {
+  edc_ctx* ctx = v->ctx;
+  if (mbytes > v->cap_msg || !v->msg) {
+    CK(hipStreamSynchronize(v->s.st));
+    if (v->msg) (void)hipFree(v->msg);
+    v->msg = nullptr;
+    v->cap_msg = 0;
+    const size_t cap = mbytes < 4096 ? 4096 : mbytes + mbytes / 8;
+    CK(dalloc(&v->msg, cap));
+    v->cap_msg = cap;
+  }
+  if (m + 1 > v->cap_off || !v->off) {
+    CK(hipStreamSynchronize(v->s.st));
+    if (v->off) (void)hipFree(v->off);
+    v->off = nullptr;
+    v->cap_off = 0;
+    const size_t cap = m + 1 < 1024 ? 1024 : m + 1 + m / 8;
+    CK(dalloc(&v->off, cap));
+    v->cap_off = cap;
+  }
+  return 0;
+}
+
+// One append from host buffers (k: prehashed challenges, or null for the message path). The
+// copies run on the copy stream; the call returns once they have left the caller's memory.
+static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                               const uint64_t* msg_off, const uint8_t* k) {
+  edc_ctx* ctx = v->ctx;
+  if (m && (!vk || !sig || (!k && !msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (!m) return 0;
+  const size_t mbytes = k ? 0 : (size_t)(msg_off[m] - msg_off[0]);
+  if (mbytes && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  int rc = verifier_reserve(v, v->n + m);
+  if (rc) return rc;
+  Slot& s = v->s;
+  const size_t n0 = v->n;
+  if (!k) {
+    rc = verifier_msg_room(v, m, mbytes);
+    if (rc) return rc;
+    if (v->chal_pending) CK(hipStreamWaitEvent(v->cs, v->ev_chal, 0));
+  }
+  CK(hipMemcpyAsync(v->vk + n0 * 32, vk, m * 32, hipMemcpyHostToDevice, v->cs));
+  CK(hipMemcpyAsync(v->sig + n0 * 64, sig, m * 64, hipMemcpyHostToDevice, v->cs));
+  if (k) {
+    CK(hipMemcpyAsync(v->k + n0 * 8, k, m * 32, hipMemcpyHostToDevice, v->cs));
+  } else {
+    v->rebased.resize(m + 1);
+    for (size_t i = 0; i <= m; ++i) v->rebased[i] = msg_off[i] - msg_off[0];
+    CK(hipMemcpyAsync(v->off, v->rebased.data(), (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, v->cs));
+    if (mbytes) CK(hipMemcpyAsync(v->msg, msg + msg_off[0], mbytes, hipMemcpyHostToDevice, v->cs));
+  }
+  CK(hipEventRecord(v->ev_copy, v->cs));
+  CK(hipStreamWaitEvent(s.st, v->ev_copy, 0));
+  if (!k) {
+    launch_challenge(s.st, (uint32_t)m, v->vk + n0 * 32, v->sig + n0 * 64, v->msg, v->off, v->k + n0 * 8);
+    CK(hipGetLastError());
+    CK(hipEventRecord(v->ev_chal, s.st));
+    v->chal_pending = true;
+  }
+  rc = verifier_enqueue_range(v, n0, m);
+  if (rc) return rc;
+  CK(hipEventSynchronize(v->ev_copy));   // nothing reads the caller's (or the rebased) buffers after this
+  v->n = n0 + m;
+  return 0;
+}
+
+// The z-dependent part over everything queued, on the verifier's slot; no host synchronization.
+static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t* z, int want_compress) {
+  edc_ctx* ctx = v->ctx;
+  Slot& s = v->s;
+  const size_t n = v->n;
+  const uint32_t N = (uint32_t)n;
+  const MsmPlan P = batch_plan(ctx, n, false, false);
+  int rc = ensure_msm(ctx, s, P, msm_entry_capacity(P, n, n + 1));
+  if (rc) return rc;
+  uint32_t seed[8];
+  seed_words(z_seed, seed);
+  hipStream_t st = s.st;
+  if (z) CK(hipMemcpyAsync(v->zexp, z, n * 16, hipMemcpyHostToDevice, st));
+  s.kin = v->k;
+  s.nmulti = 0;
+  s.timed = false;
+  s.per_sig = false;            // an overflow (FLAG_OVF) is resolved on the device
+  s.n_batch = N;
+  launch_verifier_begin(st, N, s.flags, s.key_acc, s.u_acc, s.d_out, s.counts, P.nbin());
+  launch_coef(st, N, v->sig, v->k, z ? v->zexp : nullptr, seed, 0, s.key_index, s.scal, s.key_acc, s.u_acc, s.itembad,
+              s.flags, false, s.coef_part, false);
+  launch_msm_bin(st, P, batch_terms(P, s, N, false), 1 + 2 * N, s.counts, s.offsets, s.cursor, s.entries, s.flags, true);
+  launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
+  launch_verifier_place_keys(st, N, v->vk, verifier_kpts(v), s.pts, s.keybad, s.flags, ctx->kc());
+  launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
+                    s.slice_T, 0, nullptr, nullptr, true, s.flags);
+  s.acc_nbin = P.nbin();
+  launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, want_compress, s.d_out, s.h_out);
+  CK(hipGetLastError());
+  s.pending = true;
+  return 0;
+}
+
+static int verifier_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t* z, uint8_t check8[32]) {
+  edc_ctx* ctx = v->ctx;
+  if (!z_seed == !z) { ctx->err = "exactly one of z_seed and z"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if (!v->n) {                  // the empty equation: [8] * identity
+    if (check8) {
+      memset(check8, 0, 32);
+      check8[0] = 1;
+    }
+    return EDC_OK;
+  }
+  int rc = verifier_enqueue_verify(v, z_seed, z, check8 != nullptr);
+  if (rc) return rc;
+  return finish_batch(ctx, v->s, check8, nullptr, nullptr);
+}
+
+extern "C" {
+
+edc_verifier* edc_verifier_create(edc_ctx* ctx, size_t capacity_hint) {
+  if (!ctx) return nullptr;
+  if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
+  edc_verifier* v = new edc_verifier();
+  v->ctx = ctx;
+  ctx->verifiers.push_back(v);
+  bool ok = init_slot(ctx, v->s) == 0 && hipStreamCreateWithFlags(&v->cs, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&v->ev_copy, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&v->ev_chal, hipEventDisableTiming) == hipSuccess &&
+            verifier_reserve(v, capacity_hint ? capacity_hint : 1) == 0 && hipStreamSynchronize(v->s.st) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    edc_verifier_destroy(v);
+    return nullptr;
+  }
+  return v;
+}
+
+void edc_verifier_destroy(edc_verifier* v) {
+  if (!v) return;
+  edc_ctx* ctx = v->ctx;
+  (void)hipSetDevice(ctx->device);
+  Slot& s = v->s;
+  if (v->cs) (void)hipStreamSynchronize(v->cs);
+  if (s.st) (void)hipStreamSynchronize(s.st);
+  ctx->verifiers.erase(std::remove(ctx->verifiers.begin(), ctx->verifiers.end(), v), ctx->verifiers.end());
+  free_slot_buffers(s);
+  for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->msg, (void*)v->off, (void*)s.flags,
+                  (void*)s.d_out})
+    if (p) (void)hipFree(p);
+  if (s.h_out) (void)hipHostFree(s.h_out);
+  if (s.h_acc) (void)hipHostFree(s.h_acc);
+  for (int p = 0; p <= PH_N; ++p)
+    if (s.ev[p]) (void)hipEventDestroy(s.ev[p]);
+  for (hipEvent_t e : s.ev_acc)
+    if (e) (void)hipEventDestroy(e);
+  if (v->ev_copy) (void)hipEventDestroy(v->ev_copy);
+  if (v->ev_chal) (void)hipEventDestroy(v->ev_chal);
+  if (v->cs) (void)hipStreamDestroy(v->cs);
+  if (s.st) (void)hipStreamDestroy(s.st);
+  delete v;
+}
+
+int edc_verifier_queue(edc_verifier* v, size_t m, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                       const uint64_t* msg_off) {
+  if (!v) return EDC_ERR_ARG;
+  if (m && !msg_off) { v->ctx->err = "null msg_off"; return EDC_ERR_ARG; }
+  return verifier_queue_host(v, m, vk, sig, msg, msg_off, nullptr);
+}
+
+int edc_verifier_queue_prehashed(edc_verifier* v, size_t m, const uint8_t* vk, const uint8_t* sig, const uint8_t* k) {
+  if (!v) return EDC_ERR_ARG;
+  if (m && !k) { v->ctx->err = "null k"; return EDC_ERR_ARG; }
+  return verifier_queue_host(v, m, vk, sig, nullptr, nullptr, k);
+}
+
+int edc_verifier_queue_device(edc_verifier* v, size_t m, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
+                              const uint64_t* d_msg_off, const uint8_t* d_k) {
+  if (!v) return EDC_ERR_ARG;
+  edc_ctx* ctx = v->ctx;
+  if (!m) return 0;
+  if (!d_vk || !d_sig || (!d_k && (!d_msg || !d_msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k))) {
+    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
+    return EDC_ERR_ARG;
+  }
+  CK(hipSetDevice(ctx->device));
+  int rc = verifier_reserve(v, v->n + m);
+  if (rc) return rc;
+  Slot& s = v->s;
+  const size_t n0 = v->n;
+  CK(hipMemcpyAsync(v->vk + n0 * 32, d_vk, m * 32, hipMemcpyDeviceToDevice, v->cs));
+  CK(hipMemcpyAsync(v->sig + n0 * 64, d_sig, m * 64, hipMemcpyDeviceToDevice, v->cs));
+  if (d_k) CK(hipMemcpyAsync(v->k + n0 * 8, d_k, m * 32, hipMemcpyDeviceToDevice, v->cs));
+  CK(hipEventRecord(v->ev_copy, v->cs));
+  CK(hipStreamWaitEvent(s.st, v->ev_copy, 0));
+  if (!d_k) {
+    // SHA-512 reads the caller's arena in place (offsets relative to d_msg, as the other _device entries)
+    launch_challenge(s.st, (uint32_t)m, v->vk + n0 * 32, v->sig + n0 * 64, d_msg, d_msg_off, v->k + n0 * 8);
+    CK(hipGetLastError());
+    CK(hipEventRecord(v->ev_chal, s.st));
+  }
+  rc = verifier_enqueue_range(v, n0, m);
+  if (rc) return rc;
+  // the caller's device memory is not read after the call returns: the copies have run and, on
+  // the message path, so has this range's SHA-512 pass (the decode and key work may still be queued)
+  CK(hipEventSynchronize(v->ev_copy));
+  if (!d_k) CK(hipEventSynchronize(v->ev_chal));
+  v->n = n0 + m;
+  return 0;
+}
+
+size_t edc_verifier_size(const edc_verifier* v) { return v ? v->n : 0; }
+
+int edc_verifier_verify(edc_verifier* v, const uint8_t z_seed[32], const uint8_t* z, uint8_t check8[32]) {
+  if (!v) return EDC_ERR_ARG;
+  return verifier_verify(v, z_seed, z, check8);
+}
+
+int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
+                                 uint8_t check8[32]) {
+  if (!v || !z_seed || (v->n && !verdicts)) return EDC_ERR_ARG;
+  edc_ctx* ctx = v->ctx;
+  Slot& s = v->s;
+  const size_t n = v->n;
+  if (n_invalid) *n_invalid = 0;
+  int rc = verifier_verify(v, z_seed, nullptr, check8);
+  if (rc <= 0) {
+    if (rc == 0 && n) memset(verdicts, 0, n);
+    return rc;
+  }
+  bool per_sig;
+  uint32_t m;
+  int r2 = slot_grouping(ctx, s, &per_sig, &m);
+  if (r2) return r2;
+  // with too many distinct keys for per-(range, key) sums the fallback redoes the prefix with one
+  // key term per signature on this slot (fallback_ranges), which overwrites the verifier's grouped
+  // key state: it is rebuilt below
+  const uint32_t bpr = make_plan(ctx->fb_bits, ctx->fb_bits, 1).bins_per_range;
+  const uint32_t gmax = MSM_MAX_BINS / bpr, granges = ctx->fb_ranges < gmax ? ctx->fb_ranges : gmax;
+  const size_t rsize = ((n + granges - 1) / granges + COEF_CHUNK - 1) / COEF_CHUNK * COEF_CHUNK;
+  const size_t G = (n + rsize - 1) / rsize;
+  const bool redo = !per_sig && G * m > s.cap_n;
+  r2 = fallback_ranges(ctx, s, n, v->vk, v->sig, nullptr, nullptr, z_seed, 0, per_sig, m, verdicts);
+  s.kin = v->k;
+  if (redo) {
+    CK(hipStreamSynchronize(s.st));
+    int r3 = verifier_clear(v);
+    if (!r3) r3 = verifier_enqueue_range(v, 0, n);
+    if (r3) return r3;
+  }
+  if (r2 < 0) return r2;
+  if (n_invalid) *n_invalid = r2;
+  return EDC_INVALID_SIGNATURE;
+}
+
+int edc_verifier_reset(edc_verifier* v) {
+  if (!v) return EDC_ERR_ARG;
+  edc_ctx* ctx = v->ctx;
+  CK(hipSetDevice(ctx->device));
+  v->n = 0;
+  return verifier_clear(v);
 }
 
 }  // extern "C"

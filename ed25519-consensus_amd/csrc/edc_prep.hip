@@ -405,6 +405,113 @@ __global__ void __launch_bounds__(256) k_key_index(uint32_t n, const uint32_t* _
   key_index[i] = slot_key[key_slot_of_sig[i]];
 }
 
+// ---- incremental verifier (edc_verifier_*): key grouping and key decode of an appended range ----
+// Find-or-insert of items [n0, n0 + m) against the verifier's persistent table (slots never change
+// once claimed, key_insert_one); dense key indices continue from flags[FLAG_NKEYS]. Once an append
+// has overflowed the probe budget (FLAG_OVF) the verifier stops grouping: verify then takes one
+// key term per signature. sample: the seeding pass of a large first append (k_key_seed).
+__global__ void __launch_bounds__(256) k_key_insert_range(uint32_t n0, uint32_t m, int sample,
+                                                          const uint8_t* __restrict__ vk, uint32_t* __restrict__ table,
+                                                          uint32_t tmask, uint32_t salt0, uint32_t salt1,
+                                                          uint32_t probe_cap, uint32_t* __restrict__ slot_key,
+                                                          uint32_t* __restrict__ key_slot_of_sig,
+                                                          uint32_t* __restrict__ key_rep,
+                                                          unsigned long long* __restrict__ key_acc,
+                                                          int* __restrict__ flags) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (!sample && g >= m) return;
+  if (__hip_atomic_load(&flags[FLAG_OVF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  const uint32_t i = n0 + (sample ? (uint32_t)(((uint64_t)g * 2654435761u) % m) : g);
+  key_insert_one(i, vk, table, tmask, salt0, salt1, probe_cap, slot_key, key_slot_of_sig, key_rep, key_acc, flags);
+}
+
+// Second pass over the appended range (slot_key is written by the claimer after its CAS, so a lane
+// that found a slot claimed in the same launch reads it only here): the dense key index of every
+// item, and the decode of the keys first seen in this range -- the item whose index the claimer
+// left in key_rep decodes its own key bytes into row key_index of the verifier's key area kpts
+// (registered keys copy their cached record, as k_decompress). No lane count to guess: however many
+// new keys an append brings, each has exactly one item lane.
+__global__ void __launch_bounds__(256) k_key_finish_range(uint32_t n0, uint32_t m, const uint8_t* __restrict__ vk,
+                                                          const uint32_t* __restrict__ key_slot_of_sig,
+                                                          const uint32_t* __restrict__ slot_key,
+                                                          const uint32_t* __restrict__ key_rep,
+                                                          uint32_t* __restrict__ key_index,
+                                                          uint32_t* __restrict__ kpts, uint8_t* __restrict__ keybad,
+                                                          int* __restrict__ flags, KeyCacheView kcache) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= m || flags[FLAG_OVF]) return;
+  const uint32_t i = n0 + g;
+  const uint32_t j = slot_key[key_slot_of_sig[i]];
+  key_index[i] = j;
+  if (key_rep[j] != i) return;
+  uint32_t w[8];
+  ld_words8(vk + (size_t)i * 32, w);
+  const int ci = kc_lookup(kcache, w);
+  bool ok;
+  if (ci >= 0) {
+    copy_record(kpts, j, kcache.comb + (size_t)ci * COMB_ENTRIES * NIELS_WORDS);
+    ok = kcache.ok[ci] != 0;
+  } else {
+    ge_p3 P;
+    ok = ge_decompress(w, P);
+    st_niels(kpts, j, ge_to_niels_affine(P));
+    if (kcache.table) atomicAdd(&flags[FLAG_UNCACHED], 1);
+  }
+  keybad[j] = ok ? 0 : 1;
+  if (!ok) atomicOr(&flags[FLAG_BAD], 1);
+}
+
+// Start of edc_verifier_verify over n queued items: the per-call sums and result block are
+// cleared (the flags are not: FLAG_BAD / FLAG_KARG / FLAG_NKEYS describe the queued items). After
+// an overflow the key terms are per signature: FLAG_NKEYS = n, as k_key_index leaves it.
+__global__ void __launch_bounds__(256) k_verifier_begin(uint32_t n, int* __restrict__ flags,
+                                                        unsigned long long* __restrict__ key_acc,
+                                                        unsigned long long* __restrict__ u_acc,
+                                                        uint32_t* __restrict__ d_out, uint32_t* __restrict__ counts,
+                                                        uint32_t nbin) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  const bool ovf = flags[FLAG_OVF] != 0;
+  const size_t acc = ovf ? 0 : (size_t)(uint32_t)flags[FLAG_NKEYS] * KEY_ACC_LIMBS;   // read before the store below
+  if (i < KEY_ACC_LIMBS) u_acc[i] = 0;
+  if (i < 64) d_out[i] = 0;
+  for (uint32_t j = i; j < nbin; j += stride) counts[j] = 0;
+  for (size_t j = i; j < acc; j += stride) key_acc[j] = 0;
+  if (ovf && i == 0) flags[FLAG_NKEYS] = (int)n;    // only read by the other lanes when !ovf
+}
+
+// The key rows of the batch layout, once n is known: key j's record moves from the verifier's key
+// area to row 1 + n + j (16 bytes per lane). After an overflow every A_i is decoded here instead
+// (row 1 + n + i), the per-signature key path of k_decompress.
+__global__ void __launch_bounds__(256) k_verifier_place_keys(uint32_t n, const uint8_t* __restrict__ vk,
+                                                             const uint32_t* __restrict__ kpts,
+                                                             uint32_t* __restrict__ pts, uint8_t* __restrict__ keybad,
+                                                             int* __restrict__ flags, KeyCacheView kcache) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  if (!flags[FLAG_OVF]) {
+    const uint32_t chunks = (uint32_t)flags[FLAG_NKEYS] * (NIELS_WORDS / 4);
+    const uint4* src = reinterpret_cast<const uint4*>(kpts);
+    uint4* dst = reinterpret_cast<uint4*>(pts + (size_t)(1 + n) * NIELS_WORDS);
+    for (uint32_t c = g; c < chunks; c += stride) dst[c] = src[c];
+    return;
+  }
+  for (uint32_t i = g; i < n; i += stride) {
+    uint32_t w[8];
+    ld_words8(vk + (size_t)i * 32, w);
+    const int ci = kc_lookup(kcache, w);
+    bool ok;
+    if (ci >= 0) {
+      copy_record(pts, 1 + n + i, kcache.comb + (size_t)ci * COMB_ENTRIES * NIELS_WORDS);
+      ok = kcache.ok[ci] != 0;
+    } else {
+      ge_p3 P;
+      ok = ge_decompress(w, P);
+      st_niels(pts, 1 + n + i, ge_to_niels_affine(P));
+    }
+    keybad[i] = ok ? 0 : 1;
+    if (!ok) atomicOr(&flags[FLAG_BAD], 1);
+  }
+}
+
 struct seed8 { uint32_t w[8]; };
 
 constexpr int COEF_SIGS_PER_THREAD = 8;             // two ChaCha blocks -> z for 8 signatures
@@ -801,6 +908,31 @@ void launch_keys(hipStream_t st, uint32_t n, const uint8_t* vk, uint32_t* table,
                      slot_key, key_slot_of_sig, key_rep, key_acc, flags);
   hipLaunchKernelGGL(k_key_index, dim3(cdiv(n, 256)), dim3(256), 0, st, n, key_slot_of_sig, slot_key,
                      key_index, flags, kcap);
+}
+void launch_keys_range(hipStream_t st, uint32_t n0, uint32_t m, const uint8_t* vk, uint32_t* table, uint32_t tmask,
+                       const uint32_t salt[2], bool force_overflow, bool seed_pass, uint32_t* slot_key,
+                       uint32_t* key_slot_of_sig, uint32_t* key_rep, uint32_t* key_index, unsigned long long* key_acc,
+                       uint32_t* kpts, uint8_t* keybad, int* flags, const KeyCacheView& kc) {
+  if (!m) return;
+  const uint32_t cap = force_overflow ? 0u : KEY_PROBE_CAP;
+  if (seed_pass && m > 4 * KEY_SEED_SAMPLE)
+    hipLaunchKernelGGL(k_key_insert_range, dim3(KEY_SEED_SAMPLE / 256), dim3(256), 0, st, n0, m, 1, vk, table, tmask,
+                       salt[0], salt[1], cap, slot_key, key_slot_of_sig, key_rep, key_acc, flags);
+  hipLaunchKernelGGL(k_key_insert_range, dim3(cdiv(m, 256)), dim3(256), 0, st, n0, m, 0, vk, table, tmask, salt[0],
+                     salt[1], cap, slot_key, key_slot_of_sig, key_rep, key_acc, flags);
+  hipLaunchKernelGGL(k_key_finish_range, dim3(cdiv(m, 256)), dim3(256), 0, st, n0, m, vk, key_slot_of_sig, slot_key,
+                     key_rep, key_index, kpts, keybad, flags, kc);
+}
+void launch_verifier_begin(hipStream_t st, uint32_t n, int* flags, unsigned long long* key_acc,
+                           unsigned long long* u_acc, uint8_t* d_out, uint32_t* counts, uint32_t nbin) {
+  hipLaunchKernelGGL(k_verifier_begin, dim3(grid_cap(cdiv(n > 256 ? n : 256, 256), 1024)), dim3(256), 0, st, n, flags,
+                     key_acc, u_acc, reinterpret_cast<uint32_t*>(d_out), counts, nbin);
+}
+void launch_verifier_place_keys(hipStream_t st, uint32_t n, const uint8_t* vk, const uint32_t* kpts, uint32_t* pts,
+                                uint8_t* keybad, int* flags, const KeyCacheView& kc) {
+  if (n)
+    hipLaunchKernelGGL(k_verifier_place_keys, dim3(grid_cap(cdiv(n, 256), 1024)), dim3(256), 0, st, n, vk, kpts, pts,
+                       keybad, flags, kc);
 }
 // One launch for the per-batch resets (flags, global coefficient sums, result block, key table,
 // MSM bin counts) instead of five runtime fills: each fill is a launch of its own, ~8 us apiece in

@@ -450,6 +450,57 @@ int edc_last_msm_accum(const edc_ctx* ctx, float* ms, uint64_t* entries);
 int edc_synchronize(edc_ctx* ctx);
 
 /*
+ * Incremental batch verifier: batch::Verifier as an object (reference src/batch.rs:110-217). The
+ * reference does the per-item work when an item is queued (Item::from hashes, src/batch.rs:82-94;
+ * Verifier::queue groups by key bytes, :127-137) and Verifier::verify(rng) gets its RNG only at the
+ * end, where it evaluates the equation (:149-217). A node that receives a block's votes over a whole
+ * round queues them as they arrive and pays only the z-dependent part once the last one is in.
+ *
+ * edc_verifier_create  Verifier::default() (src/batch.rs:110-124), bound to ctx: its own workspace
+ *   and streams (never the context's slot 0, so every other call on ctx keeps working between
+ *   queue calls; the one-context-per-thread rule covers the context's verifiers too). Arrays and
+ *   the key table are sized for capacity_hint items (0: grow on demand); queueing past the
+ *   capacity grows the verifier, which never changes a result. Destroy every verifier before its
+ *   context. NULL on failure.
+ * edc_verifier_queue / _prehashed / _device  Verifier::queue x m (src/batch.rs:127-137) with
+ *   Item::from (:82-94): m >= 0 items appended in queue order, from host buffers with their
+ *   messages, from host buffers with the caller's k (canonical scalars, as the other prehashed
+ *   entries), or from this GPU's memory (d_k nullable; when given the messages are not read;
+ *   vk / sig / k 16-byte aligned and the arena mapped in whole 16-byte chunks, as the other _device
+ *   entries). Each call enqueues, for the appended range only, the copies, SHA-512 -> k, the ZIP215
+ *   decode of R, the key find-or-insert and the decode of keys first seen in the range, and may
+ *   return before that work has run; the caller's memory is not read after the call returns. The
+ *   verifier keeps vk, sig and k; messages are dead once their k exists. The forms may be mixed.
+ *   Returns 0 or <0.
+ * edc_verifier_size    Verifier::batch_size.
+ * edc_verifier_verify  Verifier::verify(rng) (src/batch.rs:149-217): exactly one of z_seed (z as in
+ *   edc_batch_verify) and z (n * 16 bytes drawn by the caller, z_i for queue index i). Runs only
+ *   what depends on z -- coefficients and the MSM -- over everything queued. Return codes and
+ *   check8 as edc_batch_verify, bit-identical to it on the same items and z; nothing queued is
+ *   EDC_OK. A prehashed k >= l makes it return EDC_ERR_ARG. The queue survives the call: more
+ *   items may be queued, and a later verify covers everything queued (draw fresh z for it).
+ * edc_verifier_verify_fallback  verify and, if it fails, the grouped fallback on the retained k,
+ *   points and grouping (the flow of reference tests/batch.rs:18-44): semantics, and the z_seed
+ *   warning, of edc_batch_verify_fallback_device. verdicts: n bytes.
+ * edc_verifier_reset   forget the items, keep the allocations (Verifier::default() for the next block).
+ * edc_set_key_grouping modes 2 and 3 make a verifier take one key term per signature (the path a
+ * probe overflow takes: every A_i is decoded at verify); split coefficients are not used.
+ */
+typedef struct edc_verifier edc_verifier;
+edc_verifier* edc_verifier_create(edc_ctx* ctx, size_t capacity_hint);
+void edc_verifier_destroy(edc_verifier* v);
+int edc_verifier_queue(edc_verifier* v, size_t m, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                       const uint64_t* msg_off);
+int edc_verifier_queue_prehashed(edc_verifier* v, size_t m, const uint8_t* vk, const uint8_t* sig, const uint8_t* k);
+int edc_verifier_queue_device(edc_verifier* v, size_t m, const uint8_t* d_vk, const uint8_t* d_sig,
+                              const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k);
+size_t edc_verifier_size(const edc_verifier* v);
+int edc_verifier_verify(edc_verifier* v, const uint8_t z_seed[32], const uint8_t* z, uint8_t check8[32]);
+int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
+                                 uint8_t check8[32]);
+int edc_verifier_reset(edc_verifier* v);
+
+/*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
  * one batch::Verifier::verify (reference src/batch.rs:149-217) split into contiguous shards, one
  * per listed device (a device may be listed more than once: several contexts on one GPU). Shard g

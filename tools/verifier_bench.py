@@ -1,0 +1,139 @@
+"""Latency of the incremental verifier's last step: verify() alone, after the batch was queued in
+16 pieces (edc_verifier_queue* then edc_verifier_verify), against the one-call entries a caller
+had before, in the same process on the same data (reference src/batch.rs:127-137 queue, :149-217
+verify). Per size (150 validators, 120-byte messages):
+  one-call     edc_batch_verify_device (device inputs), edc_batch_verify and
+               edc_batch_verify_prehashed (host inputs)
+  verifier     queued from host memory with messages, from host memory prehashed, from device
+               memory; the device is idle when verify() starts (the votes arrived earlier)
+Warm-up calls first, then the median of --reps repetitions; queue_verify_ms is the whole cycle
+(reset, 16 queue calls, verify) and gives the total throughput beside the latency.
+  python tools/verifier_bench.py [--reps 20] [--warmup 3] [--sizes 150,131072,1048576] [--out FILE]"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+PIECES = 16
+
+
+def median_ms(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return round(statistics.median(ts), 4), round(min(ts), 4)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--sizes", default="150,131072,1048576")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    a = ap.parse_args()
+    import torch
+    dev = torch.device("cuda:0")
+    torch.zeros(1, device=dev)
+    pkg = bench.load_pkg()
+    eng = pkg.Engine(0)
+    lib, ctx = eng.lib, eng.ctx
+    zseed = bytes([0x33]) * 32
+    u8p, u64p = ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)
+    lines = []
+    for n in [int(x) for x in a.sizes.split(",")]:
+        vk, sig, msg, off = bench.make_workload(pkg, eng, torch, dev, n, 150, 120, 0)
+        torch.cuda.synchronize()
+        hvk, hsig, hmsg = vk.cpu().numpy(), sig.cpu().numpy(), msg.cpu().numpy()
+        hoff = off.cpu().numpy().astype("uint64")
+        hk = (ctypes.c_uint8 * (32 * n))()
+        at = lambda arr, byte: ctypes.cast(arr.ctypes.data + byte, u8p)       # noqa: E731
+        eng._check(lib.edc_challenge(ctx, n, at(hvk, 0), at(hsig, 0), at(hmsg, 0),
+                                     ctypes.cast(hoff.ctypes.data, u64p), hk))
+        hk_addr = ctypes.addressof(hk)
+        dk = torch.frombuffer(bytearray(hk), dtype=torch.uint8).to(dev)
+        torch.cuda.synchronize()
+        bounds = [n * p // PIECES for p in range(PIECES + 1)]
+
+        def one_device():
+            assert lib.edc_batch_verify_device(ctx, n, vk.data_ptr(), sig.data_ptr(), msg.data_ptr(), off.data_ptr(),
+                                               zseed, 0, None, None) == 0
+
+        def one_host():
+            assert lib.edc_batch_verify(ctx, n, at(hvk, 0), at(hsig, 0), at(hmsg, 0),
+                                        ctypes.cast(hoff.ctypes.data, u64p), zseed, None) == 0
+
+        def one_prehashed():
+            assert lib.edc_batch_verify_prehashed(ctx, n, at(hvk, 0), at(hsig, 0), ctypes.cast(hk_addr, u8p), zseed, None,
+                                                  None) == 0
+
+        v = lib.edc_verifier_create(ctx, n)
+        assert v
+
+        def q_host(p0, p1):
+            return lib.edc_verifier_queue(v, p1 - p0, at(hvk, 32 * p0), at(hsig, 64 * p0), at(hmsg, 0),
+                                          ctypes.cast(hoff.ctypes.data + 8 * p0, u64p))
+
+        def q_prehashed(p0, p1):
+            return lib.edc_verifier_queue_prehashed(v, p1 - p0, at(hvk, 32 * p0), at(hsig, 64 * p0),
+                                                    ctypes.cast(hk_addr + 32 * p0, u8p))
+
+        def q_device(p0, p1):
+            return lib.edc_verifier_queue_device(v, p1 - p0, vk.data_ptr() + 32 * p0, sig.data_ptr() + 64 * p0,
+                                                 msg.data_ptr(), off.data_ptr() + 8 * p0, None)
+
+        def q_device_k(p0, p1):
+            return lib.edc_verifier_queue_device(v, p1 - p0, vk.data_ptr() + 32 * p0, sig.data_ptr() + 64 * p0, None, None,
+                                                 dk.data_ptr() + 32 * p0)
+
+        def cycle(qfn):
+            """reset, queue in 16 pieces, idle device, verify: (verify ms, whole cycle ms)"""
+            t0 = time.perf_counter()
+            eng._check(lib.edc_verifier_reset(v))
+            for p in range(PIECES):
+                if bounds[p + 1] > bounds[p]:
+                    eng._check(qfn(bounds[p], bounds[p + 1]))
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            rc = lib.edc_verifier_verify(v, zseed, None, None)
+            t2 = time.perf_counter()
+            assert rc == 0, rc
+            return (t2 - t1) * 1e3, (t2 - t0) * 1e3
+
+        out = {"n": n, "validators": 150, "msg_len": 120, "pieces": PIECES, "reps": a.reps}
+        for label, fn in (("batch_verify_device_ms", one_device), ("batch_verify_host_ms", one_host),
+                          ("batch_verify_prehashed_host_ms", one_prehashed)):
+            out[label], out[label + "_min"] = median_ms(fn, a.warmup, a.reps)
+        for label, qfn in (("host_msgs", q_host), ("host_prehashed", q_prehashed), ("device_msgs", q_device),
+                           ("device_prehashed", q_device_k)):
+            for _ in range(a.warmup):
+                cycle(qfn)
+            rs = [cycle(qfn) for _ in range(a.reps)]
+            out[f"verify_after_queue_{label}_ms"] = round(statistics.median(r[0] for r in rs), 4)
+            out[f"verify_after_queue_{label}_ms_min"] = round(min(r[0] for r in rs), 4)
+            tot = statistics.median(r[1] for r in rs)
+            out[f"queue_verify_{label}_ms"] = round(tot, 4)
+            out[f"queue_verify_{label}_sigs_per_s"] = round(n / (tot * 1e-3), 1)
+        lib.edc_verifier_destroy(v)
+        line = json.dumps(out)
+        print(line, flush=True)
+        lines.append(line)
+        del vk, sig, msg, off, dk
+    eng.close()
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
