@@ -56,7 +56,7 @@ ABI_SYMBOLS = [
     "edc_batch_submit_multi_device", "edc_batch_wait_multi", "edc_combine_records_device", "edc_debug_sc_reduce_wide",
     "edc_verifier_create", "edc_verifier_destroy", "edc_verifier_queue", "edc_verifier_queue_prehashed",
     "edc_verifier_queue_device", "edc_verifier_size", "edc_verifier_verify", "edc_verifier_verify_fallback",
-    "edc_verifier_reset",
+    "edc_verifier_reset", "edc_vfy_queue_indexed", "edc_vfy_last_split",
 ]
 
 
@@ -226,6 +226,10 @@ def load_library(path=None):
             lib.edc_verifier_verify.argtypes = [c_vp, c_u8p, c_u8p, c_vp]
             lib.edc_verifier_verify_fallback.argtypes = [c_vp, c_u8p, c_vp, ctypes.POINTER(ctypes.c_int), c_vp]
             lib.edc_verifier_reset.argtypes = [c_vp]
+        if hasattr(lib, "edc_vfy_queue_indexed"):            # absent from older A/B builds (tools/)
+            lib.edc_vfy_queue_indexed.argtypes = [c_vp, c_sz, ctypes.POINTER(ctypes.c_uint32), c_u8p, c_u8p, c_u64p,
+                                                  c_u8p]
+            lib.edc_vfy_last_split.argtypes = [c_vp]
         if path is None:
             _lib = lib
         return lib
@@ -1009,6 +1013,35 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
                     arena, offs = _arena(msgs)
                     rc = eng.lib.edc_verifier_queue(v, n, vkb, sgb, arena, offs)
             eng._check(rc)
+
+        def queue_indexed(self, key_idx, sigs, msgs=None, ks=None):
+            """queue_many with the keys given as positions in the list last passed to
+            Engine.keycache_load (4 bytes per item over PCIe; edc_vfy_queue_indexed)."""
+            n = len(key_idx)
+            if (msgs is None) == (ks is None):
+                raise ValueError("queue_indexed takes either msgs or ks")
+            if len(sigs) != n or len(msgs if ks is None else ks) != n:
+                raise ValueError("queue_indexed: lists of different lengths")
+            if not n:
+                return
+            eng, v = self._engine, self._handle()
+            idx = (ctypes.c_uint32 * n)(*key_idx)
+            sgb = b"".join(_as_bytes(x, 64) for x in sigs)
+            with eng._lock:
+                if ks is not None:
+                    rc = eng.lib.edc_vfy_queue_indexed(v, n, idx, sgb, None, None,
+                                                       b"".join(_as_bytes(x, 32) for x in ks))
+                else:
+                    arena, offs = _arena(msgs)
+                    rc = eng.lib.edc_vfy_queue_indexed(v, n, idx, sgb, arena, offs, None)
+            eng._check(rc)
+
+        @property
+        def last_split(self):
+            """1 if the last verify ran with split coefficients, 0 if not (edc_vfy_last_split);
+            EngineError before any verify."""
+            eng = self._engine
+            return eng._check(eng.lib.edc_vfy_last_split(self._handle()))
 
         def queue_device(self, n, d_vk, d_sig, d_msg=None, d_msg_off=None, d_k=None):
             """Append n items already in this GPU's memory (device pointers; d_k or the messages)."""

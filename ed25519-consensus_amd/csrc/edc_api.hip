@@ -183,6 +183,9 @@ struct edc_ctx {
   // key_split 0 = auto, 1 = never; last_uncached = keys the last batch did not find in the cache
   int key_split = 0;
   uint32_t last_uncached = 0;
+  // bumped whenever the cache's contents change (load / add / clear): a verifier's queued
+  // [2^128] rows are only used by a verify that finds the generation they were built against
+  uint64_t kc_gen = 0;
   int multi_union = 1;                  // edc_set_multi_union
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // chunked synchronous host-buffer calls (run_host_chunked): a copy stream and one event per
@@ -218,6 +221,17 @@ struct edc_verifier {
   uint32_t T = 0;               // key table slots in use (a power of two, <= s.cap_T)
   uint32_t salt[2] = {0, 0};    // fixed until reset
   std::vector<uint64_t> rebased;
+  // key areas (their own allocation, 2 s.cap_n records): rows [0, cap_n) the decoded keys in
+  // key-index order, rows [cap_n, 2 cap_n) their [2^128] multiples (split coefficients)
+  uint32_t* karea = nullptr;
+  size_t karea_cap = 0;         // the s.cap_n it was sized for
+  // the [2^128] rows are usable while every range since the last reset was queued with a key
+  // cache loaded and that cache's generation (edc_ctx::kc_gen) is still hi_gen
+  uint64_t hi_gen = 0;
+  bool hi_ok = false;
+  int last_split = -1;          // plan of the last verify: 1 split, 0 unsplit, -1 none yet
+  uint32_t* idx = nullptr;      // one indexed append's key positions (edc_vfy_queue_indexed)
+  size_t cap_idx = 0;
 };
 
 // A failed HIP call also leaves the thread's last-error state set; it is cleared here, so that a
@@ -1394,6 +1408,7 @@ static void free_keycache(edc_ctx* ctx) {
   ctx->kc_reg_m = 0;
   ctx->kc_ok = nullptr;
   ctx->kc_m = ctx->kc_tmask = ctx->kc_cap = 0;
+  ctx->kc_gen++;
   ctx->kc_words.clear();
   ctx->kc_okh.clear();
 }
@@ -2113,6 +2128,7 @@ size_t edc_keycache_size(const edc_ctx* ctx) { return ctx ? ctx->kc_m : 0; }
 static int kc_append(edc_ctx* ctx, const std::vector<uint32_t>& neww) {
   const uint32_t u0 = ctx->kc_m, un = (uint32_t)(neww.size() / 8), u = u0 + un;
   if (!un) return 0;
+  ctx->kc_gen++;                // also on a failure below: the arrays may already have moved
   hipStream_t st = ctx->st();
   const size_t comb_words = (size_t)COMB_ENTRIES * NIELS_WORDS;
   if (u > ctx->kc_cap) {
@@ -2437,12 +2453,24 @@ int edc_synchronize(edc_ctx* ctx) {
 // verify then runs what depends on z: coefficients, binning, sort, accumulation, reduction, window
 // combine and Horner.
 // Point layout: the batch layout puts key j at row 1 + n + j, and n is only known at verify. Keys
-// are decoded at queue time into a key area (rows 2 + 2 cap_n .. of the slot's point table, which
-// the unsplit verifier never uses otherwise) and k_verifier_place_keys moves the m rows into place
+// are decoded at queue time into a key area and k_verifier_place_keys moves the m rows into place
 // at verify: 128 bytes per distinct key, and the MSM then runs the very batch path (same terms,
 // same plan, same kernels) as edc_batch_verify_device, so results are bit-identical by construction.
 // The listed-terms path would need no move but changes the term order and drops the sub-bin split.
-static uint32_t* verifier_kpts(edc_verifier* v) { return v->s.pts + (2 + 2 * v->s.cap_n) * NIELS_WORDS; }
+// Split coefficients (edc_common.h): while the context holds a key cache, queue time also leaves
+// every new key's [2^128] row in a second key area, and verify places the split layout (2m + 1
+// rows from 1 + n). That layout reaches row 2 + n + 2m <= 2 + 3 cap_n, i.e. the whole point
+// table, so the key areas are the verifier's own allocation (2 x 128 bytes per item of capacity)
+// and no placement can overwrite a row that it, or a later verify of the same queue, still reads.
+static uint32_t* verifier_kpts(edc_verifier* v) { return v->karea; }
+static uint32_t* verifier_khi(edc_verifier* v) { return v->karea + v->karea_cap * NIELS_WORDS; }
+
+// the split plan is possible for a verify now (choose_split without the one-call path's back-off
+// after uncached keys: their doublings were done at queue time)
+static bool verifier_split(const edc_verifier* v) {
+  const edc_ctx* ctx = v->ctx;
+  return ctx->kc_m && ctx->bcomb && ctx->key_split == 0 && v->hi_ok && v->hi_gen == ctx->kc_gen;
+}
 
 static uint32_t verifier_table_size(size_t cap) { return (uint32_t)next_pow2(2 * (cap < 128 ? 128 : cap)); }
 
@@ -2466,11 +2494,20 @@ static int verifier_enqueue_range(edc_verifier* v, size_t n0, size_t m) {
   edc_ctx* ctx = v->ctx;
   Slot& s = v->s;
   if (!m) return 0;
+  // [2^128] rows: the first range after a reset (or a rebuild of everything queued) opens the
+  // window; a later range queued without a cache, or against another one, closes it
+  const bool cache = ctx->kc_m && ctx->bcomb;
+  if (n0 == 0) {
+    v->hi_gen = ctx->kc_gen;
+    v->hi_ok = cache;
+  } else if (!cache || ctx->kc_gen != v->hi_gen) {
+    v->hi_ok = false;
+  }
   launch_decompress_range(s.st, (uint32_t)(n0 + m), (uint32_t)n0, (uint32_t)m, 0, v->sig, v->vk, s.key_rep, false, s.pts,
                           s.itembad + s.cap_n, s.keybad, s.flags, ctx->kc(), false);
   launch_keys_range(s.st, (uint32_t)n0, (uint32_t)m, v->vk, s.table, v->T - 1, v->salt,
                     ctx->key_grouping == 2 || ctx->key_grouping == 3, n0 == 0, s.slot_key, s.key_slot, s.key_rep,
-                    s.key_index, s.key_acc, verifier_kpts(v), s.keybad, s.flags, ctx->kc());
+                    s.key_index, s.key_acc, verifier_kpts(v), verifier_khi(v), s.keybad, s.flags, ctx->kc());
   CK(hipGetLastError());
   return 0;
 }
@@ -2507,6 +2544,13 @@ static int verifier_reserve(edc_verifier* v, size_t need) {
   v->cap = cap;
   int rc = ensure_slot(ctx, s, cap);
   if (rc) return rc;
+  if (v->karea_cap != s.cap_n) {
+    if (v->karea) (void)hipFree(v->karea);
+    v->karea = nullptr;
+    v->karea_cap = 0;
+    CK(dalloc(&v->karea, 2 * s.cap_n * NIELS_WORDS));
+    v->karea_cap = s.cap_n;
+  }
   s.kin = v->k;
   rc = verifier_clear(v);
   if (rc) return rc;
@@ -2537,13 +2581,20 @@ static int verifier_msg_room(edc_verifier* v, size_t m, size_t mbytes) {
   return 0;
 }
 
-// One append from host buffers (k: prehashed challenges, or null for the message path). The
-// copies run on the copy stream; the call returns once they have left the caller's memory.
+// One append from host buffers (k: prehashed challenges, or null for the message path; key_idx:
+// positions in the registered key list instead of vk, 4 bytes per item over PCIe, expanded into the
+// retained vk range on the device). The copies run on the copy stream; the call returns once they
+// have left the caller's memory.
 static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
-                               const uint64_t* msg_off, const uint8_t* k) {
+                               const uint64_t* msg_off, const uint8_t* k, const uint32_t* key_idx = nullptr) {
   edc_ctx* ctx = v->ctx;
-  if (m && (!vk || !sig || (!k && !msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (m && ((!vk && !key_idx) || !sig || (!k && !msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
   if (!m) return 0;
+  if (key_idx) {
+    uint32_t mx = 0;
+    for (size_t i = 0; i < m; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
+    if (mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
+  }
   const size_t mbytes = k ? 0 : (size_t)(msg_off[m] - msg_off[0]);
   if (mbytes && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
@@ -2556,7 +2607,22 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
     if (rc) return rc;
     if (v->chal_pending) CK(hipStreamWaitEvent(v->cs, v->ev_chal, 0));
   }
-  CK(hipMemcpyAsync(v->vk + n0 * 32, vk, m * 32, hipMemcpyHostToDevice, v->cs));
+  if (key_idx) {
+    if (m > v->cap_idx) {
+      CK(hipStreamSynchronize(v->cs));          // the previous indexed append's expansion reads v->idx
+      if (v->idx) (void)hipFree(v->idx);
+      v->idx = nullptr;
+      v->cap_idx = 0;
+      const size_t cap = m < 1024 ? 1024 : m + m / 8;
+      CK(dalloc(&v->idx, cap));
+      v->cap_idx = cap;
+    }
+    CK(hipMemcpyAsync(v->idx, key_idx, m * sizeof(uint32_t), hipMemcpyHostToDevice, v->cs));
+    launch_expand_keys(v->cs, (uint32_t)m, v->idx, ctx->kc_reg, ctx->kc_keys, v->vk + n0 * 32);
+    CK(hipGetLastError());
+  } else {
+    CK(hipMemcpyAsync(v->vk + n0 * 32, vk, m * 32, hipMemcpyHostToDevice, v->cs));
+  }
   CK(hipMemcpyAsync(v->sig + n0 * 64, sig, m * 64, hipMemcpyHostToDevice, v->cs));
   if (k) {
     CK(hipMemcpyAsync(v->k + n0 * 8, k, m * 32, hipMemcpyHostToDevice, v->cs));
@@ -2587,9 +2653,11 @@ static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const
   Slot& s = v->s;
   const size_t n = v->n;
   const uint32_t N = (uint32_t)n;
-  const MsmPlan P = batch_plan(ctx, n, false, false);
-  int rc = ensure_msm(ctx, s, P, msm_entry_capacity(P, n, n + 1));
+  const bool split = verifier_split(v);
+  const MsmPlan P = batch_plan(ctx, n, false, split);
+  int rc = ensure_msm(ctx, s, P, split ? msm_entry_capacity(P, 2 + 3 * n, 0) : msm_entry_capacity(P, n, n + 1));
   if (rc) return rc;
+  v->last_split = split ? 1 : 0;
   uint32_t seed[8];
   seed_words(z_seed, seed);
   hipStream_t st = s.st;
@@ -2601,10 +2669,11 @@ static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const
   s.n_batch = N;
   launch_verifier_begin(st, N, s.flags, s.key_acc, s.u_acc, s.d_out, s.counts, P.nbin());
   launch_coef(st, N, v->sig, v->k, z ? v->zexp : nullptr, seed, 0, s.key_index, s.scal, s.key_acc, s.u_acc, s.itembad,
-              s.flags, false, s.coef_part, false);
-  launch_msm_bin(st, P, batch_terms(P, s, N, false), 1 + 2 * N, s.counts, s.offsets, s.cursor, s.entries, s.flags, true);
+              s.flags, false, s.coef_part, split);
+  launch_msm_bin(st, P, batch_terms(P, s, N, split), split ? 2 + 3 * N : 1 + 2 * N, s.counts, s.offsets, s.cursor,
+                 s.entries, s.flags, true);
   launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
-  launch_verifier_place_keys(st, N, v->vk, verifier_kpts(v), s.pts, s.keybad, s.flags, ctx->kc());
+  launch_verifier_place_keys(st, N, v->vk, verifier_kpts(v), verifier_khi(v), s.pts, s.keybad, s.flags, ctx->kc(), split);
   launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
                     s.slice_T, 0, nullptr, nullptr, true, s.flags);
   s.acc_nbin = P.nbin();
@@ -2619,6 +2688,7 @@ static int verifier_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t
   if (!z_seed == !z) { ctx->err = "exactly one of z_seed and z"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
   if (!v->n) {                  // the empty equation: [8] * identity
+    v->last_split = 0;
     if (check8) {
       memset(check8, 0, 32);
       check8[0] = 1;
@@ -2660,7 +2730,7 @@ void edc_verifier_destroy(edc_verifier* v) {
   ctx->verifiers.erase(std::remove(ctx->verifiers.begin(), ctx->verifiers.end(), v), ctx->verifiers.end());
   free_slot_buffers(s);
   for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->msg, (void*)v->off, (void*)s.flags,
-                  (void*)s.d_out})
+                  (void*)s.d_out, (void*)v->karea, (void*)v->idx})
     if (p) (void)hipFree(p);
   if (s.h_out) (void)hipHostFree(s.h_out);
   if (s.h_acc) (void)hipHostFree(s.h_acc);
@@ -2723,6 +2793,18 @@ int edc_verifier_queue_device(edc_verifier* v, size_t m, const uint8_t* d_vk, co
   v->n = n0 + m;
   return 0;
 }
+
+int edc_vfy_queue_indexed(edc_verifier* v, size_t m, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
+                          const uint64_t* msg_off, const uint8_t* k) {
+  if (!v) return EDC_ERR_ARG;
+  edc_ctx* ctx = v->ctx;
+  if (!k == !msg_off) { ctx->err = "exactly one of msg_off and k"; return EDC_ERR_ARG; }
+  if (!ctx->kc_reg_m) { ctx->err = "no registered key list (edc_keycache_load)"; return EDC_ERR_ARG; }
+  if (m && !key_idx) { ctx->err = "null key_idx"; return EDC_ERR_ARG; }
+  return verifier_queue_host(v, m, nullptr, sig, msg, msg_off, k, key_idx);
+}
+
+int edc_vfy_last_split(const edc_verifier* v) { return v && v->last_split >= 0 ? v->last_split : EDC_ERR_ARG; }
 
 size_t edc_verifier_size(const edc_verifier* v) { return v ? v->n : 0; }
 

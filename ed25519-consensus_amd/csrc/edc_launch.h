@@ -23,18 +23,20 @@ void launch_keys(hipStream_t st, uint32_t n, const uint8_t* vk, uint32_t* table,
                  uint32_t kcap = 0xFFFFFFFFu);
 // incremental verifier (edc_verifier_*): find-or-insert of items [n0, n0 + m) against a populated
 // table (key indices continue from flags[FLAG_NKEYS]), their key_index, and the decode of the keys
-// first seen in the range into row key_index of kpts; seed_pass: the sampling pass of launch_keys
-// for a large first append
+// first seen in the range into row key_index of kpts and, while the context has a key cache, of
+// their [2^128] multiples into khi; seed_pass: the sampling pass of launch_keys for a large first
+// append
 void launch_keys_range(hipStream_t st, uint32_t n0, uint32_t m, const uint8_t* vk, uint32_t* table, uint32_t tmask,
                        const uint32_t salt[2], bool force_overflow, bool seed_pass, uint32_t* slot_key,
                        uint32_t* key_slot_of_sig, uint32_t* key_rep, uint32_t* key_index, unsigned long long* key_acc,
-                       uint32_t* kpts, uint8_t* keybad, int* flags, const KeyCacheView& kc);
+                       uint32_t* kpts, uint32_t* khi, uint8_t* keybad, int* flags, const KeyCacheView& kc);
 // start of a verify over n queued items: clears the per-call sums, the result block and counts
 void launch_verifier_begin(hipStream_t st, uint32_t n, int* flags, unsigned long long* key_acc,
                            unsigned long long* u_acc, uint8_t* d_out, uint32_t* counts, uint32_t nbin);
-// key rows 1 + n + j of the batch layout from kpts (after an overflow: every A_i decoded)
-void launch_verifier_place_keys(hipStream_t st, uint32_t n, const uint8_t* vk, const uint32_t* kpts, uint32_t* pts,
-                                uint8_t* keybad, int* flags, const KeyCacheView& kc);
+// key rows 1 + n + j of the batch layout from kpts (after an overflow: every A_i decoded); split:
+// the split layout of edc_common.h, [2^128]B from the cache and the [2^128]A_j rows from khi
+void launch_verifier_place_keys(hipStream_t st, uint32_t n, const uint8_t* vk, const uint32_t* kpts, const uint32_t* khi,
+                                uint32_t* pts, uint8_t* keybad, int* flags, const KeyCacheView& kc, bool split);
 // per-signature key terms (no grouping): m = n, key j is signature j's own key (key_rep = null)
 void launch_coef(hipStream_t st, uint32_t n, const uint8_t* sig, const uint32_t* k, const uint8_t* zexp,
                  const uint32_t seed[8], uint64_t zbase, const uint32_t* key_index, uint32_t* scal,

@@ -425,18 +425,35 @@ __global__ void __launch_bounds__(256) k_key_insert_range(uint32_t n0, uint32_t 
   key_insert_one(i, vk, table, tmask, salt0, salt1, probe_cap, slot_key, key_slot_of_sig, key_rep, key_acc, flags);
 }
 
+// [2^128]P as affine Niels for the verifier's kernels below: shift128_niels again, as a copy of
+// their own. A callee is compiled once, for the loosest register budget among its callers, and
+// sharing it cost k_decompress its occupancy target.
+__device__ __noinline__ ge_niels shift128_niels_queue(ge_p3 P) {
+  for (int k = 0; k < 128; ++k) P = ge_dbl(P, k == 127);
+  const fe zi = fe_invert(P.Z);
+  ge_p3 A;
+  A.X = fe_mul(P.X, zi);
+  A.Y = fe_mul(P.Y, zi);
+  A.Z = fe_one();
+  A.T = fe_mul(A.X, A.Y);
+  return ge_to_niels_affine(A);
+}
+
 // Second pass over the appended range (slot_key is written by the claimer after its CAS, so a lane
 // that found a slot claimed in the same launch reads it only here): the dense key index of every
 // item, and the decode of the keys first seen in this range -- the item whose index the claimer
 // left in key_rep decodes its own key bytes into row key_index of the verifier's key area kpts
 // (registered keys copy their cached record, as k_decompress). No lane count to guess: however many
-// new keys an append brings, each has exactly one item lane.
+// new keys an append brings, each has exactly one item lane. khi (null: the context has no key
+// cache) receives the key's [2^128] row for a verify with split coefficients: the cached record,
+// or 128 doublings for a key missing from the cache, paid here while the votes still arrive.
 __global__ void __launch_bounds__(256) k_key_finish_range(uint32_t n0, uint32_t m, const uint8_t* __restrict__ vk,
                                                           const uint32_t* __restrict__ key_slot_of_sig,
                                                           const uint32_t* __restrict__ slot_key,
                                                           const uint32_t* __restrict__ key_rep,
                                                           uint32_t* __restrict__ key_index,
-                                                          uint32_t* __restrict__ kpts, uint8_t* __restrict__ keybad,
+                                                          uint32_t* __restrict__ kpts, uint32_t* __restrict__ khi,
+                                                          uint8_t* __restrict__ keybad,
                                                           int* __restrict__ flags, KeyCacheView kcache) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= m || flags[FLAG_OVF]) return;
@@ -449,13 +466,16 @@ __global__ void __launch_bounds__(256) k_key_finish_range(uint32_t n0, uint32_t 
   const int ci = kc_lookup(kcache, w);
   bool ok;
   if (ci >= 0) {
-    copy_record(kpts, j, kcache.comb + (size_t)ci * COMB_ENTRIES * NIELS_WORDS);
+    const uint32_t* comb = kcache.comb + (size_t)ci * COMB_ENTRIES * NIELS_WORDS;
+    copy_record(kpts, j, comb);
+    if (khi) copy_record(khi, j, comb + (size_t)COMB_SHIFT128 * NIELS_WORDS);
     ok = kcache.ok[ci] != 0;
   } else {
     ge_p3 P;
     ok = ge_decompress(w, P);
     st_niels(kpts, j, ge_to_niels_affine(P));
     if (kcache.table) atomicAdd(&flags[FLAG_UNCACHED], 1);
+    if (khi) st_niels(khi, j, shift128_niels_queue(P));
   }
   keybad[j] = ok ? 0 : 1;
   if (!ok) atomicOr(&flags[FLAG_BAD], 1);
@@ -480,32 +500,45 @@ __global__ void __launch_bounds__(256) k_verifier_begin(uint32_t n, int* __restr
 }
 
 // The key rows of the batch layout, once n is known: key j's record moves from the verifier's key
-// area to row 1 + n + j (16 bytes per lane). After an overflow every A_i is decoded here instead
-// (row 1 + n + i), the per-signature key path of k_decompress.
+// area to row 1 + n + j (16 bytes per lane). With split coefficients (edc_common.h) the rows
+// 1 + n .. 1 + n + 2m are one contiguous run of 2m + 1 records: A_0..A_m-1 from kpts, [2^128]B from
+// the cache's comb of B, [2^128]A_0..A_m-1 from khi; source and destination never share memory
+// (the key areas are the verifier's own allocation). After an overflow every A_i is decoded here
+// instead (row 1 + n + i, with its [2^128] row when split), the per-signature key path of
+// k_decompress.
 __global__ void __launch_bounds__(256) k_verifier_place_keys(uint32_t n, const uint8_t* __restrict__ vk,
                                                              const uint32_t* __restrict__ kpts,
+                                                             const uint32_t* __restrict__ khi,
                                                              uint32_t* __restrict__ pts, uint8_t* __restrict__ keybad,
-                                                             int* __restrict__ flags, KeyCacheView kcache) {
+                                                             int* __restrict__ flags, KeyCacheView kcache, int split) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  constexpr uint32_t RC = NIELS_WORDS / 4;                   // 16-byte chunks of a record
+  const uint4* bhi = reinterpret_cast<const uint4*>(kcache.bcomb + (size_t)COMB_SHIFT128 * NIELS_WORDS);   // split only
   if (!flags[FLAG_OVF]) {
-    const uint32_t chunks = (uint32_t)flags[FLAG_NKEYS] * (NIELS_WORDS / 4);
+    const uint32_t ka = (uint32_t)flags[FLAG_NKEYS] * RC;
+    const uint32_t chunks = split ? 2 * ka + RC : ka;
     const uint4* src = reinterpret_cast<const uint4*>(kpts);
+    const uint4* hsrc = reinterpret_cast<const uint4*>(khi);
     uint4* dst = reinterpret_cast<uint4*>(pts + (size_t)(1 + n) * NIELS_WORDS);
-    for (uint32_t c = g; c < chunks; c += stride) dst[c] = src[c];
+    for (uint32_t c = g; c < chunks; c += stride) dst[c] = c < ka ? src[c] : c < ka + RC ? bhi[c - ka] : hsrc[c - ka - RC];
     return;
   }
+  if (split && g < RC) reinterpret_cast<uint4*>(pts + (size_t)split_b_hi_point(n, n) * NIELS_WORDS)[g] = bhi[g];
   for (uint32_t i = g; i < n; i += stride) {
     uint32_t w[8];
     ld_words8(vk + (size_t)i * 32, w);
     const int ci = kc_lookup(kcache, w);
     bool ok;
     if (ci >= 0) {
-      copy_record(pts, 1 + n + i, kcache.comb + (size_t)ci * COMB_ENTRIES * NIELS_WORDS);
+      const uint32_t* comb = kcache.comb + (size_t)ci * COMB_ENTRIES * NIELS_WORDS;
+      copy_record(pts, 1 + n + i, comb);
+      if (split) copy_record(pts, split_hi_point(n, n, i), comb + (size_t)COMB_SHIFT128 * NIELS_WORDS);
       ok = kcache.ok[ci] != 0;
     } else {
       ge_p3 P;
       ok = ge_decompress(w, P);
       st_niels(pts, 1 + n + i, ge_to_niels_affine(P));
+      if (split) st_niels(pts, split_hi_point(n, n, i), shift128_niels_queue(P));
     }
     keybad[i] = ok ? 0 : 1;
     if (!ok) atomicOr(&flags[FLAG_BAD], 1);
@@ -912,7 +945,7 @@ void launch_keys(hipStream_t st, uint32_t n, const uint8_t* vk, uint32_t* table,
 void launch_keys_range(hipStream_t st, uint32_t n0, uint32_t m, const uint8_t* vk, uint32_t* table, uint32_t tmask,
                        const uint32_t salt[2], bool force_overflow, bool seed_pass, uint32_t* slot_key,
                        uint32_t* key_slot_of_sig, uint32_t* key_rep, uint32_t* key_index, unsigned long long* key_acc,
-                       uint32_t* kpts, uint8_t* keybad, int* flags, const KeyCacheView& kc) {
+                       uint32_t* kpts, uint32_t* khi, uint8_t* keybad, int* flags, const KeyCacheView& kc) {
   if (!m) return;
   const uint32_t cap = force_overflow ? 0u : KEY_PROBE_CAP;
   if (seed_pass && m > 4 * KEY_SEED_SAMPLE)
@@ -921,18 +954,18 @@ void launch_keys_range(hipStream_t st, uint32_t n0, uint32_t m, const uint8_t* v
   hipLaunchKernelGGL(k_key_insert_range, dim3(cdiv(m, 256)), dim3(256), 0, st, n0, m, 0, vk, table, tmask, salt[0],
                      salt[1], cap, slot_key, key_slot_of_sig, key_rep, key_acc, flags);
   hipLaunchKernelGGL(k_key_finish_range, dim3(cdiv(m, 256)), dim3(256), 0, st, n0, m, vk, key_slot_of_sig, slot_key,
-                     key_rep, key_index, kpts, keybad, flags, kc);
+                     key_rep, key_index, kpts, kc.bcomb ? khi : nullptr, keybad, flags, kc);
 }
 void launch_verifier_begin(hipStream_t st, uint32_t n, int* flags, unsigned long long* key_acc,
                            unsigned long long* u_acc, uint8_t* d_out, uint32_t* counts, uint32_t nbin) {
   hipLaunchKernelGGL(k_verifier_begin, dim3(grid_cap(cdiv(n > 256 ? n : 256, 256), 1024)), dim3(256), 0, st, n, flags,
                      key_acc, u_acc, reinterpret_cast<uint32_t*>(d_out), counts, nbin);
 }
-void launch_verifier_place_keys(hipStream_t st, uint32_t n, const uint8_t* vk, const uint32_t* kpts, uint32_t* pts,
-                                uint8_t* keybad, int* flags, const KeyCacheView& kc) {
+void launch_verifier_place_keys(hipStream_t st, uint32_t n, const uint8_t* vk, const uint32_t* kpts, const uint32_t* khi,
+                                uint32_t* pts, uint8_t* keybad, int* flags, const KeyCacheView& kc, bool split) {
   if (n)
-    hipLaunchKernelGGL(k_verifier_place_keys, dim3(grid_cap(cdiv(n, 256), 1024)), dim3(256), 0, st, n, vk, kpts, pts,
-                       keybad, flags, kc);
+    hipLaunchKernelGGL(k_verifier_place_keys, dim3(grid_cap(cdiv(n, 256), 1024)), dim3(256), 0, st, n, vk, kpts, khi,
+                       pts, keybad, flags, kc, split && kc.bcomb ? 1 : 0);
 }
 // One launch for the per-batch resets (flags, global coefficient sums, result block, key table,
 // MSM bin counts) instead of five runtime fills: each fill is a launch of its own, ~8 us apiece in

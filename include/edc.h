@@ -484,7 +484,32 @@ int edc_synchronize(edc_ctx* ctx);
  *   warning, of edc_batch_verify_fallback_device. verdicts: n bytes.
  * edc_verifier_reset   forget the items, keep the allocations (Verifier::default() for the next block).
  * edc_set_key_grouping modes 2 and 3 make a verifier take one key term per signature (the path a
- * probe overflow takes: every A_i is decoded at verify); split coefficients are not used.
+ * probe overflow takes: every A_i is decoded at verify).
+ *
+ * With a registered validator set (edc_keycache_load / _add):
+ * Split coefficients. While the context holds a key cache, every queue call also leaves the
+ *   [2^128] multiple of each key first seen in it: a copy of the cached record, or 128 doublings
+ *   at queue time for a key missing from the cache. verify then plans with split coefficients
+ *   (every MSM term at most 128 bits, about 128 Horner doublings instead of about 250) when
+ *   edc_set_key_split is 0, a cache is loaded, and every item queued since the last reset was
+ *   queued against that same cache. Unlike the one-call entries the verifier does not stop
+ *   splitting after uncached keys: their doublings are done before verify is called. In every
+ *   key-grouping mode; after a grouping overflow verify takes the per-signature split path.
+ *   edc_keycache_load / _add / _clear may run while items are queued: a call that changes the
+ *   cache's contents starts a new cache generation (an _add that finds every key already cached
+ *   changes nothing), and a verify that finds another generation than the one its rows were built
+ *   against, or an item queued with no cache loaded, runs unsplit. Growth and edc_verifier_reset
+ *   rebuild / restart against the cache loaded then. Verdict, check8 and fallback codes are
+ *   bit-identical either way. The key rows live in the verifier's own allocation: 256 bytes per
+ *   item of capacity.
+ * edc_vfy_queue_indexed  edc_verifier_queue / _prehashed with the keys given as positions in the
+ *   list last passed to edc_keycache_load (4 bytes per item over PCIe instead of 32; the raw key
+ *   bytes are expanded into the retained vk range on the device, and the range then takes the
+ *   same path as any other). Exactly one of msg_off (with msg) and k. An index outside the list,
+ *   or no registered list, is EDC_ERR_ARG with nothing appended. May be mixed with the other
+ *   queue forms.
+ * edc_vfy_last_split  1 if the last edc_verifier_verify / _verify_fallback on v ran the split
+ *   plan, 0 if not; EDC_ERR_ARG before any verify and for NULL.
  */
 typedef struct edc_verifier edc_verifier;
 edc_verifier* edc_verifier_create(edc_ctx* ctx, size_t capacity_hint);
@@ -499,6 +524,9 @@ int edc_verifier_verify(edc_verifier* v, const uint8_t z_seed[32], const uint8_t
 int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
                                  uint8_t check8[32]);
 int edc_verifier_reset(edc_verifier* v);
+int edc_vfy_queue_indexed(edc_verifier* v, size_t m, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
+                          const uint64_t* msg_off, const uint8_t* k);
+int edc_vfy_last_split(const edc_verifier* v);
 
 /*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
