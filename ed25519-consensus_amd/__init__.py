@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "edc_verifier_create", "edc_verifier_destroy", "edc_verifier_queue", "edc_verifier_queue_prehashed",
     "edc_verifier_queue_device", "edc_verifier_size", "edc_verifier_verify", "edc_verifier_verify_fallback",
     "edc_verifier_reset", "edc_vfy_queue_indexed", "edc_vfy_last_split",
+    "edc_vfy_begin_eager", "edc_vfy_set_fold", "edc_vfy_folded", "edc_vfy_eager",
 ]
 
 
@@ -230,6 +231,11 @@ def load_library(path=None):
             lib.edc_vfy_queue_indexed.argtypes = [c_vp, c_sz, ctypes.POINTER(ctypes.c_uint32), c_u8p, c_u8p, c_u64p,
                                                   c_u8p]
             lib.edc_vfy_last_split.argtypes = [c_vp]
+        if hasattr(lib, "edc_vfy_begin_eager"):              # absent from older A/B builds (tools/)
+            lib.edc_vfy_begin_eager.argtypes = [c_vp, c_u8p]
+            lib.edc_vfy_set_fold.argtypes = [c_vp, c_sz]
+            lib.edc_vfy_folded.argtypes = [c_vp, c_u64p, c_u64p]
+            lib.edc_vfy_eager.argtypes = [c_vp]
         if path is None:
             _lib = lib
         return lib
@@ -946,19 +952,51 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         per-item work on the GPU as items arrive (copy, SHA-512 -> k, ZIP215 decode of R, key
         grouping, decode of new keys; edc_verifier_queue*), and verify(rng) only evaluates the
         equation (edc_verifier_verify). Results equal batch.Verifier's on the same items and z.
-        The queue survives verify(); reset() starts the next block with the same allocations."""
+        The queue survives verify(); reset() starts the next block with the same allocations.
+        eager=True (or begin_eager()) commits the block's z seed up front, so that queue calls also
+        sum the [z_i]R_i terms on the GPU and verify() runs an MSM over B, the keys and the short
+        unfolded tail only (edc_vfy_begin_eager; soundness in include/edc.h)."""
 
-        def __init__(self, engine=None, capacity=0):
+        def __init__(self, engine=None, capacity=0, eager=False):
             self._engine = engine or default_engine()
+            self._always_eager = bool(eager)
             self._v = self._engine.lib.edc_verifier_create(self._engine.ctx, int(capacity))
             if not self._v:
                 raise EngineError("edc_verifier_create failed: "
                                   + self._engine.lib.edc_last_error(self._engine.ctx).decode())
             self._engine._verifiers.add(self)
+            if eager:
+                self.begin_eager()
 
         @classmethod
-        def new(cls, engine=None, capacity=0):
-            return cls(engine, capacity)
+        def new(cls, engine=None, capacity=0, eager=False):
+            return cls(engine, capacity, eager)
+
+        def begin_eager(self, seed=None):
+            """Enter eager mode for this block with a committed 32-byte z seed (None: fresh OS
+            randomness drawn by the library). Only while nothing is queued."""
+            eng = self._engine
+            with eng._lock:
+                rc = eng.lib.edc_vfy_begin_eager(self._handle(), None if seed is None else _as_bytes(seed, 32))
+            eng._check(rc)
+
+        @property
+        def eager(self):
+            return self._engine.lib.edc_vfy_eager(self._handle()) == 1
+
+        @property
+        def folded(self):
+            """(items whose R term is in the running point, folds since the last reset)."""
+            items, folds = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            eng = self._engine
+            eng._check(eng.lib.edc_vfy_folded(self._handle(), ctypes.byref(items), ctypes.byref(folds)))
+            return int(items.value), int(folds.value)
+
+        def set_fold(self, min_items):
+            """Fold once at least min_items queued items are pending (0: the library default);
+            results never depend on it."""
+            eng = self._engine
+            eng._check(eng.lib.edc_vfy_set_fold(self._handle(), int(min_items)))
 
         def close(self):
             if getattr(self, "_v", None):
@@ -1053,11 +1091,15 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         def verify_detailed(self, rng=None):
             """(code, check8) as batch.Verifier.verify_detailed: rng is a 32-byte ChaCha20 seed, an
             object with fill_bytes(n) / token_bytes(n) (z drawn per item in queue order,
-            src/batch.rs:64-68), or None (fresh OS randomness)."""
+            src/batch.rs:64-68), or None (fresh OS randomness). In eager mode z is already
+            committed: rng must be None."""
             eng, v = self._engine, self._handle()
             n = self.batch_size
             seed = z = None
-            if isinstance(rng, (bytes, bytearray)) and len(rng) == 32:
+            if self.eager:
+                if rng is not None:
+                    raise ValueError("eager StreamVerifier: z was committed by begin_eager, verify takes rng=None")
+            elif isinstance(rng, (bytes, bytearray)) and len(rng) == 32:
                 seed = bytes(rng)
             elif rng is None:
                 seed = secrets.token_bytes(32)
@@ -1091,8 +1133,11 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             return rc, list(verdicts.raw[:n]), check8.raw
 
         def reset(self):
-            """Forget the queued items, keep the allocations."""
+            """Forget the queued items, keep the allocations. Leaves eager mode, unless the object was
+            made with eager=True: then the next block begins eagerly with a fresh OS seed."""
             eng = self._engine
             with eng._lock:
                 rc = eng.lib.edc_verifier_reset(self._handle())
             eng._check(rc)
+            if self._always_eager:
+                self.begin_eager()

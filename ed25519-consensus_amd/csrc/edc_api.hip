@@ -11,10 +11,13 @@
 #include <thread>
 #include <unordered_map>
 #include <vector>
+#include <errno.h>
+#include <sys/random.h>
 #include <hip/hip_ext.h>
 #include "edc.h"
 #include "edc_common.h"
 #include "edc_launch.h"
+#include "vfy_fold.h"
 
 using namespace edc;
 
@@ -232,6 +235,13 @@ struct edc_verifier {
   int last_split = -1;          // plan of the last verify: 1 split, 0 unsplit, -1 none yet
   uint32_t* idx = nullptr;      // one indexed append's key positions (edc_vfy_queue_indexed)
   size_t cap_idx = 0;
+  // eager mode (edc_vfy_begin_eager): the block's z seed is committed before the items arrive and
+  // queue calls fold sum [z_i]R_i of the items [fold.folded, n) into the running point `run`
+  // (EXT_WORDS words, then the 256-byte result block of the last fold's MSM); verify's MSM then
+  // leaves those R terms out and adds `run` before the x8. Both survive a growth.
+  FoldState fold;
+  uint8_t eager_seed[32] = {};
+  uint32_t* run = nullptr;
 };
 
 // A failed HIP call also leaves the thread's last-error state set; it is cleared here, so that a
@@ -492,8 +502,9 @@ static MsmPlan batch_plan(const edc_ctx* ctx, size_t n, bool per_sig, bool split
   return P;
 }
 
-static MsmTerms batch_terms(const MsmPlan& P, const Slot& s, uint32_t n, bool split) {
-  return MsmTerms{n, 0, 0, 0, P.sum_ranges ? P.nranges : 1u, s.scal, nullptr, nullptr, nullptr, split ? 1u : 0u};
+static MsmTerms batch_terms(const MsmPlan& P, const Slot& s, uint32_t n, bool split, uint32_t skip = 0) {
+  return MsmTerms{n - skip, 0, 0, 0, P.sum_ranges ? P.nranges : 1u, s.scal, nullptr, nullptr, nullptr, split ? 1u : 0u,
+                  0u, skip};
 }
 
 // Split coefficients need [2^128]A of every key of the batch; the cache holds it for registered
@@ -2581,6 +2592,63 @@ static int verifier_msg_room(edc_verifier* v, size_t m, size_t mbytes) {
   return 0;
 }
 
+// ---- eager mode (edc_vfy_begin_eager) ----
+// Plan of a fold: every term is a 128-bit z, so there are no windows above bit 128 (the layout of
+// the split plan), and the slices are split into sub-bins as batch_plan splits them.
+static MsmPlan fold_plan(const edc_ctx* ctx, size_t cnt) {
+  const int c = ctx->win_bits ? ctx->win_bits : auto_window_bits(cnt);
+  MsmPlan P = make_plan(c, c, 1, false);
+  const double total = (double)cnt * P.nwin;
+  double target = ctx->bin_entries ? (double)ctx->bin_entries : (total / 1024.0 > 4096.0 ? total / 1024.0 : 4096.0);
+  for (;;) {
+    for (uint32_t w = 0; w < P.nwin; ++w) P.nsub[w] = (uint8_t)floor_pow2((double)cnt / P.nslice[w] / target);
+    plan_layout(P);
+    if (P.bins_per_range <= MSM_MAX_BINS) break;
+    target *= 2;
+  }
+  return P;
+}
+
+// After a queue call: once enough items are pending, sum [z_i]R_i over the pending range
+// [folded, n) as an R-only MSM on the slot stream (z from the committed seed at the items' queue
+// indices, the R rows the range's decode left in s.pts) and add the sum into the running point.
+// No host synchronization. A range holding an undecodable R has set FLAG_BAD before its fold runs
+// (same stream), and k_msm_final then reports the identity as the fold's partial point: the
+// running point stays a point of the curve and the batch is rejected by the flag at verify.
+static int verifier_fold(edc_verifier* v) {
+  size_t a, b;
+  if (!fold_due(v->fold, v->n, &a, &b)) return 0;
+  edc_ctx* ctx = v->ctx;
+  Slot& s = v->s;
+  const uint32_t cnt = (uint32_t)(b - a);
+  const MsmPlan P = fold_plan(ctx, cnt);
+  int rc = ensure_msm(ctx, s, P, msm_entry_capacity(P, cnt, 0));
+  if (rc) return rc;
+  uint32_t seed[8];
+  seed_words(v->eager_seed, seed);
+  hipStream_t st = s.st;
+  launch_z_range(st, seed, (uint32_t)a, cnt, s.scal);
+  // one range of cnt short terms, term t = R of item a + t (MsmTerms::skip)
+  const MsmTerms terms{cnt, 0x80000000u, cnt, 0u, 1u, s.scal, nullptr, nullptr, nullptr, 0u, 0u, (uint32_t)a};
+  launch_msm_bin(st, P, terms, cnt, s.counts, s.offsets, s.cursor, s.entries, s.flags);
+  launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
+  launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
+                    s.slice_T, 0, nullptr, nullptr, true, s.flags);
+  uint8_t* blk = reinterpret_cast<uint8_t*>(v->run + 64);
+  launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, 0, blk);
+  launch_point_accum(st, v->run, blk);
+  CK(hipGetLastError());
+  fold_done(v->fold, b);
+  return 0;
+}
+
+// a failed eager verify has revealed a z-dependent point: no more queue / verify under that seed
+static int verifier_spent(edc_verifier* v) {
+  if (!(v->fold.eager && v->fold.spent)) return 0;
+  v->ctx->err = "eager verifier: the seed is spent after a failed verify (edc_verifier_reset, then edc_vfy_begin_eager)";
+  return EDC_ERR_ARG;
+}
+
 // One append from host buffers (k: prehashed challenges, or null for the message path; key_idx:
 // positions in the registered key list instead of vk, 4 bytes per item over PCIe, expanded into the
 // retained vk range on the device). The copies run on the copy stream; the call returns once they
@@ -2589,6 +2657,7 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
                                const uint64_t* msg_off, const uint8_t* k, const uint32_t* key_idx = nullptr) {
   edc_ctx* ctx = v->ctx;
   if (m && ((!vk && !key_idx) || !sig || (!k && !msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (verifier_spent(v)) return EDC_ERR_ARG;
   if (!m) return 0;
   if (key_idx) {
     uint32_t mx = 0;
@@ -2644,18 +2713,24 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
   if (rc) return rc;
   CK(hipEventSynchronize(v->ev_copy));   // nothing reads the caller's (or the rebased) buffers after this
   v->n = n0 + m;
-  return 0;
+  return verifier_fold(v);
 }
 
 // The z-dependent part over everything queued, on the verifier's slot; no host synchronization.
-static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t* z, int want_compress) {
+// Eager (z_seed = the committed seed): the coefficients still run over all n items (the B and key
+// sums need every z_i s_i and z_i k_i), but the MSM leaves out the R terms of the `skip` folded
+// items, is planned for the nl = n - skip that remain, and k_msm_final adds the running point
+// before the x8: the same group element as the whole batch's MSM.
+static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t* z, int want_compress,
+                                   bool eager = false) {
   edc_ctx* ctx = v->ctx;
   Slot& s = v->s;
-  const size_t n = v->n;
+  const size_t n = v->n, skip = eager ? v->fold.folded : 0, nl = n - skip;
   const uint32_t N = (uint32_t)n;
   const bool split = verifier_split(v);
-  const MsmPlan P = batch_plan(ctx, n, false, split);
-  int rc = ensure_msm(ctx, s, P, split ? msm_entry_capacity(P, 2 + 3 * n, 0) : msm_entry_capacity(P, n, n + 1));
+  const MsmPlan P = batch_plan(ctx, nl, false, split);
+  // (after a grouping overflow every signature has its own key term: n of them, n + 1 with B)
+  int rc = ensure_msm(ctx, s, P, split ? msm_entry_capacity(P, 2 + nl + 2 * n, 0) : msm_entry_capacity(P, nl, n + 1));
   if (rc) return rc;
   v->last_split = split ? 1 : 0;
   uint32_t seed[8];
@@ -2670,22 +2745,32 @@ static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const
   launch_verifier_begin(st, N, s.flags, s.key_acc, s.u_acc, s.d_out, s.counts, P.nbin());
   launch_coef(st, N, v->sig, v->k, z ? v->zexp : nullptr, seed, 0, s.key_index, s.scal, s.key_acc, s.u_acc, s.itembad,
               s.flags, false, s.coef_part, split);
-  launch_msm_bin(st, P, batch_terms(P, s, N, split), split ? 2 + 3 * N : 1 + 2 * N, s.counts, s.offsets, s.cursor,
-                 s.entries, s.flags, true);
+  launch_msm_bin(st, P, batch_terms(P, s, N, split, (uint32_t)skip), (uint32_t)(split ? 2 + nl + 2 * n : 1 + nl + n),
+                 s.counts, s.offsets, s.cursor, s.entries, s.flags, true);
   launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
   launch_verifier_place_keys(st, N, v->vk, verifier_kpts(v), verifier_khi(v), s.pts, s.keybad, s.flags, ctx->kc(), split);
   launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
                     s.slice_T, 0, nullptr, nullptr, true, s.flags);
   s.acc_nbin = P.nbin();
-  launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, want_compress, s.d_out, s.h_out);
+  launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, want_compress, s.d_out, s.h_out, eager ? v->run : nullptr);
   CK(hipGetLastError());
   s.pending = true;
   return 0;
 }
 
-static int verifier_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t* z, uint8_t check8[32]) {
+static int verifier_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t* z, uint8_t check8[32],
+                           bool plain = false) {
   edc_ctx* ctx = v->ctx;
-  if (!z_seed == !z) { ctx->err = "exactly one of z_seed and z"; return EDC_ERR_ARG; }
+  // eager (edc_vfy_begin_eager): z is already committed; `plain` is the fallback's own verify of a
+  // spent eager verifier, which draws fresh z from the caller's seed over every item
+  const bool eager = v->fold.eager && !plain;
+  if (eager) {
+    if (z_seed || z) { ctx->err = "eager verifier: z is committed, pass neither z_seed nor z"; return EDC_ERR_ARG; }
+    if (verifier_spent(v)) return EDC_ERR_ARG;
+  } else if (!z_seed == !z) {
+    ctx->err = "exactly one of z_seed and z";
+    return EDC_ERR_ARG;
+  }
   CK(hipSetDevice(ctx->device));
   if (!v->n) {                  // the empty equation: [8] * identity
     v->last_split = 0;
@@ -2695,9 +2780,11 @@ static int verifier_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t
     }
     return EDC_OK;
   }
-  int rc = verifier_enqueue_verify(v, z_seed, z, check8 != nullptr);
+  int rc = verifier_enqueue_verify(v, eager ? v->eager_seed : z_seed, z, check8 != nullptr, eager);
   if (rc) return rc;
-  return finish_batch(ctx, v->s, check8, nullptr, nullptr);
+  rc = finish_batch(ctx, v->s, check8, nullptr, nullptr);
+  if (eager && rc == EDC_INVALID_SIGNATURE) v->fold.spent = true;   // a z-dependent point has left the library
+  return rc;
 }
 
 extern "C" {
@@ -2730,7 +2817,7 @@ void edc_verifier_destroy(edc_verifier* v) {
   ctx->verifiers.erase(std::remove(ctx->verifiers.begin(), ctx->verifiers.end(), v), ctx->verifiers.end());
   free_slot_buffers(s);
   for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->msg, (void*)v->off, (void*)s.flags,
-                  (void*)s.d_out, (void*)v->karea, (void*)v->idx})
+                  (void*)s.d_out, (void*)v->karea, (void*)v->idx, (void*)v->run})
     if (p) (void)hipFree(p);
   if (s.h_out) (void)hipHostFree(s.h_out);
   if (s.h_acc) (void)hipHostFree(s.h_acc);
@@ -2762,6 +2849,7 @@ int edc_verifier_queue_device(edc_verifier* v, size_t m, const uint8_t* d_vk, co
                               const uint64_t* d_msg_off, const uint8_t* d_k) {
   if (!v) return EDC_ERR_ARG;
   edc_ctx* ctx = v->ctx;
+  if (verifier_spent(v)) return EDC_ERR_ARG;
   if (!m) return 0;
   if (!d_vk || !d_sig || (!d_k && (!d_msg || !d_msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
   if (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k))) {
@@ -2791,7 +2879,7 @@ int edc_verifier_queue_device(edc_verifier* v, size_t m, const uint8_t* d_vk, co
   CK(hipEventSynchronize(v->ev_copy));
   if (!d_k) CK(hipEventSynchronize(v->ev_chal));
   v->n = n0 + m;
-  return 0;
+  return verifier_fold(v);
 }
 
 int edc_vfy_queue_indexed(edc_verifier* v, size_t m, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
@@ -2820,7 +2908,11 @@ int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint
   Slot& s = v->s;
   const size_t n = v->n;
   if (n_invalid) *n_invalid = 0;
-  int rc = verifier_verify(v, z_seed, nullptr, check8);
+  // eager mode: the eager verify first (its check8); a spent seed takes the plain verify with the
+  // caller's fresh seed instead. Either leaves what the fallback reads: the key rows placed for
+  // all n items, the per-item s bits, the grouping flags. The fallback draws its own z from z_seed.
+  const bool eager = v->fold.eager && !v->fold.spent;
+  int rc = eager ? verifier_verify(v, nullptr, nullptr, check8) : verifier_verify(v, z_seed, nullptr, check8, true);
   if (rc <= 0) {
     if (rc == 0 && n) memset(verdicts, 0, n);
     return rc;
@@ -2855,8 +2947,50 @@ int edc_verifier_reset(edc_verifier* v) {
   edc_ctx* ctx = v->ctx;
   CK(hipSetDevice(ctx->device));
   v->n = 0;
+  fold_reset(v->fold);          // the next block commits its own seed (edc_vfy_begin_eager)
   return verifier_clear(v);
 }
+
+int edc_vfy_begin_eager(edc_verifier* v, const uint8_t z_seed[32]) {
+  if (!v) return EDC_ERR_ARG;
+  edc_ctx* ctx = v->ctx;
+  if (v->n) { ctx->err = "edc_vfy_begin_eager: items are queued (call it after create or edc_verifier_reset)"; return EDC_ERR_ARG; }
+  uint8_t seed[32];
+  if (z_seed) {
+    memcpy(seed, z_seed, 32);
+  } else {                      // OS randomness, or no eager mode at all: never a fixed seed
+    size_t got = 0;
+    while (got < sizeof(seed)) {
+      const ssize_t r = getrandom(seed + got, sizeof(seed) - got, 0);
+      if (r < 0 && errno == EINTR) continue;
+      if (r <= 0) { ctx->err = "edc_vfy_begin_eager: getrandom failed"; return EDC_ERR_HIP; }
+      got += (size_t)r;
+    }
+  }
+  CK(hipSetDevice(ctx->device));
+  if (!v->run) CK(dalloc(&v->run, 128));   // the running point, then a fold's 256-byte result block
+  launch_point_accum(v->s.st, v->run, nullptr);
+  CK(hipGetLastError());
+  memcpy(v->eager_seed, seed, 32);
+  fold_reset(v->fold);
+  v->fold.eager = true;
+  return 0;
+}
+
+int edc_vfy_set_fold(edc_verifier* v, size_t min_items) {
+  if (!v) return EDC_ERR_ARG;
+  v->fold.min_items = min_items;
+  return 0;
+}
+
+int edc_vfy_folded(const edc_verifier* v, uint64_t* items, uint64_t* folds) {
+  if (!v) return EDC_ERR_ARG;
+  if (items) *items = v->fold.folded;
+  if (folds) *folds = v->fold.folds;
+  return 0;
+}
+
+int edc_vfy_eager(const edc_verifier* v) { return v ? (v->fold.eager ? 1 : 0) : EDC_ERR_ARG; }
 
 }  // extern "C"
 

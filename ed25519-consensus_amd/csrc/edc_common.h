@@ -114,6 +114,11 @@ struct MsmTerms {
   // signature: bit 1 = per signature by the host's choice, or FLAG_OVF), nx = nranges * m + nranges
   // listed terms, where the host passes nranges in nx
   uint32_t dyn;
+  // eager verifier (edc_vfy_begin_eager): the first `skip` R terms are left out. Batch: n counts the
+  // R terms that remain, term t >= 1 is point (and scalar row) t + skip, term 0 stays B. Ranges:
+  // term t < npoint is point 1 + skip + t; with npoint = n, nx = 0 and one range that is the
+  // R-only layout of a fold, sum [z_i]R_i over items [skip, skip + n).
+  uint32_t skip;
 };
 
 // signed digit of window w (bits <= 16) with carry in/out; top_unsigned keeps the raw value

@@ -37,6 +37,9 @@ void launch_verifier_begin(hipStream_t st, uint32_t n, int* flags, unsigned long
 // the split layout of edc_common.h, [2^128]B from the cache and the [2^128]A_j rows from khi
 void launch_verifier_place_keys(hipStream_t st, uint32_t n, const uint8_t* vk, const uint32_t* kpts, const uint32_t* khi,
                                 uint32_t* pts, uint8_t* keybad, int* flags, const KeyCacheView& kc, bool split);
+// eager verifier: z_i of items [a, a + cnt) drawn from the seed as launch_coef draws them (queue
+// index i: words 4 (i & 3).. of ChaCha block i >> 2), stored as the short scalar of row 1 + i
+void launch_z_range(hipStream_t st, const uint32_t seed[8], uint32_t a, uint32_t cnt, uint32_t* scal);
 // per-signature key terms (no grouping): m = n, key j is signature j's own key (key_rep = null)
 void launch_coef(hipStream_t st, uint32_t n, const uint8_t* sig, const uint32_t* k, const uint8_t* zexp,
                  const uint32_t seed[8], uint64_t zbase, const uint32_t* key_index, uint32_t* scal,
@@ -97,7 +100,10 @@ void launch_msm_bucket(hipStream_t st, const MsmPlan& P, const uint32_t* counts,
                        int* stamp_flags = nullptr);   // EDC_BATCH_STAMPS builds: the batch's flags
 size_t msm_bucket_words(uint32_t nbin);
 void launch_msm_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                     uint32_t* win, int* flags, int want_compress, uint8_t* out, uint8_t* hout = nullptr);
+                     uint32_t* win, int* flags, int want_compress, uint8_t* out, uint8_t* hout = nullptr,
+                     const uint32_t* extra = nullptr);   // extra: an extended point added before the x8
+// eager verifier: run (EXT_WORDS words) += the partial point of result block blk; blk = null: run = identity
+void launch_point_accum(hipStream_t st, uint32_t* run, const uint8_t* blk);
 void launch_msm_range_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
                            uint32_t* win, uint8_t* rverdict);
 // several batches in one launch: per range the window combine, Horner, x8 and identity, one

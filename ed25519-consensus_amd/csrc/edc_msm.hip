@@ -42,12 +42,12 @@ __device__ __forceinline__ void term_get(const MsmTerms& T, uint32_t t, uint32_t
                                          uint32_t s[8]) {
   const uint32_t* src;
   if (!T.rsize) {
-    pt = t;
+    pt = t ? t + T.skip : 0u;               // skip > 0: the R terms an eager verifier already folded
     rg = T.nparts > 1 ? t % T.nparts : 0;   // interleaved: every part gets its share of R, keys and B
     shrt = T.split || (t >= 1 && t <= T.n);
-    src = T.scal + (size_t)t * 8;
+    src = T.scal + (size_t)pt * 8;
   } else if (t < T.npoint) {       // R_i (t < n), then one key term per signature
-    pt = 1 + t;
+    pt = 1 + T.skip + t;
     rg = (t < T.n ? t : t - T.n) / T.rsize;
     shrt = t < T.n;
     src = T.scal + (size_t)pt * 8;
@@ -860,11 +860,12 @@ __device__ __forceinline__ void cache_windows(const RowCtx& c, const MsmPlan& P,
 // form the windows' addition operands, then wave 0 runs the serial chain. The 256-byte result
 // block is assembled in LDS and stored whole to `out` (device) and, when given, to `hout` (the
 // slot's pinned host mirror, written through the device mapping: no copy packet per batch).
+template <bool EXTRA>
 __global__ void __launch_bounds__(256) k_msm_final(MsmPlan P, const uint32_t* __restrict__ slice_W,
                                                    const uint32_t* __restrict__ win, const int* __restrict__ flags,
                                                    int want_compress, uint8_t* __restrict__ out,
                                                    uint8_t* __restrict__ hout, const uint32_t* __restrict__ from,
-                                                   uint32_t from_w) {
+                                                   uint32_t from_w, const uint32_t* __restrict__ extra) {
   __shared__ uint32_t cached[MSM_MAX_WIN * 64];
   __shared__ uint32_t res[2 * EXT_WORDS];
   __shared__ uint32_t blk[64];
@@ -883,7 +884,11 @@ __global__ void __launch_bounds__(256) k_msm_final(MsmPlan P, const uint32_t* __
     // partial and check point: the MSM sum then holds an off-curve point, whose value depends on
     // the order the additions ran in, and a public output must be the same on every run
     const int bad = flags[FLAG_BAD];
-    const ge_p3 acc = bad ? ge_identity() : ld_ext(res), c8 = bad ? ge_identity() : ld_ext(res + EXT_WORDS);
+    ge_p3 acc = bad ? ge_identity() : ld_ext(res), c8 = bad ? ge_identity() : ld_ext(res + EXT_WORDS);
+    if (EXTRA && !bad) {   // eager verifier: the running sum of the folded R terms joins before the x8
+      acc = ge_add(acc, ld_ext(extra));
+      c8 = ge_mul_by_cofactor(acc);
+    }
     uint8_t* b = reinterpret_cast<uint8_t*>(blk);
     ext_to_canonical_bytes(acc, b + 48);
     blk[0] = (!bad && ge_is_identity(c8)) ? 0u : 1u;
@@ -1039,6 +1044,14 @@ __global__ void k_combine_records(uint32_t g, const uint8_t* __restrict__ recs, 
   finish_point(acc, bad, 0, out);
 }
 
+// Eager verifier (edc_vfy_begin_eager): run += the partial point of a fold's result block (bytes
+// 48..176 of k_msm_final's block: the identity when the bad flag was set, so the running sum stays
+// a deterministic point whatever the fold held); blk = null starts a block: run = identity.
+__global__ void k_point_accum(uint32_t* __restrict__ run, const uint8_t* __restrict__ blk) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  st_ext(run, blk ? ge_add(ld_ext(run), ext_from_canonical_bytes(blk + 48)) : ge_identity());
+}
+
 // one shard's 256-byte result block to the first device's gather buffer (a peer store over xGMI
 // when the devices differ): a kernel on the shard's stream, so the copy stays asynchronous
 __global__ void k_copy_block(const uint4* __restrict__ src, uint4* __restrict__ dst) {
@@ -1165,21 +1178,31 @@ static bool plan_multi(const MsmPlan& P) {
   return false;
 }
 
+// k_msm_final; with `extra` the instantiation that adds it (the plain one is the batch path's kernel)
+static void launch_final(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* win, int* flags,
+                         int want_compress, uint8_t* out, uint8_t* hout, const uint32_t* from, uint32_t from_w,
+                         const uint32_t* extra) {
+  if (extra)
+    hipLaunchKernelGGL(k_msm_final<true>, dim3(1), dim3(256), 0, st, P, slice_W, win, flags, want_compress, out, hout,
+                       from, from_w, extra);
+  else
+    hipLaunchKernelGGL(k_msm_final<false>, dim3(1), dim3(256), 0, st, P, slice_W, win, flags, want_compress, out, hout,
+                       from, from_w, extra);
+}
+
 void launch_msm_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                     uint32_t* win, int* flags, int want_compress, uint8_t* out, uint8_t* hout) {
+                     uint32_t* win, int* flags, int want_compress, uint8_t* out, uint8_t* hout, const uint32_t* extra) {
   const uint32_t r = top_run_start(P);
   if (plan_multi(P) && r < P.nwin && r > 0 && P.nwin < MSM_MAX_WIN) {
     // window combines beside the top-run Horner; hbuf = the unused last window record of range 0
     uint32_t* hbuf = win + (size_t)(MSM_MAX_WIN - 1) * EXT_WORDS;
     hipLaunchKernelGGL(k_msm_window2, dim3(P.nwin + 1), dim3(256), kReduceLds, st, P, slice_W, slice_T, win, hbuf);
-    hipLaunchKernelGGL(k_msm_final, dim3(1), dim3(256), 0, st, P, slice_W, win, flags, want_compress, out, hout,
-                       (const uint32_t*)hbuf, r);
+    launch_final(st, P, slice_W, win, flags, want_compress, out, hout, hbuf, r, extra);
     return;
   }
   if (plan_multi(P) || P.sum_ranges)
     hipLaunchKernelGGL(k_msm_window, dim3(P.nwin), dim3(256), kReduceLds, st, P, slice_W, slice_T, win);
-  hipLaunchKernelGGL(k_msm_final, dim3(1), dim3(256), 0, st, P, slice_W, win, flags, want_compress, out, hout,
-                     (const uint32_t*)nullptr, 0u);
+  launch_final(st, P, slice_W, win, flags, want_compress, out, hout, nullptr, 0u, extra);
 }
 
 void launch_msm_range_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
@@ -1196,6 +1219,10 @@ void launch_msm_multi_tail(hipStream_t st, const MsmPlan& P, const uint32_t* sli
     hipLaunchKernelGGL(k_msm_window, dim3(P.nwin * P.nranges), dim3(256), kReduceLds, st, P, slice_W, slice_T, win);
   hipLaunchKernelGGL(k_msm_multi_final, dim3(P.nranges), dim3(64), 0, st, P, slice_W, win, flags, rbad, want_compress,
                      out, hout);
+}
+
+void launch_point_accum(hipStream_t st, uint32_t* run, const uint8_t* blk) {
+  hipLaunchKernelGGL(k_point_accum, dim3(1), dim3(64), 0, st, run, blk);
 }
 
 void launch_copy_block(hipStream_t st, const uint8_t* src, uint8_t* dst) {

@@ -1023,6 +1023,33 @@ void launch_coef_finish(hipStream_t st, uint32_t n, unsigned long long* key_acc,
   hipLaunchKernelGGL(k_key_final, dim3(grid_cap(cdiv(n > 0 ? n : 1, 256), 1024)), dim3(256), 0, st, n, key_acc,
                      u_acc, scal, flags, per_sig ? 1 : 0, split ? 1 : 0);
 }
+// Eager verifier (edc_vfy_begin_eager): the z of items [a, a + cnt) alone, as k_coef draws them
+// from the seed (z_i = words 4 (i & 3).. of ChaCha block i >> 2), into the short-scalar rows
+// 1 + i that the fold's R-only MSM reads. One lane per ChaCha block: the first and last blocks of
+// a range that starts or ends off a multiple of 4 store only their items inside it.
+__global__ void __launch_bounds__(256) k_z_range(seed8 seed, uint32_t a, uint32_t cnt, uint32_t* __restrict__ scal) {
+  const uint32_t b0 = a >> 2, nblk = ((a + cnt + 3) >> 2) - b0;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nblk) return;
+  uint32_t blk[16];
+  chacha20_block(seed.w, (uint64_t)(b0 + g), blk);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint32_t i = 4 * (b0 + g) + q;
+    if (i < a || i >= a + cnt) continue;
+    uint4* sp = reinterpret_cast<uint4*>(scal + (size_t)(1 + i) * 8);
+    sp[0] = make_uint4(blk[4 * q], blk[4 * q + 1], blk[4 * q + 2], blk[4 * q + 3]);
+    sp[1] = make_uint4(0, 0, 0, 0);
+  }
+}
+void launch_z_range(hipStream_t st, const uint32_t seed[8], uint32_t a, uint32_t cnt, uint32_t* scal) {
+  if (!cnt) return;
+  seed8 s;
+  for (int j = 0; j < 8; ++j) s.w[j] = seed[j];
+  const uint32_t nblk = ((a + cnt + 3) >> 2) - (a >> 2);
+  hipLaunchKernelGGL(k_z_range, dim3(cdiv(nblk, 256)), dim3(256), 0, st, s, a, cnt, scal);
+}
+
 size_t coef_part_words(size_t cap_n) {
   const size_t nwg = (cap_n + COEF_CHUNK - 1) / COEF_CHUNK;
   return ((nwg * COEF_SLOTS + 1) & ~(size_t)1) + nwg * COEF_SLOTS * PL * 2;

@@ -510,6 +510,41 @@ int edc_synchronize(edc_ctx* ctx);
  *   queue forms.
  * edc_vfy_last_split  1 if the last edc_verifier_verify / _verify_fallback on v ran the split
  *   plan, 0 if not; EDC_ERR_ARG before any verify and for NULL.
+ *
+ * Eager mode: the R terms are summed while the items arrive. z_i depends only on (z_seed, queue
+ * index i), so a seed committed when the block starts lets every queue call add [z_i]R_i of its
+ * items to a running point on the GPU; verify then runs the coefficients over all n items and an
+ * MSM over B, the keys and the short tail of R terms not folded yet, adds the running point and
+ * multiplies by 8. The group element is edc_batch_verify's with that seed: verdict and check8 are
+ * bit-identical, in every grouping mode, split or not, and whatever the fold granularity. The time
+ * from the last vote to the verdict no longer grows with the block; the queue calls cost more in
+ * total (many small MSMs instead of one large one).
+ * edc_vfy_begin_eager  v enters eager mode and commits this block's seed. Only while nothing is
+ *   queued (after create or edc_verifier_reset; EDC_ERR_ARG otherwise). z_seed NULL: the library
+ *   draws 32 bytes with getrandom(2); if that fails the call fails (EDC_ERR_HIP) and v stays as it
+ *   was, never a fixed seed. z_i for queue index i is what edc_batch_verify draws from that seed.
+ *   edc_verifier_reset leaves eager mode: begin again, with a fresh seed, for the next block.
+ * edc_verifier_verify(v, NULL, NULL, check8) is the eager verify. Passing z_seed or z in eager
+ *   mode is EDC_ERR_ARG (z is committed; caller-drawn z arrays are not available), and NULL / NULL
+ *   on a verifier that is not eager stays EDC_ERR_ARG.
+ * edc_verifier_verify_fallback(v, z_seed, ...) in eager mode runs the eager verify first (its
+ *   check8) and, if it fails, the grouped fallback with the caller's fresh z_seed on the retained
+ *   items: the per-item codes equal the non-eager call's.
+ * edc_vfy_set_fold  a queue call folds the items not folded yet once at least min_items of them
+ *   are pending (0: the library default, 131,072). Results never depend on it.
+ * edc_vfy_folded    *items = queued items whose R term is in the running point, *folds = folds
+ *   since the last reset (either may be NULL). EDC_ERR_ARG for a NULL verifier.
+ * edc_vfy_eager     1 in eager mode, 0 if not, EDC_ERR_ARG for NULL.
+ * Soundness. The batch equation needs z unpredictable to the signers when they fix their
+ *   signatures (src/batch.rs:149-217 draws it after the last queue). A seed committed before the
+ *   items arrive is just as unpredictable to them as long as it stays secret and is used for one
+ *   block: pass fresh OS randomness (or NULL) and never reuse, log or derive it from public data.
+ *   Nothing that depends on z leaves the library before verify. A verify that returns EDC_OK
+ *   reveals only the identity point: more items may be queued and verified again under the same
+ *   seed. A verify that returns EDC_INVALID_SIGNATURE reveals a z-dependent point (check8): from
+ *   then on the seed is spent, and queue and verify calls on v return EDC_ERR_ARG until
+ *   edc_verifier_reset. edc_verifier_verify_fallback is the exception: it draws its own z from
+ *   the caller's fresh seed.
  */
 typedef struct edc_verifier edc_verifier;
 edc_verifier* edc_verifier_create(edc_ctx* ctx, size_t capacity_hint);
@@ -527,6 +562,10 @@ int edc_verifier_reset(edc_verifier* v);
 int edc_vfy_queue_indexed(edc_verifier* v, size_t m, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
                           const uint64_t* msg_off, const uint8_t* k);
 int edc_vfy_last_split(const edc_verifier* v);
+int edc_vfy_begin_eager(edc_verifier* v, const uint8_t z_seed[32]);
+int edc_vfy_set_fold(edc_verifier* v, size_t min_items);
+int edc_vfy_folded(const edc_verifier* v, uint64_t* items, uint64_t* folds);
+int edc_vfy_eager(const edc_verifier* v);
 
 /*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):

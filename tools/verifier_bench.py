@@ -15,7 +15,11 @@ time also leaves the [2^128] rows and verify() runs with split coefficients, the
 index (edc_vfy_queue_indexed); edc_batch_verify_device with the cache loaded beside them. Per cycle:
 verify() alone, the mean host time of a queue call and the 16 queue calls until the device is idle.
 --lib PATH loads another build of libedc.so (A/B against an older build, which lacks the indexed
-entry and runs verify() unsplit)."""
+entry and runs verify() unsplit).
+--eager: the leg for the eager mode (edc_vfy_begin_eager) instead: per size the plain queue cycle,
+then the eager one at every fold granularity of --fold (a sweep: --fold 2048,8192,32768,131072),
+each with verify() alone, the 16 queue calls in total and the whole cycle. An older build given
+with --lib reports the plain cycle only."""
 import argparse
 import ctypes
 import json
@@ -125,6 +129,77 @@ def keycache_leg(a, pkg, eng, torch, dev):
     return lines
 
 
+def eager_leg(a, pkg, eng, torch, dev):
+    """Per size: the queue cycle (host memory, prehashed, 16 pieces) on a plain verifier, then in
+    eager mode (edc_vfy_begin_eager: the R terms are folded at queue time) at each fold granularity
+    of --fold (0 = the library default). Per cycle: verify() alone on an idle device, the 16 queue
+    calls until the device is idle, and the whole cycle (reset, begin, queue, verify)."""
+    lib, ctx = eng.lib, eng.ctx
+    zseed = bytes([0x33]) * 32
+    u8p, u64p = ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)
+    has_eager = hasattr(lib, "edc_vfy_begin_eager")
+    folds = [int(x) for x in a.fold.split(",")]
+    lines = []
+    for n in [int(x) for x in a.sizes.split(",")]:
+        vk, sig, msg, off = bench.make_workload(pkg, eng, torch, dev, n, 150, 120, 0)
+        torch.cuda.synchronize()
+        hvk, hsig, hmsg = vk.cpu().numpy(), sig.cpu().numpy(), msg.cpu().numpy()
+        hoff = off.cpu().numpy().astype("uint64")
+        hk = (ctypes.c_uint8 * (32 * n))()
+        at = lambda arr, byte: ctypes.cast(arr.ctypes.data + byte, u8p)       # noqa: E731
+        eng._check(lib.edc_challenge(ctx, n, at(hvk, 0), at(hsig, 0), at(hmsg, 0),
+                                     ctypes.cast(hoff.ctypes.data, u64p), hk))
+        hk_addr = ctypes.addressof(hk)
+        bounds = [n * p // PIECES for p in range(PIECES + 1)]
+        v = lib.edc_verifier_create(ctx, n)
+        assert v
+
+        def cycle(eager):
+            """(verify, 16 queue calls until idle, whole cycle) in ms"""
+            t0 = time.perf_counter()
+            eng._check(lib.edc_verifier_reset(v))
+            if eager:
+                eng._check(lib.edc_vfy_begin_eager(v, zseed))
+            tq = time.perf_counter()
+            for p in range(PIECES):
+                if bounds[p + 1] > bounds[p]:
+                    eng._check(lib.edc_verifier_queue_prehashed(v, bounds[p + 1] - bounds[p], at(hvk, 32 * bounds[p]),
+                                                                at(hsig, 64 * bounds[p]),
+                                                                ctypes.cast(hk_addr + 32 * bounds[p], u8p)))
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            rc = lib.edc_verifier_verify(v, None if eager else zseed, None, None)
+            t2 = time.perf_counter()
+            assert rc == 0, rc
+            return (t2 - t1) * 1e3, (t1 - tq) * 1e3, (t2 - t0) * 1e3
+
+        def measure(out, label, eager):
+            for _ in range(a.warmup):
+                cycle(eager)
+            rs = [cycle(eager) for _ in range(a.reps)]
+            out[f"verify_{label}_ms"] = round(statistics.median(r[0] for r in rs), 4)
+            out[f"verify_{label}_ms_min"] = round(min(r[0] for r in rs), 4)
+            out[f"queue_total_{label}_ms"] = round(statistics.median(r[1] for r in rs), 4)
+            out[f"cycle_{label}_ms"] = round(statistics.median(r[2] for r in rs), 4)
+
+        out = {"n": n, "eager_leg": True, "lib": os.path.basename(a.lib) if a.lib else "libedc.so", "validators": 150,
+               "pieces": PIECES, "reps": a.reps}
+        measure(out, "plain", False)
+        for f in folds if has_eager else []:
+            eng._check(lib.edc_vfy_set_fold(v, f))
+            label = f"eager_fold{f}" if f else "eager"
+            measure(out, label, True)
+            items, nfold = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            eng._check(lib.edc_vfy_folded(v, ctypes.byref(items), ctypes.byref(nfold)))
+            out[f"folded_{label}"] = [int(items.value), int(nfold.value)]
+        lib.edc_verifier_destroy(v)
+        line = json.dumps(out)
+        print(line, flush=True)
+        lines.append(line)
+        del vk, sig, msg, off
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -133,6 +208,8 @@ def main():
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--keycache", action="store_true", help="the registered-validator-set leg (see above)")
     ap.add_argument("--lib", default=None, help="another build of libedc.so to measure")
+    ap.add_argument("--eager", action="store_true", help="the eager-mode leg (plain and eager cycles side by side)")
+    ap.add_argument("--fold", default="0", help="--eager: fold granularities to measure, 0 = the library default")
     a = ap.parse_args()
     import torch
     dev = torch.device("cuda:0")
@@ -145,7 +222,9 @@ def main():
     lines = []
     if a.keycache:
         lines = keycache_leg(a, pkg, eng, torch, dev)
-    for n in [] if a.keycache else [int(x) for x in a.sizes.split(",")]:
+    elif a.eager:
+        lines = eager_leg(a, pkg, eng, torch, dev)
+    for n in [] if a.keycache or a.eager else [int(x) for x in a.sizes.split(",")]:
         vk, sig, msg, off = bench.make_workload(pkg, eng, torch, dev, n, 150, 120, 0)
         torch.cuda.synchronize()
         hvk, hsig, hmsg = vk.cpu().numpy(), sig.cpu().numpy(), msg.cpu().numpy()
