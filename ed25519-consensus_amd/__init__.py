@@ -58,6 +58,9 @@ ABI_SYMBOLS = [
     "edc_verifier_queue_device", "edc_verifier_size", "edc_verifier_verify", "edc_verifier_verify_fallback",
     "edc_verifier_reset", "edc_vfy_queue_indexed", "edc_vfy_last_split",
     "edc_vfy_begin_eager", "edc_vfy_set_fold", "edc_vfy_folded", "edc_vfy_eager",
+    "edc_sigcache_create", "edc_sigcache_clear", "edc_sigcache_advance", "edc_sigcache_stats",
+    "edc_sigcache_lookup_device", "edc_sigcache_batch_verify_device", "edc_sigcache_batch_verify",
+    "edc_sigcache_batch_verify_fallback_device", "edc_sigcache_verify_each",
 ]
 
 
@@ -236,6 +239,19 @@ def load_library(path=None):
             lib.edc_vfy_set_fold.argtypes = [c_vp, c_sz]
             lib.edc_vfy_folded.argtypes = [c_vp, c_u64p, c_u64p]
             lib.edc_vfy_eager.argtypes = [c_vp]
+        if hasattr(lib, "edc_sigcache_create"):              # absent from older A/B builds (tools/)
+            c_szp = ctypes.POINTER(c_sz)
+            lib.edc_sigcache_create.argtypes = [c_vp, c_sz, ctypes.c_int]
+            lib.edc_sigcache_clear.argtypes = [c_vp]
+            lib.edc_sigcache_advance.argtypes = [c_vp]
+            lib.edc_sigcache_stats.argtypes = [c_vp, c_u64p]
+            lib.edc_sigcache_lookup_device.argtypes = [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]
+            lib.edc_sigcache_batch_verify_device.argtypes = [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp, c_u8p, c_vp,
+                                                             c_szp]
+            lib.edc_sigcache_batch_verify.argtypes = [c_vp, c_sz, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_u8p, c_vp, c_szp]
+            lib.edc_sigcache_batch_verify_fallback_device.argtypes = [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp, c_u8p,
+                                                                      c_vp, ctypes.POINTER(ctypes.c_int), c_vp, c_szp]
+            lib.edc_sigcache_verify_each.argtypes = [c_vp, c_sz, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_vp, c_szp]
         if path is None:
             _lib = lib
         return lib
@@ -544,6 +560,88 @@ class Engine:
         with self._lock:
             self._check(self.lib.edc_sign(self.ctx, n, b"".join(seeds), len(seeds), idx, arena, offs, vk, sig))
         return [vk.raw[32 * i:32 * i + 32] for i in range(n)], [sig.raw[64 * i:64 * i + 64] for i in range(n)]
+
+    # ---- verified-signature cache (include/edc.h, edc_sigcache_*) ----
+    def sigcache_create(self, capacity, keep=0):
+        """A device table of `capacity` verified items (rounded up to a power of two), replacing any
+        existing one; capacity 0 frees it. keep: generations a record stays alive (0: default, 2)."""
+        with self._lock:
+            self._check(self.lib.edc_sigcache_create(self.ctx, int(capacity), int(keep)))
+
+    def sigcache_clear(self):
+        with self._lock:
+            self._check(self.lib.edc_sigcache_clear(self.ctx))
+
+    def sigcache_advance(self):
+        """Bump the table's generation (once per height)."""
+        with self._lock:
+            self._check(self.lib.edc_sigcache_advance(self.ctx))
+
+    def sigcache_stats(self):
+        out = (ctypes.c_uint64 * 6)()
+        self._check(self.lib.edc_sigcache_stats(self.ctx, out))
+        return dict(zip(("capacity", "generation", "hits", "misses", "inserted", "dropped"), (int(x) for x in out)))
+
+    def sigcache_lookup(self, n, d_vk, d_sig, d_k, d_hit):
+        """d_hit[i] = 1 iff item i is a live record (edc_sigcache_lookup_device; device pointers as
+        ints, d_hit n bytes). Changes neither the table nor the counters."""
+        with self._lock:
+            self._check(self.lib.edc_sigcache_lookup_device(self.ctx, n, d_vk, d_sig, d_k, d_hit))
+
+    @staticmethod
+    def _msgs_or_ks(n, msgs, ks):
+        if (msgs is None) == (ks is None):
+            raise ValueError("cached verification takes either msgs or ks")
+        if len(msgs if ks is None else ks) != n:
+            raise ValueError("lists of different lengths")
+        if ks is not None:
+            return None, None, b"".join(ks) or b"\0"
+        arena, offs = _arena(msgs)
+        return arena, offs, None
+
+    def batch_verify_cached(self, vks, sigs, msgs=None, ks=None, z_seed=None):
+        """Batch verification of the items not verified before on this engine
+        (edc_sigcache_batch_verify): (code, check8, n_miss). The misses, in queue order, are the
+        batch; when it passes they are inserted. z_seed None: fresh OS randomness (it must be
+        fresh and secret: include/edc.h, Soundness)."""
+        n = len(vks)
+        arena, offs, kb = self._msgs_or_ks(n, msgs, ks)
+        seed = secrets.token_bytes(32) if z_seed is None else _as_bytes(z_seed, 32)
+        check8 = ctypes.create_string_buffer(32)
+        miss = ctypes.c_size_t(0)
+        with self._lock:
+            rc = self.lib.edc_sigcache_batch_verify(self.ctx, n, b"".join(vks) or b"\0", b"".join(sigs) or b"\0",
+                                                    arena, offs, kb, seed, check8, ctypes.byref(miss))
+        self._check(rc)
+        return rc, check8.raw, miss.value
+
+    def batch_verify_cached_fallback(self, n, d_vk, d_sig, d_msg=None, d_msg_off=None, d_k=None, z_seed=None):
+        """edc_sigcache_batch_verify_fallback_device on device-resident items (pointers as ints; d_k
+        or the messages): (code, per-item Item::verify_single codes, n_invalid, check8, n_miss)."""
+        seed = secrets.token_bytes(32) if z_seed is None else _as_bytes(z_seed, 32)
+        check8 = ctypes.create_string_buffer(32)
+        v = ctypes.create_string_buffer(max(n, 1))
+        cnt = ctypes.c_int(0)
+        miss = ctypes.c_size_t(0)
+        with self._lock:
+            rc = self.lib.edc_sigcache_batch_verify_fallback_device(self.ctx, n, d_vk, d_sig, d_msg, d_msg_off, d_k,
+                                                                    seed, v, ctypes.byref(cnt), check8,
+                                                                    ctypes.byref(miss))
+        self._check(rc)
+        return rc, list(v.raw[:n]), cnt.value, check8.raw, miss.value
+
+    def verify_each_cached(self, vks, sigs, msgs=None, ks=None):
+        """Per-item verification of the items not verified before (edc_sigcache_verify_each), the
+        gossip-time feed of the table: (verdict codes, n_miss). Valid misses are inserted."""
+        n = len(vks)
+        arena, offs, kb = self._msgs_or_ks(n, msgs, ks)
+        out = ctypes.create_string_buffer(max(n, 1))
+        miss = ctypes.c_size_t(0)
+        with self._lock:
+            self._check(self.lib.edc_sigcache_verify_each(self.ctx, n, b"".join(vks) or b"\0",
+                                                          b"".join(sigs) or b"\0", arena, offs, kb, out,
+                                                          ctypes.byref(miss)))
+        return list(out.raw[:n]), miss.value
 
     def combine_records_device(self, stream, g, d_records, stride, d_out):
         """Enqueue the combine of g gathered 129-byte exchange records (device memory) on `stream`
@@ -890,6 +988,16 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             return eng.verify_prehashed_each([it.vk_bytes.to_bytes() for it in items],
                                              [it.sig.to_bytes() for it in items], [it.k for it in items])
 
+        @staticmethod
+        def verify_single_many_cached(items, engine=None):
+            """verify_single_many through the engine's verified-signature cache
+            (Engine.verify_each_cached): items verified before are not verified again, valid new
+            ones are remembered. Returns per-item verdict codes."""
+            eng = engine or default_engine()
+            batch.Item.hash_many(items, eng)
+            return eng.verify_each_cached([it.vk_bytes.to_bytes() for it in items],
+                                          [it.sig.to_bytes() for it in items], ks=[it.k for it in items])[0]
+
     class Verifier:
         """reference src/batch.rs:110-217. Items are kept in queue order; grouping by key
         bytes, hashing and the coalesced MSM run on the GPU inside verify()."""
@@ -946,6 +1054,35 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             code, _ = self.verify_detailed(rng)
             if code != EDC_OK:
                 raise InvalidSignature()
+
+        def verify_cached(self, rng=None):
+            """Verifier::verify through the engine's verified-signature cache
+            (Engine.batch_verify_cached): only the items not verified before on that engine are
+            verified, and remembered when their batch passes. Returns the number of misses, raises
+            InvalidSignature otherwise. rng: a 32-byte ChaCha20 seed or None (fresh OS randomness);
+            z drawn by a caller's RNG object cannot follow the miss list and is refused."""
+            if rng is None:
+                seed = None
+            elif isinstance(rng, (bytes, bytearray)) and len(rng) == 32:
+                seed = bytes(rng)
+            else:
+                raise ValueError("verify_cached takes a 32-byte seed or None, not caller-drawn z")
+            eng = self._engine or default_engine()
+            if any(k is None for k in self._ks):
+                if any(m is None for m in self._msgs):   # mixed queue: hash the rest in one launch
+                    need = [i for i, k in enumerate(self._ks) if k is None]
+                    ks = eng.challenge([self._vks[i] for i in need], [self._sigs[i] for i in need],
+                                       [self._msgs[i] for i in need])
+                    for i, k in zip(need, ks):
+                        self._ks[i] = k
+                    code, _, n_miss = eng.batch_verify_cached(self._vks, self._sigs, ks=self._ks, z_seed=seed)
+                else:
+                    code, _, n_miss = eng.batch_verify_cached(self._vks, self._sigs, msgs=self._msgs, z_seed=seed)
+            else:
+                code, _, n_miss = eng.batch_verify_cached(self._vks, self._sigs, ks=self._ks, z_seed=seed)
+            if code != EDC_OK:
+                raise InvalidSignature()
+            return n_miss
 
     class StreamVerifier:
         """reference src/batch.rs:110-217 with the reference's division of work: queue() does the

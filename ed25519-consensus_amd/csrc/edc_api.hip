@@ -18,6 +18,7 @@
 #include "edc_common.h"
 #include "edc_launch.h"
 #include "vfy_fold.h"
+#include "sigcache.h"
 
 using namespace edc;
 
@@ -190,6 +191,23 @@ struct edc_ctx {
   // [2^128] rows are only used by a verify that finds the generation they were built against
   uint64_t kc_gen = 0;
   int multi_union = 1;                  // edc_set_multi_union
+  // verified-signature cache (sigcache.h; edc_sigcache_*): the table, its generation, the
+  // per-call staging (hit flags, workgroup counts, miss index list, gathered misses, verdicts)
+  // and the counters; used on slot 0's stream only
+  unsigned long long* sc_hdr = nullptr;
+  uint4* sc_rec = nullptr;
+  size_t sc_cap = 0;                    // records (a power of two); 0 = no table
+  uint32_t sc_gen = 1, sc_keep = 2;
+  uint64_t sc_k0 = 0, sc_k1 = 0;        // table hash key, from `secret`
+  uint64_t sc_hits = 0, sc_misses = 0;
+  unsigned long long* sc_ctr = nullptr; // device: records written, inserts dropped
+  unsigned long long* sc_hctr = nullptr;   // pinned mirror (+ word 2: the miss count of the last lookup)
+  size_t sc_cap_n = 0;
+  uint8_t *sc_hit = nullptr, *sc_g = nullptr, *sc_verd = nullptr, *sc_mverd = nullptr;
+  uint32_t *sc_wg = nullptr, *sc_idx = nullptr;
+  SigCacheView sc() const {
+    return SigCacheView{sc_hdr, sc_rec, (uint32_t)(sc_cap - 1), sc_gen, sc_keep, sc_k0, sc_k1};
+  }
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // chunked synchronous host-buffer calls (run_host_chunked): a copy stream and one event per
   // chunk (+ the keys / offsets piece), created on first use
@@ -1394,6 +1412,8 @@ edc_ctx* edc_create(int device) {
     const uint64_t ks = splitmix64(ctx->secret ^ 0x6B657963616368ull);   // key-cache table hash key
     ctx->kc_s0 = (uint32_t)ks;
     ctx->kc_s1 = (uint32_t)(ks >> 32);
+    ctx->sc_k0 = splitmix64(ctx->secret ^ 0x7369676361636830ull);        // verified-signature table hash key
+    ctx->sc_k1 = splitmix64(ctx->secret ^ 0x7369676361636831ull);
   }
   (void)hipGetLastError();   // launch checks below must not see an earlier, unrelated failure
   bool ok = hipSetDevice(device) == hipSuccess && msm_init_device() == hipSuccess && init_slot(ctx, ctx->slot[0]) == 0 &&
@@ -1489,7 +1509,9 @@ void edc_destroy(edc_ctx* ctx) {
   if (ctx->hcs2) (void)hipStreamDestroy(ctx->hcs2);
   void* ptrs[] = {ctx->vk, ctx->sig, ctx->msg, ctx->zexp, ctx->off, ctx->kbuf, ctx->verdicts, ctx->vtab, ctx->aux,
                   ctx->btab, ctx->comb_in, ctx->fb_xpt, ctx->fb_xrg, ctx->fb_xscal, ctx->fb_rv, ctx->fb_idx,
-                  ctx->fb_g};
+                  ctx->fb_g, ctx->sc_hdr, ctx->sc_rec, ctx->sc_ctr, ctx->sc_hit, ctx->sc_g, ctx->sc_verd,
+                  ctx->sc_mverd, ctx->sc_wg, ctx->sc_idx};
+  if (ctx->sc_hctr) (void)hipHostFree(ctx->sc_hctr);
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete ctx;
@@ -2451,6 +2473,324 @@ int edc_synchronize(edc_ctx* ctx) {
   CK(hipSetDevice(ctx->device));
   for (Slot& s : ctx->slot)
     if (s.st) CK(hipStreamSynchronize(s.st));
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- verified-signature cache
+// sigcache.h: a cached call looks every item up, compacts the misses (queue order) into one
+// contiguous batch and hands that batch to the existing entries' own paths (run_batch_sync,
+// batch_with_fallback, the per-item kernels), so verdicts and check8 are those entries' on the miss
+// list by construction. The miss count needs one 4-byte device-to-host copy and a stream
+// synchronization before the MSM can be planned.
+static void free_sigcache(edc_ctx* ctx) {
+  if (ctx->sc_hdr) (void)hipFree(ctx->sc_hdr);
+  if (ctx->sc_rec) (void)hipFree(ctx->sc_rec);
+  ctx->sc_hdr = nullptr;
+  ctx->sc_rec = nullptr;
+  ctx->sc_cap = 0;
+}
+
+// preconditions of every cached entry: a table, and slot 0 (their stream and workspace) idle
+static int sc_ready(edc_ctx* ctx) {
+  if (!ctx->sc_cap) { ctx->err = "no signature cache on this context (edc_sigcache_create)"; return EDC_ERR_ARG; }
+  if (ctx->slot[0].pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+static int ensure_sc(edc_ctx* ctx, size_t n) {
+  if (n <= ctx->sc_cap_n && ctx->sc_hit) return 0;
+  CK(hipStreamSynchronize(ctx->st()));
+  void* ptrs[] = {ctx->sc_hit, ctx->sc_g, ctx->sc_verd, ctx->sc_mverd, ctx->sc_wg, ctx->sc_idx};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  ctx->sc_hit = ctx->sc_g = ctx->sc_verd = ctx->sc_mverd = nullptr;
+  ctx->sc_wg = ctx->sc_idx = nullptr;
+  ctx->sc_cap_n = 0;
+  const size_t cap = n < 1024 ? 1024 : n + n / 8;
+  CK(dalloc(&ctx->sc_hit, cap));
+  CK(dalloc(&ctx->sc_g, cap * 128));
+  CK(dalloc(&ctx->sc_verd, cap));
+  CK(dalloc(&ctx->sc_mverd, cap));
+  CK(dalloc(&ctx->sc_wg, cap / SC_BLOCK + 2));   // one count per workgroup + the total
+  CK(dalloc(&ctx->sc_idx, cap));
+  ctx->sc_cap_n = cap;
+  return 0;
+}
+
+// The misses of one cached call, in queue order: a contiguous batch (vk, sig, k) and, unless every
+// item missed (idx null: the batch is the caller's arrays), their queue positions. o_*: the
+// caller's arrays, which idx indexes.
+struct ScMiss {
+  size_t n = 0;
+  const uint32_t* idx = nullptr;
+  const uint8_t *vk = nullptr, *sig = nullptr;
+  const uint32_t* k = nullptr;
+  const uint8_t *o_vk = nullptr, *o_sig = nullptr;
+  const uint32_t* o_k = nullptr;
+};
+
+static int sc_partition(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint32_t* d_k,
+                        ScMiss* M) {
+  *M = ScMiss{};
+  M->vk = M->o_vk = d_vk;
+  M->sig = M->o_sig = d_sig;
+  M->k = M->o_k = d_k;
+  if (!n) return 0;
+  int rc = ensure_sc(ctx, n);
+  if (rc) return rc;
+  hipStream_t st = ctx->st();
+  const uint32_t N = (uint32_t)n, nwg = (N + SC_BLOCK - 1) / SC_BLOCK;
+  launch_sc_lookup(st, ctx->sc(), N, d_vk, d_sig, d_k, ctx->sc_hit, ctx->sc_wg);
+  launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
+  CK(hipGetLastError());
+  ctx->sc_hctr[2] = 0;
+  CK(hipMemcpyAsync(&ctx->sc_hctr[2], ctx->sc_wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  M->n = (size_t)ctx->sc_hctr[2];
+  if (M->n > n) { ctx->err = "signature cache: miss count out of range"; return EDC_ERR_HIP; }
+  ctx->sc_hits += n - M->n;
+  ctx->sc_misses += M->n;
+  if (M->n == 0 || M->n == n) return 0;   // nothing to verify / the caller's arrays are the batch
+  uint8_t* g_vk = ctx->sc_g;
+  uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
+  uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->sc_cap_n * 64);
+  launch_sc_compact(st, N, ctx->sc_hit, ctx->sc_wg, d_vk, d_sig, d_k, ctx->sc_idx, g_vk, g_sig, g_k);
+  CK(hipGetLastError());
+  M->idx = ctx->sc_idx;
+  M->vk = g_vk;
+  M->sig = g_sig;
+  M->k = g_k;
+  return 0;
+}
+
+// insert the misses whose d_mverd[j] is 0 (null: all), refresh the counters' host mirror
+static int sc_insert(edc_ctx* ctx, const ScMiss& M, const uint8_t* d_mverd) {
+  if (!M.n) return 0;
+  hipStream_t st = ctx->st();
+  launch_sc_insert(st, ctx->sc(), (uint32_t)M.n, M.idx, M.o_vk, M.o_sig, M.o_k, d_mverd, ctx->sc_ctr);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(ctx->sc_hctr, ctx->sc_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// per-item codes of the misses (device, M.n bytes) -> verdicts (host, n bytes); hits are EDC_OK
+static int sc_verdicts_out(edc_ctx* ctx, size_t n, const ScMiss& M, const uint8_t* d_mverd, uint8_t* verdicts) {
+  hipStream_t st = ctx->st();
+  if (!M.n) {
+    memset(verdicts, 0, n);
+  } else if (!M.idx) {
+    CK(hipMemcpyAsync(verdicts, d_mverd, n, hipMemcpyDeviceToHost, st));
+  } else {
+    CK(hipMemsetAsync(ctx->sc_verd, 0, n, st));
+    launch_sc_scatter(st, (uint32_t)M.n, M.idx, d_mverd, ctx->sc_verd);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(verdicts, ctx->sc_verd, n, hipMemcpyDeviceToHost, st));
+  }
+  return 0;
+}
+
+// cached batch on device-resident items; verdicts null: the plain entry, else the fallback entry
+static int sc_batch(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
+                    const uint64_t* d_off, const uint8_t* d_k, const uint8_t* z_seed, uint8_t* verdicts, int* n_invalid,
+                    uint8_t check8[32], size_t* n_miss) {
+  int rc = sc_ready(ctx);
+  if (rc) return rc;
+  if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
+  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)))) {
+    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
+    return EDC_ERR_ARG;
+  }
+  if (n_invalid) *n_invalid = 0;
+  const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
+  if (n && !k) {            // Item::from for every item: the record, and so the lookup, needs k
+    if ((rc = ensure_n(ctx, n))) return rc;
+    launch_challenge(ctx->st(), (uint32_t)n, d_vk, d_sig, d_msg, d_off, ctx->kbuf);
+    CK(hipGetLastError());
+    k = ctx->kbuf;
+  }
+  ScMiss M;
+  if ((rc = sc_partition(ctx, n, d_vk, d_sig, k, &M))) return rc;
+  if (n_miss) *n_miss = M.n;
+  // an empty miss list still runs the n = 0 batch, whose k is never read
+  const uint32_t* mk = M.n ? M.k : reinterpret_cast<const uint32_t*>(ctx->sc_hdr);
+  if (!verdicts) {
+    rc = run_batch_sync(ctx, M.n, M.vk, M.sig, nullptr, nullptr, z_seed, 0, nullptr, check8, nullptr, nullptr, mk);
+    if (rc != EDC_OK) return rc;     // a failed batch inserts nothing
+    return (rc = sc_insert(ctx, M, nullptr)) ? rc : EDC_OK;
+  }
+  std::vector<uint8_t> mv(M.n ? M.n : 1);
+  const int code = batch_with_fallback(ctx, M.n, M.vk, M.sig, nullptr, nullptr, mk, z_seed, mv.data(), n_invalid, check8);
+  if (code < 0) return code;
+  if (M.n) CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), M.n, hipMemcpyHostToDevice, ctx->st()));
+  if ((rc = sc_verdicts_out(ctx, n, M, ctx->sc_mverd, verdicts))) return rc;
+  if ((rc = sc_insert(ctx, M, ctx->sc_mverd))) return rc;     // exactly the misses whose code is EDC_OK
+  CK(hipStreamSynchronize(ctx->st()));
+  return code;
+}
+
+extern "C" {
+
+int edc_sigcache_create(edc_ctx* ctx, size_t capacity, int keep) {
+  if (!ctx || keep < 0) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  for (Slot& s : ctx->slot)
+    if (s.pending) { ctx->err = "signature cache change with a batch in flight"; return EDC_ERR_ARG; }
+  int rc = sync_all(ctx);
+  if (rc) return rc;
+  free_sigcache(ctx);
+  if (!capacity) return 0;
+  if (capacity > (1ull << 30)) { ctx->err = "signature cache capacity above 2^30 records"; return EDC_ERR_ARG; }
+  const size_t cap = next_pow2(capacity < SC_WINDOW ? SC_WINDOW : capacity);
+  if (dalloc(&ctx->sc_hdr, cap) != hipSuccess || dalloc(&ctx->sc_rec, cap * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    free_sigcache(ctx);
+    ctx->err = "signature cache: out of device memory";
+    return EDC_ERR_NOMEM;
+  }
+  if (!ctx->sc_ctr) CK(dalloc(&ctx->sc_ctr, 2));
+  if (!ctx->sc_hctr) CK(hipHostMalloc((void**)&ctx->sc_hctr, 3 * sizeof(unsigned long long)));
+  CK(hipMemsetAsync(ctx->sc_hdr, 0, cap * sizeof(unsigned long long), ctx->st()));
+  CK(hipMemsetAsync(ctx->sc_ctr, 0, 2 * sizeof(unsigned long long), ctx->st()));
+  CK(hipStreamSynchronize(ctx->st()));
+  ctx->sc_hctr[0] = ctx->sc_hctr[1] = ctx->sc_hctr[2] = 0;
+  ctx->sc_cap = cap;
+  ctx->sc_gen = 1;
+  ctx->sc_keep = keep ? (uint32_t)keep : 2u;
+  ctx->sc_hits = ctx->sc_misses = 0;
+  return 0;
+}
+
+int edc_sigcache_clear(edc_ctx* ctx) {
+  if (!ctx) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  int rc = sc_ready(ctx);
+  if (rc) return rc;
+  CK(hipMemsetAsync(ctx->sc_hdr, 0, ctx->sc_cap * sizeof(unsigned long long), ctx->st()));
+  CK(hipStreamSynchronize(ctx->st()));
+  return 0;
+}
+
+int edc_sigcache_advance(edc_ctx* ctx) {
+  if (!ctx) return EDC_ERR_ARG;
+  if (ctx->sc_gen == 0xFFFFFFFFu) {     // the generation would wrap: start over with an empty table
+    int rc = edc_sigcache_clear(ctx);
+    if (rc) return rc;
+    ctx->sc_gen = 1;
+    return 0;
+  }
+  int rc = sc_ready(ctx);
+  if (rc) return rc;
+  ctx->sc_gen++;
+  return 0;
+}
+
+int edc_sigcache_stats(const edc_ctx* ctx, uint64_t out[6]) {
+  if (!ctx || !out || !ctx->sc_cap) return EDC_ERR_ARG;
+  out[0] = ctx->sc_cap;
+  out[1] = ctx->sc_gen;
+  out[2] = ctx->sc_hits;
+  out[3] = ctx->sc_misses;
+  out[4] = ctx->sc_hctr[0];
+  out[5] = ctx->sc_hctr[1];
+  return 0;
+}
+
+int edc_sigcache_lookup_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_k,
+                               uint8_t* d_hit) {
+  if (!ctx || (n && (!d_vk || !d_sig || !d_k || !d_hit))) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  int rc = sc_ready(ctx);
+  if (rc) return rc;
+  if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
+  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || !aligned16(d_k))) {
+    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
+    return EDC_ERR_ARG;
+  }
+  launch_sc_lookup(ctx->st(), ctx->sc(), (uint32_t)n, d_vk, d_sig, reinterpret_cast<const uint32_t*>(d_k), d_hit,
+                   nullptr);
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(ctx->st()));
+  return 0;
+}
+
+int edc_sigcache_batch_verify_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
+                                     const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                                     const uint8_t z_seed[32], uint8_t check8[32], size_t* n_miss) {
+  if (!ctx || !z_seed || (n && (!d_vk || !d_sig || (!d_k && !d_msg_off)))) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  return sc_batch(ctx, n, d_vk, d_sig, d_msg, d_msg_off, d_k, z_seed, nullptr, nullptr, check8, n_miss);
+}
+
+int edc_sigcache_batch_verify_fallback_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
+                                              const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                                              const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
+                                              uint8_t check8[32], size_t* n_miss) {
+  if (!ctx || !z_seed || !verdicts || (n && (!d_vk || !d_sig || (!d_k && !d_msg_off)))) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  return sc_batch(ctx, n, d_vk, d_sig, d_msg, d_msg_off, d_k, z_seed, verdicts, n_invalid, check8, n_miss);
+}
+
+// host items into the context's staging buffers (slot 0's stream): keys, signatures and either
+// the message arena or the caller's k (into kbuf)
+static int sc_upload(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                     const uint64_t* msg_off, const uint8_t* k) {
+  if (!k) return upload(ctx, n, vk, sig, msg, msg_off);
+  int rc = init_slot(ctx, ctx->slot[0]);
+  if (rc) return rc;
+  if ((rc = ensure_n(ctx, n)) || !n) return rc;
+  hipStream_t st = ctx->st();
+  CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+int edc_sigcache_batch_verify(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                              const uint64_t* msg_off, const uint8_t* k, const uint8_t z_seed[32], uint8_t check8[32],
+                              size_t* n_miss) {
+  if (!ctx || !z_seed || (k != nullptr) == (msg_off != nullptr) || (n && (!vk || !sig))) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  int rc = sc_ready(ctx);
+  if (rc) return rc;
+  if ((rc = sc_upload(ctx, n, vk, sig, msg, msg_off, k))) return rc;
+  return sc_batch(ctx, n, ctx->vk, ctx->sig, ctx->msg, k ? nullptr : ctx->off,
+                  k ? reinterpret_cast<const uint8_t*>(ctx->kbuf) : nullptr, z_seed, nullptr, nullptr, check8, n_miss);
+}
+
+int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                             const uint64_t* msg_off, const uint8_t* k, uint8_t* verdicts, size_t* n_miss) {
+  if (!ctx || (k != nullptr) == (msg_off != nullptr) || (n && (!vk || !sig || !verdicts))) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  int rc = sc_ready(ctx);
+  if (rc) return rc;
+  // a hit is byte-identical to an inserted record, whose k was canonical: checking every k is
+  // checking the misses' (Scalar::from_hash never yields k >= l)
+  for (size_t i = 0; k && i < n; ++i) {
+    uint32_t w[8];
+    memcpy(w, k + 32 * i, 32);
+    if (!sc_is_canonical(w)) { ctx->err = "prehashed k is not a canonical scalar"; return EDC_ERR_ARG; }
+  }
+  if ((rc = sc_upload(ctx, n, vk, sig, msg, msg_off, k))) return rc;
+  hipStream_t st = ctx->st();
+  if (n && !k) {
+    launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
+    CK(hipGetLastError());
+  }
+  ScMiss M;
+  if ((rc = sc_partition(ctx, n, ctx->vk, ctx->sig, ctx->kbuf, &M))) return rc;
+  if (n_miss) *n_miss = M.n;
+  if (M.n <= kQuadVerifyMax)
+    launch_verify_quad(st, (uint32_t)M.n, M.vk, M.sig, M.k, ctx->btab, ctx->verdicts, ctx->kc(), ctx->bcomb);
+  else
+    launch_verify_single(st, (uint32_t)M.n, M.vk, M.sig, M.k, ctx->btab, ctx->vtab, ctx->verdicts, ctx->kc(),
+                         ctx->bcomb);
+  CK(hipGetLastError());
+  if ((rc = sc_verdicts_out(ctx, n, M, ctx->verdicts, verdicts))) return rc;
+  if ((rc = sc_insert(ctx, M, ctx->verdicts))) return rc;
+  CK(hipStreamSynchronize(st));
   return 0;
 }
 

@@ -568,6 +568,90 @@ int edc_vfy_folded(const edc_verifier* v, uint64_t* items, uint64_t* folds);
 int edc_vfy_eager(const edc_verifier* v);
 
 /*
+ * Verified-signature cache: skip the items that already verified on this context. A consensus
+ * node verifies the same vote several times: once when it arrives by gossip
+ * (VerificationKey::verify, src/verification_key.rs:225-258, or Item::verify_single,
+ * src/batch.rs:104-107), again inside the block's commit (Verifier::verify, src/batch.rs:149-217),
+ * again as the next block's last-commit and again in block sync. Under ZIP215 batch and single
+ * verification agree and the verdict is a pure function of (vk_bytes, sig, k), so a byte-identical
+ * item that verified before verifies again. The reference keeps no such table; nothing of its API
+ * changes meaning.
+ *
+ * The table lives in this GPU's memory, one per context: open addressing with a bounded probe
+ * window (32 slots), hashed under a key derived from the context's secret so that items chosen
+ * by the network cannot be aimed at one window. A slot is an 8-byte header (fingerprint and the
+ * generation of the insert; 0 = never used) and the 128-byte record vk || sig || k, k the
+ * canonical challenge H(R || A || M) mod l: it binds the message, so a different message is a
+ * different record. A hit is a live header AND 128 equal bytes, never a fingerprint alone. An
+ * insert that finds no free or expired slot in its window is dropped and counted; it never evicts
+ * a live record. Ageing is by generation: edc_sigcache_advance (once per height) bumps the table's
+ * generation, and a record inserted more than `keep` generations ago is dead: lookups do not
+ * return it and inserts reuse its slot.
+ *
+ * Semantics of the cached entries. The items that miss, in queue order, form the batch that is
+ * verified: miss j (0-based among the misses) draws z_j at index j of z_seed's stream, so verdict
+ * and check8 are bit-identical to edc_batch_verify_prehashed_device on the miss list with
+ * z_base = 0; no miss returns what that entry returns for n = 0. *n_miss (nullable) receives the
+ * number of misses. They run on slot 0 (refused while submitted batches are in flight, as the
+ * other synchronous calls), and return EDC_ERR_ARG while the context has no table. A prehashed
+ * k >= l in an item that misses is EDC_ERR_ARG with nothing inserted.
+ *
+ * Soundness. A hit means that a byte-identical (vk, sig, k) verified earlier on this context,
+ *   either one by one or inside a batch whose equation held: it carries the probability that
+ *   batch verification itself gives, no more. z_seed must therefore be fresh and secret for every
+ *   call: with a predictable seed, crafted items that cancel inside one batch would be planted as
+ *   records and accepted from then on, although they would not verify on their own. In the
+ *   prehashed forms the caller vouches for k, as in every prehashed entry: a record is only as
+ *   good as the k it was inserted with. The table is per context and never shared: what one
+ *   context verified says nothing to another.
+ *
+ * edc_sigcache_create  a table of `capacity` records (rounded up to a power of two, at least 32;
+ *   136 bytes of device memory each), replacing any existing table; capacity 0 only frees it.
+ *   keep 0 means the default, 2. Refused while batches are in flight. EDC_ERR_NOMEM if the device
+ *   cannot hold it (the context then has no table).
+ * edc_sigcache_clear   empties the table (generation and counters stay).
+ * edc_sigcache_advance bumps the generation (a node calls it once per height).
+ * edc_sigcache_stats   out = {capacity, generation, hits, misses, inserted, dropped}: items the
+ *   cached verify entries found / did not find, records written, inserts dropped for a full window.
+ * edc_sigcache_lookup_device  d_hit[i] = 1 iff item i is a live record (device arrays, 16-byte
+ *   aligned vk / sig / k; d_hit n bytes); changes neither the table nor the counters.
+ * edc_sigcache_batch_verify_device  Verifier::queue x n + Verifier::verify(rng) (reference
+ *   src/batch.rs:127-217) over the items not verified before. d_k nullable: when given, the
+ *   messages are not read (d_msg / d_msg_off may be NULL); otherwise k is hashed for every item
+ *   first. When the miss batch passes, every miss is inserted; when it fails, nothing is.
+ * edc_sigcache_batch_verify  the host-buffer form (src/batch.rs:127-217): exactly one of
+ *   (msg, msg_off) and k.
+ * edc_sigcache_batch_verify_fallback_device  the batch and, if it fails, the grouped fallback of
+ *   edc_batch_verify_fallback_device on the miss list (src/batch.rs:127-217, :104-107): verdicts
+ *   (host, n bytes) receive Item::verify_single's code for every item, hits EDC_OK; *n_invalid
+ *   (nullable) their count. Exactly the misses whose code is EDC_OK are inserted. z_seed as
+ *   edc_find_invalid_device.
+ * edc_sigcache_verify_each  Item::verify_single (src/batch.rs:104-107) / VerificationKey::verify
+ *   (src/verification_key.rs:225-258) for the misses only, with the per-item kernels of
+ *   edc_verify_each; host buffers, exactly one of (msg, msg_off) and k. verdicts[i] as
+ *   edc_verify_each (hits EDC_OK); the misses that are EDC_OK are inserted. This is the
+ *   gossip-time feed of the table.
+ */
+int edc_sigcache_create(edc_ctx* ctx, size_t capacity, int keep);
+int edc_sigcache_clear(edc_ctx* ctx);
+int edc_sigcache_advance(edc_ctx* ctx);
+int edc_sigcache_stats(const edc_ctx* ctx, uint64_t out[6]);
+int edc_sigcache_lookup_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_k,
+                               uint8_t* d_hit);
+int edc_sigcache_batch_verify_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
+                                     const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                                     const uint8_t z_seed[32], uint8_t check8[32], size_t* n_miss);
+int edc_sigcache_batch_verify(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                              const uint64_t* msg_off, const uint8_t* k, const uint8_t z_seed[32], uint8_t check8[32],
+                              size_t* n_miss);
+int edc_sigcache_batch_verify_fallback_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
+                                              const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                                              const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
+                                              uint8_t check8[32], size_t* n_miss);
+int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                             const uint64_t* msg_off, const uint8_t* k, uint8_t* verdicts, size_t* n_miss);
+
+/*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
  * one batch::Verifier::verify (reference src/batch.rs:149-217) split into contiguous shards, one
  * per listed device (a device may be listed more than once: several contexts on one GPU). Shard g
