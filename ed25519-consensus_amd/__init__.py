@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "edc_verifier_queue_device", "edc_verifier_size", "edc_verifier_verify", "edc_verifier_verify_fallback",
     "edc_verifier_reset", "edc_vfy_queue_indexed", "edc_vfy_last_split",
     "edc_vfy_begin_eager", "edc_vfy_set_fold", "edc_vfy_folded", "edc_vfy_eager",
+    "edc_vfy_set_cached", "edc_vfy_cached", "edc_vfy_cache_counts", "edc_vfy_verify_fallback_offered",
     "edc_sigcache_create", "edc_sigcache_clear", "edc_sigcache_advance", "edc_sigcache_stats",
     "edc_sigcache_lookup_device", "edc_sigcache_batch_verify_device", "edc_sigcache_batch_verify",
     "edc_sigcache_batch_verify_fallback_device", "edc_sigcache_verify_each",
@@ -239,6 +240,11 @@ def load_library(path=None):
             lib.edc_vfy_set_fold.argtypes = [c_vp, c_sz]
             lib.edc_vfy_folded.argtypes = [c_vp, c_u64p, c_u64p]
             lib.edc_vfy_eager.argtypes = [c_vp]
+        if hasattr(lib, "edc_vfy_set_cached"):               # absent from older A/B builds (tools/)
+            lib.edc_vfy_set_cached.argtypes = [c_vp, ctypes.c_int]
+            lib.edc_vfy_cached.argtypes = [c_vp]
+            lib.edc_vfy_cache_counts.argtypes = [c_vp, c_u64p, c_u64p]
+            lib.edc_vfy_verify_fallback_offered.argtypes = [c_vp, c_u8p, c_vp, ctypes.POINTER(ctypes.c_int), c_vp]
         if hasattr(lib, "edc_sigcache_create"):              # absent from older A/B builds (tools/)
             c_szp = ctypes.POINTER(c_sz)
             lib.edc_sigcache_create.argtypes = [c_vp, c_sz, ctypes.c_int]
@@ -1092,9 +1098,13 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         The queue survives verify(); reset() starts the next block with the same allocations.
         eager=True (or begin_eager()) commits the block's z seed up front, so that queue calls also
         sum the [z_i]R_i terms on the GPU and verify() runs an MSM over B, the keys and the short
-        unfolded tail only (edc_vfy_begin_eager; soundness in include/edc.h)."""
+        unfolded tail only (edc_vfy_begin_eager; soundness in include/edc.h).
+        cached=True (or set_cached()) makes queue calls skip the items the engine's
+        verified-signature table already vouches for (Engine.sigcache_create): only the misses
+        are retained and verified, and what verify() proves valid is remembered
+        (edc_vfy_set_cached; soundness in include/edc.h)."""
 
-        def __init__(self, engine=None, capacity=0, eager=False):
+        def __init__(self, engine=None, capacity=0, eager=False, cached=False):
             self._engine = engine or default_engine()
             self._always_eager = bool(eager)
             self._v = self._engine.lib.edc_verifier_create(self._engine.ctx, int(capacity))
@@ -1102,12 +1112,34 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
                 raise EngineError("edc_verifier_create failed: "
                                   + self._engine.lib.edc_last_error(self._engine.ctx).decode())
             self._engine._verifiers.add(self)
+            if cached:
+                self.set_cached(True)
             if eager:
                 self.begin_eager()
 
         @classmethod
-        def new(cls, engine=None, capacity=0, eager=False):
-            return cls(engine, capacity, eager)
+        def new(cls, engine=None, capacity=0, eager=False, cached=False):
+            return cls(engine, capacity, eager, cached)
+
+        def set_cached(self, on=True):
+            """Switch cached mode. Only while nothing is queued; the mode survives reset()."""
+            eng = self._engine
+            with eng._lock:
+                rc = eng.lib.edc_vfy_set_cached(self._handle(), 1 if on else 0)
+            eng._check(rc)
+
+        @property
+        def cached(self):
+            return self._engine.lib.edc_vfy_cached(self._handle()) == 1
+
+        @property
+        def cache_counts(self):
+            """(items offered to queue calls since the last reset, how many were skipped as hits);
+            batch_size is their difference."""
+            offered, hits = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            eng = self._engine
+            eng._check(eng.lib.edc_vfy_cache_counts(self._handle(), ctypes.byref(offered), ctypes.byref(hits)))
+            return int(offered.value), int(hits.value)
 
         def begin_eager(self, seed=None):
             """Enter eager mode for this block with a committed 32-byte z seed (None: fresh OS
@@ -1266,6 +1298,20 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             check8 = ctypes.create_string_buffer(32)
             with eng._lock:
                 rc = eng.lib.edc_verifier_verify_fallback(v, bytes(z_seed), verdicts, ctypes.byref(cnt), check8)
+            eng._check(rc)
+            return rc, list(verdicts.raw[:n]), check8.raw
+
+        def verify_with_fallback_offered(self, z_seed):
+            """verify_with_fallback with the codes in the order the items were offered to queue
+            calls (edc_vfy_verify_fallback_offered): (code, codes over the offered items, check8).
+            A hit of the table gets 0, a retained item its Item::verify_single code."""
+            eng, v = self._engine, self._handle()
+            n = self.cache_counts[0] if self.cached else self.batch_size
+            verdicts = ctypes.create_string_buffer(max(n, 1))
+            cnt = ctypes.c_int(0)
+            check8 = ctypes.create_string_buffer(32)
+            with eng._lock:
+                rc = eng.lib.edc_vfy_verify_fallback_offered(v, bytes(z_seed), verdicts, ctypes.byref(cnt), check8)
             eng._check(rc)
             return rc, list(verdicts.raw[:n]), check8.raw
 

@@ -18,6 +18,7 @@
 #include "edc_common.h"
 #include "edc_launch.h"
 #include "vfy_fold.h"
+#include "vfy_cached.h"
 #include "sigcache.h"
 
 using namespace edc;
@@ -193,7 +194,8 @@ struct edc_ctx {
   int multi_union = 1;                  // edc_set_multi_union
   // verified-signature cache (sigcache.h; edc_sigcache_*): the table, its generation, the
   // per-call staging (hit flags, workgroup counts, miss index list, gathered misses, verdicts)
-  // and the counters; used on slot 0's stream only
+  // and the counters. The one-call entries use it on slot 0's stream; cached verifiers
+  // (edc_vfy_set_cached) look up and insert on their own streams, see sc_ev
   unsigned long long* sc_hdr = nullptr;
   uint4* sc_rec = nullptr;
   size_t sc_cap = 0;                    // records (a power of two); 0 = no table
@@ -205,6 +207,11 @@ struct edc_ctx {
   size_t sc_cap_n = 0;
   uint8_t *sc_hit = nullptr, *sc_g = nullptr, *sc_verd = nullptr, *sc_mverd = nullptr;
   uint32_t *sc_wg = nullptr, *sc_idx = nullptr;
+  // recorded after every deferred insert of a cached verifier (which returns without waiting for
+  // it): every other access to the table first orders itself after it, so that lookup and insert
+  // never run together across streams either. sc_ev_set: it has been recorded at least once
+  hipEvent_t sc_ev = nullptr;
+  bool sc_ev_set = false;
   SigCacheView sc() const {
     return SigCacheView{sc_hdr, sc_rec, (uint32_t)(sc_cap - 1), sc_gen, sc_keep, sc_k0, sc_k1};
   }
@@ -260,6 +267,22 @@ struct edc_verifier {
   FoldState fold;
   uint8_t eager_seed[32] = {};
   uint32_t* run = nullptr;
+  // cached mode (edc_vfy_set_cached): a queue call stages its range (st_*), looks it up in the
+  // context's verified-signature table and appends only the misses; origin[i] = offered position
+  // of retained item i. hit / wg: the range's lookup flags and workgroup miss counts (+ total);
+  // h_cnt: pinned word the miss count comes back in; ev_cnt: after that copy; ev_gather: after the
+  // range's gather, which is the last reader of the staging area; verd / offv: per-item codes of a
+  // fallback on the device (retained order, offered order)
+  CachedState cached;
+  uint32_t* origin = nullptr;
+  uint8_t *st_vk = nullptr, *st_sig = nullptr, *hit = nullptr;
+  uint32_t *st_k = nullptr, *wg = nullptr;
+  size_t st_cap = 0;
+  uint32_t* h_cnt = nullptr;
+  hipEvent_t ev_cnt = nullptr, ev_gather = nullptr;
+  bool gather_pending = false;
+  uint8_t *verd = nullptr, *offv = nullptr;
+  size_t verd_cap = 0, offv_cap = 0;
 };
 
 // A failed HIP call also leaves the thread's last-error state set; it is cleared here, so that a
@@ -1512,6 +1535,7 @@ void edc_destroy(edc_ctx* ctx) {
                   ctx->fb_g, ctx->sc_hdr, ctx->sc_rec, ctx->sc_ctr, ctx->sc_hit, ctx->sc_g, ctx->sc_verd,
                   ctx->sc_mverd, ctx->sc_wg, ctx->sc_idx};
   if (ctx->sc_hctr) (void)hipHostFree(ctx->sc_hctr);
+  if (ctx->sc_ev) (void)hipEventDestroy(ctx->sc_ev);
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete ctx;
@@ -2499,6 +2523,18 @@ static int sc_ready(edc_ctx* ctx) {
   return 0;
 }
 
+// Ordering against the deferred inserts of cached verifiers (edc_ctx::sc_ev): work enqueued on st
+// after this call starts once the last such insert has run ...
+static int sc_order_after_inserts(edc_ctx* ctx, hipStream_t st) {
+  if (ctx->sc_ev_set) CK(hipStreamWaitEvent(st, ctx->sc_ev, 0));
+  return 0;
+}
+
+// ... and the host-side form, for the entries that change or read the table's state from the host
+static hipError_t sc_wait_inserts(const edc_ctx* ctx) {
+  return ctx->sc_ev_set ? hipEventSynchronize(ctx->sc_ev) : hipSuccess;
+}
+
 static int ensure_sc(edc_ctx* ctx, size_t n) {
   if (n <= ctx->sc_cap_n && ctx->sc_hit) return 0;
   CK(hipStreamSynchronize(ctx->st()));
@@ -2541,6 +2577,7 @@ static int sc_partition(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8
   int rc = ensure_sc(ctx, n);
   if (rc) return rc;
   hipStream_t st = ctx->st();
+  if ((rc = sc_order_after_inserts(ctx, st))) return rc;
   const uint32_t N = (uint32_t)n, nwg = (N + SC_BLOCK - 1) / SC_BLOCK;
   launch_sc_lookup(st, ctx->sc(), N, d_vk, d_sig, d_k, ctx->sc_hit, ctx->sc_wg);
   launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
@@ -2640,6 +2677,7 @@ int edc_sigcache_create(edc_ctx* ctx, size_t capacity, int keep) {
     if (s.pending) { ctx->err = "signature cache change with a batch in flight"; return EDC_ERR_ARG; }
   int rc = sync_all(ctx);
   if (rc) return rc;
+  CK(sc_wait_inserts(ctx));
   free_sigcache(ctx);
   if (!capacity) return 0;
   if (capacity > (1ull << 30)) { ctx->err = "signature cache capacity above 2^30 records"; return EDC_ERR_ARG; }
@@ -2668,6 +2706,7 @@ int edc_sigcache_clear(edc_ctx* ctx) {
   CK(hipSetDevice(ctx->device));
   int rc = sc_ready(ctx);
   if (rc) return rc;
+  CK(sc_wait_inserts(ctx));
   CK(hipMemsetAsync(ctx->sc_hdr, 0, ctx->sc_cap * sizeof(unsigned long long), ctx->st()));
   CK(hipStreamSynchronize(ctx->st()));
   return 0;
@@ -2683,12 +2722,19 @@ int edc_sigcache_advance(edc_ctx* ctx) {
   }
   int rc = sc_ready(ctx);
   if (rc) return rc;
+  CK(sc_wait_inserts(ctx));
   ctx->sc_gen++;
   return 0;
 }
 
 int edc_sigcache_stats(const edc_ctx* ctx, uint64_t out[6]) {
   if (!ctx || !out || !ctx->sc_cap) return EDC_ERR_ARG;
+  // a cached verifier's deferred insert ends with the copy of the counters into their pinned
+  // mirror: once it has run the mirror is current
+  if (sc_wait_inserts(ctx) != hipSuccess) {
+    (void)hipGetLastError();
+    return EDC_ERR_HIP;
+  }
   out[0] = ctx->sc_cap;
   out[1] = ctx->sc_gen;
   out[2] = ctx->sc_hits;
@@ -2709,6 +2755,7 @@ int edc_sigcache_lookup_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, cons
     ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
     return EDC_ERR_ARG;
   }
+  if ((rc = sc_order_after_inserts(ctx, ctx->st()))) return rc;
   launch_sc_lookup(ctx->st(), ctx->sc(), (uint32_t)n, d_vk, d_sig, reinterpret_cast<const uint32_t*>(d_k), d_hit,
                    nullptr);
   CK(hipGetLastError());
@@ -2876,18 +2923,21 @@ static int verifier_reserve(edc_verifier* v, size_t need) {
   size_t cap = v->cap * 2 > need ? v->cap * 2 : need;
   if (cap < 1) cap = 1;
   uint8_t *nvk = nullptr, *nsig = nullptr, *nz = nullptr;
-  uint32_t* nk = nullptr;
+  uint32_t *nk = nullptr, *norg = nullptr;
   CK(dalloc(&nvk, cap * 32));
   CK(dalloc(&nsig, cap * 64));
   CK(dalloc(&nz, cap * 16));
   CK(dalloc(&nk, cap * 8));
+  if (v->cached.on) CK(dalloc(&norg, cap));   // only a cached verifier keeps offered positions
   if (v->n) {
     CK(hipMemcpy(nvk, v->vk, v->n * 32, hipMemcpyDeviceToDevice));
     CK(hipMemcpy(nsig, v->sig, v->n * 64, hipMemcpyDeviceToDevice));
     CK(hipMemcpy(nk, v->k, v->n * 32, hipMemcpyDeviceToDevice));
+    if (v->cached.on) CK(hipMemcpy(norg, v->origin, v->n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
   }
-  for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k})
+  for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->origin})
     if (p) (void)hipFree(p);
+  v->origin = norg;
   v->vk = nvk;
   v->sig = nsig;
   v->zexp = nz;
@@ -2989,6 +3039,155 @@ static int verifier_spent(edc_verifier* v) {
   return EDC_ERR_ARG;
 }
 
+// ---- cached mode (edc_vfy_set_cached) ----
+// A queue call brings its range to the device (the staging area, or a device caller's own arrays),
+// looks it up in the context's verified-signature table and appends only the misses, in offered
+// order, to the retained arrays; from there on they are queued items like any other, so verify,
+// the folds and the fallback run unchanged over the retained items. What a verdict proves valid
+// is inserted behind it on the verifier's stream (verifier_insert).
+
+// what a cached queue call of m items needs, checked before anything is copied
+static int verifier_cached_check(edc_verifier* v, size_t m) {
+  edc_ctx* ctx = v->ctx;
+  if (!ctx->sc_cap) {
+    ctx->err = "cached verifier: no signature cache on this context (edc_sigcache_create)";
+    return EDC_ERR_ARG;
+  }
+  if (m >= (1ull << 28)) { ctx->err = "batch too large for one verifier (max 2^28 items)"; return EDC_ERR_ARG; }
+  if (!cached_room(v->cached, m)) {
+    ctx->err = "cached verifier: more than 2^32 - 1 items offered since the last reset";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// Staging for a range of m items (vk, sig, k, hit flags, workgroup counts). The previous range's
+// gather is the last reader of the old contents: the copy stream waits for it.
+static int verifier_stage_room(edc_verifier* v, size_t m) {
+  edc_ctx* ctx = v->ctx;
+  if (!v->h_cnt) CK(hipHostMalloc((void**)&v->h_cnt, 2 * sizeof(uint32_t)));
+  if (!v->ev_cnt) CK(hipEventCreateWithFlags(&v->ev_cnt, hipEventDisableTiming));
+  if (!v->ev_gather) CK(hipEventCreateWithFlags(&v->ev_gather, hipEventDisableTiming));
+  if (m > v->st_cap || !v->hit) {
+    CK(hipStreamSynchronize(v->s.st));
+    CK(hipStreamSynchronize(v->cs));
+    for (void* p : {(void*)v->st_vk, (void*)v->st_sig, (void*)v->st_k, (void*)v->hit, (void*)v->wg})
+      if (p) (void)hipFree(p);
+    v->st_vk = v->st_sig = v->hit = nullptr;
+    v->st_k = v->wg = nullptr;
+    v->st_cap = 0;
+    v->gather_pending = false;
+    const size_t cap = m < 1024 ? 1024 : m + m / 8;
+    CK(dalloc(&v->st_vk, cap * 32));
+    CK(dalloc(&v->st_sig, cap * 64));
+    CK(dalloc(&v->st_k, cap * 8));
+    CK(dalloc(&v->hit, cap));
+    CK(dalloc(&v->wg, cap / SC_BLOCK + 2));   // one count per workgroup + the total
+    v->st_cap = cap;
+  }
+  if (v->gather_pending) CK(hipStreamWaitEvent(v->cs, v->ev_gather, 0));
+  return 0;
+}
+
+// The rest of a cached queue call, once everything that produces the range's vk / sig / k (at
+// s_*) is on the slot stream or ordered before it: lookup, miss count to the host (the call's one
+// added synchronization), room for the misses, gather, and the per-item work of the appended
+// misses. in_place: s_* are a device caller's arrays, which the gather still reads, so the call
+// also waits for the gather.
+static int verifier_append_misses(edc_verifier* v, size_t m, const uint8_t* s_vk, const uint8_t* s_sig,
+                                  const uint32_t* s_k, bool in_place) {
+  edc_ctx* ctx = v->ctx;
+  hipStream_t st = v->s.st;
+  int rc = sc_order_after_inserts(ctx, st);
+  if (rc) return rc;
+  const uint32_t M = (uint32_t)m, nwg = (M + SC_BLOCK - 1) / SC_BLOCK;
+  launch_sc_lookup(st, ctx->sc(), M, s_vk, s_sig, s_k, v->hit, v->wg);
+  launch_sc_scan(st, nwg, v->wg, v->wg + nwg);
+  CK(hipGetLastError());
+  v->h_cnt[0] = 0xFFFFFFFFu;
+  CK(hipMemcpyAsync(v->h_cnt, v->wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CK(hipEventRecord(v->ev_cnt, st));
+  CK(hipEventSynchronize(v->ev_cnt));
+  v->chal_pending = false;      // a SHA-512 pass of this range ran before its lookup
+  const size_t c = v->h_cnt[0], n0 = v->n;
+  if (c > m) { ctx->err = "cached verifier: miss count out of range"; return EDC_ERR_HIP; }
+  ctx->sc_hits += m - c;        // the table's statistics count the lookup, whatever becomes of the append
+  ctx->sc_misses += c;
+  if (c) {
+    if ((rc = verifier_reserve(v, n0 + c))) return rc;
+    launch_sc_gather_range(st, M, v->hit, v->wg, s_vk, s_sig, s_k, (uint32_t)v->cached.offered, n0, v->vk, v->sig,
+                           v->k, v->origin);
+    CK(hipGetLastError());
+    CK(hipEventRecord(v->ev_gather, st));
+    v->gather_pending = true;
+    rc = verifier_enqueue_range(v, n0, c);
+    // a device caller's arrays are not read after the call returns, also when it fails
+    if (in_place) CK(hipEventSynchronize(v->ev_gather));
+    if (rc) return rc;
+  }
+  // the range is appended: only now do the verifier's counts move
+  cached_offer(v->cached, m, c);
+  v->n = n0 + c;
+  return 0;
+}
+
+// Enqueue, behind the verdict on the verifier's stream, the insert of the retained items that are
+// not records yet: all of them (d_codes null: a verify that passed) or those whose retained-order
+// code is EDC_OK (a fallback). The counters' mirror is refreshed behind it and the context's event
+// recorded; the call returns without waiting.
+static int verifier_insert(edc_verifier* v, const uint8_t* d_codes) {
+  edc_ctx* ctx = v->ctx;
+  size_t a, b;
+  if (!cached_insert_due(v->cached, v->n, &a, &b) || !ctx->sc_cap) return 0;
+  hipStream_t st = v->s.st;
+  if (!ctx->sc_ev) CK(hipEventCreateWithFlags(&ctx->sc_ev, hipEventDisableTiming));
+  int rc = sc_order_after_inserts(ctx, st);
+  if (rc) return rc;
+  launch_sc_insert(st, ctx->sc(), (uint32_t)(b - a), nullptr, v->vk + a * 32, v->sig + a * 64, v->k + a * 8,
+                   d_codes ? d_codes + a : nullptr, ctx->sc_ctr);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(ctx->sc_hctr, ctx->sc_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  CK(hipEventRecord(ctx->sc_ev, st));
+  ctx->sc_ev_set = true;
+  cached_insert_done(v->cached, b);
+  return 0;
+}
+
+// After a failed verify's fallback in cached mode: the retained-order codes (host, n bytes) go to
+// the device, are scattered through origin into offered order when `offered` (host) is given
+// (hits stay EDC_OK), and mask the insert.
+static int verifier_codes_out(edc_verifier* v, const uint8_t* verdicts, uint8_t* offered) {
+  edc_ctx* ctx = v->ctx;
+  hipStream_t st = v->s.st;
+  const size_t n = v->n, N = (size_t)v->cached.offered;
+  if (n > v->verd_cap) {
+    CK(hipStreamSynchronize(st));
+    if (v->verd) (void)hipFree(v->verd);
+    v->verd = nullptr;
+    v->verd_cap = 0;
+    CK(dalloc(&v->verd, v->cap));
+    v->verd_cap = v->cap;
+  }
+  CK(hipMemcpyAsync(v->verd, verdicts, n, hipMemcpyHostToDevice, st));
+  if (offered) {
+    if (N > v->offv_cap) {
+      CK(hipStreamSynchronize(st));
+      if (v->offv) (void)hipFree(v->offv);
+      v->offv = nullptr;
+      v->offv_cap = 0;
+      const size_t cap = N < 1024 ? 1024 : N + N / 8;
+      CK(dalloc(&v->offv, cap));
+      v->offv_cap = cap;
+    }
+    CK(hipMemsetAsync(v->offv, 0, N, st));
+    launch_sc_scatter(st, (uint32_t)n, v->origin, v->verd, v->offv);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(offered, v->offv, N, hipMemcpyDeviceToHost, st));
+  }
+  CK(hipStreamSynchronize(st));   // the codes have left / reached the caller's memory; the insert is not waited for
+  return verifier_insert(v, v->verd);
+}
+
 // One append from host buffers (k: prehashed challenges, or null for the message path; key_idx:
 // positions in the registered key list instead of vk, 4 bytes per item over PCIe, expanded into the
 // retained vk range on the device). The copies run on the copy stream; the call returns once they
@@ -3007,10 +3206,17 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
   const size_t mbytes = k ? 0 : (size_t)(msg_off[m] - msg_off[0]);
   if (mbytes && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
-  int rc = verifier_reserve(v, v->n + m);
+  const bool cached = v->cached.on;
+  int rc = cached ? verifier_cached_check(v, m) : 0;
+  if (rc) return rc;
+  rc = cached ? verifier_stage_room(v, m) : verifier_reserve(v, v->n + m);
   if (rc) return rc;
   Slot& s = v->s;
   const size_t n0 = v->n;
+  // where the range lands: the retained arrays from n0 on, or the staging area (cached mode)
+  uint8_t* r_vk = cached ? v->st_vk : v->vk + n0 * 32;
+  uint8_t* r_sig = cached ? v->st_sig : v->sig + n0 * 64;
+  uint32_t* r_k = cached ? v->st_k : v->k + n0 * 8;
   if (!k) {
     rc = verifier_msg_room(v, m, mbytes);
     if (rc) return rc;
@@ -3027,14 +3233,14 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
       v->cap_idx = cap;
     }
     CK(hipMemcpyAsync(v->idx, key_idx, m * sizeof(uint32_t), hipMemcpyHostToDevice, v->cs));
-    launch_expand_keys(v->cs, (uint32_t)m, v->idx, ctx->kc_reg, ctx->kc_keys, v->vk + n0 * 32);
+    launch_expand_keys(v->cs, (uint32_t)m, v->idx, ctx->kc_reg, ctx->kc_keys, r_vk);
     CK(hipGetLastError());
   } else {
-    CK(hipMemcpyAsync(v->vk + n0 * 32, vk, m * 32, hipMemcpyHostToDevice, v->cs));
+    CK(hipMemcpyAsync(r_vk, vk, m * 32, hipMemcpyHostToDevice, v->cs));
   }
-  CK(hipMemcpyAsync(v->sig + n0 * 64, sig, m * 64, hipMemcpyHostToDevice, v->cs));
+  CK(hipMemcpyAsync(r_sig, sig, m * 64, hipMemcpyHostToDevice, v->cs));
   if (k) {
-    CK(hipMemcpyAsync(v->k + n0 * 8, k, m * 32, hipMemcpyHostToDevice, v->cs));
+    CK(hipMemcpyAsync(r_k, k, m * 32, hipMemcpyHostToDevice, v->cs));
   } else {
     v->rebased.resize(m + 1);
     for (size_t i = 0; i <= m; ++i) v->rebased[i] = msg_off[i] - msg_off[0];
@@ -3044,10 +3250,19 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
   CK(hipEventRecord(v->ev_copy, v->cs));
   CK(hipStreamWaitEvent(s.st, v->ev_copy, 0));
   if (!k) {
-    launch_challenge(s.st, (uint32_t)m, v->vk + n0 * 32, v->sig + n0 * 64, v->msg, v->off, v->k + n0 * 8);
+    launch_challenge(s.st, (uint32_t)m, r_vk, r_sig, v->msg, v->off, r_k);
     CK(hipGetLastError());
     CK(hipEventRecord(v->ev_chal, s.st));
     v->chal_pending = true;
+  }
+  if (cached) {
+    // the lookup runs behind the copies, so the wait for its miss count covers them; after an
+    // error the copies are waited for all the same
+    rc = verifier_append_misses(v, m, r_vk, r_sig, r_k, false);
+    const hipError_t e = hipEventSynchronize(v->ev_copy);
+    if (rc) return rc;
+    CK(e);
+    return verifier_fold(v);
   }
   rc = verifier_enqueue_range(v, n0, m);
   if (rc) return rc;
@@ -3099,7 +3314,7 @@ static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const
 }
 
 static int verifier_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t* z, uint8_t check8[32],
-                           bool plain = false) {
+                           bool plain = false, bool insert = true) {
   edc_ctx* ctx = v->ctx;
   // eager (edc_vfy_begin_eager): z is already committed; `plain` is the fallback's own verify of a
   // spent eager verifier, which draws fresh z from the caller's seed over every item
@@ -3124,6 +3339,12 @@ static int verifier_verify(edc_verifier* v, const uint8_t* z_seed, const uint8_t
   if (rc) return rc;
   rc = finish_batch(ctx, v->s, check8, nullptr, nullptr);
   if (eager && rc == EDC_INVALID_SIGNATURE) v->fold.spent = true;   // a z-dependent point has left the library
+  // cached mode: what this verdict proved valid becomes records, behind the verdict and unwaited
+  // (`insert` false: the fallback, which inserts by its per-item codes)
+  if (rc == EDC_OK && insert) {
+    const int r2 = verifier_insert(v, nullptr);
+    if (r2) return r2;
+  }
   return rc;
 }
 
@@ -3157,8 +3378,12 @@ void edc_verifier_destroy(edc_verifier* v) {
   ctx->verifiers.erase(std::remove(ctx->verifiers.begin(), ctx->verifiers.end(), v), ctx->verifiers.end());
   free_slot_buffers(s);
   for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->msg, (void*)v->off, (void*)s.flags,
-                  (void*)s.d_out, (void*)v->karea, (void*)v->idx, (void*)v->run})
+                  (void*)s.d_out, (void*)v->karea, (void*)v->idx, (void*)v->run, (void*)v->origin, (void*)v->st_vk,
+                  (void*)v->st_sig, (void*)v->st_k, (void*)v->hit, (void*)v->wg, (void*)v->verd, (void*)v->offv})
     if (p) (void)hipFree(p);
+  if (v->h_cnt) (void)hipHostFree(v->h_cnt);
+  if (v->ev_cnt) (void)hipEventDestroy(v->ev_cnt);
+  if (v->ev_gather) (void)hipEventDestroy(v->ev_gather);
   if (s.h_out) (void)hipHostFree(s.h_out);
   if (s.h_acc) (void)hipHostFree(s.h_acc);
   for (int p = 0; p <= PH_N; ++p)
@@ -3197,6 +3422,19 @@ int edc_verifier_queue_device(edc_verifier* v, size_t m, const uint8_t* d_vk, co
     return EDC_ERR_ARG;
   }
   CK(hipSetDevice(ctx->device));
+  if (v->cached.on) {
+    // the caller's vk / sig (and k) are read in place: nothing is staged but the k of the message form
+    int rc = verifier_cached_check(v, m);
+    if (rc || (rc = verifier_stage_room(v, m))) return rc;
+    const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
+    if (!k) {
+      launch_challenge(v->s.st, (uint32_t)m, d_vk, d_sig, d_msg, d_msg_off, v->st_k);
+      CK(hipGetLastError());
+      k = v->st_k;
+    }
+    if ((rc = verifier_append_misses(v, m, d_vk, d_sig, k, true))) return rc;
+    return verifier_fold(v);
+  }
   int rc = verifier_reserve(v, v->n + m);
   if (rc) return rc;
   Slot& s = v->s;
@@ -3241,9 +3479,12 @@ int edc_verifier_verify(edc_verifier* v, const uint8_t z_seed[32], const uint8_t
   return verifier_verify(v, z_seed, z, check8);
 }
 
-int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
-                                 uint8_t check8[32]) {
-  if (!v || !z_seed || (v->n && !verdicts)) return EDC_ERR_ARG;
+}  // extern "C"
+
+// edc_verifier_verify_fallback (verdicts: n bytes, retained order); offered (nullable, cached mode):
+// the same codes in offered order, hits EDC_OK
+static int verifier_fallback(edc_verifier* v, const uint8_t* z_seed, uint8_t* verdicts, int* n_invalid,
+                             uint8_t check8[32], uint8_t* offered) {
   edc_ctx* ctx = v->ctx;
   Slot& s = v->s;
   const size_t n = v->n;
@@ -3252,9 +3493,15 @@ int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint
   // caller's fresh seed instead. Either leaves what the fallback reads: the key rows placed for
   // all n items, the per-item s bits, the grouping flags. The fallback draws its own z from z_seed.
   const bool eager = v->fold.eager && !v->fold.spent;
-  int rc = eager ? verifier_verify(v, nullptr, nullptr, check8) : verifier_verify(v, z_seed, nullptr, check8, true);
+  int rc = eager ? verifier_verify(v, nullptr, nullptr, check8, false, false)
+                 : verifier_verify(v, z_seed, nullptr, check8, true, false);
   if (rc <= 0) {
-    if (rc == 0 && n) memset(verdicts, 0, n);
+    if (rc == 0) {
+      if (n) memset(verdicts, 0, n);
+      if (offered) memset(offered, 0, (size_t)v->cached.offered);
+      const int r1 = verifier_insert(v, nullptr);
+      if (r1) return r1;
+    }
     return rc;
   }
   bool per_sig;
@@ -3278,8 +3525,29 @@ int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint
     if (r3) return r3;
   }
   if (r2 < 0) return r2;
+  if (v->cached.on) {           // exactly the retained items whose code is EDC_OK become records
+    const int r3 = verifier_codes_out(v, verdicts, offered);
+    if (r3) return r3;
+  }
   if (n_invalid) *n_invalid = r2;
   return EDC_INVALID_SIGNATURE;
+}
+
+extern "C" {
+
+int edc_verifier_verify_fallback(edc_verifier* v, const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
+                                 uint8_t check8[32]) {
+  if (!v || !z_seed || (v->n && !verdicts)) return EDC_ERR_ARG;
+  return verifier_fallback(v, z_seed, verdicts, n_invalid, check8, nullptr);
+}
+
+int edc_vfy_verify_fallback_offered(edc_verifier* v, const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
+                                    uint8_t check8[32]) {
+  if (!v) return EDC_ERR_ARG;
+  if (!v->cached.on) return edc_verifier_verify_fallback(v, z_seed, verdicts, n_invalid, check8);
+  if (!z_seed || (v->cached.offered && !verdicts)) return EDC_ERR_ARG;
+  std::vector<uint8_t> retained(v->n ? v->n : 1);
+  return verifier_fallback(v, z_seed, retained.data(), n_invalid, check8, verdicts);
 }
 
 int edc_verifier_reset(edc_verifier* v) {
@@ -3288,7 +3556,35 @@ int edc_verifier_reset(edc_verifier* v) {
   CK(hipSetDevice(ctx->device));
   v->n = 0;
   fold_reset(v->fold);          // the next block commits its own seed (edc_vfy_begin_eager)
+  cached_reset(v->cached);      // the counts and the insert watermark start over; the mode stays
   return verifier_clear(v);
+}
+
+int edc_vfy_set_cached(edc_verifier* v, int on) {
+  if (!v) return EDC_ERR_ARG;
+  if (!cached_can_switch(v->cached, v->n)) {
+    v->ctx->err = "edc_vfy_set_cached: items are queued (call it after create or edc_verifier_reset)";
+    return EDC_ERR_ARG;
+  }
+  edc_ctx* ctx = v->ctx;
+  CK(hipSetDevice(ctx->device));
+  // A passing verify may have left its insert running on the verifier's stream, reading the
+  // retained arrays. A cached queue call only reaches those arrays through that stream; the plain
+  // queue path writes them from the copy stream, which nothing orders behind the insert. So the
+  // mode never changes under a pending insert: records are only ever made of bytes that verified.
+  CK(hipStreamSynchronize(v->s.st));
+  if (on && !v->origin) CK(dalloc(&v->origin, v->cap));   // one offered position per retained item
+  v->cached.on = on != 0;
+  return 0;
+}
+
+int edc_vfy_cached(const edc_verifier* v) { return v ? (v->cached.on ? 1 : 0) : EDC_ERR_ARG; }
+
+int edc_vfy_cache_counts(const edc_verifier* v, uint64_t* offered, uint64_t* hits) {
+  if (!v) return EDC_ERR_ARG;
+  if (offered) *offered = v->cached.offered;
+  if (hits) *hits = v->cached.hits;
+  return 0;
 }
 
 int edc_vfy_begin_eager(edc_verifier* v, const uint8_t z_seed[32]) {

@@ -1,5 +1,7 @@
 // Verified-signature cache kernels (sigcache.h): lookup, order-preserving compaction of the
-// misses (per-workgroup ballot counts, scan, scatter + gather), insert, verdict scatter.
+// misses (per-workgroup ballot counts, scan, scatter + gather; for a cached verifier's queued
+// range, gather into the retained arrays at an offset with the offered positions), insert, verdict
+// scatter.
 // One lane per item; items and records move as uint4.
 #include "sigcache.h"
 
@@ -132,13 +134,14 @@ __global__ void __launch_bounds__(SC_SCAN_TILE) k_sc_scan(uint32_t nwg, uint32_t
   if (tid == 0) total[0] = carry;
 }
 
-__global__ void __launch_bounds__(SC_BLOCK) k_sc_compact(uint32_t n, const uint8_t* __restrict__ hit,
-                                                         const uint32_t* __restrict__ wg_off,
-                                                         const uint8_t* __restrict__ vk,
-                                                         const uint8_t* __restrict__ sig,
-                                                         const uint32_t* __restrict__ k, uint32_t* __restrict__ idx,
-                                                         uint8_t* __restrict__ out_vk, uint8_t* __restrict__ out_sig,
-                                                         uint32_t* __restrict__ out_k) {
+// Order-preserving compaction of the misses of n items, shared by the two kernels below: rank
+// inside the workgroup from the waves' ballots, the workgroup's start from the scanned counts.
+// Miss j gets pos[j] = base + i and its vk / sig / k in row j of the out arrays.
+__device__ __forceinline__ void sc_compact_body(uint32_t n, const uint8_t* __restrict__ hit,
+                                                const uint32_t* __restrict__ wg_off, const uint8_t* __restrict__ vk,
+                                                const uint8_t* __restrict__ sig, const uint32_t* __restrict__ k,
+                                                uint32_t base, uint32_t* __restrict__ pos, uint8_t* __restrict__ out_vk,
+                                                uint8_t* __restrict__ out_sig, uint32_t* __restrict__ out_k) {
   __shared__ uint32_t wsum[SC_BLOCK / 64];
   const uint32_t i = blockIdx.x * SC_BLOCK + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -149,7 +152,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_compact(uint32_t n, const uint8
   if (!miss) return;
   uint32_t j = wg_off[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1));
   for (uint32_t w = 0; w < wave; ++w) j += wsum[w];
-  idx[j] = i;
+  pos[j] = base + i;
   uint4 q[8];
   sc_load_item(vk, sig, k, i, q);
   uint4* da = reinterpret_cast<uint4*>(out_vk + (size_t)j * 32);
@@ -158,6 +161,30 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_compact(uint32_t n, const uint8
   da[0] = q[0]; da[1] = q[1];
   db[0] = q[2]; db[1] = q[3]; db[2] = q[4]; db[3] = q[5];
   dc[0] = q[6]; dc[1] = q[7];
+}
+
+// one cached call: idx[j] = queue index of miss j, the misses gathered to the staging arrays
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_compact(uint32_t n, const uint8_t* __restrict__ hit,
+                                                         const uint32_t* __restrict__ wg_off,
+                                                         const uint8_t* __restrict__ vk,
+                                                         const uint8_t* __restrict__ sig,
+                                                         const uint32_t* __restrict__ k, uint32_t* __restrict__ idx,
+                                                         uint8_t* __restrict__ out_vk, uint8_t* __restrict__ out_sig,
+                                                         uint32_t* __restrict__ out_k) {
+  sc_compact_body(n, hit, wg_off, vk, sig, k, 0u, idx, out_vk, out_sig, out_k);
+}
+
+// one queued range of a cached verifier: miss j of the range lands in row dst0 + j of the retained
+// arrays (the caller passes them, and origin, already offset by dst0) and its offered position
+// base + i in origin
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_gather_range(uint32_t n, const uint8_t* __restrict__ hit,
+                                                              const uint32_t* __restrict__ wg_off,
+                                                              const uint8_t* __restrict__ vk,
+                                                              const uint8_t* __restrict__ sig,
+                                                              const uint32_t* __restrict__ k, uint32_t base,
+                                                              uint8_t* __restrict__ out_vk, uint8_t* __restrict__ out_sig,
+                                                              uint32_t* __restrict__ out_k, uint32_t* __restrict__ origin) {
+  sc_compact_body(n, hit, wg_off, vk, sig, k, base, origin, out_vk, out_sig, out_k);
 }
 
 __global__ void __launch_bounds__(SC_BLOCK) k_sc_insert(SigCacheView sc, uint32_t c, const uint32_t* __restrict__ idx,
@@ -248,6 +275,14 @@ void launch_sc_insert(hipStream_t st, const SigCacheView& sc, uint32_t c, const 
 
 void launch_sc_scatter(hipStream_t st, uint32_t c, const uint32_t* idx, const uint8_t* v, uint8_t* out) {
   if (c) hipLaunchKernelGGL(k_sc_scatter, dim3(sc_blocks(c)), dim3(SC_BLOCK), 0, st, c, idx, v, out);
+}
+
+void launch_sc_gather_range(hipStream_t st, uint32_t n, const uint8_t* hit, const uint32_t* wg_off, const uint8_t* vk,
+                            const uint8_t* sig, const uint32_t* k, uint32_t base, size_t dst0, uint8_t* out_vk,
+                            uint8_t* out_sig, uint32_t* out_k, uint32_t* origin) {
+  if (n)
+    hipLaunchKernelGGL(k_sc_gather_range, dim3(sc_blocks(n)), dim3(SC_BLOCK), 0, st, n, hit, wg_off, vk, sig, k, base,
+                       out_vk + dst0 * 32, out_sig + dst0 * 64, out_k + dst0 * 8, origin + dst0);
 }
 
 }  // namespace edc

@@ -21,7 +21,9 @@
 // Ageing. The table has a generation (>= 1), bumped by edc_sigcache_advance (once per height). A
 // record inserted more than `keep` generations ago is dead: lookups skip it, inserts reuse it.
 //
-// Concurrency. Lookup and insert never run together (one stream, kernel boundaries). Inside one
+// Concurrency. Lookup and insert never run together: kernel boundaries on one stream for the
+// one-call entries; a cached verifier's deferred insert runs on its own stream and records the
+// context's event, which every other table access waits for first (edc_api.hip, sc_ev). Inside one
 // insert launch a slot is claimed by a 64-bit CAS on its header and only the claimer writes the
 // record. A lane that meets a header claimed in the same launch may read a half-written record,
 // find it unequal and claim another slot: a duplicate copy, which is harmless. An insert that
@@ -60,5 +62,12 @@ void launch_sc_insert(hipStream_t st, const SigCacheView& sc, uint32_t c, const 
                       const uint8_t* sig, const uint32_t* k, const uint8_t* verdict, unsigned long long* ctr);
 // out[idx[j]] = v[j], j < c (per-item verdicts of the misses back to their queue positions)
 void launch_sc_scatter(hipStream_t st, uint32_t c, const uint32_t* idx, const uint8_t* v, uint8_t* out);
+// cached incremental verifier (edc_vfy_set_cached): the misses of one queued range of n items, in
+// offered order, appended to the retained arrays from row dst0 on (hit / wg_off: this range's
+// lookup flags and scanned workgroup counts); origin[dst0 + j] = base + range index of miss j,
+// its position among everything offered since the last reset
+void launch_sc_gather_range(hipStream_t st, uint32_t n, const uint8_t* hit, const uint32_t* wg_off, const uint8_t* vk,
+                            const uint8_t* sig, const uint32_t* k, uint32_t base, size_t dst0, uint8_t* out_vk,
+                            uint8_t* out_sig, uint32_t* out_k, uint32_t* origin);
 
 }  // namespace edc

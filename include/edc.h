@@ -545,6 +545,50 @@ int edc_synchronize(edc_ctx* ctx);
  *   then on the seed is spent, and queue and verify calls on v return EDC_ERR_ARG until
  *   edc_verifier_reset. edc_verifier_verify_fallback is the exception: it draws its own z from
  *   the caller's fresh seed.
+ *
+ * Cached mode: queue calls skip the items the context's verified-signature table (edc_sigcache_*,
+ * below) already vouches for. A node queues a block's votes as they arrive and saw most of them
+ * at gossip time: the lookup runs at queue time, where the call already waits for its copies, and
+ * a hit costs neither the R decode, nor the key grouping, nor any term of verify's MSM.
+ * edc_vfy_set_cached  switches the mode (on != 0). Only while nothing is queued (after create or
+ *   edc_verifier_reset; EDC_ERR_ARG otherwise). The mode is configuration: it survives
+ *   edc_verifier_reset (eager mode does not). The call waits for an insert that an earlier verify
+ *   on v left running. A verifier that is not in cached mode never touches the table.
+ * edc_vfy_cached      1 in cached mode, 0 if not, EDC_ERR_ARG for NULL.
+ * In cached mode every queue form (edc_verifier_queue / _prehashed / _device,
+ *   edc_vfy_queue_indexed) brings its m items to the device (a staging area of the verifier; the
+ *   _device form with d_k reads the caller's arrays in place), looks them up, and appends only
+ *   the misses, in the order they were offered, as the retained items [n, n + c). The miss count
+ *   c comes back to the host inside the call: its one added synchronization (the _device form
+ *   also waits for the gather of the misses, the last read of the caller's arrays). Queue index
+ *   i, and with it z_i, is the retained index: edc_verifier_verify is bit-identical (verdict and
+ *   check8) to edc_batch_verify_prehashed_device on the miss list with z_base = 0, and to
+ *   edc_batch_verify of it, also in eager mode with the committed seed and in every grouping and
+ *   split mode; caller-drawn z holds one z_i per retained item (edc_verifier_size of them).
+ *   Without a table on the context the call returns EDC_ERR_ARG and appends nothing; so does a
+ *   call that would take the items offered since the last reset past 2^32 - 1. The lookups count
+ *   in the table's hits / misses (edc_sigcache_stats).
+ * edc_verifier_size   stays the number of retained items: offered - hits.
+ * edc_vfy_cache_counts  *offered = items given to queue calls since the last reset, *hits = how
+ *   many of them were skipped as records (either may be NULL). EDC_ERR_ARG for a NULL verifier.
+ * Inserts. An edc_verifier_verify that returns EDC_OK inserts the retained items that are not
+ *   records yet (the queue survives verify; a later verify inserts only what was queued since). A
+ *   verify that fails, eager or not, inserts nothing. edc_verifier_verify_fallback and
+ *   edc_vfy_verify_fallback_offered insert exactly the retained items whose code is EDC_OK. The
+ *   insert runs on the verifier's stream behind the verdict and the call does not wait for it;
+ *   every other use of the table (another verifier's queue call, the edc_sigcache_* entries)
+ *   orders itself after it, so a record is never read while it is written.
+ * edc_vfy_verify_fallback_offered  edc_verifier_verify_fallback with the codes in the order the
+ *   items were offered: verdicts has `offered` bytes, a hit gets EDC_OK, a retained item its
+ *   Item::verify_single code (src/batch.rs:104-107). On a verifier that is not in cached mode it
+ *   is edc_verifier_verify_fallback, which itself keeps its meaning in cached mode:
+ *   edc_verifier_size codes, in retained order.
+ * Soundness of cached mode. A hit is worth what the verified-signature cache says below: a
+ *   byte-identical (vk, sig, k) verified earlier on this context, one by one or inside a batch
+ *   whose equation held. A verify that passes plants records, so its z must be fresh and secret,
+ *   also in eager mode, where the seed is committed before the items arrive: with a predictable
+ *   seed, crafted items that cancel inside one block would be accepted from then on. In the
+ *   prehashed queue forms the caller vouches for k, as in every prehashed entry.
  */
 typedef struct edc_verifier edc_verifier;
 edc_verifier* edc_verifier_create(edc_ctx* ctx, size_t capacity_hint);
@@ -566,6 +610,11 @@ int edc_vfy_begin_eager(edc_verifier* v, const uint8_t z_seed[32]);
 int edc_vfy_set_fold(edc_verifier* v, size_t min_items);
 int edc_vfy_folded(const edc_verifier* v, uint64_t* items, uint64_t* folds);
 int edc_vfy_eager(const edc_verifier* v);
+int edc_vfy_set_cached(edc_verifier* v, int on);
+int edc_vfy_cached(const edc_verifier* v);
+int edc_vfy_cache_counts(const edc_verifier* v, uint64_t* offered, uint64_t* hits);
+int edc_vfy_verify_fallback_offered(edc_verifier* v, const uint8_t z_seed[32], uint8_t* verdicts, int* n_invalid,
+                                    uint8_t check8[32]);
 
 /*
  * Verified-signature cache: skip the items that already verified on this context. A consensus
@@ -612,7 +661,9 @@ int edc_vfy_eager(const edc_verifier* v);
  * edc_sigcache_clear   empties the table (generation and counters stay).
  * edc_sigcache_advance bumps the generation (a node calls it once per height).
  * edc_sigcache_stats   out = {capacity, generation, hits, misses, inserted, dropped}: items the
- *   cached verify entries found / did not find, records written, inserts dropped for a full window.
+ *   cached verify entries found / did not find, records written, inserts dropped for a full window
+ *   (lookups and inserts of cached verifiers, edc_vfy_set_cached, included; the call waits for an
+ *   insert such a verifier left running).
  * edc_sigcache_lookup_device  d_hit[i] = 1 iff item i is a live record (device arrays, 16-byte
  *   aligned vk / sig / k; d_hit n bytes); changes neither the table nor the counters.
  * edc_sigcache_batch_verify_device  Verifier::queue x n + Verifier::verify(rng) (reference
