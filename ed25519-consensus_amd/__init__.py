@@ -62,7 +62,16 @@ ABI_SYMBOLS = [
     "edc_sigcache_create", "edc_sigcache_clear", "edc_sigcache_advance", "edc_sigcache_stats",
     "edc_sigcache_lookup_device", "edc_sigcache_batch_verify_device", "edc_sigcache_batch_verify",
     "edc_sigcache_batch_verify_fallback_device", "edc_sigcache_verify_each",
+    "edc_tmpl_expand_device", "edc_tmpl_challenge", "edc_tmpl_batch_verify", "edc_tmpl_batch_verify_device",
+    "edc_tmpl_batch_submit", "edc_vfy_queue_templated",
 ]
+
+
+class EdcTemplates(ctypes.Structure):
+    """struct edc_templates (include/edc.h): one call's template set, host memory."""
+    _fields_ = [("count", ctypes.c_uint32),
+                ("head", ctypes.c_char_p), ("head_off", ctypes.POINTER(ctypes.c_uint32)),
+                ("tail", ctypes.c_char_p), ("tail_off", ctypes.POINTER(ctypes.c_uint32))]
 
 
 class Error(Exception):
@@ -258,6 +267,19 @@ def load_library(path=None):
             lib.edc_sigcache_batch_verify_fallback_device.argtypes = [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp, c_u8p,
                                                                       c_vp, ctypes.POINTER(ctypes.c_int), c_vp, c_szp]
             lib.edc_sigcache_verify_each.argtypes = [c_vp, c_sz, c_u8p, c_u8p, c_u8p, c_u64p, c_u8p, c_vp, c_szp]
+        if hasattr(lib, "edc_tmpl_expand_device"):           # absent from older A/B builds (tools/)
+            c_tsp, c_u16p = ctypes.POINTER(EdcTemplates), ctypes.POINTER(ctypes.c_uint16)
+            c_u32p = ctypes.POINTER(ctypes.c_uint32)
+            lib.edc_tmpl_expand_device.argtypes = [c_vp, c_tsp, c_sz, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]
+            lib.edc_tmpl_challenge.argtypes = [c_vp, c_tsp, c_sz, c_u8p, c_u8p, c_u16p, c_u8p, c_u32p, c_vp]
+            lib.edc_tmpl_batch_verify.argtypes = [c_vp, c_tsp, c_sz, c_u8p, c_u32p, c_u8p, c_u16p, c_u8p, c_u32p, c_u8p,
+                                                  c_vp]
+            lib.edc_tmpl_batch_verify_device.argtypes = [c_vp, c_tsp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_u8p,
+                                                         ctypes.c_uint64, c_vp, c_vp]
+            lib.edc_tmpl_batch_submit.restype = ctypes.c_int64
+            lib.edc_tmpl_batch_submit.argtypes = [c_vp, c_tsp, c_sz, c_u8p, c_u32p, c_u8p, c_u16p, c_u8p, c_u32p, c_u8p,
+                                                  ctypes.c_uint64, ctypes.c_int]
+            lib.edc_vfy_queue_templated.argtypes = [c_vp, c_tsp, c_sz, c_u8p, c_u32p, c_u8p, c_u16p, c_u8p, c_u32p]
         if path is None:
             _lib = lib
         return lib
@@ -285,6 +307,27 @@ def _arena(msgs):
         total += len(m)
     offs[len(msgs)] = total
     return b"".join(bytes(m) for m in msgs) or b"\0", offs
+
+
+def _tmpl_items(tpl, holes, var_off=None):
+    """(uint16 tpl[n], var bytes, uint32 var_off[n+1]) of a templated call: the holes packed back to
+    back. var_off overrides the offsets computed from the holes (tests of the refusals)."""
+    n = len(tpl)
+    t = (ctypes.c_uint16 * max(n, 1))(*tpl)
+    if var_off is None:
+        var_off, total = [0], 0
+        for h in holes:
+            total += len(h)
+            var_off.append(total)
+    off = (ctypes.c_uint32 * (n + 1))(*var_off)
+    return t, b"".join(bytes(h) for h in holes) or b"\0", off
+
+
+def _tmpl_keys(n, vks, key_idx):
+    """(vk bytes or None, uint32 key_idx[n] or None) as the templated host entries take them."""
+    vkb = None if vks is None else (b"".join(_as_bytes(x, 32) for x in vks) or b"\0")
+    idx = None if key_idx is None else (ctypes.c_uint32 * max(n, 1))(*key_idx)
+    return vkb, idx
 
 
 class Engine:
@@ -417,6 +460,70 @@ class Engine:
                 self._check(t)
             self._host_inflight[t] = bufs
         return t
+
+    # ---- templated messages (edc_tmpl_*): msg_i = head[tpl[i]] || hole_i || tail[tpl[i]] ----
+    def tmpl_expand_device(self, templates, n, d_tpl, d_var, d_var_off, var_bytes, d_msg_out, msg_cap, d_msg_off_out):
+        """Materialise the arena and its n + 1 uint64 offsets into caller device buffers
+        (edc_tmpl_expand_device; device pointers as ints)."""
+        ts, _keep = templates.struct()
+        with self._lock:
+            rc = self.lib.edc_tmpl_expand_device(self.ctx, ctypes.byref(ts), n, d_tpl, d_var, d_var_off, var_bytes,
+                                                 d_msg_out, msg_cap, d_msg_off_out)
+        self._check(rc)
+
+    def tmpl_challenge(self, templates, vks, sigs, tpl, holes, var_off=None):
+        """edc_challenge for templated messages: the k of every item."""
+        n = len(sigs)
+        ts, _keep = templates.struct()
+        t, var, off = _tmpl_items(tpl, holes, var_off)
+        out = ctypes.create_string_buffer(max(32 * n, 1))
+        with self._lock:
+            self._check(self.lib.edc_tmpl_challenge(self.ctx, ctypes.byref(ts), n, b"".join(vks) or b"\0",
+                                                    b"".join(sigs) or b"\0", t, var, off, out))
+        return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+
+    def batch_verify_templated(self, templates, sigs, tpl, holes, z_seed, vks=None, key_idx=None, want_check8=False,
+                               var_off=None):
+        """edc_tmpl_batch_verify: (code, check8 or None). Exactly one of vks and key_idx (positions
+        in the last keycache_load list)."""
+        n = len(sigs)
+        ts, _keep = templates.struct()
+        t, var, off = _tmpl_items(tpl, holes, var_off)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        check8 = ctypes.create_string_buffer(32) if want_check8 else None
+        with self._lock:
+            rc = self.lib.edc_tmpl_batch_verify(self.ctx, ctypes.byref(ts), n, vkb, idx, b"".join(sigs) or b"\0", t, var,
+                                                off, bytes(z_seed), check8)
+        self._check(rc)
+        return rc, (check8.raw if check8 is not None else None)
+
+    def batch_verify_templated_device(self, templates, n, d_vk, d_sig, d_tpl, d_var, d_var_off, var_bytes, z_seed,
+                                      z_base=0, d_z=None, want_check8=False):
+        """edc_tmpl_batch_verify_device (device pointers as ints): (code, check8 or None)."""
+        ts, _keep = templates.struct()
+        check8 = ctypes.create_string_buffer(32) if want_check8 else None
+        with self._lock:
+            rc = self.lib.edc_tmpl_batch_verify_device(self.ctx, ctypes.byref(ts), n, d_vk, d_sig, d_tpl, d_var,
+                                                       d_var_off, var_bytes, bytes(z_seed), z_base, d_z, check8)
+        self._check(rc)
+        return rc, (check8.raw if check8 is not None else None)
+
+    def batch_submit_templated(self, templates, sigs, tpl, holes, z_seed, z_base=0, vks=None, key_idx=None,
+                               want_check8=False, var_off=None):
+        """edc_tmpl_batch_submit: a ticket for batch_wait; the host buffers, the set included, are
+        kept alive here until then."""
+        n = len(sigs)
+        ts, keep = templates.struct()
+        t, var, off = _tmpl_items(tpl, holes, var_off)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        bufs = (ts, keep, vkb, idx, b"".join(sigs) or b"\0", t, var, off, bytes(z_seed))
+        with self._lock:
+            tk = self.lib.edc_tmpl_batch_submit(self.ctx, ctypes.byref(ts), n, vkb, idx, bufs[4], t, var, off, bufs[8],
+                                                z_base, 1 if want_check8 else 0)
+            if tk < 0:
+                self._check(tk)
+            self._host_inflight[tk] = bufs
+        return tk
 
     def batch_submit_multi_device(self, nb, n_per, d_vk, d_sig, d_msg, d_off, z_seed, z_base=0, d_k=None,
                                   want_check8=False):
@@ -1004,6 +1111,40 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             return eng.verify_each_cached([it.vk_bytes.to_bytes() for it in items],
                                           [it.sig.to_bytes() for it in items], ks=[it.k for it in items])[0]
 
+    class Templates:
+        """A block's template set (struct edc_templates): message i of a templated call is
+        heads[tpl[i]] + hole_i + tails[tpl[i]]. 1..65535 templates; a head or tail may be empty."""
+
+        def __init__(self, heads, tails):
+            if len(heads) != len(tails) or not 1 <= len(heads) <= 65535:
+                raise ValueError("Templates: 1..65535 heads and as many tails")
+            self.heads = [bytes(h) for h in heads]
+            self.tails = [bytes(t) for t in tails]
+
+        @property
+        def count(self):
+            return len(self.heads)
+
+        def materialize(self, tpl, var_list):
+            """The messages as bytes, built on the host (tests and documentation)."""
+            if len(tpl) != len(var_list):
+                raise ValueError("materialize: lists of different lengths")
+            return [self.heads[t] + bytes(v) + self.tails[t] for t, v in zip(tpl, var_list)]
+
+        def struct(self):
+            """(EdcTemplates, the buffers it points into: keep them alive for the call)."""
+            def blob(parts):
+                off = (ctypes.c_uint32 * (len(parts) + 1))()
+                total = 0
+                for i, p in enumerate(parts):
+                    off[i] = total
+                    total += len(p)
+                off[len(parts)] = total
+                return b"".join(parts) or b"\0", off
+            head, head_off = blob(self.heads)
+            tail, tail_off = blob(self.tails)
+            return EdcTemplates(self.count, head, head_off, tail, tail_off), (head, head_off, tail, tail_off)
+
     class Verifier:
         """reference src/batch.rs:110-217. Items are kept in queue order; grouping by key
         bytes, hashing and the coalesced MSM run on the GPU inside verify()."""
@@ -1241,6 +1382,19 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
                 else:
                     arena, offs = _arena(msgs)
                     rc = eng.lib.edc_vfy_queue_indexed(v, n, idx, sgb, arena, offs, None)
+            eng._check(rc)
+
+        def queue_templated(self, templates, sigs, tpl, holes, vks=None, key_idx=None, var_off=None):
+            """Append len(sigs) items whose messages are templates.materialize(tpl, holes), assembled
+            on the GPU (edc_vfy_queue_templated). Exactly one of vks and key_idx."""
+            n = len(sigs)
+            eng, v = self._engine, self._handle()
+            ts, _keep = templates.struct()
+            t, var, off = _tmpl_items(tpl, holes, var_off)
+            vkb, idx = _tmpl_keys(n, vks, key_idx)
+            sgb = b"".join(_as_bytes(x, 64) for x in sigs) or b"\0"
+            with eng._lock:
+                rc = eng.lib.edc_vfy_queue_templated(v, ctypes.byref(ts), n, vkb, idx, sgb, t, var, off)
             eng._check(rc)
 
         @property

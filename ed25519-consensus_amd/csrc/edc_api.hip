@@ -19,6 +19,7 @@
 #include "edc_launch.h"
 #include "vfy_fold.h"
 #include "vfy_cached.h"
+#include "tmpl.h"
 #include "sigcache.h"
 
 using namespace edc;
@@ -61,6 +62,20 @@ constexpr uint32_t kMultiMax = 16;            // batches per edc_batch_submit_mu
 constexpr uint32_t kMultiKeys = 4096;         // distinct keys with per-(batch, key) sums; more -> per signature
 
 }  // namespace
+
+// Templated messages (edc_tmpl_*): what a slot or a verifier needs to turn one call's template set
+// and items into a message arena on the device. Grow-only; nothing of a call survives it.
+struct TmplWs {
+  uint8_t* set = nullptr;       // the call's template set: head_off | tail_off | head | tail
+  uint64_t* bsum = nullptr;     // the scan's workgroup sums
+  uint8_t* in = nullptr;        // host forms: var_off | tpl | var staged for the expansion
+  uint8_t* arena = nullptr;     // the expanded messages and their offsets (a verifier uses its own)
+  uint64_t* off = nullptr;
+  size_t set_cap = 0, bsum_cap = 0, in_cap = 0, arena_cap = 0, off_cap = 0;
+  int* flag = nullptr;          // raised by k_tmpl_len on a malformed item (device forms)
+  int* h_flag = nullptr;        // pinned mirror, read at the wait when `check` is set
+  bool check = false;
+};
 
 // One in-flight batch: its own HIP stream and every per-batch device buffer.
 struct Slot {
@@ -125,6 +140,7 @@ struct Slot {
   uint32_t n_batch = 0;
   int64_t ticket = -1;
   uint32_t probe_runs = 0;      // batches enqueued (EDC_PROBE_SKIP timing builds only)
+  TmplWs tw;                    // templated submissions (edc_tmpl_*)
   uint64_t t_submit_us = 0;     // host time of the submission (EDC_BATCH_STAMPS builds only)
 };
 
@@ -320,6 +336,13 @@ static void free_slot_buffers(Slot& s) {
   s.itembad = s.keybad = nullptr;
   free_msm_buffers(s);
   s.cap_n = s.cap_T = 0;
+}
+
+static void free_tmpl(TmplWs& w) {
+  for (void* p : {(void*)w.set, (void*)w.bsum, (void*)w.in, (void*)w.arena, (void*)w.off, (void*)w.flag})
+    if (p) (void)hipFree(p);
+  if (w.h_flag) (void)hipHostFree(w.h_flag);
+  w = TmplWs();
 }
 
 static size_t next_pow2(size_t x) {
@@ -1128,6 +1151,13 @@ static int finish_batch(edc_ctx* ctx, Slot& s, uint8_t check8[32], uint8_t parti
     ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
     return EDC_ERR_ARG;
   }
+  if (s.tw.check) {             // templated device form: the batch ran over n empty messages
+    s.tw.check = false;
+    if (*s.tw.h_flag) {
+      ctx->err = "templated items: template index or hole offsets out of range";
+      return EDC_ERR_ARG;
+    }
+  }
   if (check8) {
     if (bad) memset(check8, 0, 32);
     else memcpy(check8, s.h_out + 16, 32);
@@ -1418,6 +1448,146 @@ static int run_host_sync(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_
   return finish_batch(ctx, s, check8, nullptr, nullptr);
 }
 
+// ---- templated messages (edc_tmpl_*, include/edc.h) ----
+// message i = head[tpl[i]] || var[var_off[i] .. var_off[i+1]) || tail[tpl[i]] (Item::from, reference
+// src/batch.rs:82-94, hashes exactly these bytes). The set and the items go to the device as they
+// are, three kernels (edc_tmpl.hip) build the arena and its 64-bit offsets there, and from then on
+// every entry runs the message path's pipeline on that arena. The arena is sized from
+// tmpl_arena_bound, so nothing comes back to the host in between.
+struct TmplItems {
+  const edc_templates* ts;
+  const uint16_t* tpl;
+  const uint8_t* var;
+  const uint32_t* var_off;
+};
+
+template <typename T>
+static int tmpl_room(edc_ctx* ctx, hipStream_t st, T** p, size_t* cap, size_t need) {
+  if (need <= *cap && *p) return 0;
+  CK(hipStreamSynchronize(st));
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t c = need < 1024 ? 1024 : need + need / 8;
+  CK(dalloc(p, c));
+  *cap = c;
+  return 0;
+}
+
+static int tmpl_check(edc_ctx* ctx, const edc_templates* ts, TmplShape* shape) {
+  if (!ts || !tmpl_check_set(ts->count, ts->head, ts->head_off, ts->tail, ts->tail_off, shape)) {
+    ctx->err = "template set: count 1..65535, monotone offsets, at most 1 MiB of head and tail bytes";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// The (checked) set into w's device copy on stream st.
+static int tmpl_upload_set(edc_ctx* ctx, TmplWs& w, hipStream_t st, const edc_templates* ts, const TmplShape& sh,
+                           TmplView* view) {
+  w.check = false;
+  if (!w.flag) CK(dalloc(&w.flag, 1));
+  if (!w.h_flag) CK(hipHostMalloc((void**)&w.h_flag, sizeof(int)));
+  const size_t nof = (size_t)ts->count + 1, set_bytes = 8 * nof + sh.head_bytes + sh.tail_bytes;
+  int rc = tmpl_room(ctx, st, &w.set, &w.set_cap, set_bytes + 16);   // k_tmpl_expand copies whole 16-byte rows
+  if (rc) return rc;
+  uint8_t* head = w.set + 8 * nof;
+  CK(hipMemcpyAsync(w.set, ts->head_off, 4 * nof, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(w.set + 4 * nof, ts->tail_off, 4 * nof, hipMemcpyHostToDevice, st));
+  if (sh.head_bytes) CK(hipMemcpyAsync(head, ts->head, sh.head_bytes, hipMemcpyHostToDevice, st));
+  if (sh.tail_bytes) CK(hipMemcpyAsync(head + sh.head_bytes, ts->tail, sh.tail_bytes, hipMemcpyHostToDevice, st));
+  *view = TmplView{reinterpret_cast<const uint32_t*>(w.set), reinterpret_cast<const uint32_t*>(w.set + 4 * nof), head,
+                   head + sh.head_bytes, ts->count, sh.head_bytes, (uint32_t)set_bytes};
+  return 0;
+}
+
+// The three kernels on st: n items (device arrays) -> out (>= tmpl_arena_bound bytes) and off[n + 1].
+static int tmpl_expand(edc_ctx* ctx, TmplWs& w, hipStream_t st, const TmplView& view, size_t n, const uint16_t* d_tpl,
+                       const uint8_t* d_var, const uint32_t* d_var_off, size_t var_bytes, uint8_t* out, uint64_t* off) {
+  if (!n) return 0;
+  int rc = tmpl_room(ctx, st, &w.bsum, &w.bsum_cap, tmpl_scan_words(n));
+  if (rc) return rc;
+  CK(hipMemsetAsync(w.flag, 0, sizeof(int), st));
+  launch_tmpl_expand(st, (uint32_t)n, view, d_tpl, d_var, d_var_off, var_bytes, w.flag, w.bsum, out, off);
+  CK(hipGetLastError());
+  return 0;
+}
+
+// Host items (already checked) into w's staging area on st, then the expansion into out / off.
+static int tmpl_expand_host(edc_ctx* ctx, TmplWs& w, hipStream_t st, const TmplView& view, size_t n, const TmplItems& it,
+                            uint8_t* out, uint64_t* off) {
+  if (!n) return 0;
+  const size_t var_bytes = it.var_off[n], o_tpl = 4 * (n + 1), o_var = (o_tpl + 2 * n + 15) & ~(size_t)15;
+  if (var_bytes && !it.var) { ctx->err = "null var"; return EDC_ERR_ARG; }
+  int rc = tmpl_room(ctx, st, &w.in, &w.in_cap, o_var + var_bytes);
+  if (rc) return rc;
+  CK(hipMemcpyAsync(w.in, it.var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(w.in + o_tpl, it.tpl, 2 * n, hipMemcpyHostToDevice, st));
+  if (var_bytes) CK(hipMemcpyAsync(w.in + o_var, it.var, var_bytes, hipMemcpyHostToDevice, st));
+  return tmpl_expand(ctx, w, st, view, n, reinterpret_cast<const uint16_t*>(w.in + o_tpl), w.in + o_var,
+                     reinterpret_cast<const uint32_t*>(w.in), var_bytes, out, off);
+}
+
+// w's own arena and offsets for n items of a set with shape sh
+static int tmpl_arena_room(edc_ctx* ctx, TmplWs& w, hipStream_t st, size_t n, const TmplShape& sh, size_t var_bytes) {
+  int rc = tmpl_room(ctx, st, &w.arena, &w.arena_cap, tmpl_arena_bound(n, sh, var_bytes));
+  if (rc) return rc;
+  return tmpl_room(ctx, st, &w.off, &w.off_cap, n + 1);
+}
+
+// What every host form checks before anything is launched: the set, the items, the keys.
+static int tmpl_check_host(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                           const TmplItems& it, TmplShape* sh) {
+  int rc = tmpl_check(ctx, it.ts, sh);
+  if (rc) return rc;
+  if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
+  if (!n) return 0;
+  if (!vk == !key_idx) { ctx->err = "exactly one of vk and key_idx"; return EDC_ERR_ARG; }
+  if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (!tmpl_check_items(it.ts->count, n, it.tpl, it.var_off) || (it.var_off[n] && !it.var)) {
+    ctx->err = "templated items: template index or hole offsets out of range";
+    return EDC_ERR_ARG;
+  }
+  if (key_idx) {
+    uint32_t mx = 0;
+    for (size_t i = 0; i < n; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
+    if (mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
+  }
+  return 0;
+}
+
+// A checked host batch into slot s (as upload_slot): keys or key indices, signatures, and the
+// messages expanded into the slot's own arena.
+static int tmpl_upload_slot(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* vk, const uint32_t* key_idx,
+                            const uint8_t* sig, const TmplItems& it, const TmplShape& sh) {
+  int rc = ensure_slot_inputs(ctx, s, n, 0);
+  if (rc) return rc;
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, s.tw, s.st, it.ts, sh, &view))) return rc;
+  if (!n) return 0;
+  if ((rc = tmpl_arena_room(ctx, s.tw, s.st, n, sh, it.var_off[n]))) return rc;
+  if (key_idx) {
+    CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.st));
+    launch_expand_keys(s.st, (uint32_t)n, s.in_idx, ctx->kc_reg, ctx->kc_keys, s.in_vk);
+    CK(hipGetLastError());
+  } else {
+    CK(hipMemcpyAsync(s.in_vk, vk, n * 32, hipMemcpyHostToDevice, s.st));
+  }
+  CK(hipMemcpyAsync(s.in_sig, sig, n * 64, hipMemcpyHostToDevice, s.st));
+  return tmpl_expand_host(ctx, s.tw, s.st, view, n, it, s.tw.arena, s.tw.off);
+}
+
+// What the device forms check on the host; the items themselves are checked by k_tmpl_len.
+static int tmpl_check_device(edc_ctx* ctx, size_t n, const edc_templates* ts, const uint16_t* d_tpl, const uint8_t* d_var,
+                             const uint32_t* d_var_off, size_t var_bytes, TmplShape* sh) {
+  int rc = tmpl_check(ctx, ts, sh);
+  if (rc) return rc;
+  if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
+  if (var_bytes > 0xFFFFFFFFull) { ctx->err = "var arena must be below 4 GiB"; return EDC_ERR_ARG; }
+  if (n && (!d_tpl || !d_var_off || (var_bytes && !d_var))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  return 0;
+}
+
 extern "C" {
 
 int edc_device_count(void) {
@@ -1496,6 +1666,7 @@ void edc_destroy(edc_ctx* ctx) {
       for (void* p : mb)
         if (p) (void)hipFree(p);
     }
+    free_tmpl(s.tw);
     if (s.flags) (void)hipFree(s.flags);
     if (s.d_out) (void)hipFree(s.d_out);
     if (s.h_out) (void)hipHostFree(s.h_out);
@@ -1770,6 +1941,129 @@ int edc_challenge(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig,
   CK(hipMemcpyAsync(k_out, ctx->kbuf, n * 32, hipMemcpyDeviceToHost, ctx->st()));
   CK(hipStreamSynchronize(ctx->st()));
   return 0;
+}
+
+int edc_tmpl_expand_device(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint16_t* d_tpl, const uint8_t* d_var,
+                           const uint32_t* d_var_off, size_t var_bytes, uint8_t* d_msg_out, size_t msg_cap,
+                           uint64_t* d_msg_off_out) {
+  if (!ctx) return EDC_ERR_ARG;
+  TmplShape sh;
+  int rc = tmpl_check_device(ctx, n, ts, d_tpl, d_var, d_var_off, var_bytes, &sh);
+  if (rc) return rc;
+  if (!d_msg_off_out || (n && !d_msg_out)) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  if (n && msg_cap < tmpl_arena_bound(n, sh, var_bytes)) {
+    ctx->err = "msg_cap below n (max head + max tail) + var_bytes + 16";
+    return EDC_ERR_ARG;
+  }
+  if (n && !aligned16(d_msg_out)) { ctx->err = "the message arena must be 16-byte aligned"; return EDC_ERR_ARG; }
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = init_slot(ctx, s))) return rc;
+  if (!n) {
+    CK(hipMemsetAsync(d_msg_off_out, 0, sizeof(uint64_t), s.st));
+    CK(hipStreamSynchronize(s.st));
+    return 0;
+  }
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, s.tw, s.st, ts, sh, &view))) return rc;
+  if ((rc = tmpl_expand(ctx, s.tw, s.st, view, n, d_tpl, d_var, d_var_off, var_bytes, d_msg_out, d_msg_off_out)))
+    return rc;
+  CK(hipMemcpyAsync(s.tw.h_flag, s.tw.flag, sizeof(int), hipMemcpyDeviceToHost, s.st));
+  CK(hipStreamSynchronize(s.st));
+  if (*s.tw.h_flag) { ctx->err = "templated items: template index or hole offsets out of range"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+int edc_tmpl_challenge(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint8_t* sig,
+                       const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off, uint8_t* k_out) {
+  if (!ctx || (n && !k_out)) return EDC_ERR_ARG;
+  const TmplItems it{ts, tpl, var, var_off};
+  TmplShape sh;
+  int rc = tmpl_check_host(ctx, n, vk, nullptr, sig, it, &sh);
+  if (rc) return rc;
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = init_slot(ctx, s)) || (rc = ensure_n(ctx, n))) return rc;
+  if (!n) return 0;
+  hipStream_t st = s.st;
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, s.tw, st, ts, sh, &view)) || (rc = tmpl_arena_room(ctx, s.tw, st, n, sh, var_off[n])))
+    return rc;
+  CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
+  if ((rc = tmpl_expand_host(ctx, s.tw, st, view, n, it, s.tw.arena, s.tw.off))) return rc;
+  launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, s.tw.arena, s.tw.off, ctx->kbuf);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(k_out, ctx->kbuf, n * 32, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  return 0;
+}
+
+int edc_tmpl_batch_verify(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint32_t* key_idx,
+                          const uint8_t* sig, const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off,
+                          const uint8_t z_seed[32], uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  const TmplItems it{ts, tpl, var, var_off};
+  TmplShape sh;
+  int rc = tmpl_check_host(ctx, n, vk, key_idx, sig, it, &sh);
+  if (rc) return rc;
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = tmpl_upload_slot(ctx, s, n, vk, key_idx, sig, it, sh))) return rc;
+  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.tw.arena, s.tw.off, z_seed, 0, nullptr, check8 != nullptr, nullptr,
+                     true);
+  if (rc) return rc;
+  return finish_batch(ctx, s, check8, nullptr, nullptr);
+}
+
+int edc_tmpl_batch_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* d_vk,
+                                 const uint8_t* d_sig, const uint16_t* d_tpl, const uint8_t* d_var,
+                                 const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32], uint64_t z_base,
+                                 const uint8_t* d_z, uint8_t check8[32]) {
+  if (!ctx || (!z_seed && !d_z)) return EDC_ERR_ARG;
+  TmplShape sh;
+  int rc = tmpl_check_device(ctx, n, ts, d_tpl, d_var, d_var_off, var_bytes, &sh);
+  if (rc) return rc;
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = init_slot(ctx, s))) return rc;
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, s.tw, s.st, ts, sh, &view))) return rc;
+  if (n) {
+    if ((rc = tmpl_arena_room(ctx, s.tw, s.st, n, sh, var_bytes)) ||
+        (rc = tmpl_expand(ctx, s.tw, s.st, view, n, d_tpl, d_var, d_var_off, var_bytes, s.tw.arena, s.tw.off)))
+      return rc;
+    // the flag travels behind the expansion; the wait reads it before it believes the verdict
+    CK(hipMemcpyAsync(s.tw.h_flag, s.tw.flag, sizeof(int), hipMemcpyDeviceToHost, s.st));
+    s.tw.check = true;
+  }
+  rc = run_batch_sync(ctx, n, d_vk, d_sig, s.tw.arena, s.tw.off, z_seed, z_base, d_z, check8, nullptr, nullptr);
+  s.tw.check = false;           // also when the batch never reached its wait
+  return rc;
+}
+
+int64_t edc_tmpl_batch_submit(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint32_t* key_idx,
+                              const uint8_t* sig, const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off,
+                              const uint8_t z_seed[32], uint64_t z_base, int want_check8) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  const TmplItems it{ts, tpl, var, var_off};
+  TmplShape sh;
+  int rc = tmpl_check_host(ctx, n, vk, key_idx, sig, it, &sh);
+  if (rc) return rc;
+  CK(hipSetDevice(ctx->device));
+  const int64_t ticket = ctx->next_ticket;
+  Slot& s = ctx->slot[ticket % ctx->nslots];
+  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  if ((rc = tmpl_upload_slot(ctx, s, n, vk, key_idx, sig, it, sh))) return rc;
+  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.tw.arena, s.tw.off, z_seed, z_base, nullptr, want_check8 != 0);
+  if (rc) return rc;
+  s.ticket = ticket;
+  ctx->next_ticket++;
+  return ticket;
 }
 
 int edc_verify_prehashed_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* k,
@@ -3193,9 +3487,10 @@ static int verifier_codes_out(edc_verifier* v, const uint8_t* verdicts, uint8_t*
 // retained vk range on the device). The copies run on the copy stream; the call returns once they
 // have left the caller's memory.
 static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
-                               const uint64_t* msg_off, const uint8_t* k, const uint32_t* key_idx = nullptr) {
+                               const uint64_t* msg_off, const uint8_t* k, const uint32_t* key_idx = nullptr,
+                               const TmplItems* tm = nullptr, const TmplShape* tsh = nullptr) {
   edc_ctx* ctx = v->ctx;
-  if (m && ((!vk && !key_idx) || !sig || (!k && !msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (m && ((!vk && !key_idx) || !sig || (!k && !msg_off && !tm))) { ctx->err = "null input"; return EDC_ERR_ARG; }
   if (verifier_spent(v)) return EDC_ERR_ARG;
   if (!m) return 0;
   if (key_idx) {
@@ -3203,8 +3498,9 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
     for (size_t i = 0; i < m; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
     if (mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
   }
-  const size_t mbytes = k ? 0 : (size_t)(msg_off[m] - msg_off[0]);
-  if (mbytes && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
+  // templated items (tm, already checked): the arena is built on the device, sized by its bound
+  const size_t mbytes = k ? 0 : tm ? tmpl_arena_bound(m, *tsh, tm->var_off[m]) : (size_t)(msg_off[m] - msg_off[0]);
+  if (mbytes && !msg && !tm) { ctx->err = "null msg"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
   const bool cached = v->cached.on;
   int rc = cached ? verifier_cached_check(v, m) : 0;
@@ -3241,6 +3537,11 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
   CK(hipMemcpyAsync(r_sig, sig, m * 64, hipMemcpyHostToDevice, v->cs));
   if (k) {
     CK(hipMemcpyAsync(r_k, k, m * 32, hipMemcpyHostToDevice, v->cs));
+  } else if (tm) {
+    TmplView view;
+    if ((rc = tmpl_upload_set(ctx, s.tw, v->cs, tm->ts, *tsh, &view)) ||
+        (rc = tmpl_expand_host(ctx, s.tw, v->cs, view, m, *tm, v->msg, v->off)))
+      return rc;
   } else {
     v->rebased.resize(m + 1);
     for (size_t i = 0; i <= m; ++i) v->rebased[i] = msg_off[i] - msg_off[0];
@@ -3377,6 +3678,7 @@ void edc_verifier_destroy(edc_verifier* v) {
   if (s.st) (void)hipStreamSynchronize(s.st);
   ctx->verifiers.erase(std::remove(ctx->verifiers.begin(), ctx->verifiers.end(), v), ctx->verifiers.end());
   free_slot_buffers(s);
+  free_tmpl(s.tw);
   for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->msg, (void*)v->off, (void*)s.flags,
                   (void*)s.d_out, (void*)v->karea, (void*)v->idx, (void*)v->run, (void*)v->origin, (void*)v->st_vk,
                   (void*)v->st_sig, (void*)v->st_k, (void*)v->hit, (void*)v->wg, (void*)v->verd, (void*)v->offv})
@@ -3468,6 +3770,19 @@ int edc_vfy_queue_indexed(edc_verifier* v, size_t m, const uint32_t* key_idx, co
   if (!ctx->kc_reg_m) { ctx->err = "no registered key list (edc_keycache_load)"; return EDC_ERR_ARG; }
   if (m && !key_idx) { ctx->err = "null key_idx"; return EDC_ERR_ARG; }
   return verifier_queue_host(v, m, nullptr, sig, msg, msg_off, k, key_idx);
+}
+
+int edc_vfy_queue_templated(edc_verifier* v, const edc_templates* ts, size_t m, const uint8_t* vk,
+                            const uint32_t* key_idx, const uint8_t* sig, const uint16_t* tpl, const uint8_t* var,
+                            const uint32_t* var_off) {
+  if (!v) return EDC_ERR_ARG;
+  edc_ctx* ctx = v->ctx;
+  const TmplItems it{ts, tpl, var, var_off};
+  TmplShape sh;
+  if (key_idx && !ctx->kc_reg_m) { ctx->err = "no registered key list (edc_keycache_load)"; return EDC_ERR_ARG; }
+  int rc = tmpl_check_host(ctx, m, vk, key_idx, sig, it, &sh);
+  if (rc) return rc;
+  return verifier_queue_host(v, m, vk, sig, nullptr, nullptr, nullptr, key_idx, &it, &sh);
 }
 
 int edc_vfy_last_split(const edc_verifier* v) { return v && v->last_split >= 0 ? v->last_split : EDC_ERR_ARG; }

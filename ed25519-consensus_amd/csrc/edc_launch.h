@@ -82,6 +82,20 @@ void launch_expand_keys(hipStream_t st, uint32_t n, const uint32_t* key_idx, con
 // block, table[0..T) = 0xFFFFFFFF, counts[0..nbin) = 0 (T / nbin may be 0)
 void launch_init_batch(hipStream_t st, int* flags, int nkeys, unsigned long long* u_acc, uint8_t* d_out, uint32_t* table,
                        uint32_t T, uint32_t* counts, uint32_t nbin);
+// edc_tmpl.hip: templated messages. The device copy of a template set is one allocation,
+// head_off | tail_off (count + 1 words each) | head | tail, readable up to the next multiple of
+// 16 bytes past set_bytes.
+struct TmplView {
+  const uint32_t *head_off, *tail_off;
+  const uint8_t *head, *tail;
+  uint32_t count, head_bytes, set_bytes;
+};
+// lengths (validated: *flag, zeroed by the caller, is raised on a bad index / offset), scan and
+// expansion of n items into out / msg_off[n + 1]; out 16-byte aligned, bsum tmpl_scan_words(n) words
+void launch_tmpl_expand(hipStream_t st, uint32_t n, const TmplView& ts, const uint16_t* tpl, const uint8_t* var,
+                        const uint32_t* var_off, uint64_t var_bytes, int* flag, uint64_t* bsum, uint8_t* out,
+                        uint64_t* msg_off);
+size_t tmpl_scan_words(size_t n);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

@@ -1,0 +1,202 @@
+// Templated messages (edc_tmpl_*, include/edc.h; Item::from, reference src/batch.rs:82-94, sees
+// message i = head[tpl[i]] || var[var_off[i] .. var_off[i+1]) || tail[tpl[i]]): the message arena
+// and its 64-bit offsets are built on the device, and k_challenge runs on them unchanged.
+//
+//   k_tmpl_len      len_i with validation (flag on a bad index / offset), one sum per workgroup
+//   k_tmpl_scan     exclusive scan of the workgroup sums (one workgroup)
+//   k_tmpl_expand   msg_off[i] and the bytes: a workgroup's 256 items are one contiguous span of
+//                   the arena, written in whole aligned 16-byte stores (byte stores only in the
+//                   span's two partial end chunks, which the neighbouring workgroups share)
+//
+// The flag: k_tmpl_len raises it when tpl[i] >= count or var_off[i] <= var_off[i+1] <= var_bytes
+// does not hold. The other two kernels read it first and then produce n empty messages, so
+// nothing outside the declared arrays is read and nothing outside the workspace written.
+#include "edc_common.h"
+#include "edc_launch.h"
+
+namespace edc {
+
+constexpr int TMPL_BLOCK = 256;          // items per workgroup
+constexpr int TMPL_SCAN_THREADS = 1024;
+constexpr uint32_t TMPL_LDS_MAX = 16384; // a set up to this many bytes (offsets + blobs) is staged in LDS
+
+__global__ void __launch_bounds__(TMPL_BLOCK) k_tmpl_len(uint32_t n, TmplView ts, const uint16_t* __restrict__ tpl,
+                                                        const uint32_t* __restrict__ var_off, uint64_t var_bytes,
+                                                        int* __restrict__ flag, uint64_t* __restrict__ bsum) {
+  __shared__ uint64_t s_sum[TMPL_BLOCK];
+  const uint32_t tid = threadIdx.x, i = blockIdx.x * TMPL_BLOCK + tid;
+  uint64_t len = 0;
+  if (i < n) {
+    const uint32_t t = tpl[i], a = var_off[i], b = var_off[i + 1];
+    if (t >= ts.count || a > b || (uint64_t)b > var_bytes) atomicOr(flag, 1);
+    else len = (uint64_t)(ts.head_off[t + 1] - ts.head_off[t]) + (b - a) + (ts.tail_off[t + 1] - ts.tail_off[t]);
+  }
+  s_sum[tid] = len;
+  __syncthreads();
+#pragma unroll
+  for (int d = TMPL_BLOCK / 2; d >= 1; d >>= 1) {
+    if (tid < (uint32_t)d) s_sum[tid] += s_sum[tid + d];
+    __syncthreads();
+  }
+  if (tid == 0) bsum[blockIdx.x] = s_sum[0];
+}
+
+// bsum[0, nb) -> its exclusive prefix sums, in place; all zero when the flag is up
+__global__ void __launch_bounds__(TMPL_SCAN_THREADS) k_tmpl_scan(uint32_t nb, const int* __restrict__ flag,
+                                                                 uint64_t* __restrict__ bsum) {
+  __shared__ uint64_t s_part[TMPL_SCAN_THREADS];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t per = (nb + TMPL_SCAN_THREADS - 1) / TMPL_SCAN_THREADS;
+  const uint32_t j0 = tid * per < nb ? tid * per : nb, j1 = j0 + per < nb ? j0 + per : nb;
+  const bool bad = *flag != 0;
+  uint64_t sum = 0;
+  if (!bad)
+    for (uint32_t j = j0; j < j1; ++j) sum += bsum[j];
+  s_part[tid] = sum;
+  __syncthreads();
+  for (int d = 1; d < TMPL_SCAN_THREADS; d <<= 1) {
+    const uint64_t add = tid >= (uint32_t)d ? s_part[tid - d] : 0;
+    __syncthreads();
+    s_part[tid] += add;
+    __syncthreads();
+  }
+  uint64_t run = s_part[tid] - sum;
+  for (uint32_t j = j0; j < j1; ++j) {
+    const uint64_t v = bad ? 0 : bsum[j];
+    bsum[j] = run;
+    run += v;
+  }
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(TMPL_BLOCK) k_tmpl_expand(uint32_t n, TmplView ts, const uint16_t* __restrict__ tpl,
+                                                           const uint8_t* __restrict__ var,
+                                                           const uint32_t* __restrict__ var_off,
+                                                           const int* __restrict__ flag,
+                                                           const uint64_t* __restrict__ bsum, uint8_t* __restrict__ out,
+                                                           uint64_t* __restrict__ msg_off) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
+  // all LDS in the dynamic region: the staged set first (16-byte multiple), then the item tables
+  const uint32_t set_room = LDS ? (ts.set_bytes + 15u) & ~15u : 0u;
+  uint64_t* s_off = reinterpret_cast<uint64_t*>(s_dyn + set_room);                  // 257 span offsets
+  uint32_t* s_vo = reinterpret_cast<uint32_t*>(s_off + TMPL_BLOCK + 2);             // 257 hole offsets
+  uint16_t* s_t = reinterpret_cast<uint16_t*>(s_vo + TMPL_BLOCK + 4);               // 256 template indices
+  const uint32_t tid = threadIdx.x, i0 = blockIdx.x * TMPL_BLOCK;
+  const uint32_t cnt = n - i0 < (uint32_t)TMPL_BLOCK ? n - i0 : (uint32_t)TMPL_BLOCK;
+  const bool last = i0 + cnt == n;
+  if (*flag != 0) {                      // malformed input: n empty messages, nothing else touched
+    if (tid < cnt) msg_off[i0 + tid] = 0;
+    if (last && tid == 0) msg_off[n] = 0;
+    return;
+  }
+  const uint32_t* HO = ts.head_off;
+  const uint32_t* TO = ts.tail_off;
+  const uint8_t* H = ts.head;
+  const uint8_t* T = ts.tail;
+  if (LDS) {
+    // the device copy of the set is one piece: head_off | tail_off | head | tail (padded to 16)
+    const uint32_t* src = ts.head_off;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(s_dyn);
+    for (uint32_t w = tid; w < set_room / 4; w += TMPL_BLOCK) dst[w] = src[w];
+    HO = dst;
+    TO = dst + ts.count + 1;
+    H = s_dyn + 8u * (ts.count + 1);
+    T = H + ts.head_bytes;
+  }
+  uint64_t len = 0;
+  if (tid < cnt) {
+    const uint32_t t = tpl[i0 + tid], a = var_off[i0 + tid], b = var_off[i0 + tid + 1];
+    len = (uint64_t)(ts.head_off[t + 1] - ts.head_off[t]) + (b - a) + (ts.tail_off[t + 1] - ts.tail_off[t]);
+    s_t[tid] = (uint16_t)t;
+    s_vo[tid] = a;
+    if (tid == cnt - 1) s_vo[cnt] = b;
+  }
+  // inclusive scan of the lengths into s_off[1..]
+  s_off[tid + 1] = len;
+  if (tid == 0) s_off[0] = 0;
+  __syncthreads();
+  for (int d = 1; d < TMPL_BLOCK; d <<= 1) {
+    const uint64_t add = tid >= (uint32_t)d ? s_off[tid + 1 - d] : 0;
+    __syncthreads();
+    s_off[tid + 1] += add;
+    __syncthreads();
+  }
+  const uint64_t base = bsum[blockIdx.x];
+  const uint64_t incl = s_off[tid + 1];
+  __syncthreads();
+  s_off[tid + 1] = base + incl;
+  if (tid == 0) s_off[0] = base;
+  if (tid < cnt) msg_off[i0 + tid] = base + incl - len;
+  if (last && tid == cnt - 1) msg_off[n] = base + incl;
+  __syncthreads();
+
+  const uint64_t B = base, E = s_off[cnt];
+  for (uint64_t c = (B >> 4) + tid; c < ((E + 15) >> 4); c += TMPL_BLOCK) {
+    const uint64_t p0 = (c << 4) > B ? (c << 4) : B, p1 = (c << 4) + 16 < E ? (c << 4) + 16 : E;
+    // the item holding byte p0: the first j with s_off[j + 1] > p0 (p0 < E, so there is one)
+    uint32_t lo = 0, hi = cnt - 1;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (s_off[mid + 1] > p0) hi = mid;
+      else lo = mid + 1;
+    }
+    uint32_t j = lo;
+    uint64_t start, end;
+    uint32_t ho, hl, vo, vl, to;
+    auto item = [&]() {
+      const uint32_t t = s_t[j];
+      start = s_off[j];
+      end = s_off[j + 1];
+      ho = HO[t];
+      hl = HO[t + 1] - ho;
+      vo = s_vo[j];
+      vl = s_vo[j + 1] - vo;
+      to = TO[t];
+    };
+    item();
+    auto byte_at = [&](uint64_t p) -> uint32_t {
+      while (p >= end) {                 // empty items in between are skipped
+        ++j;
+        item();
+      }
+      const uint64_t r = p - start;
+      if (r < hl) return H[ho + (uint32_t)r];
+      if (r < (uint64_t)hl + vl) return var[(size_t)vo + (size_t)(r - hl)];
+      return T[to + (uint32_t)(r - hl - vl)];
+    };
+    if (p1 - p0 == 16) {
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 16; ++k) w[k >> 2] |= byte_at(p0 + k) << (8 * (k & 3));
+      *reinterpret_cast<uint4*>(out + p0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+      for (uint64_t p = p0; p < p1; ++p) out[p] = (uint8_t)byte_at(p);
+    }
+  }
+}
+
+static size_t tmpl_expand_lds(const TmplView& ts, bool lds) {
+  const size_t set_room = lds ? (ts.set_bytes + 15u) & ~15u : 0u;
+  return set_room + (TMPL_BLOCK + 2) * sizeof(uint64_t) + (TMPL_BLOCK + 4) * sizeof(uint32_t) +
+         TMPL_BLOCK * sizeof(uint16_t);
+}
+
+size_t tmpl_scan_words(size_t n) { return (n + TMPL_BLOCK - 1) / TMPL_BLOCK + 1; }
+
+void launch_tmpl_expand(hipStream_t st, uint32_t n, const TmplView& ts, const uint16_t* tpl, const uint8_t* var,
+                        const uint32_t* var_off, uint64_t var_bytes, int* flag, uint64_t* bsum, uint8_t* out,
+                        uint64_t* msg_off) {
+  if (!n) return;
+  const uint32_t nb = (n + TMPL_BLOCK - 1) / TMPL_BLOCK;
+  hipLaunchKernelGGL(k_tmpl_len, dim3(nb), dim3(TMPL_BLOCK), 0, st, n, ts, tpl, var_off, var_bytes, flag, bsum);
+  hipLaunchKernelGGL(k_tmpl_scan, dim3(1), dim3(TMPL_SCAN_THREADS), 0, st, nb, flag, bsum);
+  const bool lds = ts.set_bytes <= TMPL_LDS_MAX;
+  if (lds)
+    hipLaunchKernelGGL(k_tmpl_expand<true>, dim3(nb), dim3(TMPL_BLOCK), tmpl_expand_lds(ts, true), st, n, ts, tpl, var,
+                       var_off, flag, bsum, out, msg_off);
+  else
+    hipLaunchKernelGGL(k_tmpl_expand<false>, dim3(nb), dim3(TMPL_BLOCK), tmpl_expand_lds(ts, false), st, n, ts, tpl, var,
+                       var_off, flag, bsum, out, msg_off);
+}
+
+}  // namespace edc

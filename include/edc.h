@@ -617,6 +617,82 @@ int edc_vfy_verify_fallback_offered(edc_verifier* v, const uint8_t z_seed[32], u
                                     uint8_t check8[32]);
 
 /*
+ * Templated messages: a block's votes from shared heads and tails plus a per-item hole. In a
+ * canonical vote the type, height, round, block id and chain id are the same for every validator
+ * and only a short field in the middle (the timestamp) differs, so the messages that Item::from
+ * hashes (reference src/batch.rs:82-94: k = H(R || A || M)) are described as
+ *     msg_i = head[tpl[i]] || var[var_off[i] .. var_off[i+1]) || tail[tpl[i]]
+ * and assembled on the GPU: about 4 + 64 + 2 + 4 + |hole| bytes per vote over PCIe instead of a
+ * whole message and an 8-byte offset, and no hashing on the host. Everything behind the assembled
+ * arena is the message path of Verifier::queue / verify (src/batch.rs:127-217): k, verdict and
+ * check8 are bit-identical to edc_challenge / edc_batch_verify[_device] / edc_verifier_queue on the
+ * materialised messages with the same keys and z.
+ *
+ * edc_templates  the set of one call: `count` (1..65535) templates, template t's head is
+ *   head[head_off[t] .. head_off[t+1]) and its tail likewise (count + 1 monotone offsets each; a
+ *   head or tail may be empty; head and tail blobs together at most 1 MiB). Always host memory,
+ *   borrowed like the call's other host buffers; the library copies it to the device. Nothing of it
+ *   persists on the context: the height is part of the message, so the set changes every block.
+ * Items: tpl[i] (uint16_t) < count; the hole bytes packed back to back in `var` (below 4 GiB) with
+ *   n + 1 offsets var_off, var_off[0] = 0, monotone; a hole may be empty.
+ * Host forms check the set and the items before anything is launched: any violation is EDC_ERR_ARG
+ *   with nothing launched, appended or inserted. Exactly one of vk (n x 32 bytes) and key_idx
+ *   (positions in the list last given to edc_keycache_load, as edc_batch_submit_indexed; an index
+ *   outside the list is EDC_ERR_ARG).
+ * Device forms take d_tpl / d_var / d_var_off in this GPU's memory and var_bytes, the declared size
+ *   of d_var. The device checks tpl[i] < count and var_off[i] <= var_off[i+1] <= var_bytes; on any
+ *   violation the messages are assembled as n empty messages, nothing outside the declared arrays
+ *   is read, and the call returns EDC_ERR_ARG, never a verdict.
+ * The assembled arena is sized without a read-back from the bound
+ *   n (longest head + longest tail) + var_bytes + 16.
+ *
+ * edc_tmpl_expand_device  Item::from's message bytes (src/batch.rs:82-94) only: the arena into
+ *   d_msg_out (16-byte aligned, msg_cap bytes; EDC_ERR_ARG if msg_cap is below the bound above) and
+ *   the n + 1 uint64_t offsets into d_msg_off_out, ready for every *_device entry that takes a
+ *   message arena (the fallback, edc_verify_each_device, the edc_sigcache_* and multi-GPU entries,
+ *   whose Verifier::queue / verify, src/batch.rs:127-217, then run on it). Synchronous.
+ * edc_tmpl_challenge  edc_challenge (Item::from, src/batch.rs:82-94) for templated messages: the k
+ *   that Verifier::queue / verify (src/batch.rs:127-217) would take for each item; host buffers.
+ * edc_tmpl_batch_verify  edc_batch_verify (Item::from, src/batch.rs:82-94, hashed on the device;
+ *   Verifier::queue x n + verify, src/batch.rs:127-217); host buffers, synchronous, copied in one
+ *   piece.
+ * edc_tmpl_batch_verify_device  edc_batch_verify_device (src/batch.rs:82-94, :127-217) with the
+ *   messages assembled into the context's workspace first; z as edc_batch_verify_device.
+ * edc_tmpl_batch_submit  edc_batch_submit / edc_batch_submit_indexed (src/batch.rs:82-94,
+ *   :127-217): staged into the slot's own buffers, waited with edc_batch_wait; host buffers, the
+ *   set included, are borrowed until the wait.
+ * edc_vfy_queue_templated  edc_verifier_queue / edc_vfy_queue_indexed (Item::from, src/batch.rs:82-94,
+ *   and Verifier::queue x m, :127-137; verify, :149-217, later covers the items like any other):
+ *   appends m items to an incremental verifier. Once the arena is on the device the range takes the
+ *   path of edc_verifier_queue, so it works in eager and cached mode and mixes with the other queue
+ *   forms. key_idx without a registered list is EDC_ERR_ARG with nothing appended.
+ * A NULL ctx / verifier is EDC_ERR_ARG; n = 0 returns what the message entry returns for n = 0.
+ */
+typedef struct edc_templates {      /* host memory, borrowed for the call */
+  uint32_t count;
+  const uint8_t* head; const uint32_t* head_off;   /* count + 1 */
+  const uint8_t* tail; const uint32_t* tail_off;   /* count + 1 */
+} edc_templates;
+int edc_tmpl_expand_device(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint16_t* d_tpl, const uint8_t* d_var,
+                           const uint32_t* d_var_off, size_t var_bytes, uint8_t* d_msg_out, size_t msg_cap,
+                           uint64_t* d_msg_off_out);
+int edc_tmpl_challenge(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint8_t* sig,
+                       const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off, uint8_t* k_out);
+int edc_tmpl_batch_verify(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint32_t* key_idx,
+                          const uint8_t* sig, const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off,
+                          const uint8_t z_seed[32], uint8_t check8[32]);
+int edc_tmpl_batch_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* d_vk,
+                                 const uint8_t* d_sig, const uint16_t* d_tpl, const uint8_t* d_var,
+                                 const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32], uint64_t z_base,
+                                 const uint8_t* d_z, uint8_t check8[32]);
+int64_t edc_tmpl_batch_submit(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint32_t* key_idx,
+                              const uint8_t* sig, const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off,
+                              const uint8_t z_seed[32], uint64_t z_base, int want_check8);
+int edc_vfy_queue_templated(edc_verifier* v, const edc_templates* ts, size_t m, const uint8_t* vk,
+                            const uint32_t* key_idx, const uint8_t* sig, const uint16_t* tpl, const uint8_t* var,
+                            const uint32_t* var_off);
+
+/*
  * Verified-signature cache: skip the items that already verified on this context. A consensus
  * node verifies the same vote several times: once when it arrives by gossip
  * (VerificationKey::verify, src/verification_key.rs:225-258, or Item::verify_single,
