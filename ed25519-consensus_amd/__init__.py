@@ -64,6 +64,8 @@ ABI_SYMBOLS = [
     "edc_sigcache_batch_verify_fallback_device", "edc_sigcache_verify_each",
     "edc_tmpl_expand_device", "edc_tmpl_challenge", "edc_tmpl_batch_verify", "edc_tmpl_batch_verify_device",
     "edc_tmpl_batch_submit", "edc_vfy_queue_templated",
+    "edc_commits_verify_device", "edc_commits_verify", "edc_tmpl_commits_verify", "edc_commits_submit",
+    "edc_tmpl_commits_submit", "edc_commits_submit_device", "edc_commits_wait", "edc_debug_tmpl_commit_map",
 ]
 
 
@@ -280,6 +282,25 @@ def load_library(path=None):
             lib.edc_tmpl_batch_submit.argtypes = [c_vp, c_tsp, c_sz, c_u8p, c_u32p, c_u8p, c_u16p, c_u8p, c_u32p, c_u8p,
                                                   ctypes.c_uint64, ctypes.c_int]
             lib.edc_vfy_queue_templated.argtypes = [c_vp, c_tsp, c_sz, c_u8p, c_u32p, c_u8p, c_u16p, c_u8p, c_u32p]
+        if hasattr(lib, "edc_commits_verify"):               # absent from older A/B builds (tools/)
+            c_tsp, c_u16p = ctypes.POINTER(EdcTemplates), ctypes.POINTER(ctypes.c_uint16)
+            c_u32p, c_ip = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)
+            lib.edc_commits_verify_device.argtypes = [c_vp, c_sz, c_u32p, c_vp, c_vp, c_vp, c_vp, c_vp, c_u8p, c_vp,
+                                                      c_vp, c_ip]
+            lib.edc_commits_verify.argtypes = [c_vp, c_sz, c_u32p, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u8p,
+                                               c_vp, c_vp, c_ip]
+            lib.edc_tmpl_commits_verify.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, c_u8p, c_u32p, c_u8p, c_u8p,
+                                                    c_u32p, c_u8p, c_vp, c_vp, c_ip]
+            lib.edc_commits_submit.restype = ctypes.c_int64
+            lib.edc_commits_submit.argtypes = [c_vp, c_sz, c_u32p, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u8p]
+            lib.edc_tmpl_commits_submit.restype = ctypes.c_int64
+            lib.edc_tmpl_commits_submit.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, c_u8p, c_u32p, c_u8p, c_u8p,
+                                                    c_u32p, c_u8p]
+            lib.edc_commits_submit_device.restype = ctypes.c_int64
+            lib.edc_commits_submit_device.argtypes = [c_vp, c_sz, c_u32p, c_vp, c_vp, c_vp, c_vp, c_vp, c_u8p]
+            lib.edc_commits_wait.argtypes = [c_vp, ctypes.c_int64, c_vp, c_vp, c_ip]
+            lib.edc_debug_tmpl_commit_map.argtypes = [c_vp, c_sz, c_u32p, c_u16p, c_u16p, ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_float)]
         if path is None:
             _lib = lib
         return lib
@@ -347,6 +368,7 @@ class Engine:
         self._lock = threading.Lock()
         self._kc_keys = set()          # host mirror of the key cache's key bytes (keycache_missing)
         self._host_inflight = {}        # ticket -> host buffers borrowed by edc_batch_submit
+        self._commits_inflight = {}     # ticket -> (nc, n, host buffers) of a submitted commit set
         self._verifiers = weakref.WeakSet()   # open batch.StreamVerifier objects (destroyed before the context)
 
     def close(self):
@@ -524,6 +546,124 @@ class Engine:
                 self._check(tk)
             self._host_inflight[tk] = bufs
         return tk
+
+    # ---- commit sets (edc_commits_*): many variable-size batches in one launch ----
+    # commit_off: nc + 1 offsets, commit c = items [commit_off[c], commit_off[c+1]). Every result is
+    # (code, [verdict per commit], [Item::verify_single code per item], number of commits not Ok).
+    @staticmethod
+    def _commit_offsets(commit_off):
+        off = [int(x) for x in commit_off]
+        if any(x < 0 or x >= 1 << 32 for x in off):
+            raise ValueError("commit offsets are uint32")
+        nc = max(len(off) - 1, 0)
+        return nc, (ctypes.c_uint32 * max(len(off), 1))(*off)
+
+    def _commits_out(self, nc, n):
+        return ctypes.create_string_buffer(max(nc, 1)), ctypes.create_string_buffer(max(n, 1)), ctypes.c_int(0)
+
+    @staticmethod
+    def _commits_result(rc, nc, n, out):
+        return rc, list(out[0].raw[:nc]), list(out[1].raw[:n]), out[2].value
+
+    def _commits_host(self, commit_off, sigs, vks, key_idx, msgs, ks):
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        arena, moff = _arena(msgs) if msgs is not None else (None, None)
+        kb = None if ks is None else (b"".join(ks) or b"\0")
+        return nc, n, (off, vkb, idx, b"".join(sigs) or b"\0", arena, moff, kb)
+
+    def commits_verify(self, commit_off, sigs, z_seed, vks=None, key_idx=None, msgs=None, ks=None):
+        """edc_commits_verify: host buffers, synchronous. Exactly one of vks and key_idx (positions
+        in the last keycache_load list), exactly one of msgs and ks (prehashed)."""
+        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
+        out = self._commits_out(nc, n)
+        with self._lock:
+            rc = self.lib.edc_commits_verify(self.ctx, nc, *b, bytes(z_seed), out[0], out[1], ctypes.byref(out[2]))
+        self._check(rc)
+        return self._commits_result(rc, nc, n, out)
+
+    def commits_submit(self, commit_off, sigs, z_seed, vks=None, key_idx=None, msgs=None, ks=None):
+        """edc_commits_submit: a ticket for commits_wait; the host buffers are kept alive here until then."""
+        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
+        seed = bytes(z_seed)
+        with self._lock:
+            t = self.lib.edc_commits_submit(self.ctx, nc, *b, seed)
+            if t < 0:
+                self._check(t)
+            self._commits_inflight[t] = (nc, n, b, seed)
+        return t
+
+    def commits_verify_templated(self, templates, commit_off, commit_tpl, sigs, holes, z_seed, vks=None, key_idx=None,
+                                 var_off=None):
+        """edc_tmpl_commits_verify: one template per commit (commit_tpl[c]); the items carry their
+        signature, hole and key or key index."""
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        ts, _keep = templates.struct()
+        _, var, voff = _tmpl_items([0] * n, holes, var_off)
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        out = self._commits_out(nc, n)
+        with self._lock:
+            rc = self.lib.edc_tmpl_commits_verify(self.ctx, ctypes.byref(ts), nc, off, ctpl, vkb, idx,
+                                                  b"".join(sigs) or b"\0", var, voff, bytes(z_seed), out[0], out[1],
+                                                  ctypes.byref(out[2]))
+        self._check(rc)
+        return self._commits_result(rc, nc, n, out)
+
+    def commits_submit_templated(self, templates, commit_off, commit_tpl, sigs, holes, z_seed, vks=None, key_idx=None,
+                                 var_off=None):
+        """edc_tmpl_commits_submit: a ticket for commits_wait."""
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        ts, keep = templates.struct()
+        _, var, voff = _tmpl_items([0] * n, holes, var_off)
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        bufs = (ts, keep, off, ctpl, vkb, idx, b"".join(sigs) or b"\0", var, voff, bytes(z_seed))
+        with self._lock:
+            t = self.lib.edc_tmpl_commits_submit(self.ctx, ctypes.byref(ts), nc, off, ctpl, vkb, idx, bufs[6], var, voff,
+                                                 bufs[9])
+            if t < 0:
+                self._check(t)
+            self._commits_inflight[t] = (nc, n, bufs, None)
+        return t
+
+    def commits_verify_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, z_seed, d_k=None):
+        """edc_commits_verify_device (device pointers as ints; d_k given: the messages are not read)."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        out = self._commits_out(nc, n)
+        with self._lock:
+            rc = self.lib.edc_commits_verify_device(self.ctx, nc, off, d_vk, d_sig, d_msg, d_msg_off, d_k, bytes(z_seed),
+                                                    out[0], out[1], ctypes.byref(out[2]))
+        self._check(rc)
+        return self._commits_result(rc, nc, n, out)
+
+    def commits_submit_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, z_seed, d_k=None):
+        """edc_commits_submit_device: a ticket for commits_wait; the device arrays stay the caller's."""
+        nc, off = self._commit_offsets(commit_off)
+        seed = bytes(z_seed)
+        with self._lock:
+            t = self.lib.edc_commits_submit_device(self.ctx, nc, off, d_vk, d_sig, d_msg, d_msg_off, d_k, seed)
+            if t < 0:
+                self._check(t)
+            self._commits_inflight[t] = (nc, off[nc] if nc else 0, (off,), seed)
+        return t
+
+    def commits_wait(self, ticket):
+        """edc_commits_wait: the results of a submitted commit set; a failed union runs its
+        fallback here, on the ticket's own slot. The ticket's host buffers are released."""
+        with self._lock:
+            if ticket not in self._commits_inflight:
+                raise EngineError(f"ticket {ticket} is not a commit-set ticket in flight")
+            nc, n = self._commits_inflight[ticket][:2]
+            out = self._commits_out(nc, n)
+            rc = self.lib.edc_commits_wait(self.ctx, ticket, out[0], out[1], ctypes.byref(out[2]))
+            self._commits_inflight.pop(ticket, None)
+        self._check(rc)
+        return self._commits_result(rc, nc, n, out)
 
     def batch_submit_multi_device(self, nb, n_per, d_vk, d_sig, d_msg, d_off, z_seed, z_base=0, d_k=None,
                                   want_check8=False):
@@ -1230,6 +1370,44 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             if code != EDC_OK:
                 raise InvalidSignature()
             return n_miss
+
+    @staticmethod
+    def verify_many(verifiers, z_seed=None, engine=None):
+        """Verifier::verify for many Verifiers in ONE launch (a commit set, edc_commits_verify): one
+        bool per verifier, True where Verifier::verify would return Ok. The verifiers' items run as
+        one batch; only if that fails are the failing verifiers found (include/edc.h, "Commit
+        sets"). z_seed: 32 bytes, or None for fresh OS randomness (anything else than a fresh secret
+        seed is for reproducible tests only). Nothing to verify needs no engine."""
+        verifiers = list(verifiers)
+        for v in verifiers:
+            if not isinstance(v, batch.Verifier):
+                raise TypeError("verify_many takes batch.Verifier objects")
+        if z_seed is None:
+            z_seed = secrets.token_bytes(32)
+        elif not isinstance(z_seed, (bytes, bytearray)) or len(z_seed) != 32:
+            raise ValueError("z_seed: 32 bytes or None")
+        off = [0]
+        for v in verifiers:
+            off.append(off[-1] + v.batch_size)
+        if off[-1] >= 1 << 28:
+            raise ValueError("verify_many: fewer than 2^28 items in one call")
+        if off[-1] == 0:
+            return [True] * len(verifiers)
+        eng = engine or next((v._engine for v in verifiers if v._engine is not None), None) or default_engine()
+        vks = [x for v in verifiers for x in v._vks]
+        sigs = [x for v in verifiers for x in v._sigs]
+        msgs = [x for v in verifiers for x in v._msgs]
+        if all(m is not None for m in msgs):
+            res = eng.commits_verify(off, sigs, z_seed, vks=vks, msgs=msgs)
+        else:                                    # some items carry only their k: hash the rest in one launch
+            ks = [x for v in verifiers for x in v._ks]
+            need = [i for i, k in enumerate(ks) if k is None]
+            if need:
+                for i, k in zip(need, eng.challenge([vks[i] for i in need], [sigs[i] for i in need],
+                                                    [msgs[i] for i in need])):
+                    ks[i] = k
+            res = eng.commits_verify(off, sigs, z_seed, vks=vks, ks=ks)
+        return [c == EDC_OK for c in res[1]]
 
     class StreamVerifier:
         """reference src/batch.rs:110-217 with the reference's division of work: queue() does the

@@ -20,6 +20,7 @@
 #include "vfy_fold.h"
 #include "vfy_cached.h"
 #include "tmpl.h"
+#include "commits.h"
 #include "sigcache.h"
 
 using namespace edc;
@@ -122,6 +123,15 @@ struct Slot {
   uint8_t mu_seed[32] = {};
   uint64_t mu_zbase = 0;
   int mu_compress = 0;
+  // commit set (edc_commits_*): the launch ran as ONE batch over all the commits' items; its
+  // boundaries (host, borrowed until the wait) and the device inputs it read are kept, so that the
+  // wait can run the grouped fallback on this slot when that union fails
+  bool commits = false;
+  size_t cm_nc = 0;
+  const uint32_t* cm_off = nullptr;
+  const uint8_t *cm_vk = nullptr, *cm_sig = nullptr, *cm_msg = nullptr;
+  const uint64_t* cm_moff = nullptr;
+  uint8_t cm_seed[32] = {};
   hipEvent_t ev[PH_N + 1] = {};
   hipEvent_t ev_acc[2] = {};    // timed batches: around k_msm_accum_dma (edc_last_msm_accum)
   // EDC_DUAL_STREAM builds: the decode runs on a second stream beside SHA-512 / coefficients /
@@ -1116,6 +1126,7 @@ extern "C" int edc_debug_batch_stamps(uint32_t* out, size_t cap_words) {
 static int finish_batch(edc_ctx* ctx, Slot& s, uint8_t check8[32], uint8_t partial[128], int* bad_out) {
   if (!s.pending) { ctx->err = "no batch pending in this slot"; return EDC_ERR_ARG; }
   if (s.nmulti) { ctx->err = "multi-batch ticket: wait with edc_batch_wait_multi"; return EDC_ERR_ARG; }
+  if (s.commits) { ctx->err = "commit-set ticket: wait with edc_commits_wait"; return EDC_ERR_ARG; }
   s.pending = false;
   CK(hipStreamSynchronize(s.st));
   if (s.timed) {
@@ -2424,6 +2435,363 @@ int edc_batch_verify_prehashed_fallback_device(edc_ctx* ctx, size_t n, const uin
   CK(hipSetDevice(ctx->device));
   return batch_with_fallback(ctx, n, d_vk, d_sig, nullptr, nullptr, reinterpret_cast<const uint32_t*>(d_k), z_seed,
                              verdicts, n_invalid, check8);
+}
+
+}  // extern "C"
+
+// ---- commit sets (edc_commits_*, include/edc.h): many variable-size batches in one launch ----
+// n items cut into nc commits by nc + 1 host offsets, each commit its own batch::Verifier
+// (reference src/batch.rs:110-217, the per-commit flow of tests/batch.rs:18-44). The launch is ONE
+// batch over all n items, exactly enqueue_batch: the batch equation is linear, so when the union
+// holds every commit holds (finish_multi's union-first argument) and nothing else runs. When it
+// fails, the wait runs the grouped fallback on the state the batch left in ITS OWN slot and the
+// per-item codes are reduced to per-commit verdicts on the host (commits.h).
+//
+// The fallback on a slot other than 0, with other tickets in flight. What fallback_ranges and
+// verify_listed touch: the slot's own arrays and MSM workspace, on the slot's stream only; the
+// context's fb_xpt / fb_xrg / fb_xscal / fb_rv / fb_idx / fb_g, verdicts and vtab, also on that
+// stream only; and, read-only, btab, bcomb and the key cache, which cannot change while a ticket
+// is pending. Both end in hipStreamSynchronize of the slot's stream, and a context belongs to one
+// thread, so there is one fallback at a time and each finds the context's buffers idle: whoever
+// used them last has synchronized. Their growth paths (ensure_fb, ensure_n, ensure_msm) free
+// buffers no enqueued kernel reads: in-flight tickets only read their own slot's buffers (host
+// submissions are staged into in_* / tw of their slot, never into the context's vk / sig / msg).
+// The grouping state is read on the slot's stream here (slot_grouping's hipMemcpy would wait for
+// every in-flight slot).
+static int commits_check(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, size_t* n) {
+  if (!commits_check_offsets(nc, commit_off, n)) {
+    ctx->err = "commit offsets: commit_off[0] = 0, monotone, fewer than 2^28 items";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// keys of a host form: exactly one of vk and key_idx, every index inside the registered list
+static int commits_check_keys(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint32_t* key_idx) {
+  if (!vk == !key_idx) { ctx->err = "exactly one of vk and key_idx"; return EDC_ERR_ARG; }
+  if (key_idx) {
+    uint32_t mx = 0;
+    for (size_t i = 0; i < n; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
+    if (mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
+  }
+  return 0;
+}
+
+// the host checks of edc_commits_verify / _submit (nothing is launched before they pass)
+static int commits_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                              const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                              const uint8_t* k, size_t* n) {
+  int rc = commits_check(ctx, nc, commit_off, n);
+  if (rc || !*n) return rc;
+  if ((rc = commits_check_keys(ctx, *n, vk, key_idx))) return rc;
+  if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (!msg_off == !k || (msg && k)) { ctx->err = "exactly one of (msg, msg_off) and k"; return EDC_ERR_ARG; }
+  if (msg_off) {
+    if (msg_off[*n] < msg_off[0]) { ctx->err = "message offsets decrease"; return EDC_ERR_ARG; }
+    if (msg_off[*n] > msg_off[0] && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
+  } else {
+    for (size_t i = 0; i < *n; ++i) {      // Scalar::from_hash never yields k >= l
+      uint32_t w[8];
+      memcpy(w, k + 32 * i, 32);
+      if (w[7] >= 0x10000000u && !sc_is_canonical(w)) {   // below 2^252 is below l
+        ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
+        return EDC_ERR_ARG;
+      }
+    }
+  }
+  return 0;
+}
+
+static int commits_check_tmpl(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                              const uint16_t* commit_tpl, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                              const uint8_t* var, const uint32_t* var_off, TmplShape* sh, size_t* n) {
+  int rc = tmpl_check(ctx, ts, sh);
+  if (rc || (rc = commits_check(ctx, nc, commit_off, n))) return rc;
+  if (!commits_check_tpl(ts->count, nc, commit_tpl)) {
+    ctx->err = "commit templates: one index below the set's count per commit";
+    return EDC_ERR_ARG;
+  }
+  if (!*n) return 0;
+  if ((rc = commits_check_keys(ctx, *n, vk, key_idx))) return rc;
+  if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (!commits_check_holes(*n, var_off) || (var_off[*n] && !var)) {
+    ctx->err = "templated items: hole offsets out of range";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// A checked host commit set into slot s (as upload_slot / upload_slot_prehashed) and the union
+// batch behind it on the slot's stream.
+static int commits_enqueue(edc_ctx* ctx, Slot& s, size_t nc, const uint32_t* commit_off, size_t n, const uint8_t* d_vk,
+                           const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_off, const uint32_t* d_k,
+                           const uint8_t* z_seed, bool latency) {
+  int rc = enqueue_batch(ctx, s, n, d_vk, d_sig, d_msg, d_off, z_seed, 0, nullptr, 0, d_k, latency);
+  if (rc) return rc;
+  s.commits = true;
+  s.cm_nc = nc;
+  s.cm_off = commit_off;
+  s.cm_vk = d_vk;
+  s.cm_sig = d_sig;
+  s.cm_msg = d_msg;
+  s.cm_moff = d_off;
+  memcpy(s.cm_seed, z_seed, 32);
+  return 0;
+}
+
+static int commits_enqueue_host(edc_ctx* ctx, Slot& s, size_t nc, const uint32_t* commit_off, size_t n,
+                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
+                                const uint64_t* msg_off, const uint8_t* k, const uint8_t* z_seed, bool latency) {
+  static const uint64_t no_off[1] = {0};
+  int rc;
+  if (k && n) {
+    if ((rc = upload_slot_prehashed(ctx, s, n, vk, sig, k, key_idx))) return rc;
+    return commits_enqueue(ctx, s, nc, commit_off, n, s.in_vk, s.in_sig, nullptr, nullptr, s.k, z_seed, latency);
+  }
+  if ((rc = upload_slot(ctx, s, n, vk, sig, msg, n ? msg_off : no_off, key_idx))) return rc;
+  return commits_enqueue(ctx, s, nc, commit_off, n, s.in_vk, s.in_sig, s.in_msg, s.in_off, nullptr, z_seed, latency);
+}
+
+// A checked templated commit set into slot s (as tmpl_upload_slot): the per-item template array
+// is made on the device from the commit offsets (k_tmpl_commit_map), then the existing expansion.
+// Staging area: var_off | tpl | var | commit_off | commit_tpl, each at a 16-byte boundary.
+static int commits_enqueue_tmpl(edc_ctx* ctx, Slot& s, const edc_templates* ts, const TmplShape& sh, size_t nc,
+                                const uint32_t* commit_off, const uint16_t* commit_tpl, size_t n, const uint8_t* vk,
+                                const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                                const uint8_t* z_seed, bool latency) {
+  int rc = ensure_slot_inputs(ctx, s, n, 0);
+  if (rc) return rc;
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, s.tw, s.st, ts, sh, &view))) return rc;
+  if (n) {
+    TmplWs& w = s.tw;
+    hipStream_t st = s.st;
+    const size_t var_bytes = var_off[n];
+    const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_tpl = up16(4 * (n + 1)), o_var = up16(o_tpl + 2 * n), o_coff = up16(o_var + var_bytes),
+                 o_ctpl = up16(o_coff + 4 * (nc + 1));
+    if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) || (rc = tmpl_room(ctx, st, &w.in, &w.in_cap, o_ctpl + 2 * nc)))
+      return rc;
+    if (key_idx) {
+      CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      launch_expand_keys(st, (uint32_t)n, s.in_idx, ctx->kc_reg, ctx->kc_keys, s.in_vk);
+      CK(hipGetLastError());
+    } else {
+      CK(hipMemcpyAsync(s.in_vk, vk, n * 32, hipMemcpyHostToDevice, st));
+    }
+    CK(hipMemcpyAsync(s.in_sig, sig, n * 64, hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(w.in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
+    if (var_bytes) CK(hipMemcpyAsync(w.in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(w.in + o_coff, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(w.in + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
+    uint16_t* d_tpl = reinterpret_cast<uint16_t*>(w.in + o_tpl);
+    launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(w.in + o_coff),
+                           reinterpret_cast<const uint16_t*>(w.in + o_ctpl), d_tpl);
+    CK(hipGetLastError());
+    if ((rc = tmpl_expand(ctx, w, st, view, n, d_tpl, w.in + o_var, reinterpret_cast<const uint32_t*>(w.in), var_bytes,
+                          w.arena, w.off)))
+      return rc;
+  }
+  return commits_enqueue(ctx, s, nc, commit_off, n, s.in_vk, s.in_sig, s.tw.arena, s.tw.off, nullptr, z_seed, latency);
+}
+
+// Wait for a commit-set slot. The union passed: every commit Ok. It failed: the grouped fallback on
+// this slot (k, decoded points, grouping, failure bits and z seed of the failed batch; the inputs
+// are still borrowed or staged in the slot), then the reduction to commits.
+static int commits_finish(edc_ctx* ctx, Slot& s, uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad) {
+  const size_t nc = s.cm_nc;
+  const uint32_t* off = s.cm_off;
+  const size_t n = nc ? off[nc] : 0;
+  s.commits = false;
+  if (n_bad) *n_bad = 0;
+  int rc = finish_batch(ctx, s, nullptr, nullptr, nullptr);
+  if (rc < 0) return rc;
+  if (rc == EDC_OK) {
+    if (commit_verdicts && nc) memset(commit_verdicts, 0, nc);
+    if (item_verdicts && n) memset(item_verdicts, 0, n);
+    return EDC_OK;
+  }
+  int f[FLAG_COUNT];
+  CK(hipMemcpyAsync(f, s.flags, sizeof(f), hipMemcpyDeviceToHost, s.st));
+  CK(hipStreamSynchronize(s.st));
+  const bool per_sig = s.per_sig || f[FLAG_OVF] != 0;
+  std::vector<uint8_t> own;
+  uint8_t* codes = item_verdicts;
+  if (!codes) {
+    own.resize(n);
+    codes = own.data();
+  }
+  rc = fallback_ranges(ctx, s, n, s.cm_vk, s.cm_sig, s.cm_msg, s.cm_moff, s.cm_seed, 0, per_sig, (uint32_t)f[FLAG_NKEYS],
+                       codes);
+  if (rc < 0) return rc;
+  const size_t bad = commits_reduce(nc, off, codes, commit_verdicts);
+  if (n_bad) *n_bad = (int)bad;
+  return bad ? EDC_INVALID_SIGNATURE : EDC_OK;
+}
+
+// the slot of the next ticket, or the reason there is none
+static int commits_next_slot(edc_ctx* ctx, Slot** s) {
+  *s = &ctx->slot[ctx->next_ticket % ctx->nslots];
+  if ((*s)->pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+static int64_t commits_ticket(edc_ctx* ctx, Slot& s) {
+  s.ticket = ctx->next_ticket;
+  return ctx->next_ticket++;
+}
+
+// nc == 0 of a synchronous form: nothing to verify
+static int commits_none(int* n_bad) {
+  if (n_bad) *n_bad = 0;
+  return EDC_OK;
+}
+
+extern "C" {
+
+int edc_commits_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                              const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                              const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                              int* n_bad_commits) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  if (!nc) return commits_none(n_bad_commits);
+  size_t n;
+  int rc = commits_check(ctx, nc, commit_off, &n);
+  if (rc) return rc;
+  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  rc = commits_enqueue(ctx, s, nc, commit_off, n, d_vk, d_sig, d_k ? nullptr : d_msg, d_k ? nullptr : d_msg_off,
+                       reinterpret_cast<const uint32_t*>(d_k), z_seed, true);
+  if (rc) return rc;
+  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+}
+
+int edc_commits_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
+                       const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k,
+                       const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  if (!nc) return commits_none(n_bad_commits);
+  size_t n;
+  int rc = commits_check_host(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, &n);
+  if (rc) return rc;
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_host(ctx, s, nc, commit_off, n, vk, key_idx, sig, msg, msg_off, k, z_seed, true))) return rc;
+  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+}
+
+int edc_tmpl_commits_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                            const uint16_t* commit_tpl, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                            const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32],
+                            uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  if (!nc) return commits_none(n_bad_commits);
+  size_t n;
+  TmplShape sh;
+  int rc = commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, vk, key_idx, sig, var, var_off, &sh, &n);
+  if (rc) return rc;
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_tmpl(ctx, s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
+                                 true)))
+    return rc;
+  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+}
+
+int64_t edc_commits_submit_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                  const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                  const uint8_t* d_k, const uint8_t z_seed[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  size_t n = 0;
+  int rc = nc ? commits_check(ctx, nc, commit_off, &n) : 0;
+  if (rc) return rc;
+  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  Slot* s;
+  if ((rc = commits_next_slot(ctx, &s))) return rc;
+  CK(hipSetDevice(ctx->device));
+  rc = commits_enqueue(ctx, *s, nc, commit_off, n, d_vk, d_sig, d_k ? nullptr : d_msg, d_k ? nullptr : d_msg_off,
+                       reinterpret_cast<const uint32_t*>(d_k), z_seed, false);
+  if (rc) return rc;
+  return commits_ticket(ctx, *s);
+}
+
+int64_t edc_commits_submit(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                           const uint8_t* k, const uint8_t z_seed[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  size_t n = 0;
+  int rc = nc ? commits_check_host(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, &n) : 0;
+  if (rc) return rc;
+  Slot* s;
+  if ((rc = commits_next_slot(ctx, &s))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_host(ctx, *s, nc, commit_off, n, vk, key_idx, sig, msg, msg_off, k, z_seed, false))) return rc;
+  return commits_ticket(ctx, *s);
+}
+
+int64_t edc_tmpl_commits_submit(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, const uint8_t* vk, const uint32_t* key_idx,
+                                const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                                const uint8_t z_seed[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  size_t n = 0;
+  TmplShape sh;
+  int rc = nc ? commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, vk, key_idx, sig, var, var_off, &sh, &n)
+              : tmpl_check(ctx, ts, &sh);
+  if (rc) return rc;
+  Slot* s;
+  if ((rc = commits_next_slot(ctx, &s))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_tmpl(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
+                                 false)))
+    return rc;
+  return commits_ticket(ctx, *s);
+}
+
+int edc_commits_wait(edc_ctx* ctx, int64_t ticket, uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                     int* n_bad_commits) {
+  if (!ctx || ticket < 0) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  Slot& s = ctx->slot[ticket % ctx->nslots];
+  if (!s.pending || s.ticket != ticket) { ctx->err = "unknown or already-waited ticket"; return EDC_ERR_ARG; }
+  if (!s.commits) { ctx->err = "not a commit-set ticket: wait with edc_batch_wait / edc_batch_wait_multi"; return EDC_ERR_ARG; }
+  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+}
+
+int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
+                              uint16_t* tpl_out, int reps, float* ms) {
+  if (!ctx || !nc || !commit_tpl || reps < 1) return EDC_ERR_ARG;
+  size_t n;
+  int rc = commits_check(ctx, nc, commit_off, &n);
+  if (rc) return rc;
+  if (n && !tpl_out) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t o_ctpl = up16(4 * (nc + 1)), o_tpl = up16(o_ctpl + 2 * nc);
+  if ((rc = init_slot(ctx, s)) || (rc = ensure_aux(ctx, o_tpl + 2 * n))) return rc;
+  hipStream_t st = s.st;
+  CK(hipMemcpyAsync(ctx->aux, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->aux + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
+  CK(hipEventRecord(s.ev[0], st));
+  for (int r = 0; r < reps; ++r)
+    launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(ctx->aux),
+                           reinterpret_cast<const uint16_t*>(ctx->aux + o_ctpl),
+                           reinterpret_cast<uint16_t*>(ctx->aux + o_tpl));
+  CK(hipGetLastError());
+  CK(hipEventRecord(s.ev[1], st));
+  if (n) CK(hipMemcpyAsync(tpl_out, ctx->aux + o_tpl, 2 * n, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  if (ms) {
+    CK(hipEventElapsedTime(ms, s.ev[0], s.ev[1]));
+    *ms /= (float)reps;
+  }
+  return 0;
 }
 
 int edc_decompress(edc_ctx* ctx, size_t n, const uint8_t* enc, uint8_t* xy, uint8_t* ok) {

@@ -96,6 +96,10 @@ void launch_tmpl_expand(hipStream_t st, uint32_t n, const TmplView& ts, const ui
                         const uint32_t* var_off, uint64_t var_bytes, int* flag, uint64_t* bsum, uint8_t* out,
                         uint64_t* msg_off);
 size_t tmpl_scan_words(size_t n);
+// commit sets with one template per commit: tpl[i] = commit_tpl[c] for the commit c holding item i
+// (nc + 1 checked offsets, commit_off[nc] = n; empty commits allowed). All device pointers.
+void launch_tmpl_commit_map(hipStream_t st, uint32_t n, uint32_t nc, const uint32_t* commit_off,
+                            const uint16_t* commit_tpl, uint16_t* tpl);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

@@ -7,6 +7,8 @@
 //   k_tmpl_expand   msg_off[i] and the bytes: a workgroup's 256 items are one contiguous span of
 //                   the arena, written in whole aligned 16-byte stores (byte stores only in the
 //                   span's two partial end chunks, which the neighbouring workgroups share)
+//   k_tmpl_commit_map  commit sets with one template per commit: the per-item tpl array from the
+//                   commit offsets, in front of the three kernels above
 //
 // The flag: k_tmpl_len raises it when tpl[i] >= count or var_off[i] <= var_off[i+1] <= var_bytes
 // does not hold. The other two kernels read it first and then produce n empty messages, so
@@ -173,6 +175,65 @@ __global__ void __launch_bounds__(TMPL_BLOCK) k_tmpl_expand(uint32_t n, TmplView
       for (uint64_t p = p0; p < p1; ++p) out[p] = (uint8_t)byte_at(p);
     }
   }
+}
+
+// Commit sets with one template per commit (edc_tmpl_commits_*): tpl[i] = commit_tpl[c] for the
+// commit c that holds item i, i.e. the largest c with commit_off[c] <= i (after a run of repeated
+// offsets, the empty commits, that is the one the item is in; commit_off[c + 1] > i). The host has
+// checked the offsets (commit_off[0] = 0, monotone, commit_off[nc] = n) and commit_tpl.
+constexpr int TMPL_MAP_ITEMS = 8;        // consecutive items per lane: one 16-byte store
+
+// largest c in [lo, hi] with off[c] <= i (off[lo] <= i)
+__device__ __forceinline__ uint32_t tmpl_commit_of(const uint32_t* __restrict__ off, uint32_t lo, uint32_t hi, uint32_t i) {
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+    if (off[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(TMPL_BLOCK) k_tmpl_commit_map(uint32_t n, uint32_t nc,
+                                                               const uint32_t* __restrict__ commit_off,
+                                                               const uint16_t* __restrict__ commit_tpl,
+                                                               uint16_t* __restrict__ tpl) {
+  // the workgroup's items [g0, g1]: their commits bound every lane's search (two searches over all
+  // nc offsets with workgroup-uniform addresses, then a few steps per lane)
+  const uint32_t g0 = blockIdx.x * (uint32_t)(TMPL_BLOCK * TMPL_MAP_ITEMS);
+  const uint32_t g1 = (n - g0 < (uint32_t)(TMPL_BLOCK * TMPL_MAP_ITEMS) ? n : g0 + TMPL_BLOCK * TMPL_MAP_ITEMS) - 1;
+  const uint32_t clo = tmpl_commit_of(commit_off, 0, nc - 1, g0), chi = tmpl_commit_of(commit_off, clo, nc - 1, g1);
+  const uint32_t i0 = g0 + threadIdx.x * TMPL_MAP_ITEMS;
+  if (i0 >= n) return;
+  uint32_t c = tmpl_commit_of(commit_off, clo, chi, i0);
+  uint32_t end = commit_off[c + 1], t = commit_tpl[c];
+  const uint32_t cnt = n - i0 < (uint32_t)TMPL_MAP_ITEMS ? n - i0 : (uint32_t)TMPL_MAP_ITEMS;
+  uint32_t w[TMPL_MAP_ITEMS / 2] = {0, 0, 0, 0};
+#pragma unroll
+  for (uint32_t j = 0; j < (uint32_t)TMPL_MAP_ITEMS; ++j) {
+    if (j < cnt) {
+      while (i0 + j >= end) {            // next commit, empty ones skipped; i0 + j < n = commit_off[nc] ends it
+        ++c;
+        end = commit_off[c + 1];
+        t = commit_tpl[c];
+      }
+      w[j >> 1] |= t << (16 * (j & 1));
+    }
+  }
+  if (cnt == (uint32_t)TMPL_MAP_ITEMS && (reinterpret_cast<uintptr_t>(tpl) & 15u) == 0) {
+    *reinterpret_cast<uint4*>(tpl + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+  } else {
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)TMPL_MAP_ITEMS; ++j)
+      if (j < cnt) tpl[i0 + j] = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+  }
+}
+
+void launch_tmpl_commit_map(hipStream_t st, uint32_t n, uint32_t nc, const uint32_t* commit_off,
+                            const uint16_t* commit_tpl, uint16_t* tpl) {
+  if (!n || !nc) return;
+  const uint32_t per = TMPL_BLOCK * TMPL_MAP_ITEMS;
+  hipLaunchKernelGGL(k_tmpl_commit_map, dim3((n + per - 1) / per), dim3(TMPL_BLOCK), 0, st, n, nc, commit_off,
+                     commit_tpl, tpl);
 }
 
 static size_t tmpl_expand_lds(const TmplView& ts, bool lds) {

@@ -693,6 +693,97 @@ int edc_vfy_queue_templated(edc_verifier* v, const edc_templates* ts, size_t m, 
                             const uint32_t* var_off);
 
 /*
+ * Commit sets: many variable-size batches in one launch. Block sync, a light client catching up
+ * and a node replaying a chain hold thousands of commits, each its own batch::Verifier (reference
+ * src/batch.rs:110-217) over the ~150 precommits of one height, each with its own verdict (the
+ * per-commit flow of reference tests/batch.rs:18-44). A commit set is n items in queue order with
+ * nc + 1 offsets commit_off (uint32_t, host memory): commit_off[0] = 0, monotone,
+ * commit_off[nc] = n < 2^28; commit c is items [commit_off[c], commit_off[c+1]), empty commits
+ * allowed. It is verified as nc independent Verifiers:
+ *  - commit_verdicts (host, nc bytes, nullable): commit c's EDC_OK or EDC_INVALID_SIGNATURE, what
+ *    edc_batch_verify_device returns for commit c alone with a fresh seed (Verifier::verify,
+ *    src/batch.rs:149-217, reports a malformed key as InvalidSignature too; an empty Verifier
+ *    verifies, so an empty commit is EDC_OK).
+ *  - item_verdicts (host, n bytes, nullable): Item::verify_single's code (src/batch.rs:104-107) of
+ *    every item, as edc_batch_verify_fallback_device; all zeros when the launch passes.
+ *  - *n_bad_commits (nullable): the number of commits that are not EDC_OK.
+ *  - Returns EDC_OK if every commit passed, EDC_INVALID_SIGNATURE if any did not, <0 on a runtime
+ *    or argument failure.
+ * Union first: the launch runs as ONE batch over all n items, item i drawing z at index i of
+ * z_seed's stream: exactly the pipeline of edc_batch_verify_device, no kernel and no
+ * synchronization more. Its equation is the sum of the commits' equations, so when it holds every
+ * commit holds, with the probability batch verification itself gives (the argument of
+ * edc_batch_submit_multi_device). When it fails, the grouped fallback of
+ * edc_batch_verify_fallback_device runs on the state the failed batch left in its slot (k, decoded
+ * points, key grouping, failure bits, the same z_seed; nothing is uploaded or hashed again), and a
+ * commit is EDC_INVALID_SIGNATURE iff one of its items has a non-zero code.
+ * Soundness: as edc_batch_verify_fallback_device (edc_find_invalid_device above). An item of a
+ * passing range, and a commit of a passing launch, is reported valid because a batch equation
+ * holds; this relies on z being unpredictable to whoever made the signatures. z_seed MUST be fresh
+ * and secret for every call (e.g. 32 bytes of OS randomness); a known or reused seed lets crafted
+ * invalid signatures cancel inside a launch or a range and be reported valid.
+ *
+ * edc_commits_verify_device  Verifier::queue x n + verify per commit (src/batch.rs:127-137,
+ *   :149-217) on device-resident inputs; synchronous, on slot 0 like the other synchronous entries.
+ *   Device arrays as the other *_device entries (same alignment rules); d_k nullable: when given,
+ *   the messages are not read (d_msg / d_msg_off may be NULL).
+ * edc_commits_verify  the host-buffer form (src/batch.rs:127-137, :149-217): exactly one of vk and
+ *   key_idx (positions in the list last given to edc_keycache_load), exactly one of
+ *   (msg, msg_off) and k (prehashed, canonical scalars < l). Staged into the slot in one piece.
+ * edc_tmpl_commits_verify  templated messages (above; Item::from, src/batch.rs:82-94, then
+ *   src/batch.rs:127-137, :149-217) with ONE TEMPLATE PER COMMIT: commit_tpl[c] (uint16_t, host,
+ *   nc entries, each < ts->count) is the template of every item of commit c, as height and block
+ *   id are the commit's. The items carry only sig, their hole (var, var_off as the edc_tmpl_*
+ *   entries) and vk or key_idx; the per-item template array is made on the device.
+ * edc_commits_submit / edc_tmpl_commits_submit / edc_commits_submit_device  the asynchronous forms
+ *   (src/batch.rs:127-137, :149-217 per commit), under the rules of edc_batch_submit /
+ *   edc_batch_submit_device: a ticket >= 0 (or <0), inputs (commit_off too) borrowed until the
+ *   wait, tickets waited in submission order.
+ * edc_commits_wait  waits for the ticket; if the union failed, the grouped fallback
+ *   (src/batch.rs:104-107 per item) runs ON THE TICKET'S OWN SLOT, where the inputs are still
+ *   staged or borrowed, while other tickets stay in flight on theirs. A commit-set ticket given to
+ *   edc_batch_wait or edc_batch_wait_multi, and a batch or multi-batch ticket given to
+ *   edc_commits_wait, is EDC_ERR_ARG and stays pending. With nc = 1 this is the streamed
+ *   batch-with-fallback that the streaming entries (edc_batch_submit*, whose edc_batch_wait returns
+ *   one bit) never had: a failed batch gets its per-item codes without a second upload.
+ * Every argument is checked on the host before anything is launched; a violation is EDC_ERR_ARG
+ *   with nothing launched: NULL ctx or z_seed, both or neither of a one-of pair, commit_off[0] != 0,
+ *   a decreasing offset, n >= 2^28, commit_tpl[c] >= count, a template set or hole offsets the
+ *   edc_tmpl_* host forms refuse, a key index outside the registered list, a prehashed k >= l in
+ *   the host forms (a device d_k is checked by the batch itself: EDC_ERR_ARG from the call / the
+ *   wait, never a verdict). nc = 0 returns EDC_OK from the synchronous forms (commit_off is not
+ *   read); the asynchronous forms return a ticket whose wait returns EDC_OK.
+ * edc_debug_tmpl_commit_map  test / measurement hook: the commit-to-item template map alone
+ *   (tpl_out[i] = commit_tpl[c] for the commit c holding item i; host arrays, checked as above),
+ *   run `reps` times between HIP events; *ms (nullable) = the mean kernel time.
+ */
+int edc_commits_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                              const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                              const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                              int* n_bad_commits);
+int edc_commits_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
+                       const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k,
+                       const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits);
+int edc_tmpl_commits_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                            const uint16_t* commit_tpl, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                            const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32],
+                            uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits);
+int64_t edc_commits_submit(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                           const uint8_t* k, const uint8_t z_seed[32]);
+int64_t edc_tmpl_commits_submit(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, const uint8_t* vk, const uint32_t* key_idx,
+                                const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                                const uint8_t z_seed[32]);
+int64_t edc_commits_submit_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                  const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                  const uint8_t* d_k, const uint8_t z_seed[32]);
+int edc_commits_wait(edc_ctx* ctx, int64_t ticket, uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                     int* n_bad_commits);
+int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
+                              uint16_t* tpl_out, int reps, float* ms);
+
+/*
  * Verified-signature cache: skip the items that already verified on this context. A consensus
  * node verifies the same vote several times: once when it arrives by gossip
  * (VerificationKey::verify, src/verification_key.rs:225-258, or Item::verify_single,
