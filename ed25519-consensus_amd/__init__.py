@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "edc_tmpl_batch_submit", "edc_vfy_queue_templated",
     "edc_commits_verify_device", "edc_commits_verify", "edc_tmpl_commits_verify", "edc_commits_submit",
     "edc_tmpl_commits_submit", "edc_commits_submit_device", "edc_commits_wait", "edc_debug_tmpl_commit_map",
+    "edc_debug_live_allocs",
 ]
 
 
@@ -135,6 +136,8 @@ def load_library(path=None):
             lib.edc_combine_records_device.argtypes = [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]
         if hasattr(lib, "edc_debug_sc_reduce_wide"):
             lib.edc_debug_sc_reduce_wide.argtypes = [c_vp, c_sz, c_vp, c_vp]
+        if hasattr(lib, "edc_debug_live_allocs"):            # absent from older A/B builds (--lib)
+            lib.edc_debug_live_allocs.argtypes = [c_u64p]
         lib.edc_batch_submit_device.restype = ctypes.c_int64
         lib.edc_batch_submit_device.argtypes = [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_u8p, ctypes.c_uint64, c_vp,
                                                 ctypes.c_int]
@@ -1006,6 +1009,14 @@ class MultiEngine:
                                                           arena, offs, bytes(z_seed), v, ctypes.byref(cnt), check8)
         self._check(rc)
         return rc, list(v.raw[:n]), cnt.value, check8.raw
+
+
+def debug_live_allocs():
+    """edc_debug_live_allocs: (live device allocations, live pinned allocations) of this process's library objects."""
+    out = (ctypes.c_uint64 * 2)()
+    if load_library().edc_debug_live_allocs(out) != 0:
+        raise EngineError("edc_debug_live_allocs failed")
+    return int(out[0]), int(out[1])
 
 
 _default_engine = None

@@ -22,8 +22,10 @@
 #include "tmpl.h"
 #include "commits.h"
 #include "sigcache.h"
+#include "devbuf.h"
 
 using namespace edc;
+using namespace devbuf;
 
 namespace {
 
@@ -31,13 +33,6 @@ namespace {
 enum Phase { PH_KEYS, PH_CHALLENGE, PH_COEF, PH_MSM_BIN, PH_DECOMP, PH_MSM_BUCKET, PH_MSM_TAIL, PH_N };
 const char* kPhaseNames[PH_N] = {"keys_group", "challenge_sha512", "coef_chacha_scalar", "msm_bin",
                                  "decompress_R", "msm_bucket", "msm_window_final"};
-
-template <typename T>
-hipError_t dalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  return hipMalloc((void**)p, count * sizeof(T));
-}
 
 #ifndef EDC_SLOTS
 #define EDC_SLOTS 16
@@ -67,49 +62,56 @@ constexpr uint32_t kMultiKeys = 4096;         // distinct keys with per-(batch, 
 // Templated messages (edc_tmpl_*): what a slot or a verifier needs to turn one call's template set
 // and items into a message arena on the device. Grow-only; nothing of a call survives it.
 struct TmplWs {
-  uint8_t* set = nullptr;       // the call's template set: head_off | tail_off | head | tail
-  uint64_t* bsum = nullptr;     // the scan's workgroup sums
-  uint8_t* in = nullptr;        // host forms: var_off | tpl | var staged for the expansion
-  uint8_t* arena = nullptr;     // the expanded messages and their offsets (a verifier uses its own)
-  uint64_t* off = nullptr;
-  size_t set_cap = 0, bsum_cap = 0, in_cap = 0, arena_cap = 0, off_cap = 0;
-  int* flag = nullptr;          // raised by k_tmpl_len on a malformed item (device forms)
-  int* h_flag = nullptr;        // pinned mirror, read at the wait when `check` is set
+  DevBuf<uint8_t> set;          // the call's template set: head_off | tail_off | head | tail
+  DevBuf<uint64_t> bsum;        // the scan's workgroup sums
+  DevBuf<uint8_t> in;           // host forms: var_off | tpl | var staged for the expansion
+  DevBuf<uint8_t> arena;        // the expanded messages and their offsets (a verifier uses its own)
+  DevBuf<uint64_t> off;
+  DevBuf<int> flag;             // raised by k_tmpl_len on a malformed item (device forms)
+  PinnedBuf<int> h_flag;        // pinned mirror, read at the wait when `check` is set
   bool check = false;
 };
 
 // One in-flight batch: its own HIP stream and every per-batch device buffer.
 struct Slot {
-  hipStream_t st = nullptr;
+  // streams and events are declared first: members are destroyed in reverse order, so every buffer
+  // of the slot is freed before the streams and events it was used on
+  Stream st;
+  // EDC_DUAL_STREAM builds: the decode runs on a second stream beside SHA-512 / coefficients /
+  // binning (joined before the accumulation)
+  Stream st2;
+  Event ev_keys, ev_dec;
+  Event ev[PH_N + 1];
+  Event ev_acc[2];              // timed batches: around k_msm_accum_dma (edc_last_msm_accum)
   size_t cap_n = 0, cap_T = 0;
-  uint32_t *k = nullptr, *key_slot = nullptr, *key_index = nullptr, *key_rep = nullptr;
+  DevBuf<uint32_t> k, key_slot, key_index, key_rep;
   // the batch's challenges: k (computed by k_challenge) or a prehashed caller's device array
+  // (borrowed)
   const uint32_t* kin = nullptr;
-  uint32_t *table = nullptr, *slot_key = nullptr;
-  uint32_t *pts = nullptr, *scal = nullptr;
-  unsigned long long *key_acc = nullptr, *u_acc = nullptr;
-  uint32_t* coef_part = nullptr;     // k_coef's per-workgroup key slots (merged by k_coef_merge)
-  uint8_t *itembad = nullptr, *keybad = nullptr;   // per-item / per-key failure bits (fallback)
+  DevBuf<uint32_t> table, slot_key;
+  DevBuf<uint32_t> pts, scal;
+  DevBuf<unsigned long long> key_acc, u_acc;
+  DevBuf<uint32_t> coef_part;        // k_coef's per-workgroup key slots (merged by k_coef_merge)
+  DevBuf<uint8_t> itembad, keybad;   // per-item / per-key failure bits (fallback)
   // MSM workspace, grown on demand to the plan's bins / entries
   uint32_t cap_bins = 0, cap_ranges = 0;
   size_t cap_entries = 0;
-  uint32_t *counts = nullptr, *offsets = nullptr, *cursor = nullptr;
-  uint2* entries = nullptr;
-  uint32_t* sorted = nullptr;   // entries' point indices sorted by bucket within each bin
-  uint32_t *slice_W = nullptr, *slice_T = nullptr, *win = nullptr;
-  uint32_t* buckets = nullptr;  // bins x 256 bucket sums (extended)
-  uint32_t* heads = nullptr;    // bins x 256 head partials of the segmented accumulation
-  uint32_t* bucket_end = nullptr;   // bins x 256 bucket end positions of the sorted entries
-  int* flags = nullptr;
-  uint8_t* d_out = nullptr;     // 256-byte result block (kMultiMax of them for a multi-batch launch)
-  uint8_t* h_out = nullptr;     // pinned mirror
-  uint32_t* h_acc = nullptr;    // pinned: the last bin's offset and count (timed batches' entry count)
+  DevBuf<uint32_t> counts, offsets, cursor;
+  DevBuf<uint2> entries;
+  DevBuf<uint32_t> sorted;      // entries' point indices sorted by bucket within each bin
+  DevBuf<uint32_t> slice_W, slice_T, win;
+  DevBuf<uint32_t> buckets;     // bins x 256 bucket sums (extended)
+  DevBuf<uint32_t> heads;       // bins x 256 head partials of the segmented accumulation
+  DevBuf<uint32_t> bucket_end;  // bins x 256 bucket end positions of the sorted entries
+  DevBuf<int> flags;
+  DevBuf<uint8_t> d_out;        // 256-byte result block (kMultiMax of them for a multi-batch launch)
+  PinnedBuf<uint8_t> h_out;     // pinned mirror
+  PinnedBuf<uint32_t> h_acc;    // pinned: the last bin's offset and count (timed batches' entry count)
   // several batches in one launch (edc_batch_submit_multi_device): per-(batch, key) sums, listed
   // key / B terms, per-batch bad flags; nmulti = batches of the pending launch (0: one batch)
-  unsigned long long* mb_acc = nullptr;
-  uint32_t *mb_xpt = nullptr, *mb_xrg = nullptr, *mb_xscal = nullptr;
-  uint8_t* mb_bad = nullptr;
-  size_t mb_cap_acc = 0, mb_cap_terms = 0;
+  DevBuf<unsigned long long> mb_acc;
+  DevBuf<uint32_t> mb_xpt, mb_xrg, mb_xscal;
+  DevBuf<uint8_t> mb_bad;
   uint32_t nmulti = 0;
   uint32_t acc_nbin = 0;        // bins of the last enqueued single-batch MSM (timing report)
   // union-first multi launch (edc_set_multi_union): the launch ran as ONE batch over all nb * n_per
@@ -132,17 +134,11 @@ struct Slot {
   const uint8_t *cm_vk = nullptr, *cm_sig = nullptr, *cm_msg = nullptr;
   const uint64_t* cm_moff = nullptr;
   uint8_t cm_seed[32] = {};
-  hipEvent_t ev[PH_N + 1] = {};
-  hipEvent_t ev_acc[2] = {};    // timed batches: around k_msm_accum_dma (edc_last_msm_accum)
-  // EDC_DUAL_STREAM builds: the decode runs on a second stream beside SHA-512 / coefficients /
-  // binning (joined before the accumulation)
-  hipStream_t st2 = nullptr;
-  hipEvent_t ev_keys = nullptr, ev_dec = nullptr;
   // host-buffer submissions (edc_batch_submit): this slot's own device copy of the inputs
-  uint8_t *in_vk = nullptr, *in_sig = nullptr, *in_msg = nullptr;
-  uint64_t* in_off = nullptr;
-  uint32_t* in_idx = nullptr;         // key indices (edc_batch_submit_indexed)
-  size_t in_cap_n = 0, in_cap_msg = 0;
+  DevBuf<uint8_t> in_vk, in_sig, in_msg;
+  DevBuf<uint64_t> in_off;
+  DevBuf<uint32_t> in_idx;            // key indices (edc_batch_submit_indexed)
+  size_t in_cap_n = 0;
   std::vector<uint64_t> in_rebased;   // offsets rebased to 0 (host side, alive until the slot is reused)
   bool pending = false;         // submitted, not yet waited
   bool timed = false;
@@ -157,20 +153,30 @@ struct Slot {
 struct edc_ctx {
   int device = 0;
   std::string err;
-  uint32_t* btab = nullptr;     // [1..8]B, affine Niels
+  // streams and events are declared first (the slots' own likewise): members are destroyed in
+  // reverse order, so every buffer of the context is freed before them.
+  // Chunked synchronous host-buffer calls (run_host_chunked): two copy streams and one event per
+  // chunk (+ the keys / offsets piece) each, created together on first use
+  Stream hcs, hcs2;
+  Event hev[9], hev2[9];        // piece 0 + signature chunks / k or message chunks
+  // recorded after every deferred insert of a cached verifier (which returns without waiting for
+  // it): every other access to the table first orders itself after it, so that lookup and insert
+  // never run together across streams either. sc_ev_set: it has been recorded at least once
+  Event sc_ev;
+  bool sc_ev_set = false;
+  DevBuf<uint32_t> btab;        // [1..8]B, affine Niels
   Slot slot[kSlots];
   // staging for the host-pointer entry points (used on slot 0's stream)
-  size_t cap_n = 0, cap_msg = 0, cap_aux = 0;
-  uint8_t *vk = nullptr, *sig = nullptr, *msg = nullptr, *zexp = nullptr;
-  uint64_t* off = nullptr;
-  uint32_t* kbuf = nullptr;
-  uint8_t* verdicts = nullptr;
-  uint32_t* vtab = nullptr;     // per-item multiples tables of the per-signature kernel
-  uint8_t* aux = nullptr;       // decode xy / sign outputs / partials
+  size_t cap_n = 0;
+  DevBuf<uint8_t> vk, sig, msg, zexp;
+  DevBuf<uint64_t> off;
+  DevBuf<uint32_t> kbuf;
+  DevBuf<uint8_t> verdicts;
+  DevBuf<uint32_t> vtab;        // per-item multiples tables of the per-signature kernel
+  DevBuf<uint8_t> aux;          // decode xy / sign outputs / partials
   // shard-partial combination on its own stream, so it never waits behind in-flight batches
   Slot comb;
-  uint8_t* comb_in = nullptr;   // g x 128-byte partial records
-  size_t comb_cap = 0;
+  DevBuf<uint8_t> comb_in;      // g x 128-byte partial records
   bool timing = false;
   float last_ms[PH_N] = {};
   float last_acc_ms = 0.f;      // k_msm_accum_dma of the last timed batch
@@ -189,26 +195,25 @@ struct edc_ctx {
   uint64_t secret = 0;          // key-grouping hash secret (OS randomness, per context)
   uint64_t nbatches = 0;
   // grouped fallback (range MSM) staging, slot 0 only
-  size_t fb_cap_terms = 0, fb_cap_ranges = 0;
-  uint32_t *fb_xpt = nullptr, *fb_xrg = nullptr, *fb_xscal = nullptr;
-  uint8_t* fb_rv = nullptr;      // per-range verdict | pre-bad flag
-  uint32_t* fb_idx = nullptr;    // items verified one by one
-  size_t fb_cap_idx = 0;
-  uint8_t* fb_g = nullptr;       // their gathered vk | sig | k (fb_cap_g items each)
-  size_t fb_cap_g = 0;
+  size_t fb_cap_terms = 0;
+  DevBuf<uint32_t> fb_xpt, fb_xrg, fb_xscal;
+  DevBuf<uint8_t> fb_rv;         // per-range verdict | pre-bad flag (2 x ranges + 64 bytes)
+  DevBuf<uint32_t> fb_idx;       // items verified one by one
+  DevBuf<uint8_t> fb_g;          // their gathered vk | sig | k (fb_cap_g items each)
+  size_t fb_cap_g = 0;           // items fb_idx and fb_g are sized for
   uint32_t fb_ranges = 128;     // target range count of the grouped fallback (sweep: profiles/r04/r04ad_fb_sweep.log)
   int fb_bits = 9;              // its window width
   // persistent validator-key cache (keycache.h), replaced by each edc_keycache_load, grown by
   // edc_keycache_add (device arrays hold kc_cap keys; the host keeps the key words and ok bytes
   // to rebuild the hash table and answer duplicates)
-  uint32_t *kc_table = nullptr, *kc_keys = nullptr, *kc_comb = nullptr;
-  uint8_t* kc_ok = nullptr;
-  uint32_t* bcomb = nullptr;    // comb table of B, built with the first cache
+  DevBuf<uint32_t> kc_table, kc_keys, kc_comb;
+  DevBuf<uint8_t> kc_ok;
+  DevBuf<uint32_t> bcomb;       // comb table of B, built with the first cache
   uint32_t kc_m = 0, kc_tmask = 0, kc_cap = 0;
   uint32_t kc_s0 = 0, kc_s1 = 0;        // table hash key, from `secret`
   std::vector<uint32_t> kc_words;       // kc_m x 8 raw key words
   std::vector<uint8_t> kc_okh;          // kc_m decode flags
-  uint32_t* kc_reg = nullptr;   // registered position -> cache index (edc_batch_submit_indexed)
+  DevBuf<uint32_t> kc_reg;      // registered position -> cache index (edc_batch_submit_indexed)
   uint32_t kc_reg_m = 0;
   // split coefficients (edc_common.h) while the key cache covers the batches' keys:
   // key_split 0 = auto, 1 = never; last_uncached = keys the last batch did not find in the cache
@@ -222,34 +227,27 @@ struct edc_ctx {
   // per-call staging (hit flags, workgroup counts, miss index list, gathered misses, verdicts)
   // and the counters. The one-call entries use it on slot 0's stream; cached verifiers
   // (edc_vfy_set_cached) look up and insert on their own streams, see sc_ev
-  unsigned long long* sc_hdr = nullptr;
-  uint4* sc_rec = nullptr;
+  DevBuf<unsigned long long> sc_hdr;
+  DevBuf<uint4> sc_rec;
   size_t sc_cap = 0;                    // records (a power of two); 0 = no table
   uint32_t sc_gen = 1, sc_keep = 2;
   uint64_t sc_k0 = 0, sc_k1 = 0;        // table hash key, from `secret`
   uint64_t sc_hits = 0, sc_misses = 0;
-  unsigned long long* sc_ctr = nullptr; // device: records written, inserts dropped
-  unsigned long long* sc_hctr = nullptr;   // pinned mirror (+ word 2: the miss count of the last lookup)
+  DevBuf<unsigned long long> sc_ctr;    // device: records written, inserts dropped
+  PinnedBuf<unsigned long long> sc_hctr;   // pinned mirror (+ word 2: the miss count of the last lookup)
   size_t sc_cap_n = 0;
-  uint8_t *sc_hit = nullptr, *sc_g = nullptr, *sc_verd = nullptr, *sc_mverd = nullptr;
-  uint32_t *sc_wg = nullptr, *sc_idx = nullptr;
-  // recorded after every deferred insert of a cached verifier (which returns without waiting for
-  // it): every other access to the table first orders itself after it, so that lookup and insert
-  // never run together across streams either. sc_ev_set: it has been recorded at least once
-  hipEvent_t sc_ev = nullptr;
-  bool sc_ev_set = false;
+  DevBuf<uint8_t> sc_hit, sc_g, sc_verd, sc_mverd;
+  DevBuf<uint32_t> sc_wg, sc_idx;
+  // the returned view borrows the table
   SigCacheView sc() const {
     return SigCacheView{sc_hdr, sc_rec, (uint32_t)(sc_cap - 1), sc_gen, sc_keep, sc_k0, sc_k1};
   }
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
-  // chunked synchronous host-buffer calls (run_host_chunked): a copy stream and one event per
-  // chunk (+ the keys / offsets piece), created on first use
-  hipStream_t hcs = nullptr, hcs2 = nullptr;
-  hipEvent_t hev[9] = {}, hev2[9] = {};   // piece 0 + signature chunks / k or message chunks
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
   std::vector<struct edc_verifier*> verifiers;
   hipStream_t st() const { return slot[0].st; }
+  // the returned view borrows the cache
   KeyCacheView kc() const {
     if (!kc_m) return KeyCacheView{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0};
     return KeyCacheView{kc_table, kc_keys, kc_ok, kc_comb, kc_tmask, kc_m, bcomb, kc_s0, kc_s1};
@@ -262,37 +260,38 @@ struct edc_ctx {
 // decoded keys in the key area, failure bits, flags) persist from queue to queue.
 struct edc_verifier {
   edc_ctx* ctx = nullptr;
+  // streams and events are declared first (the slot's own likewise): members are destroyed in
+  // reverse order, so every buffer of the verifier is freed before them
+  Stream cs;                    // copy stream: an append's copies overlap the previous append's kernels
+  Event ev_copy, ev_chal;
+  Event ev_cnt, ev_gather;      // cached mode, see below
   Slot s;                       // never the context's slot 0: other calls keep working between queues
-  hipStream_t cs = nullptr;     // copy stream: an append's copies overlap the previous append's kernels
-  hipEvent_t ev_copy = nullptr, ev_chal = nullptr;
   size_t n = 0, cap = 0;        // queued items / items the retained arrays and the key table are sized for
-  uint8_t *vk = nullptr, *sig = nullptr, *zexp = nullptr;
-  uint32_t* k = nullptr;
-  uint8_t* msg = nullptr;       // one append's message arena and offsets (dead once its k exists)
-  uint64_t* off = nullptr;
-  size_t cap_msg = 0, cap_off = 0;
+  DevBuf<uint8_t> vk, sig, zexp;
+  DevBuf<uint32_t> k;
+  DevBuf<uint8_t> msg;          // one append's message arena and offsets (dead once its k exists)
+  DevBuf<uint64_t> off;
   bool chal_pending = false;    // ev_chal guards msg / off against the next append's copies
   uint32_t T = 0;               // key table slots in use (a power of two, <= s.cap_T)
   uint32_t salt[2] = {0, 0};    // fixed until reset
   std::vector<uint64_t> rebased;
   // key areas (their own allocation, 2 s.cap_n records): rows [0, cap_n) the decoded keys in
   // key-index order, rows [cap_n, 2 cap_n) their [2^128] multiples (split coefficients)
-  uint32_t* karea = nullptr;
+  DevBuf<uint32_t> karea;
   size_t karea_cap = 0;         // the s.cap_n it was sized for
   // the [2^128] rows are usable while every range since the last reset was queued with a key
   // cache loaded and that cache's generation (edc_ctx::kc_gen) is still hi_gen
   uint64_t hi_gen = 0;
   bool hi_ok = false;
   int last_split = -1;          // plan of the last verify: 1 split, 0 unsplit, -1 none yet
-  uint32_t* idx = nullptr;      // one indexed append's key positions (edc_vfy_queue_indexed)
-  size_t cap_idx = 0;
+  DevBuf<uint32_t> idx;         // one indexed append's key positions (edc_vfy_queue_indexed)
   // eager mode (edc_vfy_begin_eager): the block's z seed is committed before the items arrive and
   // queue calls fold sum [z_i]R_i of the items [fold.folded, n) into the running point `run`
   // (EXT_WORDS words, then the 256-byte result block of the last fold's MSM); verify's MSM then
   // leaves those R terms out and adds `run` before the x8. Both survive a growth.
   FoldState fold;
   uint8_t eager_seed[32] = {};
-  uint32_t* run = nullptr;
+  DevBuf<uint32_t> run;
   // cached mode (edc_vfy_set_cached): a queue call stages its range (st_*), looks it up in the
   // context's verified-signature table and appends only the misses; origin[i] = offered position
   // of retained item i. hit / wg: the range's lookup flags and workgroup miss counts (+ total);
@@ -300,15 +299,13 @@ struct edc_verifier {
   // range's gather, which is the last reader of the staging area; verd / offv: per-item codes of a
   // fallback on the device (retained order, offered order)
   CachedState cached;
-  uint32_t* origin = nullptr;
-  uint8_t *st_vk = nullptr, *st_sig = nullptr, *hit = nullptr;
-  uint32_t *st_k = nullptr, *wg = nullptr;
+  DevBuf<uint32_t> origin;
+  DevBuf<uint8_t> st_vk, st_sig, hit;
+  DevBuf<uint32_t> st_k, wg;
   size_t st_cap = 0;
-  uint32_t* h_cnt = nullptr;
-  hipEvent_t ev_cnt = nullptr, ev_gather = nullptr;
+  PinnedBuf<uint32_t> h_cnt;
   bool gather_pending = false;
-  uint8_t *verd = nullptr, *offv = nullptr;
-  size_t verd_cap = 0, offv_cap = 0;
+  DevBuf<uint8_t> verd, offv;
 };
 
 // A failed HIP call also leaves the thread's last-error state set; it is cleared here, so that a
@@ -323,66 +320,18 @@ struct edc_verifier {
     }                                                                   \
   } while (0)
 
-static void free_msm_buffers(Slot& s) {
-  void* ptrs[] = {s.counts, s.offsets, s.cursor, s.slice_W, s.slice_T, s.win, s.buckets, s.heads, s.entries, s.sorted,
-                  s.bucket_end};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  s.counts = s.offsets = s.cursor = s.slice_W = s.slice_T = s.win = s.buckets = s.heads = s.sorted = nullptr;
-  s.bucket_end = nullptr;
-  s.entries = nullptr;
-  s.cap_bins = s.cap_ranges = 0;
-  s.cap_entries = 0;
-}
-
-static void free_slot_buffers(Slot& s) {
-  void* ptrs[] = {s.k, s.key_slot, s.key_index, s.key_rep, s.table, s.slot_key, s.pts, s.scal, s.key_acc,
-                  s.u_acc, s.itembad, s.keybad, s.coef_part};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  s.k = s.key_slot = s.key_index = s.key_rep = s.table = s.slot_key = s.pts = s.scal = nullptr;
-  s.key_acc = s.u_acc = nullptr;
-  s.coef_part = nullptr;
-  s.itembad = s.keybad = nullptr;
-  free_msm_buffers(s);
-  s.cap_n = s.cap_T = 0;
-}
-
-static void free_tmpl(TmplWs& w) {
-  for (void* p : {(void*)w.set, (void*)w.bsum, (void*)w.in, (void*)w.arena, (void*)w.off, (void*)w.flag})
-    if (p) (void)hipFree(p);
-  if (w.h_flag) (void)hipHostFree(w.h_flag);
-  w = TmplWs();
-}
-
-static size_t next_pow2(size_t x) {
-  size_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
 // Every in-flight slot needs its own hardware queue: kernels of streams that share a queue run
-// in order, so one batch's latency-bound tail would stall the bulk kernels of another. Streams
-// created with an (all-CU) mask get a dedicated queue instead of one of the runtime's shared pool
-// (GPU_MAX_HW_QUEUES, 4 by default, one of which the process's default stream already holds).
-static hipError_t create_slot_stream(int device, hipStream_t* st) {
-  int cus = 0;
-  hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  if (e != hipSuccess || cus <= 0) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-  std::vector<uint32_t> mask((cus + 31) / 32, 0xFFFFFFFFu);
-  if (cus % 32) mask.back() = (1u << (cus % 32)) - 1u;
-  return hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data());
-}
-
+// in order, so one batch's latency-bound tail would stall the bulk kernels of another; hence the
+// slot streams are created with an all-CU mask (Stream::create_all_cus).
 static int init_slot(edc_ctx* ctx, Slot& s) {
   if (s.st) return 0;
-  CK(create_slot_stream(ctx->device, &s.st));
-  CK(dalloc(&s.flags, FLAG_ALLOC));
-  CK(dalloc(&s.d_out, 256 * kMultiMax));
-  CK(hipHostMalloc((void**)&s.h_out, 256 * kMultiMax));
-  CK(hipHostMalloc((void**)&s.h_acc, 2 * sizeof(uint32_t)));
-  for (int p = 0; p <= PH_N; ++p) CK(hipEventCreate(&s.ev[p]));
-  for (int p = 0; p < 2; ++p) CK(hipEventCreate(&s.ev_acc[p]));
+  CK(s.st.create_all_cus(ctx->device));
+  CK(s.flags.alloc(FLAG_ALLOC));
+  CK(s.d_out.alloc(256 * kMultiMax));
+  CK(s.h_out.alloc(256 * kMultiMax));
+  CK(s.h_acc.alloc(2));
+  for (Event& e : s.ev) CK(e.create());
+  for (Event& e : s.ev_acc) CK(e.create());
 #if EDC_DUAL_STREAM
   // 1: every slot; 2: slot 0 only (the synchronous calls' slot), so the pipelined slots keep one
   // hardware queue each (past ~16 user queues per GPU the scheduler time-slices them).
@@ -390,9 +339,9 @@ static int init_slot(edc_ctx* ctx, Slot& s) {
   // that must not overlap the decode with SHA-512) keeps every slot on one stream.
   static const bool single_stream = getenv("EDC_SINGLE_STREAM") && getenv("EDC_SINGLE_STREAM")[0] == '1';
   if (!single_stream && (EDC_DUAL_STREAM == 1 || &s == &ctx->slot[0])) {
-    CK(create_slot_stream(ctx->device, &s.st2));
-    CK(hipEventCreateWithFlags(&s.ev_keys, hipEventDisableTiming));
-    CK(hipEventCreateWithFlags(&s.ev_dec, hipEventDisableTiming));
+    CK(s.st2.create_all_cus(ctx->device));
+    CK(s.ev_keys.create(hipEventDisableTiming));
+    CK(s.ev_dec.create(hipEventDisableTiming));
   }
 #endif
   return 0;
@@ -401,29 +350,27 @@ static int init_slot(edc_ctx* ctx, Slot& s) {
 static int ensure_slot(edc_ctx* ctx, Slot& s, size_t n) {
   int rc = init_slot(ctx, s);
   if (rc) return rc;
-  if (n <= s.cap_n && s.pts) return 0;
-  CK(hipStreamSynchronize(s.st));
-  free_slot_buffers(s);
-  const size_t cap = n < 1024 ? 1024 : n + n / 8;
-  const size_t T = next_pow2(2 * cap);
-  CK(dalloc(&s.k, cap * 8));
-  CK(dalloc(&s.key_slot, cap));
-  CK(dalloc(&s.key_index, cap));
-  CK(dalloc(&s.key_rep, cap));
-  CK(dalloc(&s.table, T));
-  CK(dalloc(&s.slot_key, T));
-  // >= msm_num_points_split(n, m) for any m <= n (split coefficients add m + 1 points)
-  CK(dalloc(&s.pts, (3 + 3 * cap) * NIELS_WORDS));
-  CK(dalloc(&s.scal, (3 + 3 * cap) * 8));
-  CK(dalloc(&s.key_acc, cap * KEY_ACC_LIMBS));
-  CK(dalloc(&s.u_acc, (cap / COEF_CHUNK + 2) * KEY_ACC_LIMBS));   // one sum per fallback range
-  CK(dalloc(&s.coef_part, coef_part_words(cap)));
-  CK(dalloc(&s.itembad, 2 * cap));   // [0, cap): s bits (k_coef), [cap, 2 cap): R bits (k_decompress)
-  CK(dalloc(&s.keybad, cap));
-  launch_init_basepoint(s.st, s.pts);
-  CK(hipGetLastError());
-  s.cap_n = cap;
-  s.cap_T = T;
+  CK(grow_group(s.cap_n, n, item_cap, sync_of(s.st), [&](size_t cap) {
+    const size_t T = next_pow2(2 * cap);
+    s.cap_T = 0;
+    s.cap_bins = s.cap_ranges = 0;   // the MSM workspace goes with the slot's arrays
+    s.cap_entries = 0;
+    reset_all(s.counts, s.offsets, s.cursor, s.slice_W, s.slice_T, s.win, s.buckets, s.heads, s.bucket_end, s.entries,
+              s.sorted);
+    hipError_t e = alloc_all(
+        sized(s.k, cap * 8), sized(s.key_slot, cap), sized(s.key_index, cap), sized(s.key_rep, cap), sized(s.table, T),
+        sized(s.slot_key, T),
+        // >= msm_num_points_split(n, m) for any m <= n (split coefficients add m + 1 points)
+        sized(s.pts, (3 + 3 * cap) * NIELS_WORDS), sized(s.scal, (3 + 3 * cap) * 8), sized(s.key_acc, cap * KEY_ACC_LIMBS),
+        sized(s.u_acc, (cap / COEF_CHUNK + 2) * KEY_ACC_LIMBS),   // one sum per fallback range
+        sized(s.coef_part, coef_part_words(cap)),
+        sized(s.itembad, 2 * cap),   // [0, cap): s bits (k_coef), [cap, 2 cap): R bits (k_decompress)
+        sized(s.keybad, cap));
+    if (e != hipSuccess) return e;
+    launch_init_basepoint(s.st, s.pts);
+    if ((e = hipGetLastError()) == hipSuccess) s.cap_T = T;
+    return e;
+  }));
   return 0;
 }
 
@@ -431,41 +378,23 @@ static int ensure_slot(edc_ctx* ctx, Slot& s, size_t n) {
 static int ensure_msm(edc_ctx* ctx, Slot& s, const MsmPlan& P, size_t entries) {
   const uint32_t nbin = P.nbin();
   if (nbin > MSM_MAX_BINS || P.nwin > MSM_MAX_WIN) { ctx->err = "MSM plan too large"; return EDC_ERR_ARG; }
-  if (nbin > s.cap_bins || P.nranges > s.cap_ranges) {
+  if (nbin > s.cap_bins || P.nranges > s.cap_ranges) {   // two capacities: each keeps its maximum
     CK(hipStreamSynchronize(s.st));
-    for (void* p : {(void*)s.counts, (void*)s.offsets, (void*)s.cursor, (void*)s.slice_W, (void*)s.slice_T,
-                    (void*)s.win, (void*)s.buckets, (void*)s.heads, (void*)s.bucket_end})
-      if (p) (void)hipFree(p);
     const uint32_t nb = nbin > s.cap_bins ? nbin : s.cap_bins;
     const uint32_t nr = P.nranges > s.cap_ranges ? P.nranges : (s.cap_ranges ? s.cap_ranges : 1);
-    s.counts = s.offsets = s.cursor = s.slice_W = s.slice_T = s.win = s.buckets = s.heads = nullptr;
-    s.bucket_end = nullptr;
     s.cap_bins = s.cap_ranges = 0;
-    CK(dalloc(&s.counts, nb));
-    CK(dalloc(&s.offsets, nb));
-    CK(dalloc(&s.cursor, nb));
-    CK(dalloc(&s.slice_W, (size_t)nb * EXT_WORDS));
-    CK(dalloc(&s.slice_T, (size_t)nb * EXT_WORDS));
-    CK(dalloc(&s.win, (size_t)nr * MSM_MAX_WIN * EXT_WORDS));
-    CK(dalloc(&s.buckets, msm_bucket_words(nb)));
-    CK(dalloc(&s.heads, msm_bucket_words(nb)));
-    CK(dalloc(&s.bucket_end, (size_t)nb * NSLICE));
+    CK(alloc_all(sized(s.counts, nb), sized(s.offsets, nb), sized(s.cursor, nb), sized(s.slice_W, (size_t)nb * EXT_WORDS),
+                 sized(s.slice_T, (size_t)nb * EXT_WORDS), sized(s.win, (size_t)nr * MSM_MAX_WIN * EXT_WORDS),
+                 sized(s.buckets, msm_bucket_words(nb)), sized(s.heads, msm_bucket_words(nb)),
+                 sized(s.bucket_end, (size_t)nb * NSLICE)));
     s.cap_bins = nb;
     s.cap_ranges = nr;
   }
-  if (entries > s.cap_entries) {
-    CK(hipStreamSynchronize(s.st));
-    if (s.entries) (void)hipFree(s.entries);
-    if (s.sorted) (void)hipFree(s.sorted);
-    s.entries = nullptr;
-    s.sorted = nullptr;
-    s.cap_entries = 0;
-    const size_t cap = entries + entries / 8 + 1024;
-    CK(dalloc(&s.entries, cap));
-    // + 256 per possible bin: each bin's lane-major region is padded to whole rounds (k_msm_sort)
-    CK(dalloc(&s.sorted, cap + 256 * (size_t)MSM_MAX_BINS));
-    s.cap_entries = cap;
-  }
+  if (entries > s.cap_entries)
+    CK(grow_group(s.cap_entries, entries, entry_cap, sync_of(s.st), [&](size_t cap) {
+      // + 256 per possible bin: each bin's lane-major region is padded to whole rounds (k_msm_sort)
+      return alloc_all(sized(s.entries, cap), sized(s.sorted, cap + 256 * (size_t)MSM_MAX_BINS));
+    }));
   return 0;
 }
 
@@ -591,40 +520,20 @@ static bool choose_split(const edc_ctx* ctx) {
 
 // host-staging buffers (inputs of the host-pointer entry points, per-item outputs)
 static int ensure_n(edc_ctx* ctx, size_t n) {
-  if (n <= ctx->cap_n && ctx->vk) return 0;
-  CK(hipStreamSynchronize(ctx->st()));
-  void* ptrs[] = {ctx->vk, ctx->sig, ctx->zexp, ctx->off, ctx->kbuf, ctx->verdicts, ctx->vtab};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  const size_t cap = n < 1024 ? 1024 : n + n / 8;
-  CK(dalloc(&ctx->vtab, verify_single_scratch_words(cap)));
-  CK(dalloc(&ctx->vk, cap * 32));
-  CK(dalloc(&ctx->sig, cap * 64));
-  CK(dalloc(&ctx->zexp, cap * 16));
-  CK(dalloc(&ctx->off, cap + 1));
-  CK(dalloc(&ctx->kbuf, cap * 8));
-  CK(dalloc(&ctx->verdicts, cap));
-  ctx->cap_n = cap;
+  CK(grow_group(ctx->cap_n, n, item_cap, sync_of(ctx->st()), [&](size_t cap) {
+    return alloc_all(sized(ctx->vtab, verify_single_scratch_words(cap)), sized(ctx->vk, cap * 32), sized(ctx->sig, cap * 64),
+                     sized(ctx->zexp, cap * 16), sized(ctx->off, cap + 1), sized(ctx->kbuf, cap * 8), sized(ctx->verdicts, cap));
+  }));
   return 0;
 }
 
 static int ensure_msg(edc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->cap_msg && ctx->msg) return 0;
-  CK(hipStreamSynchronize(ctx->st()));
-  if (ctx->msg) (void)hipFree(ctx->msg);
-  size_t cap = bytes < 4096 ? 4096 : bytes + bytes / 8;
-  CK(dalloc(&ctx->msg, cap));
-  ctx->cap_msg = cap;
+  CK(grow(ctx->msg, bytes, byte_cap, sync_of(ctx->st())));
   return 0;
 }
 
 static int ensure_aux(edc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->cap_aux && ctx->aux) return 0;
-  CK(hipStreamSynchronize(ctx->st()));
-  if (ctx->aux) (void)hipFree(ctx->aux);
-  size_t cap = bytes < 4096 ? 4096 : bytes + bytes / 8;
-  CK(dalloc(&ctx->aux, cap));
-  ctx->cap_aux = cap;
+  CK(grow(ctx->aux, bytes, byte_cap, sync_of(ctx->st())));
   return 0;
 }
 
@@ -676,31 +585,10 @@ static int upload(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig,
 static int ensure_slot_inputs(edc_ctx* ctx, Slot& s, size_t n, size_t mbytes) {
   int rc = init_slot(ctx, s);
   if (rc) return rc;
-  if (n > s.in_cap_n || !s.in_vk) {
-    CK(hipStreamSynchronize(s.st));
-    void* in[] = {s.in_vk, s.in_sig, s.in_off, s.in_idx};
-    for (void* p : in)
-      if (p) (void)hipFree(p);
-    s.in_vk = s.in_sig = nullptr;
-    s.in_off = nullptr;
-    s.in_idx = nullptr;
-    s.in_cap_n = 0;
-    const size_t cap = n < 1024 ? 1024 : n + n / 8;
-    CK(dalloc(&s.in_vk, cap * 32));
-    CK(dalloc(&s.in_sig, cap * 64));
-    CK(dalloc(&s.in_off, cap + 1));
-    CK(dalloc(&s.in_idx, cap));
-    s.in_cap_n = cap;
-  }
-  if (mbytes > s.in_cap_msg || !s.in_msg) {
-    CK(hipStreamSynchronize(s.st));
-    if (s.in_msg) (void)hipFree(s.in_msg);
-    s.in_msg = nullptr;
-    s.in_cap_msg = 0;
-    const size_t cap = mbytes < 4096 ? 4096 : mbytes + mbytes / 8;
-    CK(dalloc(&s.in_msg, cap));
-    s.in_cap_msg = cap;
-  }
+  CK(grow_group(s.in_cap_n, n, item_cap, sync_of(s.st), [&](size_t cap) {
+    return alloc_all(sized(s.in_vk, cap * 32), sized(s.in_sig, cap * 64), sized(s.in_off, cap + 1), sized(s.in_idx, cap));
+  }));
+  CK(grow(s.in_msg, mbytes, byte_cap, sync_of(s.st)));
   return 0;
 }
 
@@ -957,23 +845,11 @@ static int enqueue_multi(edc_ctx* ctx, Slot& s, uint32_t nb, size_t n_per, const
   const size_t full_max = (N > (size_t)nb * kstride ? N : (size_t)nb * kstride) + nb;
   rc = ensure_msm(ctx, s, P, msm_entry_capacity(P, N, full_max));
   if (rc) return rc;
-  if ((size_t)nb * kstride * KEY_ACC_LIMBS > s.mb_cap_acc || nx_max > s.mb_cap_terms || !s.mb_bad) {
+  if ((size_t)nb * kstride * KEY_ACC_LIMBS > s.mb_acc.cap() || nx_max > s.mb_xpt.cap() || !s.mb_bad) {
     CK(hipStreamSynchronize(s.st));
-    void* mb[] = {s.mb_acc, s.mb_xpt, s.mb_xrg, s.mb_xscal, s.mb_bad};
-    for (void* p : mb)
-      if (p) (void)hipFree(p);
-    s.mb_acc = nullptr;
-    s.mb_xpt = s.mb_xrg = s.mb_xscal = nullptr;
-    s.mb_bad = nullptr;
-    s.mb_cap_acc = s.mb_cap_terms = 0;
     const size_t acc = (size_t)kMultiMax * kMultiKeys * KEY_ACC_LIMBS, terms = (size_t)kMultiMax * kMultiKeys + kMultiMax;
-    CK(dalloc(&s.mb_acc, acc));
-    CK(dalloc(&s.mb_xpt, terms));
-    CK(dalloc(&s.mb_xrg, terms));
-    CK(dalloc(&s.mb_xscal, terms * 8));
-    CK(dalloc(&s.mb_bad, kMultiMax));
-    s.mb_cap_acc = acc;
-    s.mb_cap_terms = terms;
+    CK(alloc_all(sized(s.mb_acc, acc), sized(s.mb_xpt, terms), sized(s.mb_xrg, terms), sized(s.mb_xscal, terms * 8),
+                 sized(s.mb_bad, kMultiMax)));
   }
   const uint32_t n = (uint32_t)N;
   const uint32_t T = (uint32_t)next_pow2(2 * (N < 128 ? 128 : N));
@@ -1036,7 +912,7 @@ static int finish_multi(edc_ctx* ctx, Slot& s, size_t nb, int* verdicts, uint8_t
     // launch is rerun range by range on the same slot (the inputs are still borrowed).
     s.mu_union = false;
     CK(hipStreamSynchronize(s.st));
-    const int* u = reinterpret_cast<const int*>(s.h_out);
+    const int* u = reinterpret_cast<const int*>(s.h_out.get());
     if (u[45]) {
       s.pending = false;
       s.nmulti = 0;
@@ -1075,7 +951,7 @@ static int finish_multi(edc_ctx* ctx, Slot& s, size_t nb, int* verdicts, uint8_t
   s.pending = false;
   s.nmulti = 0;
   CK(hipStreamSynchronize(s.st));
-  const int* h0 = reinterpret_cast<const int*>(s.h_out);
+  const int* h0 = reinterpret_cast<const int*>(s.h_out.get());
   if (h0[45]) {
     ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
     return EDC_ERR_ARG;
@@ -1136,8 +1012,8 @@ static int finish_batch(edc_ctx* ctx, Slot& s, uint8_t check8[32], uint8_t parti
     // digit entries the accumulation added: the last bin's end (queued on s.st at the enqueue)
     ctx->last_acc_entries = s.acc_nbin ? s.h_acc[0] + s.h_acc[1] : 0;
   }
-  const int verdict = reinterpret_cast<int*>(s.h_out)[0];
-  const int bad = reinterpret_cast<int*>(s.h_out)[1];
+  const int verdict = reinterpret_cast<int*>(s.h_out.get())[0];
+  const int bad = reinterpret_cast<int*>(s.h_out.get())[1];
 #ifdef EDC_BATCH_STAMPS
   if (&s != &ctx->comb) {
     std::lock_guard<std::mutex> g(g_bstamps_mu);
@@ -1145,7 +1021,7 @@ static int finish_batch(edc_ctx* ctx, Slot& s, uint8_t check8[32], uint8_t parti
     g_bstamps.push_back(s.n_batch);
     g_bstamps.push_back((uint32_t)s.t_submit_us);
     g_bstamps.push_back((uint32_t)host_us());
-    for (int k = 0; k < BST_N; ++k) g_bstamps.push_back(reinterpret_cast<uint32_t*>(s.h_out)[48 + k]);
+    for (int k = 0; k < BST_N; ++k) g_bstamps.push_back(reinterpret_cast<uint32_t*>(s.h_out.get())[48 + k]);
   }
 #endif
   if (&s != &ctx->comb && s.n_batch) {
@@ -1154,11 +1030,11 @@ static int finish_batch(edc_ctx* ctx, Slot& s, uint8_t check8[32], uint8_t parti
     } else {
       ctx->ungrouped_run = 0;
       ctx->have_key_ratio = true;
-      ctx->last_key_ratio = (double)reinterpret_cast<int*>(s.h_out)[2] / (double)s.n_batch;
+      ctx->last_key_ratio = (double)reinterpret_cast<int*>(s.h_out.get())[2] / (double)s.n_batch;
     }
-    if (ctx->kc_m) ctx->last_uncached = (uint32_t)reinterpret_cast<int*>(s.h_out)[44];
+    if (ctx->kc_m) ctx->last_uncached = (uint32_t)reinterpret_cast<int*>(s.h_out.get())[44];
   }
-  if (&s != &ctx->comb && reinterpret_cast<int*>(s.h_out)[45]) {
+  if (&s != &ctx->comb && reinterpret_cast<int*>(s.h_out.get())[45]) {
     ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
     return EDC_ERR_ARG;
   }
@@ -1263,11 +1139,17 @@ static int enqueue_host_chunked(edc_ctx* ctx, size_t n, const uint8_t* vk, const
   if (!rc) rc = ensure_slot(ctx, s, n);
   if (!rc && !k) rc = ensure_msg(ctx, mbytes);
   if (rc) return rc;
-  if (!ctx->hcs) {
-    CK(hipStreamCreateWithFlags(&ctx->hcs, hipStreamNonBlocking));
-    CK(hipStreamCreateWithFlags(&ctx->hcs2, hipStreamNonBlocking));
-    for (hipEvent_t& e : ctx->hev) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (hipEvent_t& e : ctx->hev2) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (!ctx->hcs) {   // all of them or none: a failure part-way leaves the context as it was
+    Stream cs1, cs2;
+    Event ev1[9], ev2[9];
+    CK(cs1.create(hipStreamNonBlocking));
+    CK(cs2.create(hipStreamNonBlocking));
+    for (Event& e : ev1) CK(e.create(hipEventDisableTiming));
+    for (Event& e : ev2) CK(e.create(hipEventDisableTiming));
+    ctx->hcs = std::move(cs1);
+    ctx->hcs2 = std::move(cs2);
+    std::move(ev1, ev1 + 9, ctx->hev);
+    std::move(ev2, ev2 + 9, ctx->hev2);
   }
   const bool per_sig = choose_per_sig(ctx, n), split = choose_split(ctx);
   const MsmPlan P = batch_plan(ctx, n, per_sig, split);
@@ -1473,15 +1355,8 @@ struct TmplItems {
 };
 
 template <typename T>
-static int tmpl_room(edc_ctx* ctx, hipStream_t st, T** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return 0;
-  CK(hipStreamSynchronize(st));
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t c = need < 1024 ? 1024 : need + need / 8;
-  CK(dalloc(p, c));
-  *cap = c;
+static int tmpl_room(edc_ctx* ctx, hipStream_t st, DevBuf<T>& b, size_t need) {
+  CK(grow(b, need, item_cap, sync_of(st)));
   return 0;
 }
 
@@ -1497,17 +1372,17 @@ static int tmpl_check(edc_ctx* ctx, const edc_templates* ts, TmplShape* shape) {
 static int tmpl_upload_set(edc_ctx* ctx, TmplWs& w, hipStream_t st, const edc_templates* ts, const TmplShape& sh,
                            TmplView* view) {
   w.check = false;
-  if (!w.flag) CK(dalloc(&w.flag, 1));
-  if (!w.h_flag) CK(hipHostMalloc((void**)&w.h_flag, sizeof(int)));
+  if (!w.flag) CK(w.flag.alloc(1));
+  if (!w.h_flag) CK(w.h_flag.alloc(1));
   const size_t nof = (size_t)ts->count + 1, set_bytes = 8 * nof + sh.head_bytes + sh.tail_bytes;
-  int rc = tmpl_room(ctx, st, &w.set, &w.set_cap, set_bytes + 16);   // k_tmpl_expand copies whole 16-byte rows
+  int rc = tmpl_room(ctx, st, w.set, set_bytes + 16);   // k_tmpl_expand copies whole 16-byte rows
   if (rc) return rc;
   uint8_t* head = w.set + 8 * nof;
   CK(hipMemcpyAsync(w.set, ts->head_off, 4 * nof, hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(w.set + 4 * nof, ts->tail_off, 4 * nof, hipMemcpyHostToDevice, st));
   if (sh.head_bytes) CK(hipMemcpyAsync(head, ts->head, sh.head_bytes, hipMemcpyHostToDevice, st));
   if (sh.tail_bytes) CK(hipMemcpyAsync(head + sh.head_bytes, ts->tail, sh.tail_bytes, hipMemcpyHostToDevice, st));
-  *view = TmplView{reinterpret_cast<const uint32_t*>(w.set), reinterpret_cast<const uint32_t*>(w.set + 4 * nof), head,
+  *view = TmplView{reinterpret_cast<const uint32_t*>(w.set.get()), reinterpret_cast<const uint32_t*>(w.set + 4 * nof), head,
                    head + sh.head_bytes, ts->count, sh.head_bytes, (uint32_t)set_bytes};
   return 0;
 }
@@ -1516,7 +1391,7 @@ static int tmpl_upload_set(edc_ctx* ctx, TmplWs& w, hipStream_t st, const edc_te
 static int tmpl_expand(edc_ctx* ctx, TmplWs& w, hipStream_t st, const TmplView& view, size_t n, const uint16_t* d_tpl,
                        const uint8_t* d_var, const uint32_t* d_var_off, size_t var_bytes, uint8_t* out, uint64_t* off) {
   if (!n) return 0;
-  int rc = tmpl_room(ctx, st, &w.bsum, &w.bsum_cap, tmpl_scan_words(n));
+  int rc = tmpl_room(ctx, st, w.bsum, tmpl_scan_words(n));
   if (rc) return rc;
   CK(hipMemsetAsync(w.flag, 0, sizeof(int), st));
   launch_tmpl_expand(st, (uint32_t)n, view, d_tpl, d_var, d_var_off, var_bytes, w.flag, w.bsum, out, off);
@@ -1530,20 +1405,20 @@ static int tmpl_expand_host(edc_ctx* ctx, TmplWs& w, hipStream_t st, const TmplV
   if (!n) return 0;
   const size_t var_bytes = it.var_off[n], o_tpl = 4 * (n + 1), o_var = (o_tpl + 2 * n + 15) & ~(size_t)15;
   if (var_bytes && !it.var) { ctx->err = "null var"; return EDC_ERR_ARG; }
-  int rc = tmpl_room(ctx, st, &w.in, &w.in_cap, o_var + var_bytes);
+  int rc = tmpl_room(ctx, st, w.in, o_var + var_bytes);
   if (rc) return rc;
   CK(hipMemcpyAsync(w.in, it.var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(w.in + o_tpl, it.tpl, 2 * n, hipMemcpyHostToDevice, st));
   if (var_bytes) CK(hipMemcpyAsync(w.in + o_var, it.var, var_bytes, hipMemcpyHostToDevice, st));
   return tmpl_expand(ctx, w, st, view, n, reinterpret_cast<const uint16_t*>(w.in + o_tpl), w.in + o_var,
-                     reinterpret_cast<const uint32_t*>(w.in), var_bytes, out, off);
+                     reinterpret_cast<const uint32_t*>(w.in.get()), var_bytes, out, off);
 }
 
 // w's own arena and offsets for n items of a set with shape sh
 static int tmpl_arena_room(edc_ctx* ctx, TmplWs& w, hipStream_t st, size_t n, const TmplShape& sh, size_t var_bytes) {
-  int rc = tmpl_room(ctx, st, &w.arena, &w.arena_cap, tmpl_arena_bound(n, sh, var_bytes));
+  int rc = tmpl_room(ctx, st, w.arena, tmpl_arena_bound(n, sh, var_bytes));
   if (rc) return rc;
-  return tmpl_room(ctx, st, &w.off, &w.off_cap, n + 1);
+  return tmpl_room(ctx, st, w.off, n + 1);
 }
 
 // What every host form checks before anything is launched: the set, the items, the keys.
@@ -1621,7 +1496,7 @@ edc_ctx* edc_create(int device) {
   }
   (void)hipGetLastError();   // launch checks below must not see an earlier, unrelated failure
   bool ok = hipSetDevice(device) == hipSuccess && msm_init_device() == hipSuccess && init_slot(ctx, ctx->slot[0]) == 0 &&
-            dalloc(&ctx->btab, BTAB_TOTAL * NIELS_WORDS) == hipSuccess;
+            ctx->btab.alloc(BTAB_TOTAL * NIELS_WORDS) == hipSuccess;
   if (ok) {
     launch_init_btable(ctx->st(), ctx->btab);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->st()) == hipSuccess;
@@ -1636,12 +1511,8 @@ edc_ctx* edc_create(int device) {
 }
 
 static void free_keycache(edc_ctx* ctx) {
-  void* ptrs[] = {ctx->kc_table, ctx->kc_keys, ctx->kc_comb, ctx->kc_ok, ctx->kc_reg};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  ctx->kc_table = ctx->kc_keys = ctx->kc_comb = ctx->kc_reg = nullptr;
+  reset_all(ctx->kc_table, ctx->kc_keys, ctx->kc_comb, ctx->kc_ok, ctx->kc_reg);
   ctx->kc_reg_m = 0;
-  ctx->kc_ok = nullptr;
   ctx->kc_m = ctx->kc_tmask = ctx->kc_cap = 0;
   ctx->kc_gen++;
   ctx->kc_words.clear();
@@ -1661,65 +1532,10 @@ static int sync_all(edc_ctx* ctx) {
 void edc_destroy(edc_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
+  // every stream that can still touch the context's memory, then the members free themselves
   (void)sync_all(ctx);
-  free_keycache(ctx);
-  if (ctx->bcomb) (void)hipFree(ctx->bcomb);
-  for (Slot& s : ctx->slot) {
-    if (s.st) (void)hipStreamSynchronize(s.st);
-    free_slot_buffers(s);
-    {
-      void* in[] = {s.in_vk, s.in_sig, s.in_msg, s.in_off, s.in_idx};
-      for (void* p : in)
-        if (p) (void)hipFree(p);
-    }
-    {
-      void* mb[] = {s.mb_acc, s.mb_xpt, s.mb_xrg, s.mb_xscal, s.mb_bad};
-      for (void* p : mb)
-        if (p) (void)hipFree(p);
-    }
-    free_tmpl(s.tw);
-    if (s.flags) (void)hipFree(s.flags);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.h_acc) (void)hipHostFree(s.h_acc);
-    for (int p = 0; p <= PH_N; ++p)
-      if (s.ev[p]) (void)hipEventDestroy(s.ev[p]);
-    for (hipEvent_t e : s.ev_acc)
-      if (e) (void)hipEventDestroy(e);
-    if (s.st) (void)hipStreamDestroy(s.st);
-    if (s.st2) (void)hipStreamDestroy(s.st2);
-    if (s.ev_keys) (void)hipEventDestroy(s.ev_keys);
-    if (s.ev_dec) (void)hipEventDestroy(s.ev_dec);
-  }
-  {
-    Slot& s = ctx->comb;
-    if (s.st) (void)hipStreamSynchronize(s.st);
-    if (s.flags) (void)hipFree(s.flags);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.h_acc) (void)hipHostFree(s.h_acc);
-    for (int p = 0; p <= PH_N; ++p)
-      if (s.ev[p]) (void)hipEventDestroy(s.ev[p]);
-    for (hipEvent_t e : s.ev_acc)
-      if (e) (void)hipEventDestroy(e);
-    if (s.st) (void)hipStreamDestroy(s.st);
-  }
-  if (ctx->hcs) (void)hipStreamSynchronize(ctx->hcs);
-  if (ctx->hcs2) (void)hipStreamSynchronize(ctx->hcs2);
-  for (hipEvent_t e : ctx->hev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ctx->hev2)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->hcs) (void)hipStreamDestroy(ctx->hcs);
-  if (ctx->hcs2) (void)hipStreamDestroy(ctx->hcs2);
-  void* ptrs[] = {ctx->vk, ctx->sig, ctx->msg, ctx->zexp, ctx->off, ctx->kbuf, ctx->verdicts, ctx->vtab, ctx->aux,
-                  ctx->btab, ctx->comb_in, ctx->fb_xpt, ctx->fb_xrg, ctx->fb_xscal, ctx->fb_rv, ctx->fb_idx,
-                  ctx->fb_g, ctx->sc_hdr, ctx->sc_rec, ctx->sc_ctr, ctx->sc_hit, ctx->sc_g, ctx->sc_verd,
-                  ctx->sc_mverd, ctx->sc_wg, ctx->sc_idx};
-  if (ctx->sc_hctr) (void)hipHostFree(ctx->sc_hctr);
-  if (ctx->sc_ev) (void)hipEventDestroy(ctx->sc_ev);
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  for (hipStream_t st : {(hipStream_t)ctx->comb.st, (hipStream_t)ctx->hcs, (hipStream_t)ctx->hcs2})
+    if (st) (void)hipStreamSynchronize(st);
   delete ctx;
 }
 
@@ -1883,12 +1699,8 @@ static int combine_points(edc_ctx* ctx, size_t g, const uint8_t* partials, int b
   Slot& s = ctx->comb;
   int rc = init_slot(ctx, s);
   if (rc) return rc;
-  if (g * 128 > ctx->comb_cap) {
-    if (ctx->comb_in) (void)hipFree(ctx->comb_in);
-    ctx->comb_cap = 0;
-    CK(dalloc(&ctx->comb_in, g * 128 + 1024));
-    ctx->comb_cap = g * 128 + 1024;
-  }
+  if (g * 128 > ctx->comb_in.cap())
+    CK(grow(ctx->comb_in, g * 128, [](size_t b) { return b + 1024; }, sync_of(s.st)));
   if (g) CK(hipMemcpyAsync(ctx->comb_in, partials, g * 128, hipMemcpyHostToDevice, s.st));
   CK(hipMemsetAsync(s.d_out, 0, 256, s.st));
   launch_combine(s.st, (uint32_t)g, ctx->comb_in, bad ? 1 : 0, check8 != nullptr, s.d_out);
@@ -1903,6 +1715,13 @@ int edc_combine_partials(edc_ctx* ctx, size_t g, const uint8_t* partials, int ba
   if (!ctx || (g && !partials)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
   return combine_points(ctx, g, partials, bad_any, check8, nullptr);
+}
+
+int edc_debug_live_allocs(uint64_t out[2]) {
+  if (!out) return EDC_ERR_ARG;
+  out[0] = HipAlloc::live_dev.load();
+  out[1] = HipAlloc::live_host.load();
+  return 0;
 }
 
 int edc_debug_sc_reduce_wide(edc_ctx* ctx, size_t n, const uint8_t* d_in, uint8_t* d_out) {
@@ -2136,25 +1955,10 @@ int edc_verify_each_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const ui
 
 // ---- grouped fallback: one MSM pass over ~128 contiguous ranges (edc_set_fallback_shape) ----
 static int ensure_fb(edc_ctx* ctx, size_t terms, size_t ranges) {
-  if (terms > ctx->fb_cap_terms || !ctx->fb_xpt) {
-    CK(hipStreamSynchronize(ctx->st()));
-    for (void* p : {(void*)ctx->fb_xpt, (void*)ctx->fb_xrg, (void*)ctx->fb_xscal})
-      if (p) (void)hipFree(p);
-    ctx->fb_xpt = ctx->fb_xrg = ctx->fb_xscal = nullptr;
-    ctx->fb_cap_terms = 0;
-    const size_t cap = terms + terms / 8 + 64;
-    CK(dalloc(&ctx->fb_xpt, cap));
-    CK(dalloc(&ctx->fb_xrg, cap));
-    CK(dalloc(&ctx->fb_xscal, cap * 8));
-    ctx->fb_cap_terms = cap;
-  }
-  if (ranges > ctx->fb_cap_ranges || !ctx->fb_rv) {
-    CK(hipStreamSynchronize(ctx->st()));
-    if (ctx->fb_rv) (void)hipFree(ctx->fb_rv);
-    ctx->fb_rv = nullptr;
-    CK(dalloc(&ctx->fb_rv, 2 * ranges + 64));
-    ctx->fb_cap_ranges = ranges;
-  }
+  CK(grow_group(ctx->fb_cap_terms, terms, term_cap, sync_of(ctx->st()), [&](size_t cap) {
+    return alloc_all(sized(ctx->fb_xpt, cap), sized(ctx->fb_xrg, cap), sized(ctx->fb_xscal, cap * 8));
+  }));
+  CK(grow(ctx->fb_rv, 2 * ranges + 64, exact_cap, sync_of(ctx->st())));
   return 0;
 }
 
@@ -2166,22 +1970,12 @@ static int verify_listed(edc_ctx* ctx, Slot& s, const std::vector<uint32_t>& idx
   if (!c) return 0;
   int rc = ensure_n(ctx, c);
   if (rc) return rc;
-  if (c > ctx->fb_cap_idx || !ctx->fb_idx) {
-    if (ctx->fb_idx) (void)hipFree(ctx->fb_idx);
-    ctx->fb_idx = nullptr;
-    CK(dalloc(&ctx->fb_idx, c + c / 8 + 64));
-    ctx->fb_cap_idx = c + c / 8 + 64;
-  }
   // gathered copies in their own buffer: the inputs may BE the context's staging buffers (host
   // entry points), and an in-place gather would race (item idx[j] > j is read while slot idx[j]
   // is written by another lane)
-  if (c > ctx->fb_cap_g || !ctx->fb_g) {
-    if (ctx->fb_g) (void)hipFree(ctx->fb_g);
-    ctx->fb_g = nullptr;
-    ctx->fb_cap_g = 0;
-    CK(dalloc(&ctx->fb_g, (c + c / 8 + 64) * 128));
-    ctx->fb_cap_g = c + c / 8 + 64;
-  }
+  CK(grow_group(ctx->fb_cap_g, c, term_cap, sync_of(s.st), [&](size_t cap) {
+    return alloc_all(sized(ctx->fb_idx, cap), sized(ctx->fb_g, cap * 128));
+  }));
   uint8_t* g_vk = ctx->fb_g;
   uint8_t* g_sig = g_vk + ctx->fb_cap_g * 32;
   uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->fb_cap_g * 64);
@@ -2570,7 +2364,7 @@ static int commits_enqueue_tmpl(edc_ctx* ctx, Slot& s, const edc_templates* ts, 
     const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_tpl = up16(4 * (n + 1)), o_var = up16(o_tpl + 2 * n), o_coff = up16(o_var + var_bytes),
                  o_ctpl = up16(o_coff + 4 * (nc + 1));
-    if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) || (rc = tmpl_room(ctx, st, &w.in, &w.in_cap, o_ctpl + 2 * nc)))
+    if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) || (rc = tmpl_room(ctx, st, w.in, o_ctpl + 2 * nc)))
       return rc;
     if (key_idx) {
       CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -2588,7 +2382,7 @@ static int commits_enqueue_tmpl(edc_ctx* ctx, Slot& s, const edc_templates* ts, 
     launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(w.in + o_coff),
                            reinterpret_cast<const uint16_t*>(w.in + o_ctpl), d_tpl);
     CK(hipGetLastError());
-    if ((rc = tmpl_expand(ctx, w, st, view, n, d_tpl, w.in + o_var, reinterpret_cast<const uint32_t*>(w.in), var_bytes,
+    if ((rc = tmpl_expand(ctx, w, st, view, n, d_tpl, w.in + o_var, reinterpret_cast<const uint32_t*>(w.in.get()), var_bytes,
                           w.arena, w.off)))
       return rc;
   }
@@ -2780,7 +2574,7 @@ int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   CK(hipMemcpyAsync(ctx->aux + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
   CK(hipEventRecord(s.ev[0], st));
   for (int r = 0; r < reps; ++r)
-    launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(ctx->aux),
+    launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(ctx->aux.get()),
                            reinterpret_cast<const uint16_t*>(ctx->aux + o_ctpl),
                            reinterpret_cast<uint16_t*>(ctx->aux + o_tpl));
   CK(hipGetLastError());
@@ -2854,14 +2648,10 @@ static int kc_append(edc_ctx* ctx, const std::vector<uint32_t>& neww) {
     uint32_t cap = ctx->kc_cap ? 2 * ctx->kc_cap : 16;
     while (cap < u) cap *= 2;
     if (cap > KC_MAX_KEYS) cap = KC_MAX_KEYS;
-    uint32_t *keys = nullptr, *comb = nullptr;
-    uint8_t* okd = nullptr;
-    if (dalloc(&keys, (size_t)cap * 8) != hipSuccess || dalloc(&okd, cap) != hipSuccess ||
-        dalloc(&comb, (size_t)cap * comb_words) != hipSuccess) {
+    DevBuf<uint32_t> keys, comb;
+    DevBuf<uint8_t> okd;
+    if (alloc_all(sized(keys, (size_t)cap * 8), sized(okd, cap), sized(comb, (size_t)cap * comb_words)) != hipSuccess) {
       (void)hipGetLastError();
-      if (keys) (void)hipFree(keys);
-      if (okd) (void)hipFree(okd);
-      if (comb) (void)hipFree(comb);
       ctx->err = "key cache: out of device memory";
       return EDC_ERR_NOMEM;
     }
@@ -2871,12 +2661,9 @@ static int kc_append(edc_ctx* ctx, const std::vector<uint32_t>& neww) {
       CK(hipMemcpyAsync(comb, ctx->kc_comb, (size_t)u0 * comb_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
       CK(hipStreamSynchronize(st));
     }
-    if (ctx->kc_keys) (void)hipFree(ctx->kc_keys);
-    if (ctx->kc_ok) (void)hipFree(ctx->kc_ok);
-    if (ctx->kc_comb) (void)hipFree(ctx->kc_comb);
-    ctx->kc_keys = keys;
-    ctx->kc_ok = okd;
-    ctx->kc_comb = comb;
+    ctx->kc_keys = std::move(keys);
+    ctx->kc_ok = std::move(okd);
+    ctx->kc_comb = std::move(comb);
     ctx->kc_cap = cap;
   }
   std::vector<uint32_t> all(ctx->kc_words);   // committed to the context only on success
@@ -2889,18 +2676,16 @@ static int kc_append(edc_ctx* ctx, const std::vector<uint32_t>& neww) {
     table[h] = c;
   }
   // new table and scratch first: a failed allocation leaves the previous cache fully usable
-  uint32_t *ntable = nullptr, *ext = nullptr;
+  DevBuf<uint32_t> ntable, ext;   // ext: scratch, freed on return (the stream is synchronized below)
   const bool new_table = T - 1 != ctx->kc_tmask || !ctx->kc_table;
-  if ((new_table && dalloc(&ntable, T) != hipSuccess) || dalloc(&ext, (size_t)(un + 1) * EXT_WORDS) != hipSuccess) {
+  if ((new_table && ntable.alloc(T) != hipSuccess) || ext.alloc((size_t)(un + 1) * EXT_WORDS) != hipSuccess) {
     (void)hipGetLastError();
-    if (ntable) (void)hipFree(ntable);
     ctx->err = "key cache: out of device memory";
     return EDC_ERR_NOMEM;
   }
   if (new_table) {
     CK(hipStreamSynchronize(st));
-    if (ctx->kc_table) (void)hipFree(ctx->kc_table);
-    ctx->kc_table = ntable;
+    ctx->kc_table = std::move(ntable);
   }
   CK(hipMemcpyAsync(ctx->kc_table, table.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(ctx->kc_keys + (size_t)u0 * 8, neww.data(), neww.size() * sizeof(uint32_t),
@@ -2908,7 +2693,7 @@ static int kc_append(edc_ctx* ctx, const std::vector<uint32_t>& neww) {
   launch_kc_decode(st, un, ctx->kc_keys + (size_t)u0 * 8, ext, ctx->kc_ok + u0);
   launch_kc_comb(st, un, ext, ctx->kc_comb + (size_t)u0 * comb_words);
   if (!ctx->bcomb) {
-    CK(dalloc(&ctx->bcomb, comb_words));
+    CK(ctx->bcomb.alloc(comb_words));
     uint32_t* bext = ext + (size_t)un * EXT_WORDS;
     launch_kc_basepoint(st, bext);
     launch_kc_comb(st, 1, bext, ctx->bcomb);
@@ -2917,7 +2702,6 @@ static int kc_append(edc_ctx* ctx, const std::vector<uint32_t>& neww) {
   std::vector<uint8_t> okn(un);
   CK(hipMemcpyAsync(okn.data(), ctx->kc_ok + u0, un, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
-  (void)hipFree(ext);
   ctx->kc_words.swap(all);
   ctx->kc_okh.insert(ctx->kc_okh.end(), okn.begin(), okn.end());
   ctx->kc_m = u;
@@ -2959,7 +2743,7 @@ int64_t edc_keycache_load(edc_ctx* ctx, size_t m, const uint8_t* vk, uint8_t* ok
   std::vector<uint32_t> of, words;
   if ((rc = kc_collect(ctx, m, vk, of, words))) return rc;
   if ((rc = kc_append(ctx, words))) return rc;
-  CK(dalloc(&ctx->kc_reg, m));
+  CK(ctx->kc_reg.alloc(m));
   CK(hipMemcpy(ctx->kc_reg, of.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
   ctx->kc_reg_m = (uint32_t)m;
   if (ok)
@@ -2983,10 +2767,9 @@ int64_t edc_keycache_add(edc_ctx* ctx, size_t m, const uint8_t* vk, uint8_t* ok)
   std::vector<uint8_t> code(un, 0);
   if (un) {
     hipStream_t st = ctx->st();
-    uint8_t *denc = nullptr, *dcode = nullptr;
-    if (dalloc(&denc, (size_t)un * 32) != hipSuccess || dalloc(&dcode, un) != hipSuccess) {
+    DevBuf<uint8_t> denc, dcode;   // scratch, freed at the end of this block
+    if (alloc_all(sized(denc, (size_t)un * 32), sized(dcode, un)) != hipSuccess) {
       (void)hipGetLastError();
-      if (denc) (void)hipFree(denc);
       ctx->err = "key cache: out of device memory";
       return EDC_ERR_NOMEM;
     }
@@ -2995,8 +2778,6 @@ int64_t edc_keycache_add(edc_ctx* ctx, size_t m, const uint8_t* vk, uint8_t* ok)
     CK(hipGetLastError());
     CK(hipMemcpyAsync(code.data(), dcode, un, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
-    (void)hipFree(denc);
-    (void)hipFree(dcode);
   }
   std::vector<uint32_t> keep, remap(un, UINT32_MAX);
   for (uint32_t j = 0; j < un; ++j)
@@ -3170,14 +2951,6 @@ int edc_synchronize(edc_ctx* ctx) {
 // batch_with_fallback, the per-item kernels), so verdicts and check8 are those entries' on the miss
 // list by construction. The miss count needs one 4-byte device-to-host copy and a stream
 // synchronization before the MSM can be planned.
-static void free_sigcache(edc_ctx* ctx) {
-  if (ctx->sc_hdr) (void)hipFree(ctx->sc_hdr);
-  if (ctx->sc_rec) (void)hipFree(ctx->sc_rec);
-  ctx->sc_hdr = nullptr;
-  ctx->sc_rec = nullptr;
-  ctx->sc_cap = 0;
-}
-
 // preconditions of every cached entry: a table, and slot 0 (their stream and workspace) idle
 static int sc_ready(edc_ctx* ctx) {
   if (!ctx->sc_cap) { ctx->err = "no signature cache on this context (edc_sigcache_create)"; return EDC_ERR_ARG; }
@@ -3198,22 +2971,11 @@ static hipError_t sc_wait_inserts(const edc_ctx* ctx) {
 }
 
 static int ensure_sc(edc_ctx* ctx, size_t n) {
-  if (n <= ctx->sc_cap_n && ctx->sc_hit) return 0;
-  CK(hipStreamSynchronize(ctx->st()));
-  void* ptrs[] = {ctx->sc_hit, ctx->sc_g, ctx->sc_verd, ctx->sc_mverd, ctx->sc_wg, ctx->sc_idx};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  ctx->sc_hit = ctx->sc_g = ctx->sc_verd = ctx->sc_mverd = nullptr;
-  ctx->sc_wg = ctx->sc_idx = nullptr;
-  ctx->sc_cap_n = 0;
-  const size_t cap = n < 1024 ? 1024 : n + n / 8;
-  CK(dalloc(&ctx->sc_hit, cap));
-  CK(dalloc(&ctx->sc_g, cap * 128));
-  CK(dalloc(&ctx->sc_verd, cap));
-  CK(dalloc(&ctx->sc_mverd, cap));
-  CK(dalloc(&ctx->sc_wg, cap / SC_BLOCK + 2));   // one count per workgroup + the total
-  CK(dalloc(&ctx->sc_idx, cap));
-  ctx->sc_cap_n = cap;
+  CK(grow_group(ctx->sc_cap_n, n, item_cap, sync_of(ctx->st()), [&](size_t cap) {
+    return alloc_all(sized(ctx->sc_hit, cap), sized(ctx->sc_g, cap * 128), sized(ctx->sc_verd, cap), sized(ctx->sc_mverd, cap),
+                     sized(ctx->sc_wg, cap / SC_BLOCK + 2),   // one count per workgroup + the total
+                     sized(ctx->sc_idx, cap));
+  }));
   return 0;
 }
 
@@ -3314,7 +3076,7 @@ static int sc_batch(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* 
   if ((rc = sc_partition(ctx, n, d_vk, d_sig, k, &M))) return rc;
   if (n_miss) *n_miss = M.n;
   // an empty miss list still runs the n = 0 batch, whose k is never read
-  const uint32_t* mk = M.n ? M.k : reinterpret_cast<const uint32_t*>(ctx->sc_hdr);
+  const uint32_t* mk = M.n ? M.k : reinterpret_cast<const uint32_t*>(ctx->sc_hdr.get());
   if (!verdicts) {
     rc = run_batch_sync(ctx, M.n, M.vk, M.sig, nullptr, nullptr, z_seed, 0, nullptr, check8, nullptr, nullptr, mk);
     if (rc != EDC_OK) return rc;     // a failed batch inserts nothing
@@ -3340,18 +3102,18 @@ int edc_sigcache_create(edc_ctx* ctx, size_t capacity, int keep) {
   int rc = sync_all(ctx);
   if (rc) return rc;
   CK(sc_wait_inserts(ctx));
-  free_sigcache(ctx);
+  reset_all(ctx->sc_hdr, ctx->sc_rec);
+  ctx->sc_cap = 0;
   if (!capacity) return 0;
   if (capacity > (1ull << 30)) { ctx->err = "signature cache capacity above 2^30 records"; return EDC_ERR_ARG; }
   const size_t cap = next_pow2(capacity < SC_WINDOW ? SC_WINDOW : capacity);
-  if (dalloc(&ctx->sc_hdr, cap) != hipSuccess || dalloc(&ctx->sc_rec, cap * 8) != hipSuccess) {
+  if (alloc_all(sized(ctx->sc_hdr, cap), sized(ctx->sc_rec, cap * 8)) != hipSuccess) {
     (void)hipGetLastError();
-    free_sigcache(ctx);
     ctx->err = "signature cache: out of device memory";
     return EDC_ERR_NOMEM;
   }
-  if (!ctx->sc_ctr) CK(dalloc(&ctx->sc_ctr, 2));
-  if (!ctx->sc_hctr) CK(hipHostMalloc((void**)&ctx->sc_hctr, 3 * sizeof(unsigned long long)));
+  if (!ctx->sc_ctr) CK(ctx->sc_ctr.alloc(2));
+  if (!ctx->sc_hctr) CK(ctx->sc_hctr.alloc(3));
   CK(hipMemsetAsync(ctx->sc_hdr, 0, cap * sizeof(unsigned long long), ctx->st()));
   CK(hipMemsetAsync(ctx->sc_ctr, 0, 2 * sizeof(unsigned long long), ctx->st()));
   CK(hipStreamSynchronize(ctx->st()));
@@ -3466,7 +3228,7 @@ int edc_sigcache_batch_verify(edc_ctx* ctx, size_t n, const uint8_t* vk, const u
   if (rc) return rc;
   if ((rc = sc_upload(ctx, n, vk, sig, msg, msg_off, k))) return rc;
   return sc_batch(ctx, n, ctx->vk, ctx->sig, ctx->msg, k ? nullptr : ctx->off,
-                  k ? reinterpret_cast<const uint8_t*>(ctx->kbuf) : nullptr, z_seed, nullptr, nullptr, check8, n_miss);
+                  k ? reinterpret_cast<const uint8_t*>(ctx->kbuf.get()) : nullptr, z_seed, nullptr, nullptr, check8, n_miss);
 }
 
 int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
@@ -3584,34 +3346,31 @@ static int verifier_reserve(edc_verifier* v, size_t need) {
   if (v->cs) CK(hipStreamSynchronize(v->cs));
   size_t cap = v->cap * 2 > need ? v->cap * 2 : need;
   if (cap < 1) cap = 1;
-  uint8_t *nvk = nullptr, *nsig = nullptr, *nz = nullptr;
-  uint32_t *nk = nullptr, *norg = nullptr;
-  CK(dalloc(&nvk, cap * 32));
-  CK(dalloc(&nsig, cap * 64));
-  CK(dalloc(&nz, cap * 16));
-  CK(dalloc(&nk, cap * 8));
-  if (v->cached.on) CK(dalloc(&norg, cap));   // only a cached verifier keeps offered positions
+  // the new arrays are the verifier's only once they are all there and filled
+  DevBuf<uint8_t> nvk, nsig, nz;
+  DevBuf<uint32_t> nk, norg;
+  CK(nvk.alloc(cap * 32));
+  CK(nsig.alloc(cap * 64));
+  CK(nz.alloc(cap * 16));
+  CK(nk.alloc(cap * 8));
+  if (v->cached.on) CK(norg.alloc(cap));   // only a cached verifier keeps offered positions
   if (v->n) {
     CK(hipMemcpy(nvk, v->vk, v->n * 32, hipMemcpyDeviceToDevice));
     CK(hipMemcpy(nsig, v->sig, v->n * 64, hipMemcpyDeviceToDevice));
     CK(hipMemcpy(nk, v->k, v->n * 32, hipMemcpyDeviceToDevice));
     if (v->cached.on) CK(hipMemcpy(norg, v->origin, v->n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
   }
-  for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->origin})
-    if (p) (void)hipFree(p);
-  v->origin = norg;
-  v->vk = nvk;
-  v->sig = nsig;
-  v->zexp = nz;
-  v->k = nk;
+  v->origin = std::move(norg);
+  v->vk = std::move(nvk);
+  v->sig = std::move(nsig);
+  v->zexp = std::move(nz);
+  v->k = std::move(nk);
   v->cap = cap;
   int rc = ensure_slot(ctx, s, cap);
   if (rc) return rc;
   if (v->karea_cap != s.cap_n) {
-    if (v->karea) (void)hipFree(v->karea);
-    v->karea = nullptr;
     v->karea_cap = 0;
-    CK(dalloc(&v->karea, 2 * s.cap_n * NIELS_WORDS));
+    CK(v->karea.alloc(2 * s.cap_n * NIELS_WORDS));
     v->karea_cap = s.cap_n;
   }
   s.kin = v->k;
@@ -3623,24 +3382,8 @@ static int verifier_reserve(edc_verifier* v, size_t need) {
 // The message arena of one append: reused by the next one once its SHA-512 pass has run.
 static int verifier_msg_room(edc_verifier* v, size_t m, size_t mbytes) {
   edc_ctx* ctx = v->ctx;
-  if (mbytes > v->cap_msg || !v->msg) {
-    CK(hipStreamSynchronize(v->s.st));
-    if (v->msg) (void)hipFree(v->msg);
-    v->msg = nullptr;
-    v->cap_msg = 0;
-    const size_t cap = mbytes < 4096 ? 4096 : mbytes + mbytes / 8;
-    CK(dalloc(&v->msg, cap));
-    v->cap_msg = cap;
-  }
-  if (m + 1 > v->cap_off || !v->off) {
-    CK(hipStreamSynchronize(v->s.st));
-    if (v->off) (void)hipFree(v->off);
-    v->off = nullptr;
-    v->cap_off = 0;
-    const size_t cap = m + 1 < 1024 ? 1024 : m + 1 + m / 8;
-    CK(dalloc(&v->off, cap));
-    v->cap_off = cap;
-  }
+  CK(grow(v->msg, mbytes, byte_cap, sync_of(v->s.st)));
+  CK(grow(v->off, m + 1, off_cap, sync_of(v->s.st)));
   return 0;
 }
 
@@ -3727,26 +3470,14 @@ static int verifier_cached_check(edc_verifier* v, size_t m) {
 // gather is the last reader of the old contents: the copy stream waits for it.
 static int verifier_stage_room(edc_verifier* v, size_t m) {
   edc_ctx* ctx = v->ctx;
-  if (!v->h_cnt) CK(hipHostMalloc((void**)&v->h_cnt, 2 * sizeof(uint32_t)));
-  if (!v->ev_cnt) CK(hipEventCreateWithFlags(&v->ev_cnt, hipEventDisableTiming));
-  if (!v->ev_gather) CK(hipEventCreateWithFlags(&v->ev_gather, hipEventDisableTiming));
-  if (m > v->st_cap || !v->hit) {
-    CK(hipStreamSynchronize(v->s.st));
-    CK(hipStreamSynchronize(v->cs));
-    for (void* p : {(void*)v->st_vk, (void*)v->st_sig, (void*)v->st_k, (void*)v->hit, (void*)v->wg})
-      if (p) (void)hipFree(p);
-    v->st_vk = v->st_sig = v->hit = nullptr;
-    v->st_k = v->wg = nullptr;
-    v->st_cap = 0;
-    v->gather_pending = false;
-    const size_t cap = m < 1024 ? 1024 : m + m / 8;
-    CK(dalloc(&v->st_vk, cap * 32));
-    CK(dalloc(&v->st_sig, cap * 64));
-    CK(dalloc(&v->st_k, cap * 8));
-    CK(dalloc(&v->hit, cap));
-    CK(dalloc(&v->wg, cap / SC_BLOCK + 2));   // one count per workgroup + the total
-    v->st_cap = cap;
-  }
+  if (!v->h_cnt) CK(v->h_cnt.alloc(2));
+  if (!v->ev_cnt) CK(v->ev_cnt.create(hipEventDisableTiming));
+  if (!v->ev_gather) CK(v->ev_gather.create(hipEventDisableTiming));
+  CK(grow_group(v->st_cap, m, item_cap, sync_of(v->s.st, v->cs), [&](size_t cap) {
+    v->gather_pending = false;   // both streams are drained
+    return alloc_all(sized(v->st_vk, cap * 32), sized(v->st_sig, cap * 64), sized(v->st_k, cap * 8), sized(v->hit, cap),
+                     sized(v->wg, cap / SC_BLOCK + 2));   // one count per workgroup + the total
+  }));
   if (v->gather_pending) CK(hipStreamWaitEvent(v->cs, v->ev_gather, 0));
   return 0;
 }
@@ -3802,7 +3533,7 @@ static int verifier_insert(edc_verifier* v, const uint8_t* d_codes) {
   size_t a, b;
   if (!cached_insert_due(v->cached, v->n, &a, &b) || !ctx->sc_cap) return 0;
   hipStream_t st = v->s.st;
-  if (!ctx->sc_ev) CK(hipEventCreateWithFlags(&ctx->sc_ev, hipEventDisableTiming));
+  if (!ctx->sc_ev) CK(ctx->sc_ev.create(hipEventDisableTiming));
   int rc = sc_order_after_inserts(ctx, st);
   if (rc) return rc;
   launch_sc_insert(st, ctx->sc(), (uint32_t)(b - a), nullptr, v->vk + a * 32, v->sig + a * 64, v->k + a * 8,
@@ -3822,25 +3553,10 @@ static int verifier_codes_out(edc_verifier* v, const uint8_t* verdicts, uint8_t*
   edc_ctx* ctx = v->ctx;
   hipStream_t st = v->s.st;
   const size_t n = v->n, N = (size_t)v->cached.offered;
-  if (n > v->verd_cap) {
-    CK(hipStreamSynchronize(st));
-    if (v->verd) (void)hipFree(v->verd);
-    v->verd = nullptr;
-    v->verd_cap = 0;
-    CK(dalloc(&v->verd, v->cap));
-    v->verd_cap = v->cap;
-  }
+  if (n > v->verd.cap()) CK(grow(v->verd, n, [v](size_t) { return v->cap; }, sync_of(st)));
   CK(hipMemcpyAsync(v->verd, verdicts, n, hipMemcpyHostToDevice, st));
   if (offered) {
-    if (N > v->offv_cap) {
-      CK(hipStreamSynchronize(st));
-      if (v->offv) (void)hipFree(v->offv);
-      v->offv = nullptr;
-      v->offv_cap = 0;
-      const size_t cap = N < 1024 ? 1024 : N + N / 8;
-      CK(dalloc(&v->offv, cap));
-      v->offv_cap = cap;
-    }
+    if (N > v->offv.cap()) CK(grow(v->offv, N, item_cap, sync_of(st)));
     CK(hipMemsetAsync(v->offv, 0, N, st));
     launch_sc_scatter(st, (uint32_t)n, v->origin, v->verd, v->offv);
     CK(hipGetLastError());
@@ -3887,15 +3603,8 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
     if (v->chal_pending) CK(hipStreamWaitEvent(v->cs, v->ev_chal, 0));
   }
   if (key_idx) {
-    if (m > v->cap_idx) {
-      CK(hipStreamSynchronize(v->cs));          // the previous indexed append's expansion reads v->idx
-      if (v->idx) (void)hipFree(v->idx);
-      v->idx = nullptr;
-      v->cap_idx = 0;
-      const size_t cap = m < 1024 ? 1024 : m + m / 8;
-      CK(dalloc(&v->idx, cap));
-      v->cap_idx = cap;
-    }
+    // (the previous indexed append's expansion reads v->idx on the copy stream)
+    CK(grow(v->idx, m, item_cap, sync_of(v->cs)));
     CK(hipMemcpyAsync(v->idx, key_idx, m * sizeof(uint32_t), hipMemcpyHostToDevice, v->cs));
     launch_expand_keys(v->cs, (uint32_t)m, v->idx, ctx->kc_reg, ctx->kc_keys, r_vk);
     CK(hipGetLastError());
@@ -4025,9 +3734,9 @@ edc_verifier* edc_verifier_create(edc_ctx* ctx, size_t capacity_hint) {
   edc_verifier* v = new edc_verifier();
   v->ctx = ctx;
   ctx->verifiers.push_back(v);
-  bool ok = init_slot(ctx, v->s) == 0 && hipStreamCreateWithFlags(&v->cs, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&v->ev_copy, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&v->ev_chal, hipEventDisableTiming) == hipSuccess &&
+  bool ok = init_slot(ctx, v->s) == 0 && v->cs.create(hipStreamNonBlocking) == hipSuccess &&
+            v->ev_copy.create(hipEventDisableTiming) == hipSuccess &&
+            v->ev_chal.create(hipEventDisableTiming) == hipSuccess &&
             verifier_reserve(v, capacity_hint ? capacity_hint : 1) == 0 && hipStreamSynchronize(v->s.st) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -4045,25 +3754,6 @@ void edc_verifier_destroy(edc_verifier* v) {
   if (v->cs) (void)hipStreamSynchronize(v->cs);
   if (s.st) (void)hipStreamSynchronize(s.st);
   ctx->verifiers.erase(std::remove(ctx->verifiers.begin(), ctx->verifiers.end(), v), ctx->verifiers.end());
-  free_slot_buffers(s);
-  free_tmpl(s.tw);
-  for (void* p : {(void*)v->vk, (void*)v->sig, (void*)v->zexp, (void*)v->k, (void*)v->msg, (void*)v->off, (void*)s.flags,
-                  (void*)s.d_out, (void*)v->karea, (void*)v->idx, (void*)v->run, (void*)v->origin, (void*)v->st_vk,
-                  (void*)v->st_sig, (void*)v->st_k, (void*)v->hit, (void*)v->wg, (void*)v->verd, (void*)v->offv})
-    if (p) (void)hipFree(p);
-  if (v->h_cnt) (void)hipHostFree(v->h_cnt);
-  if (v->ev_cnt) (void)hipEventDestroy(v->ev_cnt);
-  if (v->ev_gather) (void)hipEventDestroy(v->ev_gather);
-  if (s.h_out) (void)hipHostFree(s.h_out);
-  if (s.h_acc) (void)hipHostFree(s.h_acc);
-  for (int p = 0; p <= PH_N; ++p)
-    if (s.ev[p]) (void)hipEventDestroy(s.ev[p]);
-  for (hipEvent_t e : s.ev_acc)
-    if (e) (void)hipEventDestroy(e);
-  if (v->ev_copy) (void)hipEventDestroy(v->ev_copy);
-  if (v->ev_chal) (void)hipEventDestroy(v->ev_chal);
-  if (v->cs) (void)hipStreamDestroy(v->cs);
-  if (s.st) (void)hipStreamDestroy(s.st);
   delete v;
 }
 
@@ -4256,7 +3946,7 @@ int edc_vfy_set_cached(edc_verifier* v, int on) {
   // queue path writes them from the copy stream, which nothing orders behind the insert. So the
   // mode never changes under a pending insert: records are only ever made of bytes that verified.
   CK(hipStreamSynchronize(v->s.st));
-  if (on && !v->origin) CK(dalloc(&v->origin, v->cap));   // one offered position per retained item
+  if (on && !v->origin) CK(v->origin.alloc(v->cap));   // one offered position per retained item
   v->cached.on = on != 0;
   return 0;
 }
@@ -4287,7 +3977,7 @@ int edc_vfy_begin_eager(edc_verifier* v, const uint8_t z_seed[32]) {
     }
   }
   CK(hipSetDevice(ctx->device));
-  if (!v->run) CK(dalloc(&v->run, 128));   // the running point, then a fold's 256-byte result block
+  if (!v->run) CK(v->run.alloc(128));   // the running point, then a fold's 256-byte result block
   launch_point_accum(v->s.st, v->run, nullptr);
   CK(hipGetLastError());
   memcpy(v->eager_seed, seed, 32);
@@ -4338,11 +4028,13 @@ struct MultiSlot {
   int64_t ticket = -1;
   bool want = false;
   std::vector<int64_t> shard;        // shard tickets, one per context
-  std::vector<hipEvent_t> copied;    // recorded on each shard's slot stream after its block copy
-  hipEvent_t done = nullptr;         // first device, after the combine
-  uint8_t* blocks = nullptr;         // first device: ndev x 256 bytes
-  uint8_t* d_out = nullptr;          // first device: 256-byte verdict block
-  uint8_t* h_out = nullptr;          // pinned mirror
+  // the owners below are emptied by multi_slot_free with the owning device current (the shards'
+  // events each with their shard's device, the rest with the first device)
+  std::vector<Event> copied;         // recorded on each shard's slot stream after its block copy
+  Event done;                        // first device, after the combine
+  DevBuf<uint8_t> blocks;            // first device: ndev x 256 bytes
+  DevBuf<uint8_t> d_out;             // first device: 256-byte verdict block
+  PinnedBuf<uint8_t> h_out;          // pinned mirror
 };
 
 enum { ROUTE_LOCAL = 0, ROUTE_PEER = 1, ROUTE_STAGED = 2 };
@@ -4355,7 +4047,8 @@ struct edc_multi {
   MultiSlot ms[kSlots];
   int ring = kSlots;                 // multi-batches in flight = the smallest shard context's slot count
   int64_t next_ticket = 0;
-  hipStream_t comb = nullptr;        // first device: every batch's combine, in submission order
+  Stream comb;                       // first device: every batch's combine, in submission order
+                                     // (reset by edc_destroy_multi with that device current)
 };
 
 struct Shard {
@@ -4434,15 +4127,16 @@ static int multi_slot_init(edc_multi* M, MultiSlot& ms) {
   MCK(hipSetDevice(M->ctx[0]->device));
   // the combines are tiny and in order: one ordinary stream for all of them (the shard contexts'
   // slot streams already hold a hardware queue each)
-  if (!M->comb) MCK(hipStreamCreateWithFlags(&M->comb, hipStreamNonBlocking));
-  MCK(hipEventCreateWithFlags(&ms.done, hipEventDisableTiming));
-  MCK(hipMalloc((void**)&ms.blocks, 256 * g));
-  MCK(hipMalloc((void**)&ms.d_out, 256));
-  MCK(hipHostMalloc((void**)&ms.h_out, 256));
-  ms.copied.assign(g, nullptr);
+  if (!M->comb) MCK(M->comb.create(hipStreamNonBlocking));
+  MCK(ms.done.create(hipEventDisableTiming));
+  MCK(ms.blocks.alloc(256 * g));
+  MCK(ms.d_out.alloc(256));
+  MCK(ms.h_out.alloc(256));
+  ms.copied.clear();
+  ms.copied.resize(g);
   for (size_t i = 0; i < g; ++i) {
     MCK(hipSetDevice(M->ctx[i]->device));
-    MCK(hipEventCreateWithFlags(&ms.copied[i], hipEventDisableTiming));
+    MCK(ms.copied[i].create(hipEventDisableTiming));
   }
   return 0;
 }
@@ -4451,12 +4145,11 @@ static void multi_slot_free(edc_multi* M, MultiSlot& ms) {
   if (!ms.done) return;
   (void)hipSetDevice(M->ctx[0]->device);
   (void)hipEventSynchronize(ms.done);
-  for (hipEvent_t e : ms.copied)
-    if (e) (void)hipEventDestroy(e);
-  if (ms.done) (void)hipEventDestroy(ms.done);
-  if (ms.blocks) (void)hipFree(ms.blocks);
-  if (ms.d_out) (void)hipFree(ms.d_out);
-  if (ms.h_out) (void)hipHostFree(ms.h_out);
+  for (size_t i = 0; i < ms.copied.size(); ++i) {
+    (void)hipSetDevice(M->ctx[i]->device);
+    ms.copied[i].reset();
+  }
+  (void)hipSetDevice(M->ctx[0]->device);
   ms = MultiSlot();
 }
 
@@ -4570,7 +4263,7 @@ void edc_destroy_multi(edc_multi* M) {
   for (MultiSlot& ms : M->ms) multi_slot_free(M, ms);
   if (M->comb) {
     (void)hipSetDevice(M->ctx[0]->device);
-    (void)hipStreamDestroy(M->comb);
+    M->comb.reset();
   }
   for (edc_ctx* c : M->ctx) edc_destroy(c);
   delete M;
@@ -4644,8 +4337,8 @@ int edc_multi_wait(edc_multi* M, int64_t ticket, uint8_t check8[32]) {
     return err;
   }
   MCK(hipEventSynchronize(ms.done));
-  const int verdict = reinterpret_cast<int*>(ms.h_out)[0];
-  const int bad = reinterpret_cast<int*>(ms.h_out)[1];
+  const int verdict = reinterpret_cast<int*>(ms.h_out.get())[0];
+  const int bad = reinterpret_cast<int*>(ms.h_out.get())[1];
   if (check8) {
     if (bad || !ms.want) memset(check8, 0, 32);
     else memcpy(check8, ms.h_out + 16, 32);

@@ -413,6 +413,13 @@ int edc_debug_set_scatter_stage(uint32_t max_entries);
 int edc_debug_sc_reduce_wide(edc_ctx* ctx, size_t n, const uint8_t* d_in, uint8_t* d_out);
 
 /*
+ * Test hook (process-wide): out[0] = live device allocations, out[1] = live pinned host
+ * allocations made by this library's contexts, verifiers and multi-device objects. Lets a test
+ * assert that create / run / destroy leaked nothing on a device other processes allocate on.
+ */
+int edc_debug_live_allocs(uint64_t out[2]);
+
+/*
  * Shape of the grouped fallback's range MSM (tuning / measurement): about `ranges` contiguous
  * ranges (1..1024, default 32) with `bits`-bit windows (8..13, default 10). The range count is
  * capped so that ranges x bins per range stays within the MSM's 8192 bins (e.g. at most 24 ranges

@@ -9,10 +9,10 @@ context plans dense/grouped, the second adaptively: few-keys windows, per-signat
 Cases: vote batches (150 validators) and distinct keys; ragged n (a partial last chunk) and n at
 the 2^16 threshold; 0..1024-byte messages with offsets that do not start at 0; a wrong signature in
 the last chunk (a non-identity check8); an undecodable R in the last chunk and an s = l in the first
-(the bad flag: code 1, zero check8); caller-drawn z. Grouped batches accumulate each chunk's R
-terms into the MSM buckets as the chunk lands and add the key / B terms at the end; key grouping
-forced for distinct keys (70,001 key terms at the end) and the device's grouping overflow (one A_i
-term per signature at the end, FLAG_OVF) are covered too."""
+(the bad flag: code 1, zero check8); caller-drawn z. Each chunk gets its decode, SHA-512 and
+coefficients as it lands; binning, sort and the one MSM over all terms run after the last chunk. Key
+grouping forced for distinct keys (70,001 key terms) and the device's grouping overflow (one A_i
+term per signature, FLAG_OVF) are covered too."""
 import ctypes
 import os
 import sys
