@@ -66,6 +66,8 @@ ABI_SYMBOLS = [
     "edc_tmpl_batch_submit", "edc_vfy_queue_templated",
     "edc_commits_verify_device", "edc_commits_verify", "edc_tmpl_commits_verify", "edc_commits_submit",
     "edc_tmpl_commits_submit", "edc_commits_submit_device", "edc_commits_wait", "edc_debug_tmpl_commit_map",
+    "edc_tmpl_commits_verify_alt", "edc_tmpl_commits_submit_alt", "edc_tmpl_commits_verify_device",
+    "edc_tmpl_commits_submit_device", "edc_debug_tmpl_commit_map_alt",
     "edc_debug_live_allocs",
 ]
 
@@ -304,6 +306,21 @@ def load_library(path=None):
             lib.edc_commits_wait.argtypes = [c_vp, ctypes.c_int64, c_vp, c_vp, c_ip]
             lib.edc_debug_tmpl_commit_map.argtypes = [c_vp, c_sz, c_u32p, c_u16p, c_u16p, ctypes.c_int,
                                                       ctypes.POINTER(ctypes.c_float)]
+        if hasattr(lib, "edc_tmpl_commits_verify_alt"):      # absent from older A/B builds (tools/)
+            c_tsp, c_u16p = ctypes.POINTER(EdcTemplates), ctypes.POINTER(ctypes.c_uint16)
+            c_u32p, c_ip, c_u32 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int), ctypes.c_uint32
+            lib.edc_tmpl_commits_verify_alt.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, c_u32, c_vp, c_u8p, c_u32p,
+                                                        c_u8p, c_u8p, c_u32p, c_u8p, c_vp, c_vp, c_ip]
+            lib.edc_tmpl_commits_submit_alt.restype = ctypes.c_int64
+            lib.edc_tmpl_commits_submit_alt.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, c_u32, c_vp, c_u8p, c_u32p,
+                                                        c_u8p, c_u8p, c_u32p, c_u8p]
+            lib.edc_tmpl_commits_verify_device.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, c_u32, c_vp, c_vp, c_vp,
+                                                           c_vp, c_vp, c_sz, c_u8p, c_vp, c_vp, c_ip]
+            lib.edc_tmpl_commits_submit_device.restype = ctypes.c_int64
+            lib.edc_tmpl_commits_submit_device.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, c_u32, c_vp, c_vp, c_vp,
+                                                           c_vp, c_vp, c_sz, c_u8p]
+            lib.edc_debug_tmpl_commit_map_alt.argtypes = [c_vp, c_sz, c_u32p, c_u16p, c_u32, c_vp, c_vp, c_ip,
+                                                          ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         if path is None:
             _lib = lib
         return lib
@@ -631,6 +648,92 @@ class Engine:
             if t < 0:
                 self._check(t)
             self._commits_inflight[t] = (nc, n, bufs, None)
+        return t
+
+    # Template variants: every commit owns the window [commit_tpl[c], commit_tpl[c] + alt_span) of the
+    # set and item i takes template commit_tpl[c] + item_alt[i] (item_alt None: all zeros).
+    @staticmethod
+    def _item_alt(item_alt):
+        if item_alt is None:
+            return None
+        if any(not 0 <= int(a) <= 255 for a in item_alt):
+            raise ValueError("item_alt entries are uint8")
+        return bytes(bytearray(int(a) for a in item_alt)) or b"\0"
+
+    def commits_verify_templated_alt(self, templates, commit_off, commit_tpl, alt_span, item_alt, sigs, holes, z_seed,
+                                     vks=None, key_idx=None, var_off=None):
+        """edc_tmpl_commits_verify_alt: commits_verify_templated with a variant byte per item."""
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        ts, _keep = templates.struct()
+        _, var, voff = _tmpl_items([0] * n, holes, var_off)
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        out = self._commits_out(nc, n)
+        with self._lock:
+            rc = self.lib.edc_tmpl_commits_verify_alt(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
+                                                      self._item_alt(item_alt), vkb, idx, b"".join(sigs) or b"\0", var,
+                                                      voff, bytes(z_seed), out[0], out[1], ctypes.byref(out[2]))
+        self._check(rc)
+        return self._commits_result(rc, nc, n, out)
+
+    def commits_submit_templated_alt(self, templates, commit_off, commit_tpl, alt_span, item_alt, sigs, holes, z_seed,
+                                     vks=None, key_idx=None, var_off=None):
+        """edc_tmpl_commits_submit_alt: a ticket for commits_wait."""
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        ts, keep = templates.struct()
+        _, var, voff = _tmpl_items([0] * n, holes, var_off)
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        bufs = (ts, keep, off, ctpl, vkb, idx, b"".join(sigs) or b"\0", var, voff, bytes(z_seed), self._item_alt(item_alt))
+        with self._lock:
+            t = self.lib.edc_tmpl_commits_submit_alt(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span, bufs[10], vkb,
+                                                     idx, bufs[6], var, voff, bufs[9])
+            if t < 0:
+                self._check(t)
+            self._commits_inflight[t] = (nc, n, bufs, None)
+        return t
+
+    @staticmethod
+    def _dev_ptr(x):
+        """A device pointer given as an int, None, or a torch tensor (its data_ptr())."""
+        return x.data_ptr() if hasattr(x, "data_ptr") else x
+
+    def commits_verify_templated_device(self, templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig,
+                                        d_var, d_var_off, var_bytes, z_seed):
+        """edc_tmpl_commits_verify_device: keys, signatures, holes and variant bytes as torch tensors
+        or device pointers (ints; d_item_alt None: all zeros); commit_off, commit_tpl and the set on the host."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        ts, _keep = templates.struct()
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        out = self._commits_out(nc, n)
+        p = self._dev_ptr
+        with self._lock:
+            rc = self.lib.edc_tmpl_commits_verify_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
+                                                         p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
+                                                         var_bytes, bytes(z_seed), out[0], out[1], ctypes.byref(out[2]))
+        self._check(rc)
+        return self._commits_result(rc, nc, n, out)
+
+    def commits_submit_templated_device(self, templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig,
+                                        d_var, d_var_off, var_bytes, z_seed):
+        """edc_tmpl_commits_submit_device: a ticket for commits_wait; the device arrays (kept alive
+        here when given as tensors) stay the caller's until then."""
+        nc, off = self._commit_offsets(commit_off)
+        ts, keep = templates.struct()
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        seed = bytes(z_seed)
+        p = self._dev_ptr
+        bufs = (ts, keep, off, ctpl, seed, d_item_alt, d_vk, d_sig, d_var, d_var_off)
+        with self._lock:
+            t = self.lib.edc_tmpl_commits_submit_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
+                                                        p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
+                                                        var_bytes, seed)
+            if t < 0:
+                self._check(t)
+            self._commits_inflight[t] = (nc, off[nc] if nc else 0, bufs, None)
         return t
 
     def commits_verify_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, z_seed, d_k=None):

@@ -30,6 +30,27 @@ inline bool commits_check_tpl(uint32_t count, size_t nc, const uint16_t* commit_
   return true;
 }
 
+// Template variants (edc_tmpl_commits_*_alt / _device): every commit, empty ones included, owns
+// the window [commit_tpl[c], commit_tpl[c] + alt_span) of the set, alt_span in 1..COMMITS_MAX_ALT_SPAN
+// (a variant is one byte), and the whole window lies inside the set.
+constexpr uint32_t COMMITS_MAX_ALT_SPAN = 256;
+
+inline bool commits_check_alt_span(uint32_t count, size_t nc, const uint16_t* commit_tpl, uint32_t alt_span) {
+  if (!commit_tpl || alt_span < 1 || alt_span > COMMITS_MAX_ALT_SPAN) return false;
+  for (size_t c = 0; c < nc; ++c)
+    if ((uint64_t)commit_tpl[c] + alt_span > count) return false;
+  return true;
+}
+
+// item_alt[i] < alt_span for every item; a null item_alt is n zeros.
+inline bool commits_check_item_alt(size_t n, const uint8_t* item_alt, uint32_t alt_span) {
+  if (alt_span < 1) return false;
+  if (!item_alt) return true;
+  uint8_t mx = 0;                        // a byte maximum with no early exit: the loop vectorizes 16 items wide
+  for (size_t i = 0; i < n; ++i) mx = item_alt[i] > mx ? item_alt[i] : mx;
+  return (uint32_t)mx < alt_span;
+}
+
 // The holes of a templated commit set (tmpl_check_items without the per-item template array,
 // which such a call does not have): var_off[0] == 0, monotone.
 inline bool commits_check_holes(size_t n, const uint32_t* var_off) {

@@ -1388,12 +1388,15 @@ static int tmpl_upload_set(edc_ctx* ctx, TmplWs& w, hipStream_t st, const edc_te
 }
 
 // The three kernels on st: n items (device arrays) -> out (>= tmpl_arena_bound bytes) and off[n + 1].
+// keep_flag: the caller cleared w.flag on st itself and a kernel in front of these may have raised it
+// (k_tmpl_commit_map_alt).
 static int tmpl_expand(edc_ctx* ctx, TmplWs& w, hipStream_t st, const TmplView& view, size_t n, const uint16_t* d_tpl,
-                       const uint8_t* d_var, const uint32_t* d_var_off, size_t var_bytes, uint8_t* out, uint64_t* off) {
+                       const uint8_t* d_var, const uint32_t* d_var_off, size_t var_bytes, uint8_t* out, uint64_t* off,
+                       bool keep_flag = false) {
   if (!n) return 0;
   int rc = tmpl_room(ctx, st, w.bsum, tmpl_scan_words(n));
   if (rc) return rc;
-  CK(hipMemsetAsync(w.flag, 0, sizeof(int), st));
+  if (!keep_flag) CK(hipMemsetAsync(w.flag, 0, sizeof(int), st));
   launch_tmpl_expand(st, (uint32_t)n, view, d_tpl, d_var, d_var_off, var_bytes, w.flag, w.bsum, out, off);
   CK(hipGetLastError());
   return 0;
@@ -2315,6 +2318,50 @@ static int commits_check_tmpl(edc_ctx* ctx, const edc_templates* ts, size_t nc, 
   return 0;
 }
 
+// Template variants: every commit's window [commit_tpl[c], commit_tpl[c] + alt_span) inside the set.
+static int commits_check_windows(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint16_t* commit_tpl,
+                                 uint32_t alt_span) {
+  if (!commits_check_alt_span(ts->count, nc, commit_tpl, alt_span)) {
+    ctx->err = "template variants: alt_span in 1..256 and commit_tpl[c] + alt_span <= the set's count for every commit";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// the host checks of edc_tmpl_commits_verify_alt / _submit_alt: those of the one-template form,
+// then the windows and the variant bytes
+static int commits_check_tmpl_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
+                                  const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var,
+                                  const uint32_t* var_off, TmplShape* sh, size_t* n) {
+  int rc = commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, vk, key_idx, sig, var, var_off, sh, n);
+  if (rc || (rc = commits_check_windows(ctx, ts, nc, commit_tpl, alt_span))) return rc;
+  if (!commits_check_item_alt(*n, item_alt, alt_span)) {
+    ctx->err = "template variants: item_alt[i] < alt_span for every item";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// What the device forms of a templated commit set check on the host: the set, the offsets, the
+// windows, the pointers. The holes and the variant bytes are checked on the device.
+static int commits_check_tmpl_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                     const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_vk,
+                                     const uint8_t* d_sig, const uint8_t* d_var, const uint32_t* d_var_off,
+                                     size_t var_bytes, TmplShape* sh, size_t* n) {
+  int rc = tmpl_check(ctx, ts, sh);
+  if (rc || (rc = commits_check(ctx, nc, commit_off, n)) || (rc = commits_check_windows(ctx, ts, nc, commit_tpl, alt_span)))
+    return rc;
+  if (var_bytes > 0xFFFFFFFFull) { ctx->err = "var arena must be below 4 GiB"; return EDC_ERR_ARG; }
+  if (!*n) return 0;
+  if (!d_vk || !d_sig || !d_var_off || (var_bytes && !d_var)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (!aligned16(d_vk) || !aligned16(d_sig) || ((uintptr_t)d_var_off & 3u)) {
+    ctx->err = "device vk / sig arrays must be 16-byte aligned, d_var_off 4-byte aligned";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
 // A checked host commit set into slot s (as upload_slot / upload_slot_prehashed) and the union
 // batch behind it on the slot's stream.
 static int commits_enqueue(edc_ctx* ctx, Slot& s, size_t nc, const uint32_t* commit_off, size_t n, const uint8_t* d_vk,
@@ -2348,11 +2395,14 @@ static int commits_enqueue_host(edc_ctx* ctx, Slot& s, size_t nc, const uint32_t
 
 // A checked templated commit set into slot s (as tmpl_upload_slot): the per-item template array
 // is made on the device from the commit offsets (k_tmpl_commit_map), then the existing expansion.
-// Staging area: var_off | tpl | var | commit_off | commit_tpl, each at a 16-byte boundary.
+// Staging area: var_off | tpl | var | commit_off | commit_tpl | item_alt, each at a 16-byte boundary.
+// alt_span = 0: one template per commit. alt_span >= 1: the checked variants (k_tmpl_commit_map_alt;
+// item_alt, n bytes, is staged unless it is null).
 static int commits_enqueue_tmpl(edc_ctx* ctx, Slot& s, const edc_templates* ts, const TmplShape& sh, size_t nc,
                                 const uint32_t* commit_off, const uint16_t* commit_tpl, size_t n, const uint8_t* vk,
                                 const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
-                                const uint8_t* z_seed, bool latency) {
+                                const uint8_t* z_seed, bool latency, uint32_t alt_span = 0,
+                                const uint8_t* item_alt = nullptr) {
   int rc = ensure_slot_inputs(ctx, s, n, 0);
   if (rc) return rc;
   TmplView view;
@@ -2363,8 +2413,9 @@ static int commits_enqueue_tmpl(edc_ctx* ctx, Slot& s, const edc_templates* ts, 
     const size_t var_bytes = var_off[n];
     const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_tpl = up16(4 * (n + 1)), o_var = up16(o_tpl + 2 * n), o_coff = up16(o_var + var_bytes),
-                 o_ctpl = up16(o_coff + 4 * (nc + 1));
-    if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) || (rc = tmpl_room(ctx, st, w.in, o_ctpl + 2 * nc)))
+                 o_ctpl = up16(o_coff + 4 * (nc + 1)), o_alt = up16(o_ctpl + 2 * nc);
+    if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) ||
+        (rc = tmpl_room(ctx, st, w.in, item_alt ? o_alt + n : o_ctpl + 2 * nc)))
       return rc;
     if (key_idx) {
       CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -2379,14 +2430,59 @@ static int commits_enqueue_tmpl(edc_ctx* ctx, Slot& s, const edc_templates* ts, 
     CK(hipMemcpyAsync(w.in + o_coff, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(w.in + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
     uint16_t* d_tpl = reinterpret_cast<uint16_t*>(w.in + o_tpl);
-    launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(w.in + o_coff),
-                           reinterpret_cast<const uint16_t*>(w.in + o_ctpl), d_tpl);
+    if (alt_span) {
+      if (item_alt) CK(hipMemcpyAsync(w.in + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
+      // the host has checked every byte, so the kernel never raises the flag here: tmpl_expand clears it as always
+      launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(w.in + o_coff),
+                                 reinterpret_cast<const uint16_t*>(w.in + o_ctpl), alt_span,
+                                 item_alt ? w.in + o_alt : nullptr, d_tpl, w.flag);
+    } else {
+      launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(w.in + o_coff),
+                             reinterpret_cast<const uint16_t*>(w.in + o_ctpl), d_tpl);
+    }
     CK(hipGetLastError());
     if ((rc = tmpl_expand(ctx, w, st, view, n, d_tpl, w.in + o_var, reinterpret_cast<const uint32_t*>(w.in.get()), var_bytes,
                           w.arena, w.off)))
       return rc;
   }
   return commits_enqueue(ctx, s, nc, commit_off, n, s.in_vk, s.in_sig, s.tw.arena, s.tw.off, nullptr, z_seed, latency);
+}
+
+// A templated commit set whose items are device-resident (edc_tmpl_commits_*_device): only
+// commit_off and commit_tpl are staged (tpl | commit_off | commit_tpl in the slot's staging area) and
+// the set uploaded; keys, signatures, holes and variant bytes are read where the caller has them.
+// The device checks the holes and the variant bytes; the flag travels behind the expansion and the
+// wait reads it before it believes a verdict (finish_batch, as edc_tmpl_batch_verify_device).
+static int commits_enqueue_tmpl_device(edc_ctx* ctx, Slot& s, const edc_templates* ts, const TmplShape& sh, size_t nc,
+                                       const uint32_t* commit_off, const uint16_t* commit_tpl, size_t n,
+                                       uint32_t alt_span, const uint8_t* d_item_alt, const uint8_t* d_vk,
+                                       const uint8_t* d_sig, const uint8_t* d_var, const uint32_t* d_var_off,
+                                       size_t var_bytes, const uint8_t* z_seed, bool latency) {
+  int rc = init_slot(ctx, s);
+  if (rc) return rc;
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, s.tw, s.st, ts, sh, &view))) return rc;
+  if (n) {
+    TmplWs& w = s.tw;
+    hipStream_t st = s.st;
+    const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_coff = up16(2 * n), o_ctpl = up16(o_coff + 4 * (nc + 1));
+    if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) || (rc = tmpl_room(ctx, st, w.in, o_ctpl + 2 * nc)))
+      return rc;
+    CK(hipMemcpyAsync(w.in + o_coff, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(w.in + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
+    uint16_t* d_tpl = reinterpret_cast<uint16_t*>(w.in.get());
+    CK(hipMemsetAsync(w.flag, 0, sizeof(int), st));
+    launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(w.in + o_coff),
+                               reinterpret_cast<const uint16_t*>(w.in + o_ctpl), alt_span, d_item_alt, d_tpl, w.flag);
+    CK(hipGetLastError());
+    if ((rc = tmpl_expand(ctx, w, st, view, n, d_tpl, d_var, d_var_off, var_bytes, w.arena, w.off, true))) return rc;
+    CK(hipMemcpyAsync(w.h_flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    w.check = true;
+  }
+  rc = commits_enqueue(ctx, s, nc, commit_off, n, d_vk, d_sig, s.tw.arena, s.tw.off, nullptr, z_seed, latency);
+  if (rc) s.tw.check = false;     // the batch never reaches its wait
+  return rc;
 }
 
 // Wait for a commit-set slot. The union passed: every commit Ok. It failed: the grouped fallback on
@@ -2546,6 +2642,96 @@ int64_t edc_tmpl_commits_submit(edc_ctx* ctx, const edc_templates* ts, size_t nc
   return commits_ticket(ctx, *s);
 }
 
+int edc_tmpl_commits_verify_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
+                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                                const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32],
+                                uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  if (!nc) return commits_none(n_bad_commits);
+  size_t n;
+  TmplShape sh;
+  int rc = commits_check_tmpl_alt(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
+                                  &sh, &n);
+  if (rc) return rc;
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_tmpl(ctx, s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
+                                 true, alt_span, item_alt)))
+    return rc;
+  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+}
+
+int64_t edc_tmpl_commits_submit_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                    const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
+                                    const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                                    const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  size_t n = 0;
+  TmplShape sh;
+  int rc = nc ? commits_check_tmpl_alt(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var,
+                                       var_off, &sh, &n)
+              : tmpl_check(ctx, ts, &sh);
+  if (rc) return rc;
+  if (!nc && (alt_span < 1 || alt_span > COMMITS_MAX_ALT_SPAN)) {
+    ctx->err = "template variants: alt_span in 1..256";
+    return EDC_ERR_ARG;
+  }
+  Slot* s;
+  if ((rc = commits_next_slot(ctx, &s))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_tmpl(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
+                                 false, alt_span, item_alt)))
+    return rc;
+  return commits_ticket(ctx, *s);
+}
+
+int edc_tmpl_commits_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                   const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                   const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                   const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32],
+                                   uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  if (!nc) return commits_none(n_bad_commits);
+  size_t n;
+  TmplShape sh;
+  int rc = commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
+                                     var_bytes, &sh, &n);
+  if (rc) return rc;
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_tmpl_device(ctx, s, ts, sh, nc, commit_off, commit_tpl, n, alt_span, d_item_alt, d_vk, d_sig,
+                                        d_var, d_var_off, var_bytes, z_seed, true)))
+    return rc;
+  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+}
+
+int64_t edc_tmpl_commits_submit_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                       const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                       const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                       const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  size_t n = 0;
+  TmplShape sh;
+  int rc = nc ? commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
+                                          var_bytes, &sh, &n)
+              : tmpl_check(ctx, ts, &sh);
+  if (rc) return rc;
+  if (!nc && (alt_span < 1 || alt_span > COMMITS_MAX_ALT_SPAN)) {
+    ctx->err = "template variants: alt_span in 1..256";
+    return EDC_ERR_ARG;
+  }
+  Slot* s;
+  if ((rc = commits_next_slot(ctx, &s))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = commits_enqueue_tmpl_device(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, alt_span, d_item_alt, d_vk, d_sig,
+                                        d_var, d_var_off, var_bytes, z_seed, false)))
+    return rc;
+  return commits_ticket(ctx, *s);
+}
+
 int edc_commits_wait(edc_ctx* ctx, int64_t ticket, uint8_t* commit_verdicts, uint8_t* item_verdicts,
                      int* n_bad_commits) {
   if (!ctx || ticket < 0) return EDC_ERR_ARG;
@@ -2581,6 +2767,52 @@ int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   CK(hipEventRecord(s.ev[1], st));
   if (n) CK(hipMemcpyAsync(tpl_out, ctx->aux + o_tpl, 2 * n, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
+  if (ms) {
+    CK(hipEventElapsedTime(ms, s.ev[0], s.ev[1]));
+    *ms /= (float)reps;
+  }
+  return 0;
+}
+
+int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
+                                  uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl_out, int* flagged,
+                                  int reps, float* ms) {
+  if (!ctx || !nc || !commit_tpl || reps < 1) return EDC_ERR_ARG;
+  size_t n;
+  int rc = commits_check(ctx, nc, commit_off, &n);
+  if (rc) return rc;
+  if (!commits_check_alt_span(65535, nc, commit_tpl, alt_span)) {      // the windows inside the largest set there is
+    ctx->err = "template variants: alt_span in 1..256 and commit_tpl[c] + alt_span <= 65535";
+    return EDC_ERR_ARG;
+  }
+  if (n && !tpl_out) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  Slot& s = ctx->slot[0];
+  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  // the device copies of item_alt and tpl_out start at the host pointers' offsets from a 16-byte
+  // boundary, so a caller picks the kernel's wide or narrow access paths by how it places its arrays
+  const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t o_ctpl = up16(4 * (nc + 1)), o_alt = up16(o_ctpl + 2 * nc) + ((uintptr_t)item_alt & 15u),
+               o_flag = up16(o_alt + n), o_tpl = o_flag + 16 + ((uintptr_t)tpl_out & 14u);
+  if ((rc = init_slot(ctx, s)) || (rc = ensure_aux(ctx, o_tpl + 2 * n))) return rc;
+  hipStream_t st = s.st;
+  int* d_flag = reinterpret_cast<int*>(ctx->aux + o_flag);
+  CK(hipMemcpyAsync(ctx->aux, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->aux + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
+  if (item_alt && n) CK(hipMemcpyAsync(ctx->aux + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
+  CK(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  CK(hipEventRecord(s.ev[0], st));
+  for (int r = 0; r < reps; ++r)
+    launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(ctx->aux.get()),
+                               reinterpret_cast<const uint16_t*>(ctx->aux + o_ctpl), alt_span,
+                               item_alt ? ctx->aux + o_alt : nullptr, reinterpret_cast<uint16_t*>(ctx->aux + o_tpl), d_flag);
+  CK(hipGetLastError());
+  CK(hipEventRecord(s.ev[1], st));
+  int flag = 0;
+  if (n) CK(hipMemcpyAsync(tpl_out, ctx->aux + o_tpl, 2 * n, hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  if (flagged) *flagged = flag != 0;
   if (ms) {
     CK(hipEventElapsedTime(ms, s.ev[0], s.ev[1]));
     *ms /= (float)reps;

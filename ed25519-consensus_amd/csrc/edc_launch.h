@@ -100,6 +100,12 @@ size_t tmpl_scan_words(size_t n);
 // (nc + 1 checked offsets, commit_off[nc] = n; empty commits allowed). All device pointers.
 void launch_tmpl_commit_map(hipStream_t st, uint32_t n, uint32_t nc, const uint32_t* commit_off,
                             const uint16_t* commit_tpl, uint16_t* tpl);
+// the same with template variants: tpl[i] = commit_tpl[c] + item_alt[i] (item_alt null: zeros). The
+// windows [commit_tpl[c], commit_tpl[c] + alt_span) are checked by the host; a byte >= alt_span
+// raises *flag (the expansion's, cleared by the caller before this launch) and maps to the base.
+void launch_tmpl_commit_map_alt(hipStream_t st, uint32_t n, uint32_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl,
+                                int* flag);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

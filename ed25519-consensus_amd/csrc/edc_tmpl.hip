@@ -9,6 +9,8 @@
 //                   span's two partial end chunks, which the neighbouring workgroups share)
 //   k_tmpl_commit_map  commit sets with one template per commit: the per-item tpl array from the
 //                   commit offsets, in front of the three kernels above
+//   k_tmpl_commit_map_alt  the same with a variant byte per item: tpl[i] = commit_tpl[c] + item_alt[i];
+//                   raises the flag on a byte outside the commit's window
 //
 // The flag: k_tmpl_len raises it when tpl[i] >= count or var_off[i] <= var_off[i+1] <= var_bytes
 // does not hold. The other two kernels read it first and then produce n empty messages, so
@@ -234,6 +236,78 @@ void launch_tmpl_commit_map(hipStream_t st, uint32_t n, uint32_t nc, const uint3
   const uint32_t per = TMPL_BLOCK * TMPL_MAP_ITEMS;
   hipLaunchKernelGGL(k_tmpl_commit_map, dim3((n + per - 1) / per), dim3(TMPL_BLOCK), 0, st, n, nc, commit_off,
                      commit_tpl, tpl);
+}
+
+// Commit sets with template variants (edc_tmpl_commits_*_alt / _device): tpl[i] = commit_tpl[c] +
+// item_alt[i], one variant byte per item (null: all zeros). The host has checked the offsets and
+// that every commit's window [commit_tpl[c], commit_tpl[c] + alt_span) lies inside the set; the
+// variant bytes of a device form are checked here. A byte >= alt_span raises the flag of the
+// expansion (which then produces n empty messages) and its item gets the commit's base, so every
+// value written is below the set's count whether or not the flag has been read.
+__global__ void __launch_bounds__(TMPL_BLOCK) k_tmpl_commit_map_alt(uint32_t n, uint32_t nc,
+                                                                   const uint32_t* __restrict__ commit_off,
+                                                                   const uint16_t* __restrict__ commit_tpl,
+                                                                   uint32_t alt_span,
+                                                                   const uint8_t* __restrict__ item_alt,
+                                                                   uint16_t* __restrict__ tpl, int* __restrict__ flag) {
+  // the workgroup's items [g0, g1] bound the lanes' searches, as in k_tmpl_commit_map
+  const uint32_t g0 = blockIdx.x * (uint32_t)(TMPL_BLOCK * TMPL_MAP_ITEMS);
+  const uint32_t g1 = (n - g0 < (uint32_t)(TMPL_BLOCK * TMPL_MAP_ITEMS) ? n : g0 + TMPL_BLOCK * TMPL_MAP_ITEMS) - 1;
+  const uint32_t clo = tmpl_commit_of(commit_off, 0, nc - 1, g0), chi = tmpl_commit_of(commit_off, clo, nc - 1, g1);
+  const uint32_t i0 = g0 + threadIdx.x * TMPL_MAP_ITEMS;
+  if (i0 >= n) return;
+  uint32_t c = tmpl_commit_of(commit_off, clo, chi, i0);
+  uint32_t end = commit_off[c + 1], t = commit_tpl[c];
+  const uint32_t cnt = n - i0 < (uint32_t)TMPL_MAP_ITEMS ? n - i0 : (uint32_t)TMPL_MAP_ITEMS;
+  // the lane's 8 variant bytes: one 8-byte load where the address is 8-byte aligned, else bytes
+  uint32_t a[TMPL_MAP_ITEMS / 4] = {0, 0};
+  if (item_alt) {
+    const uint8_t* p = item_alt + i0;
+    if (cnt == (uint32_t)TMPL_MAP_ITEMS && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
+      const uint2 v = *reinterpret_cast<const uint2*>(p);
+      a[0] = v.x;
+      a[1] = v.y;
+    } else {
+#pragma unroll
+      for (uint32_t j = 0; j < (uint32_t)TMPL_MAP_ITEMS; ++j)
+        if (j < cnt) a[j >> 2] |= (uint32_t)p[j] << (8 * (j & 3));
+    }
+  }
+  bool bad = false;
+  uint32_t w[TMPL_MAP_ITEMS / 2] = {0, 0, 0, 0};
+#pragma unroll
+  for (uint32_t j = 0; j < (uint32_t)TMPL_MAP_ITEMS; ++j) {
+    if (j < cnt) {
+      while (i0 + j >= end) {            // next commit, empty ones skipped; i0 + j < n = commit_off[nc] ends it
+        ++c;
+        end = commit_off[c + 1];
+        t = commit_tpl[c];
+      }
+      uint32_t v = (a[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+      if (v >= alt_span) {               // outside the window: the commit's base, and the flag
+        bad = true;
+        v = 0;
+      }
+      w[j >> 1] |= (t + v) << (16 * (j & 1));   // t + v < count <= 65535
+    }
+  }
+  if (bad) atomicOr(flag, 1);
+  if (cnt == (uint32_t)TMPL_MAP_ITEMS && (reinterpret_cast<uintptr_t>(tpl + i0) & 15u) == 0) {
+    *reinterpret_cast<uint4*>(tpl + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+  } else {
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)TMPL_MAP_ITEMS; ++j)
+      if (j < cnt) tpl[i0 + j] = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+  }
+}
+
+void launch_tmpl_commit_map_alt(hipStream_t st, uint32_t n, uint32_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl,
+                                int* flag) {
+  if (!n || !nc) return;
+  const uint32_t per = TMPL_BLOCK * TMPL_MAP_ITEMS;
+  hipLaunchKernelGGL(k_tmpl_commit_map_alt, dim3((n + per - 1) / per), dim3(TMPL_BLOCK), 0, st, n, nc, commit_off,
+                     commit_tpl, alt_span, item_alt, tpl, flag);
 }
 
 static size_t tmpl_expand_lds(const TmplView& ts, bool lds) {

@@ -791,6 +791,76 @@ int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
                               uint16_t* tpl_out, int reps, float* ms);
 
 /*
+ * Templated commit sets with per-item template variants, and their device-resident forms. A real
+ * commit does not fit one template: a precommit for nil signs another block id than a precommit
+ * for the block, and the sign bytes start with their own length, so a vote whose hole (the
+ * timestamp) encodes a byte longer or shorter has another first head byte. Two more inputs
+ * describe that at one byte per vote:
+ *   alt_span (1..256, one per call): every commit c, empty ones included, owns the window
+ *     [commit_tpl[c], commit_tpl[c] + alt_span) of the set; commit_tpl[c] + alt_span <= ts->count.
+ *   item_alt[i] (uint8_t, n entries, < alt_span; NULL = all zeros): the template of item i is
+ *     commit_tpl[c] + item_alt[i] for the commit c that holds it.
+ * With alt_span = 1 and item_alt = NULL every entry below is the one-template-per-commit call: the
+ * same verdicts and item codes. Everything behind the per-item template array is unchanged (the
+ * expansion, SHA-512, union first, the fallback at the wait on the ticket's own slot, the
+ * reduction to commits), so for the same keys and z_seed the commit verdicts, item verdicts and
+ * n_bad_commits are bit-identical to edc_commits_verify on the materialised messages. Results,
+ * return values and the soundness requirement on z_seed are those of the commit-set entries above;
+ * commit_off, commit_tpl and the template set are host memory in every form.
+ *
+ * edc_tmpl_commits_verify_alt  edc_tmpl_commits_verify with variants (Item::from,
+ *   src/batch.rs:82-94, then Verifier::queue x n + verify per commit, src/batch.rs:127-137,
+ *   :149-217; the item codes are Item::verify_single's, src/batch.rs:104-107); host buffers,
+ *   synchronous. item_alt is staged into the slot beside commit_off and commit_tpl.
+ * edc_tmpl_commits_submit_alt  the asynchronous host form (src/batch.rs:82-94, :127-137, :149-217
+ *   per commit; :104-107 per item at the wait): a ticket for edc_commits_wait under its ticket
+ *   rules; the inputs, item_alt included, are borrowed until the wait.
+ *   Host forms check everything before anything is launched, as edc_tmpl_commits_verify does, and
+ *   in addition: alt_span outside 1..256, a window that leaves the set, an item_alt[i] >= alt_span.
+ *   Any violation is EDC_ERR_ARG with nothing launched.
+ * edc_tmpl_commits_verify_device  the items in this GPU's memory (src/batch.rs:82-94, :127-137,
+ *   :149-217 per commit; :104-107 per item): d_vk (n x 32) and d_sig (n x 64) 16-byte aligned as
+ *   the other *_device entries, d_var / d_var_off / var_bytes as edc_tmpl_batch_verify_device,
+ *   d_item_alt n bytes of any alignment (NULL = all zeros). Only commit_off, commit_tpl and the set
+ *   are copied; the arrays are read in place. The host checks the offsets, alt_span and the
+ *   windows (EDC_ERR_ARG, nothing launched); the device checks the holes and d_item_alt[i] <
+ *   alt_span. On a violation the messages are assembled as n empty messages, nothing outside the
+ *   declared arrays is read, no template index at or above ts->count is formed, and the call
+ *   returns EDC_ERR_ARG, never a verdict; the context stays usable. Synchronous, on slot 0.
+ * edc_tmpl_commits_submit_device  its asynchronous form (src/batch.rs:82-94, :127-137, :149-217;
+ *   :104-107 at the wait): a ticket for edc_commits_wait; the device arrays and commit_off stay
+ *   the caller's until the wait, which returns EDC_ERR_ARG where the synchronous form would.
+ * edc_debug_tmpl_commit_map_alt  test / measurement hook: the map with variants alone
+ *   (tpl_out[i] = commit_tpl[c] + item_alt[i]; host arrays; offsets and alt_span checked as above,
+ *   the variant bytes by the device), run `reps` times between HIP events. *flagged (nullable) = 1
+ *   if the device found an item_alt[i] >= alt_span; such an item gets its commit's base. The device
+ *   copies of item_alt and tpl_out start at the host pointers' offsets from a 16-byte boundary, so
+ *   a test reaches the kernel's unaligned paths by offsetting its arrays. *ms as above.
+ * nc = 0 and a NULL ctx or z_seed: as the commit-set entries above.
+ */
+int edc_tmpl_commits_verify_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
+                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                                const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32],
+                                uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits);
+int64_t edc_tmpl_commits_submit_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
+                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                                const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32]);
+int edc_tmpl_commits_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32],
+                                uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits);
+int64_t edc_tmpl_commits_submit_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32]);
+int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
+                                uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl_out, int* flagged,
+                                int reps, float* ms);
+
+/*
  * Verified-signature cache: skip the items that already verified on this context. A consensus
  * node verifies the same vote several times: once when it arrives by gossip
  * (VerificationKey::verify, src/verification_key.rs:225-258, or Item::verify_single,

@@ -15,6 +15,14 @@ one run and the medians of --reps timings are reported:
                     in every round: 150 items from 150 validators make the context's automatic key
                     grouping give up for the next batches, so 8 untimed union batches follow it
   map               k_tmpl_commit_map alone (edc_debug_tmpl_commit_map, HIP events)
+  variants          the same votes with alt_span 4 and the four templates spread over the ITEMS (a
+                    hash of the item index), signed as such: edc_tmpl_commits_submit_alt with key
+                    indices  |  the stream row's edc_tmpl_commits_submit, and
+                    edc_tmpl_batch_submit on the variants workload (what the spread templates
+                    alone cost the expansion);
+                    edc_tmpl_commits_verify_device  |  the device row's edc_commits_verify_device;
+                    k_tmpl_commit_map_alt alone  |  the map row. Every message is 120 bytes in both
+                    workloads, so the rows differ by the variant byte and the map kernel only.
 
   python tools/commits_bench.py [--n 1048576] [--reps 20] [--inflight 4]
 """
@@ -81,6 +89,26 @@ def main():
     d_vk = torch.empty(n * 32, dtype=torch.uint8, device=dev)
     d_sig = torch.empty(n * 64, dtype=torch.uint8, device=dev)
     eng._check(lib.edc_sign_device(eng.ctx, n, vp(seeds), vp(kidx), vp(d_msg), vp(d_off), vp(d_vk), vp(d_sig)))
+    # the variants workload: every commit owns templates [0, 4) and item i takes template alt[i]
+    alt_np = ((np.arange(n, dtype=np.uint64) * 2654435761 >> 13) % 4).astype(np.uint8)
+    alt_h = torch.from_numpy(alt_np)
+    ctpl0_np = np.zeros(nc, dtype=np.uint16)
+    commit_tpl0 = ctpl0_np.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))
+    tpl2_h = torch.from_numpy(alt_np.astype(np.int16))
+    d_alt, d_tpl2 = alt_h.to(dev), tpl2_h.to(dev)
+    d_sig2 = torch.empty(n * 64, dtype=torch.uint8, device=dev)
+    d_msg2 = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    d_off2 = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    eng._check(lib.edc_tmpl_expand_device(eng.ctx, ctypes.byref(ts), n, vp(d_tpl2), vp(d_var), vp(d_voff), var_bytes,
+                                          vp(d_msg2), cap, vp(d_off2)))
+    assert int(d_off2[n]) == 120 * n
+    d_vk2 = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+    eng._check(lib.edc_sign_device(eng.ctx, n, vp(seeds), vp(kidx), vp(d_msg2), vp(d_off2), vp(d_vk2), vp(d_sig2)))
+    torch.cuda.synchronize()
+    assert torch.equal(d_vk2, d_vk)
+    h_sig2 = d_sig2.cpu()
+    del d_msg2, d_off2, d_vk2, d_tpl2
     d_sig_bad = d_sig.clone()
     bad_item = n // 2 + 7
     d_sig_bad[64 * bad_item + 40] = d_sig_bad[64 * bad_item + 40] ^ 1
@@ -131,6 +159,9 @@ def main():
                                                                    vp(d_off), None, zseed, cv, iv, ctypes.byref(nbad))),
         "device_batch": lambda: ok(lib.edc_batch_verify_device(eng.ctx, n, vp(d_vk), vp(d_sig), vp(d_msg), vp(d_off), zseed,
                                                                0, None, None)),
+        "device_tmpl_commits_alt": lambda: ok(lib.edc_tmpl_commits_verify_device(
+            eng.ctx, ctypes.byref(ts), nc, commit_off, commit_tpl0, 4, vp(d_alt), vp(d_vk), vp(d_sig2), vp(d_var), vp(d_voff),
+            var_bytes, zseed, cv, iv, ctypes.byref(nbad))),
         "failing_commits_wait": failing_commits,
         "failing_commits_sync": failing_sync,
         "failing_batch_alone": failing_batch,
@@ -141,6 +172,16 @@ def main():
             lambda: lib.edc_tmpl_commits_submit(eng.ctx, ctypes.byref(ts), nc, commit_off, commit_tpl, None, u32(h_idx),
                                                 cp(h_sig), cp(var_h), u32(voff_h), zseed),
             lambda tk: lib.edc_commits_wait(eng.ctx, tk, cv, iv, ctypes.byref(nbad))),
+        "stream_tmpl_commits_alt_key_idx": (
+            lambda: lib.edc_tmpl_commits_submit_alt(eng.ctx, ctypes.byref(ts), nc, commit_off, commit_tpl0, 4, vp(alt_h), None,
+                                                    u32(h_idx), cp(h_sig2), cp(var_h), u32(voff_h), zseed),
+            lambda tk: lib.edc_commits_wait(eng.ctx, tk, cv, iv, ctypes.byref(nbad))),
+        # the variants workload through the existing per-item entry: what the spread templates alone cost
+        "stream_tmpl_batch_spread_key_idx": (
+            lambda: lib.edc_tmpl_batch_submit(eng.ctx, ctypes.byref(ts), n, None, u32(h_idx), cp(h_sig2),
+                                              ctypes.cast(ctypes.c_void_p(tpl2_h.data_ptr()), ctypes.POINTER(ctypes.c_uint16)),
+                                              cp(var_h), u32(voff_h), zseed, 0, 0),
+            lambda tk: lib.edc_batch_wait(eng.ctx, tk, None, None, None)),
         "stream_tmpl_batch_key_idx": (
             lambda: lib.edc_tmpl_batch_submit(eng.ctx, ctypes.byref(ts), n, None, u32(h_idx), cp(h_sig), u16, cp(var_h),
                                               u32(voff_h), zseed, 0, 0),
@@ -191,6 +232,11 @@ def main():
                                              tpl_out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), 50,
                                              ctypes.byref(map_ms)))
     assert (tpl_out == tpl_h.numpy().view(np.uint16)).all()
+    map_alt_ms, flagged = ctypes.c_float(0), ctypes.c_int(-1)
+    eng._check(lib.edc_debug_tmpl_commit_map_alt(eng.ctx, nc, commit_off, commit_tpl0, 4, vp(alt_h),
+                                                 ctypes.c_void_p(tpl_out.ctypes.data), ctypes.byref(flagged), 50,
+                                                 ctypes.byref(map_alt_ms)))
+    assert flagged.value == 0 and (tpl_out == alt_np).all()
     med = {k: round(statistics.median(v), 3) for k, v in ms.items()}
     out = {
         "n": n, "validators": keys, "commits": nc, "items_per_commit": per, "msg_bytes": 120, "templates": t.count,
@@ -204,6 +250,8 @@ def main():
             "stream_tmpl_commits_key_idx": round(n / med["stream_tmpl_commits_key_idx"] * 1e3, 1),
             "stream_tmpl_batch_key_idx": round(n / med["stream_tmpl_batch_key_idx"] * 1e3, 1),
             "failing_commits_wait": round(n / med["failing_commits_wait"] * 1e3, 1),
+            "stream_tmpl_commits_alt_key_idx": round(n / med["stream_tmpl_commits_alt_key_idx"] * 1e3, 1),
+            "device_tmpl_commits_alt": round(n / med["device_tmpl_commits_alt"] * 1e3, 1),
         },
         "loop_commits": loop_commits,
         "failing_over_batch_alone": round(med["failing_commits_wait"] / med["failing_batch_alone"], 3),
@@ -211,6 +259,13 @@ def main():
         "stream_commits_over_batch": round(med["stream_tmpl_commits_key_idx"] / med["stream_tmpl_batch_key_idx"], 3),
         "map_kernel_us": round(map_ms.value * 1e3, 2),
         "map_kernel_bytes": int(2 * n + 4 * (nc + 1) + 2 * nc),
+        "alt_span": 4,
+        "stream_alt_over_tmpl_commits": round(med["stream_tmpl_commits_alt_key_idx"] / med["stream_tmpl_commits_key_idx"], 4),
+        "stream_alt_over_tmpl_batch_spread": round(med["stream_tmpl_commits_alt_key_idx"] /
+                                                   med["stream_tmpl_batch_spread_key_idx"], 4),
+        "device_tmpl_alt_over_device_commits": round(med["device_tmpl_commits_alt"] / med["device_commits"], 4),
+        "map_alt_kernel_us": round(map_alt_ms.value * 1e3, 2),
+        "map_alt_kernel_bytes": int(3 * n + 4 * (nc + 1) + 2 * nc),
     }
     print(json.dumps(out), flush=True)
     eng.close()
