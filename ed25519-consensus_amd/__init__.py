@@ -35,6 +35,11 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libedc.so")
 EDC_OK = 0
 EDC_INVALID_SIGNATURE = 1
 EDC_MALFORMED_PUBLIC_KEY = 2
+# quorum commit sets (include/edc.h, edc_quorum_*)
+EDC_QUORUM_SHORT = 3
+NOT_CHECKED = 255
+VOTE_ABSENT, VOTE_COMMIT, VOTE_NIL = 0, 1, 2
+QUORUM_FULL, QUORUM_LIGHT = 0, 1
 
 # every symbol include/edc.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -69,6 +74,7 @@ ABI_SYMBOLS = [
     "edc_tmpl_commits_verify_alt", "edc_tmpl_commits_submit_alt", "edc_tmpl_commits_verify_device",
     "edc_tmpl_commits_submit_device", "edc_debug_tmpl_commit_map_alt",
     "edc_debug_live_allocs",
+    "edc_quorum_plan", "edc_quorum_verify_device", "edc_quorum_verify", "edc_debug_quorum_select",
 ]
 
 
@@ -97,6 +103,11 @@ class InvalidSignature(Error):
 
 class InvalidSliceLength(Error):
     pass
+
+
+class QuorumShort(Error):
+    """Every checked vote of the commit verified, but its tally is not above the threshold
+    (EDC_QUORUM_SHORT; CometBFT's ErrNotEnoughVotingPowerSigned). Not an error of the reference crate."""
 
 
 class EngineError(RuntimeError):
@@ -321,6 +332,15 @@ def load_library(path=None):
                                                            c_vp, c_vp, c_sz, c_u8p]
             lib.edc_debug_tmpl_commit_map_alt.argtypes = [c_vp, c_sz, c_u32p, c_u16p, c_u32, c_vp, c_vp, c_ip,
                                                           ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+        if hasattr(lib, "edc_quorum_verify"):                # absent from older A/B builds (tools/)
+            c_u32p, c_ip, c_szp = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(c_sz)
+            lib.edc_quorum_plan.argtypes = [c_vp, c_sz, c_u32p, c_u64p, c_u8p, c_u64p, ctypes.c_int, c_vp, c_vp, c_szp]
+            lib.edc_quorum_verify_device.argtypes = [c_vp, c_sz, c_u32p, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                     c_u64p, ctypes.c_int, c_u8p, c_vp, c_vp, c_vp, c_ip, c_szp, c_vp]
+            lib.edc_quorum_verify.argtypes = [c_vp, c_sz, c_u32p, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p,
+                                              c_u8p, c_u64p, ctypes.c_int, c_u8p, c_vp, c_vp, c_vp, c_ip, c_szp, c_vp]
+            lib.edc_debug_quorum_select.argtypes = [c_vp, c_sz, c_u32p, c_u64p, c_u8p, c_u64p, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         if path is None:
             _lib = lib
         return lib
@@ -770,6 +790,86 @@ class Engine:
             self._commits_inflight.pop(ticket, None)
         self._check(rc)
         return self._commits_result(rc, nc, n, out)
+
+    # ---- quorum commit sets (edc_quorum_*): tally voting power, verify only the votes needed ----
+    # powers / flags: one per item; thresholds: one per commit; light: EDC_QUORUM_LIGHT, else _FULL.
+    @staticmethod
+    def _quorum_votes(n, nc, powers, flags, thresholds):
+        powers, flags, thresholds = [int(x) for x in powers], [int(x) for x in flags], [int(x) for x in thresholds]
+        if len(powers) != n or len(flags) != n or len(thresholds) != nc:
+            raise ValueError("one power and flag per item, one threshold per commit")
+        if any(x < 0 or x >= 1 << 64 for x in powers + thresholds) or any(x < 0 or x > 255 for x in flags):
+            raise ValueError("powers and thresholds are uint64, flags uint8")
+        return ((ctypes.c_uint64 * max(n, 1))(*powers), bytes(flags) or b"\0",
+                (ctypes.c_uint64 * max(nc, 1))(*thresholds))
+
+    def quorum_plan(self, commit_off, powers, flags, thresholds, light=True):
+        """edc_quorum_plan: the selection alone -> ([checked 0/1 per item], [planned tally per commit], n_checked)."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
+        checked = ctypes.create_string_buffer(max(n, 1))
+        planned = (ctypes.c_uint64 * max(nc, 1))()
+        cnt = ctypes.c_size_t(0)
+        with self._lock:
+            rc = self.lib.edc_quorum_plan(self.ctx, nc, off, pw, fl, th, int(bool(light)), checked, planned,
+                                          ctypes.byref(cnt))
+        self._check(rc)
+        return list(checked.raw[:n]), list(planned[:nc]), cnt.value
+
+    def _quorum_out(self, nc, n):
+        return (ctypes.create_string_buffer(max(nc, 1)), ctypes.create_string_buffer(max(n, 1)),
+                (ctypes.c_uint64 * max(nc, 1))(), ctypes.c_int(0), ctypes.c_size_t(0), ctypes.create_string_buffer(32))
+
+    @staticmethod
+    def _quorum_result(rc, nc, n, out):
+        return {"code": rc, "commit_verdicts": list(out[0].raw[:nc]), "item_verdicts": list(out[1].raw[:n]),
+                "tally": list(out[2][:nc]), "n_bad_commits": out[3].value, "n_checked": out[4].value,
+                "check8": out[5].raw}
+
+    def quorum_verify(self, commit_off, sigs, powers, flags, thresholds, z_seed, light=True, vks=None, key_idx=None,
+                      msgs=None, ks=None):
+        """edc_quorum_verify: host buffers, synchronous. Exactly one of vks and key_idx, exactly one
+        of msgs and ks, as commits_verify. Returns a dict: code, commit_verdicts, item_verdicts
+        (NOT_CHECKED for the votes left out), tally, n_bad_commits, n_checked, check8."""
+        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
+        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
+        out = self._quorum_out(nc, n)
+        with self._lock:
+            rc = self.lib.edc_quorum_verify(self.ctx, nc, *b, pw, fl, th, int(bool(light)), bytes(z_seed), out[0],
+                                            out[1], out[2], ctypes.byref(out[3]), ctypes.byref(out[4]), out[5])
+        self._check(rc)
+        return self._quorum_result(rc, nc, n, out)
+
+    def quorum_verify_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_power, d_flag, thresholds, z_seed,
+                             light=True, d_k=None):
+        """edc_quorum_verify_device: the items, powers (uint64) and flags (uint8) as torch tensors or
+        device pointers; commit_off and thresholds on the host. d_k given: the messages are not read."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        thresholds = [int(x) for x in thresholds]
+        if len(thresholds) != nc:
+            raise ValueError("one threshold per commit")
+        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
+        out = self._quorum_out(nc, n)
+        p = self._dev_ptr
+        with self._lock:
+            rc = self.lib.edc_quorum_verify_device(self.ctx, nc, off, p(d_vk), p(d_sig), p(d_msg), p(d_msg_off), p(d_k),
+                                                   p(d_power), p(d_flag), th, int(bool(light)), bytes(z_seed), out[0],
+                                                   out[1], out[2], ctypes.byref(out[3]), ctypes.byref(out[4]), out[5])
+        self._check(rc)
+        return self._quorum_result(rc, nc, n, out)
+
+    def quorum_select_ms(self, commit_off, powers, flags, thresholds, light=True, reps=20):
+        """edc_debug_quorum_select: mean time of the selection kernels alone, in milliseconds."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
+        ms = ctypes.c_float(0)
+        with self._lock:
+            rc = self.lib.edc_debug_quorum_select(self.ctx, nc, off, pw, fl, th, int(bool(light)), reps, ctypes.byref(ms))
+        self._check(rc)
+        return ms.value
 
     def batch_submit_multi_device(self, nb, n_per, d_vk, d_sig, d_msg, d_off, z_seed, z_base=0, d_k=None,
                                   want_check8=False):
@@ -1522,6 +1622,55 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
                     ks[i] = k
             res = eng.commits_verify(off, sigs, z_seed, vks=vks, ks=ks)
         return [c == EDC_OK for c in res[1]]
+
+    @staticmethod
+    def verify_quorum(verifiers, powers, flags, thresholds, light=True, z_seed=None, engine=None):
+        """Quorum check of many commits in ONE launch (a quorum commit set, edc_quorum_verify; not an
+        API of the reference). verifiers: one batch.Verifier per commit, holding an item for EVERY
+        validator of its set (any bytes for an absent one); powers / flags: one list per verifier, one
+        entry per item (VOTE_ABSENT, VOTE_COMMIT, VOTE_NIL); thresholds: one per verifier, a commit
+        has its quorum iff its tally is strictly greater. light=True verifies votes for the block
+        only until the threshold is passed (VerifyCommitLight), False every vote that carries a
+        signature (VerifyCommit). Returns (commit verdicts, tallies, item codes per verifier): a
+        verdict is EDC_OK, EDC_INVALID_SIGNATURE or EDC_QUORUM_SHORT, an item code Item::verify_single's
+        or NOT_CHECKED. z_seed as verify_many."""
+        verifiers = list(verifiers)
+        for v in verifiers:
+            if not isinstance(v, batch.Verifier):
+                raise TypeError("verify_quorum takes batch.Verifier objects")
+        powers, flags, thresholds = [list(p) for p in powers], [list(f) for f in flags], list(thresholds)
+        if len(powers) != len(verifiers) or len(flags) != len(verifiers) or len(thresholds) != len(verifiers):
+            raise ValueError("verify_quorum: one powers list, flags list and threshold per verifier")
+        if z_seed is None:
+            z_seed = secrets.token_bytes(32)
+        elif not isinstance(z_seed, (bytes, bytearray)) or len(z_seed) != 32:
+            raise ValueError("z_seed: 32 bytes or None")
+        off = [0]
+        for v, p, f in zip(verifiers, powers, flags):
+            if len(p) != v.batch_size or len(f) != v.batch_size:
+                raise ValueError("verify_quorum: one power and flag per queued item")
+            off.append(off[-1] + v.batch_size)
+        if off[-1] >= 1 << 28:
+            raise ValueError("verify_quorum: fewer than 2^28 items in one call")
+        if not verifiers:
+            return [], [], []
+        eng = engine or next((v._engine for v in verifiers if v._engine is not None), None) or default_engine()
+        vks = [x for v in verifiers for x in v._vks]
+        sigs = [x for v in verifiers for x in v._sigs]
+        msgs = [x for v in verifiers for x in v._msgs]
+        pw, fl = [x for p in powers for x in p], [x for f in flags for x in f]
+        if all(m is not None for m in msgs):
+            res = eng.quorum_verify(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, msgs=msgs)
+        else:                                    # some items carry only their k: hash the rest in one launch
+            ks = [x for v in verifiers for x in v._ks]
+            need = [i for i, k in enumerate(ks) if k is None]
+            if need:
+                for i, k in zip(need, eng.challenge([vks[i] for i in need], [sigs[i] for i in need],
+                                                    [msgs[i] for i in need])):
+                    ks[i] = k
+            res = eng.quorum_verify(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, ks=ks)
+        codes = [res["item_verdicts"][off[c]:off[c + 1]] for c in range(len(verifiers))]
+        return res["commit_verdicts"], res["tally"], codes
 
     class StreamVerifier:
         """reference src/batch.rs:110-217 with the reference's division of work: queue() does the

@@ -21,6 +21,7 @@
 #include "vfy_cached.h"
 #include "tmpl.h"
 #include "commits.h"
+#include "quorum.h"
 #include "sigcache.h"
 #include "devbuf.h"
 
@@ -242,6 +243,16 @@ struct edc_ctx {
   SigCacheView sc() const {
     return SigCacheView{sc_hdr, sc_rec, (uint32_t)(sc_cap - 1), sc_gen, sc_keep, sc_k0, sc_k1};
   }
+  // quorum commit sets (quorum.h; edc_quorum_*), on slot 0's stream: the staged offsets and
+  // thresholds and the per-commit results (q_cap_c commits); the items' commit indices, the staged
+  // power / flag of the host forms and the scan's tile words (q_cap_n items); the error flag; the
+  // pinned words the flag and the checked count come back in. The gather uses the sc_* staging.
+  size_t q_cap_c = 0, q_cap_n = 0;
+  DevBuf<uint32_t> q_coff, q_cor, q_cidx, q_aggf;
+  DevBuf<uint64_t> q_thr, q_planned, q_tally, q_power, q_aggv, q_carry;
+  DevBuf<uint8_t> q_flag;
+  DevBuf<int> q_err;
+  PinnedBuf<uint32_t> q_h;
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -3495,6 +3506,319 @@ int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const ui
   if ((rc = sc_insert(ctx, M, ctx->verdicts))) return rc;
   CK(hipStreamSynchronize(st));
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- quorum commit sets
+// quorum.h / edc_quorum.hip: the selection marks the votes that are not checked, the cached
+// entries' compaction (sc_* staging, allocated here without a table) gathers the checked ones in
+// queue order into one contiguous batch, and that batch runs through batch_with_fallback, so the
+// union verdict, check8 and the item codes are edc_batch_verify_prehashed_device's and the grouped
+// fallback's on the gathered list by construction. The checked count needs one 8-byte
+// device-to-host copy (with the device checks' flag) and a stream synchronization before the MSM
+// can be planned. A passing union's tally is planned[]; a failed one scatters the codes back and
+// runs the tally kernel. All on slot 0.
+static int ensure_quorum(edc_ctx* ctx, size_t n, size_t nc) {
+  hipStream_t st = ctx->st();
+  CK(grow_group(ctx->q_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
+    return alloc_all(sized(ctx->q_coff, cap + 1), sized(ctx->q_thr, cap), sized(ctx->q_planned, cap), sized(ctx->q_tally, cap),
+                     sized(ctx->q_cor, cap));
+  }));
+  CK(grow_group(ctx->q_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
+    const size_t tiles = quorum_tiles(cap);
+    return alloc_all(sized(ctx->q_cidx, cap), sized(ctx->q_power, cap), sized(ctx->q_flag, cap), sized(ctx->q_aggv, tiles),
+                     sized(ctx->q_aggf, tiles), sized(ctx->q_carry, tiles));
+  }));
+  if (!ctx->q_err) CK(ctx->q_err.alloc(1));
+  if (!ctx->q_h) CK(ctx->q_h.alloc(2));
+  return 0;
+}
+
+// what every form checks on the host first; *n = the item count
+static int quorum_check(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
+                        size_t* n) {
+  int rc = commits_check(ctx, nc, commit_off, n);
+  if (rc) return rc;
+  if (!threshold) { ctx->err = "null threshold"; return EDC_ERR_ARG; }
+  if (!quorum_check_mode(mode)) { ctx->err = "mode is EDC_QUORUM_FULL or EDC_QUORUM_LIGHT"; return EDC_ERR_ARG; }
+  if (ctx->slot[0].pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+// the votes of a host form
+static int quorum_check_votes(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power,
+                              const uint8_t* flag) {
+  if (!quorum_check_flags(commit_off[nc], flag)) {
+    ctx->err = "vote flags: EDC_VOTE_ABSENT, EDC_VOTE_COMMIT or EDC_VOTE_NIL";
+    return EDC_ERR_ARG;
+  }
+  if (!quorum_check_powers(nc, commit_off, power, flag)) {
+    ctx->err = "voting power: every power and every commit's counted sum at most 2^63 - 1";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// Workspace, the staged offsets and thresholds, then the selection and the scan of its workgroup
+// counts on device-resident power / flag. *n_checked = the size of the gathered list. A vote the
+// device checks refuse is EDC_ERR_ARG here, before anything is gathered or verified.
+static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                             int mode, const uint64_t* d_power, const uint8_t* d_flag, size_t* n_checked) {
+  int rc = init_slot(ctx, ctx->slot[0]);
+  if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
+  hipStream_t st = ctx->st();
+  if ((rc = sc_order_after_inserts(ctx, st))) return rc;
+  CK(hipMemsetAsync(ctx->q_planned, 0, nc * sizeof(uint64_t), st));
+  *n_checked = 0;
+  if (!n) return 0;
+  const uint32_t N = (uint32_t)n, nwg = (uint32_t)quorum_tiles(n);
+  CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->q_thr, threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  CK(hipMemsetAsync(ctx->q_err, 0, sizeof(int), st));
+  launch_quorum_select(st, N, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, d_power, d_flag, ctx->q_cidx,
+                       ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->sc_hit, ctx->sc_wg, ctx->q_planned, ctx->q_err);
+  launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
+  CK(hipGetLastError());
+  ctx->q_h[0] = ctx->q_h[1] = 0;
+  CK(hipMemcpyAsync(&ctx->q_h[0], ctx->q_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(&ctx->q_h[1], ctx->sc_wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  if (ctx->q_h[0]) {
+    ctx->err = "votes: a flag above 2, a power above 2^63 - 1 or a commit whose counted power passes 2^63 - 1";
+    return EDC_ERR_ARG;
+  }
+  if (ctx->q_h[1] > n) { ctx->err = "quorum selection: checked count out of range"; return EDC_ERR_HIP; }
+  *n_checked = ctx->q_h[1];
+  return 0;
+}
+
+struct QuorumOut {
+  uint8_t *commit_verdicts, *item_verdicts;
+  uint64_t* tally;
+  int* n_bad_commits;
+  size_t* n_checked;
+  uint8_t* check8;
+};
+
+// A checked quorum commit set whose items (vk, sig, k, power, flag) are on the device.
+static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode, size_t n,
+                      const uint8_t* d_vk, const uint8_t* d_sig, const uint32_t* d_k, const uint64_t* d_power,
+                      const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out) {
+  size_t m = 0;
+  int rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag, &m);
+  if (rc) return rc;
+  hipStream_t st = ctx->st();
+  const uint8_t *b_vk = d_vk, *b_sig = d_sig;
+  // an empty list still runs the n = 0 batch, whose k is never read
+  const uint32_t *b_k = m ? d_k : reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), *idx = nullptr;
+  if (m && m < n) {
+    uint8_t* g_vk = ctx->sc_g;
+    uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
+    uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->sc_cap_n * 64);
+    launch_sc_compact(st, (uint32_t)n, ctx->sc_hit, ctx->sc_wg, d_vk, d_sig, d_k, ctx->sc_idx, g_vk, g_sig, g_k);
+    CK(hipGetLastError());
+    idx = ctx->sc_idx;
+    b_vk = g_vk;
+    b_sig = g_sig;
+    b_k = g_k;
+  }
+  std::vector<uint8_t> mv(m ? m : 1);
+  const int code = batch_with_fallback(ctx, m, b_vk, b_sig, nullptr, nullptr, b_k, z_seed, mv.data(), nullptr, out.check8);
+  if (code < 0) return code;
+  std::vector<uint64_t> tal(nc);
+  std::vector<uint32_t> cor32;
+  std::vector<uint8_t> cor;
+  if (code == EDC_OK) {                 // every checked item verified: the tally is the plan
+    CK(hipMemcpyAsync(tal.data(), ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (out.item_verdicts && n) CK(hipMemcpyAsync(out.item_verdicts, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    if (out.item_verdicts)
+      for (size_t i = 0; i < n; ++i) out.item_verdicts[i] = out.item_verdicts[i] ? QUORUM_NOT_CHECKED : 0;
+  } else {                              // m > 0: codes back to queue order, then the tally kernel
+    const uint8_t* d_codes = ctx->sc_mverd;
+    CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
+    if (idx) {
+      CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
+      launch_sc_scatter(st, (uint32_t)m, idx, ctx->sc_mverd, ctx->sc_verd);
+      d_codes = ctx->sc_verd;
+    }
+    CK(hipMemsetAsync(ctx->q_tally, 0, nc * sizeof(uint64_t), st));
+    CK(hipMemsetAsync(ctx->q_cor, 0, nc * sizeof(uint32_t), st));
+    launch_quorum_tally(st, (uint32_t)n, ctx->q_cidx, d_power, d_flag, d_codes, ctx->q_tally, ctx->q_cor);
+    CK(hipGetLastError());
+    cor32.resize(nc);
+    CK(hipMemcpyAsync(tal.data(), ctx->q_tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(cor32.data(), ctx->q_cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (out.item_verdicts) CK(hipMemcpyAsync(out.item_verdicts, d_codes, n, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    cor.resize(nc);
+    for (size_t c = 0; c < nc; ++c) cor[c] = cor32[c] ? 1 : 0;
+  }
+  size_t bad = 0;
+  const int res = quorum_reduce(nc, cor.empty() ? nullptr : cor.data(), tal.data(), threshold, out.commit_verdicts, &bad);
+  if (out.tally) memcpy(out.tally, tal.data(), nc * sizeof(uint64_t));
+  if (out.n_bad_commits) *out.n_bad_commits = (int)bad;
+  if (out.n_checked) *out.n_checked = m;
+  return res;
+}
+
+// nc == 0: nothing to verify
+static int quorum_none(const QuorumOut& out) {
+  if (out.n_bad_commits) *out.n_bad_commits = 0;
+  if (out.n_checked) *out.n_checked = 0;
+  return EDC_OK;
+}
+
+// power and flag of a host form beside the other staged inputs (slot 0's stream)
+static int quorum_stage_votes(edc_ctx* ctx, size_t n, size_t nc, const uint64_t* power, const uint8_t* flag) {
+  int rc = init_slot(ctx, ctx->slot[0]);
+  if (rc || (rc = ensure_quorum(ctx, n, nc)) || !n) return rc;
+  CK(hipMemcpyAsync(ctx->q_power, power, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->st()));
+  CK(hipMemcpyAsync(ctx->q_flag, flag, n, hipMemcpyHostToDevice, ctx->st()));
+  return 0;
+}
+
+extern "C" {
+
+int edc_quorum_plan(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power, const uint8_t* flag,
+                    const uint64_t* threshold, int mode, uint8_t* checked, uint64_t* planned, size_t* n_checked) {
+  if (!ctx) return EDC_ERR_ARG;
+  if (!nc) {
+    if (n_checked) *n_checked = 0;
+    return EDC_OK;
+  }
+  size_t n, m = 0;
+  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
+  if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = quorum_stage_votes(ctx, n, nc, power, flag)) ||
+      (rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, &m)))
+    return rc;
+  hipStream_t st = ctx->st();
+  if (planned) CK(hipMemcpyAsync(planned, ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (checked && n) CK(hipMemcpyAsync(checked, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  if (checked)
+    for (size_t i = 0; i < n; ++i) checked[i] = checked[i] ? 0 : 1;      // the kernel writes the skip byte
+  if (n_checked) *n_checked = m;
+  return EDC_OK;
+}
+
+int edc_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                             const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                             const uint64_t* d_power, const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                             const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                             int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return quorum_none(out);
+  size_t n;
+  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
+  if (rc) return rc;
+  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off) || !d_power || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)) || ((uintptr_t)d_power & 7u))) {
+    ctx->err = "device vk / sig / k arrays must be 16-byte aligned, d_power 8-byte aligned";
+    return EDC_ERR_ARG;
+  }
+  CK(hipSetDevice(ctx->device));
+  const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
+  if (n && !k) {            // Item::from for every item, skipped votes included (as sc_batch)
+    if ((rc = init_slot(ctx, ctx->slot[0])) || (rc = ensure_n(ctx, n))) return rc;
+    launch_challenge(ctx->st(), (uint32_t)n, d_vk, d_sig, d_msg, d_msg_off, ctx->kbuf);
+    CK(hipGetLastError());
+    k = ctx->kbuf;
+  }
+  return quorum_run(ctx, nc, commit_off, threshold, mode, n, d_vk, d_sig, k, d_power, d_flag, z_seed, out);
+}
+
+int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
+                      const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k,
+                      const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
+                      const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                      int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return quorum_none(out);
+  size_t n;
+  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
+  if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
+  if (n) {
+    if ((rc = commits_check_keys(ctx, n, vk, key_idx))) return rc;
+    if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
+    if (!msg_off == !k || (msg && k)) { ctx->err = "exactly one of (msg, msg_off) and k"; return EDC_ERR_ARG; }
+    if (msg_off) {
+      if (msg_off[n] < msg_off[0]) { ctx->err = "message offsets decrease"; return EDC_ERR_ARG; }
+      if (msg_off[n] > msg_off[0] && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
+    } else {                // only a checked vote's k reaches the batch (Scalar::from_hash never yields k >= l)
+      std::vector<uint8_t> chk(n);
+      quorum_select(nc, commit_off, power, flag, threshold, mode, chk.data(), nullptr);
+      for (size_t i = 0; i < n; ++i) {
+        uint32_t w[8];
+        memcpy(w, k + 32 * i, 32);
+        if (chk[i] && w[7] >= 0x10000000u && !sc_is_canonical(w)) {
+          ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
+          return EDC_ERR_ARG;
+        }
+      }
+    }
+  }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = quorum_stage_votes(ctx, n, nc, power, flag))) return rc;
+  hipStream_t st = ctx->st();
+  if (k) {
+    if ((rc = ensure_n(ctx, n))) return rc;
+    if (n) CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
+  } else if ((rc = upload_msgs(ctx, n, msg, n ? msg_off : nullptr))) {
+    return rc;
+  }
+  if (n) {
+    if (key_idx) {          // 4 bytes per item over PCIe; q_cidx is free until the selection writes it
+      CK(hipMemcpyAsync(ctx->q_cidx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      launch_expand_keys(st, (uint32_t)n, ctx->q_cidx, ctx->kc_reg, ctx->kc_keys, ctx->vk);
+      CK(hipGetLastError());
+    } else {
+      CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
+    }
+    CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
+    if (!k) {
+      launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
+      CK(hipGetLastError());
+    }
+  }
+  return quorum_run(ctx, nc, commit_off, threshold, mode, n, ctx->vk, ctx->sig, ctx->kbuf, ctx->q_power, ctx->q_flag,
+                    z_seed, out);
+}
+
+int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power,
+                            const uint8_t* flag, const uint64_t* threshold, int mode, int reps, float* ms) {
+  if (!ctx || reps < 1) return EDC_ERR_ARG;
+  if (ms) *ms = 0.f;
+  if (!nc) return EDC_OK;
+  size_t n, m = 0;
+  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
+  if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = quorum_stage_votes(ctx, n, nc, power, flag)) ||
+      (rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, &m)))
+    return rc;
+  if (!n) return EDC_OK;
+  hipStream_t st = ctx->st();
+  Event e0, e1;
+  CK(e0.create());
+  CK(e1.create());
+  CK(hipEventRecord(e0, st));
+  for (int r = 0; r < reps; ++r)        // planned is a maximum: repeating the launch leaves it unchanged
+    launch_quorum_select(st, (uint32_t)n, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, ctx->q_power,
+                         ctx->q_flag, ctx->q_cidx, ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->sc_hit, ctx->sc_wg,
+                         ctx->q_planned, ctx->q_err);
+  CK(hipGetLastError());
+  CK(hipEventRecord(e1, st));
+  CK(hipEventSynchronize(e1));
+  float t = 0.f;
+  CK(hipEventElapsedTime(&t, e0, e1));
+  if (ms) *ms = t / (float)reps;
+  return EDC_OK;
 }
 
 }  // extern "C"

@@ -106,6 +106,24 @@ void launch_tmpl_commit_map(hipStream_t st, uint32_t n, uint32_t nc, const uint3
 void launch_tmpl_commit_map_alt(hipStream_t st, uint32_t n, uint32_t nc, const uint32_t* commit_off,
                                 const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl,
                                 int* flag);
+// edc_quorum.hip (quorum.h): the selection of a quorum commit set. All device pointers; commit_off
+// (nc + 1 checked offsets, commit_off[nc] = n) and threshold (nc) staged by the caller. Outputs:
+// skip[i] = 0 iff item i is checked (the byte k_sc_compact reads), wg_checked = checked items per
+// workgroup of QR_TILE (= SC_BLOCK) items for launch_sc_scan, planned[c] (zeroed by the caller) =
+// the power of commit c's checked flag-1 items, cidx[i] = the commit of item i. *err (zeroed by
+// the caller) is raised on a flag above 2, a power above 2^63 - 1 or a commit whose counted sum
+// passes 2^63 - 1; the other outputs then mean nothing (every index formed stays inside the arrays).
+// agg_v / agg_f / carry: quorum_tiles(n) words each. n = 0 launches nothing.
+constexpr uint32_t QR_TILE = 256;
+size_t quorum_tiles(size_t n);
+void launch_quorum_select(hipStream_t st, uint32_t n, uint32_t nc, int light, const uint32_t* commit_off,
+                          const uint64_t* threshold, const uint64_t* power, const uint8_t* flag, uint32_t* cidx,
+                          uint64_t* agg_v, uint32_t* agg_f, uint64_t* carry, uint8_t* skip, uint32_t* wg_checked,
+                          uint64_t* planned, int* err);
+// after a failed union: code[i] = item i's code, 255 where it was not checked. tally[c] += power of
+// the checked flag-1 items with code 0, cor[c] |= the checked items' codes (both zeroed by the caller)
+void launch_quorum_tally(hipStream_t st, uint32_t n, const uint32_t* cidx, const uint64_t* power, const uint8_t* flag,
+                         const uint8_t* code, uint64_t* tally, uint32_t* cor);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

@@ -861,6 +861,98 @@ int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commi
                                 int reps, float* ms);
 
 /*
+ * Quorum commit sets: tally voting power and verify only the votes that are needed. A consensus
+ * node does not ask "does every signature of commit c verify" but "did validators holding more
+ * than the required voting power sign this block": CometBFT's VerifyCommit (every vote that
+ * carries a signature is verified, only the votes for the block count), VerifyCommitLight (votes
+ * for the block are verified only until the tally passes 2/3 of the set's power) and
+ * VerifyCommitLightTrusting (the same against 1/3 of a trusted set's power). The reference crate
+ * has no such API and none of its APIs changes meaning: every vote that is checked is one
+ * batch::Item (src/batch.rs:76-94) in ONE batch::Verifier (queue + verify, src/batch.rs:127-137,
+ * :149-217), and its code is Item::verify_single's (src/batch.rs:104-107).
+ *
+ * A quorum commit set is a commit set as defined above (n items in queue order, nc + 1 offsets
+ * commit_off in host memory, the same limits; a commit lists EVERY validator of its set) with
+ *   power[i]      uint64_t, n entries: the voting power of item i's validator. Every power is at
+ *                 most 2^63 - 1, and so is the sum of the counted (flag 1) powers of one commit.
+ *   flag[i]       uint8_t, n entries: EDC_VOTE_ABSENT (no signature: never verified, never counted;
+ *                 its vk / sig / message bytes are never interpreted), EDC_VOTE_COMMIT (a precommit
+ *                 for the block: verified, counted) or EDC_VOTE_NIL (a precommit for nil: verified
+ *                 in full mode, never counted). Any other value is an argument error.
+ *   threshold[c]  uint64_t, nc entries, host memory. Commit c has its quorum iff its tally is
+ *                 STRICTLY GREATER than threshold[c]: pass floor(2T/3) for a commit of a set with
+ *                 total power T, floor(T/3) for the trusting check.
+ *   mode          EDC_QUORUM_FULL (VerifyCommit): the checked items are those with flag 1 or 2.
+ *                 EDC_QUORUM_LIGHT (VerifyCommitLight): item i is checked iff its flag is 1 and the
+ *                 sum of power over the flag-1 items before it in its commit is <= threshold[c],
+ *                 i.e. the quorum was not yet reached when the loop arrives at it. The trusting
+ *                 check is light mode with the trusted set's powers and EDC_VOTE_ABSENT for the
+ *                 signers that set does not know.
+ * Only the checked items are verified. They are gathered in queue order into one batch, checked
+ * item j drawing z at index j of z_seed's stream: the union verdict and check8 (nullable) are
+ * bit-identical to edc_batch_verify_prehashed_device on the gathered (vk, sig, k) list with
+ * z_base = 0 (the contract of the verified-signature cache for its miss list), and when that union
+ * fails the grouped fallback runs on that list as edc_batch_verify_fallback_device. Soundness and
+ * the requirement on z_seed (fresh and secret for every call) are those of the commit-set entries.
+ * Outputs (host, all nullable):
+ *   item_verdicts    n bytes: Item::verify_single's code of a checked item, EDC_NOT_CHECKED for
+ *                    every other item.
+ *   tally            uint64_t, nc: the sum of power over the checked items with flag 1 and code EDC_OK.
+ *   commit_verdicts  nc bytes: EDC_INVALID_SIGNATURE if any checked item of the commit has a non-zero
+ *                    code (also when the commit is short only because that item's power is missing);
+ *                    otherwise EDC_QUORUM_SHORT if tally[c] <= threshold[c]; otherwise EDC_OK. "Strictly
+ *                    greater" decides the empty case: an empty or all-absent commit has tally 0 and is
+ *                    EDC_QUORUM_SHORT, also with threshold 0.
+ *   *n_bad_commits   the commits that are not EDC_OK.   *n_checked  the size of the gathered list.
+ * Return value: EDC_OK iff every commit is EDC_OK; EDC_INVALID_SIGNATURE if any commit is
+ * EDC_INVALID_SIGNATURE; otherwise EDC_QUORUM_SHORT; <0 on a runtime or argument failure.
+ *
+ * edc_quorum_plan  the selection alone, on host arrays (no signatures): checked[i] (n bytes, 0 / 1),
+ *   planned[c] (the tally commit c gets if every checked item verifies) and *n_checked, all
+ *   nullable. It runs the kernels every form below runs, so a caller can size its work with it.
+ * edc_quorum_verify_device  the items in this GPU's memory: d_vk, d_sig and d_msg / d_msg_off or d_k
+ *   as edc_commits_verify_device (16-byte aligned), d_power 8-byte aligned, d_flag of any
+ *   alignment; commit_off and threshold on the host. Synchronous, on slot 0 (EDC_ERR_ARG while a
+ *   submitted batch is pending there). Without d_k, k is hashed for all n items first, skipped
+ *   votes included: their messages must be mapped like any other.
+ * edc_quorum_verify  host buffers: exactly one of vk and key_idx, exactly one of (msg, msg_off) and
+ *   k, as edc_commits_verify; power and flag are staged beside them. A prehashed k must be
+ *   canonical for the checked items only.
+ * Argument checks: a violation is EDC_ERR_ARG with nothing verified and no output written. The host
+ *   forms (plan included) check the offsets, the flags, the power bounds and the per-commit sums
+ *   before anything is launched. The device form checks the offsets on the host and the flags,
+ *   bounds and sums ON THE DEVICE, before anything is gathered: on a violation no index outside the
+ *   declared arrays is formed, the call returns EDC_ERR_ARG, never a verdict, and the context stays
+ *   usable. nc = 0 returns EDC_OK (no array is read); a NULL ctx or z_seed is EDC_ERR_ARG. These
+ *   entries need no verified-signature table on the context.
+ * edc_debug_quorum_select  measurement hook: the selection kernels alone on host arrays (checked as
+ *   edc_quorum_plan), run `reps` times between HIP events; *ms (nullable) = the mean time.
+ * Out of scope: asynchronous submit / wait forms, templated forms, the incremental verifier and
+ *   the multi-GPU engine have no quorum entries.
+ */
+#define EDC_QUORUM_SHORT 3           /* every checked vote verified, tally <= threshold */
+#define EDC_NOT_CHECKED 255          /* item_verdicts: the vote was not verified */
+#define EDC_VOTE_ABSENT 0
+#define EDC_VOTE_COMMIT 1
+#define EDC_VOTE_NIL 2
+#define EDC_QUORUM_FULL 0
+#define EDC_QUORUM_LIGHT 1
+int edc_quorum_plan(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power, const uint8_t* flag,
+                    const uint64_t* threshold, int mode, uint8_t* checked, uint64_t* planned, size_t* n_checked);
+int edc_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                             const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                             const uint64_t* d_power, const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                             const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                             int* n_bad_commits, size_t* n_checked, uint8_t check8[32]);
+int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
+                      const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k,
+                      const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
+                      const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                      int* n_bad_commits, size_t* n_checked, uint8_t check8[32]);
+int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power,
+                            const uint8_t* flag, const uint64_t* threshold, int mode, int reps, float* ms);
+
+/*
  * Verified-signature cache: skip the items that already verified on this context. A consensus
  * node verifies the same vote several times: once when it arrives by gossip
  * (VerificationKey::verify, src/verification_key.rs:225-258, or Item::verify_single,
