@@ -61,7 +61,7 @@ ABI_SYMBOLS = [
     "edc_batch_submit_multi_device", "edc_batch_wait_multi", "edc_combine_records_device", "edc_debug_sc_reduce_wide",
     "edc_verifier_create", "edc_verifier_destroy", "edc_verifier_queue", "edc_verifier_queue_prehashed",
     "edc_verifier_queue_device", "edc_verifier_size", "edc_verifier_verify", "edc_verifier_verify_fallback",
-    "edc_verifier_reset", "edc_vfy_queue_indexed", "edc_vfy_last_split",
+    "edc_verifier_reset", "edc_vfy_queue_indexed", "edc_vfy_last_split", "edc_vfy_last_plan",
     "edc_vfy_begin_eager", "edc_vfy_set_fold", "edc_vfy_folded", "edc_vfy_eager",
     "edc_vfy_set_cached", "edc_vfy_cached", "edc_vfy_cache_counts", "edc_vfy_verify_fallback_offered",
     "edc_sigcache_create", "edc_sigcache_clear", "edc_sigcache_advance", "edc_sigcache_stats",
@@ -73,7 +73,7 @@ ABI_SYMBOLS = [
     "edc_tmpl_commits_submit", "edc_commits_submit_device", "edc_commits_wait", "edc_debug_tmpl_commit_map",
     "edc_tmpl_commits_verify_alt", "edc_tmpl_commits_submit_alt", "edc_tmpl_commits_verify_device",
     "edc_tmpl_commits_submit_device", "edc_debug_tmpl_commit_map_alt",
-    "edc_debug_live_allocs",
+    "edc_debug_live_allocs", "edc_debug_last_plan",
     "edc_quorum_plan", "edc_quorum_verify_device", "edc_quorum_verify", "edc_debug_quorum_select",
 ]
 
@@ -83,6 +83,23 @@ class EdcTemplates(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint32),
                 ("head", ctypes.c_char_p), ("head_off", ctypes.POINTER(ctypes.c_uint32)),
                 ("tail", ctypes.c_char_p), ("tail_off", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class EdcPlanInfo(ctypes.Structure):
+    """struct edc_plan_info (include/edc.h): the MSM plan of the last batch, as the host chose it."""
+    _fields_ = [("nwin", ctypes.c_uint32), ("nwin_short", ctypes.c_uint32), ("nranges", ctypes.c_uint32),
+                ("sum_ranges", ctypes.c_uint32), ("bins_per_range", ctypes.c_uint32),
+                ("per_sig", ctypes.c_uint32), ("split", ctypes.c_uint32), ("few", ctypes.c_uint32),
+                ("fold", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("target", ctypes.c_double),
+                ("bits", ctypes.c_uint8 * 32), ("nsub", ctypes.c_uint8 * 32), ("nslice", ctypes.c_uint16 * 32)]
+
+    def as_dict(self):
+        w = int(self.nwin)
+        d = {k: int(getattr(self, k)) for k in ("nwin", "nwin_short", "nranges", "sum_ranges", "bins_per_range")}
+        d.update({k: bool(getattr(self, k)) for k in ("per_sig", "split", "few", "fold")})
+        d.update(target=float(self.target), bits=list(self.bits[:w]), nsub=list(self.nsub[:w]),
+                 nslice=list(self.nslice[:w]))
+        return d
 
 
 class Error(Exception):
@@ -151,6 +168,9 @@ def load_library(path=None):
             lib.edc_debug_sc_reduce_wide.argtypes = [c_vp, c_sz, c_vp, c_vp]
         if hasattr(lib, "edc_debug_live_allocs"):            # absent from older A/B builds (--lib)
             lib.edc_debug_live_allocs.argtypes = [c_u64p]
+        if hasattr(lib, "edc_debug_last_plan"):              # absent from older A/B builds (--lib)
+            lib.edc_debug_last_plan.argtypes = [c_vp, ctypes.POINTER(EdcPlanInfo)]
+            lib.edc_vfy_last_plan.argtypes = [c_vp, ctypes.POINTER(EdcPlanInfo)]
         lib.edc_batch_submit_device.restype = ctypes.c_int64
         lib.edc_batch_submit_device.argtypes = [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_u8p, ctypes.c_uint64, c_vp,
                                                 ctypes.c_int]
@@ -1000,6 +1020,14 @@ class Engine:
         """Target MSM entries per bin (>= 256); 0 = chosen from the batch size."""
         self._check(self.lib.edc_set_msm_bin_entries(self.ctx, int(entries)))
 
+    def last_plan(self):
+        """The MSM plan of the last batch on this context as a dict (edc_debug_last_plan; test hook):
+        nwin, nwin_short, nranges, sum_ranges, bins_per_range, bits / nslice / nsub per window, the
+        entry target finally used, and per_sig / split / few / fold. EngineError before any batch."""
+        info = EdcPlanInfo()
+        self._check(self.lib.edc_debug_last_plan(self.ctx, ctypes.byref(info)))
+        return info.as_dict()
+
     def keycache_clear(self):
         with self._lock:
             self._check(self.lib.edc_keycache_clear(self.ctx))
@@ -1018,7 +1046,8 @@ class Engine:
             idx = (ctypes.c_uint32 * n)(*seed_index)
         with self._lock:
             self._check(self.lib.edc_sign(self.ctx, n, b"".join(seeds), len(seeds), idx, arena, offs, vk, sig))
-        return [vk.raw[32 * i:32 * i + 32] for i in range(n)], [sig.raw[64 * i:64 * i + 64] for i in range(n)]
+        vkb, sgb = vk.raw, sig.raw    # one copy each (.raw copies the whole buffer on every access)
+        return [vkb[32 * i:32 * i + 32] for i in range(n)], [sgb[64 * i:64 * i + 64] for i in range(n)]
 
     # ---- verified-signature cache (include/edc.h, edc_sigcache_*) ----
     def sigcache_create(self, capacity, keep=0):
@@ -1844,6 +1873,14 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
             EngineError before any verify."""
             eng = self._engine
             return eng._check(eng.lib.edc_vfy_last_split(self._handle()))
+
+        @property
+        def last_plan(self):
+            """Engine.last_plan() for the last verify or eager fold of this verifier, whichever came
+            last (edc_vfy_last_plan); EngineError before either."""
+            eng, info = self._engine, EdcPlanInfo()
+            eng._check(eng.lib.edc_vfy_last_plan(self._handle(), ctypes.byref(info)))
+            return info.as_dict()
 
         def queue_device(self, n, d_vk, d_sig, d_msg=None, d_msg_off=None, d_k=None):
             """Append n items already in this GPU's memory (device pointers; d_k or the messages)."""

@@ -193,6 +193,8 @@ struct edc_ctx {
   int win_bits = 0;             // MSM window width override (edc_set_msm_shape), 0 = by batch size
   uint32_t bin_entries = 0;     // target entries per MSM bin (edc_set_msm_bin_entries), 0 = by batch size
   uint32_t msm_parts = 0;       // MSM parts override (edc_set_msm_shape), 0 = by batch size
+  edc_plan_info last_plan = {}; // host copy of the last batch_plan / fold_plan (edc_debug_last_plan)
+  bool have_plan = false;
   uint64_t secret = 0;          // key-grouping hash secret (OS randomness, per context)
   uint64_t nbatches = 0;
   // grouped fallback (range MSM) staging, slot 0 only
@@ -295,6 +297,8 @@ struct edc_verifier {
   uint64_t hi_gen = 0;
   bool hi_ok = false;
   int last_split = -1;          // plan of the last verify: 1 split, 0 unsplit, -1 none yet
+  edc_plan_info last_plan = {}; // plan of the last verify or fold on this verifier (edc_vfy_last_plan)
+  bool have_plan = false;
   DevBuf<uint32_t> idx;         // one indexed append's key positions (edc_vfy_queue_indexed)
   // eager mode (edc_vfy_begin_eager): the block's z seed is committed before the items arrive and
   // queue calls fold sum [z_i]R_i of the items [fold.folded, n) into the running point `run`
@@ -465,6 +469,19 @@ static MsmPlan make_plan(int c, int hi, uint32_t nranges, bool hi_windows = true
   return P;
 }
 
+// Host-side record of the plan just chosen, for edc_debug_last_plan (tests): no device work.
+// target 0: explicit parts, the sub-bin split did not run.
+static void note_plan(edc_ctx* ctx, const MsmPlan& P, double target, bool per_sig, bool split, bool few, bool fold) {
+  edc_plan_info& I = ctx->last_plan;
+  I = edc_plan_info{};
+  I.nwin = P.nwin; I.nwin_short = P.nwin_short; I.nranges = P.nranges; I.sum_ranges = P.sum_ranges;
+  I.bins_per_range = P.bins_per_range;
+  I.per_sig = per_sig; I.split = split; I.few = few; I.fold = fold;
+  I.target = target;
+  for (uint32_t w = 0; w < P.nwin; ++w) { I.bits[w] = P.bits[w]; I.nsub[w] = P.nsub[w]; I.nslice[w] = P.nslice[w]; }
+  ctx->have_plan = true;
+}
+
 static uint32_t floor_pow2(double x) {
   uint32_t p = 1;
   while (p * 2.0 <= x && p < 64) p *= 2;
@@ -478,7 +495,7 @@ static uint32_t floor_pow2(double x) {
 // index, summed per slice by k_msm_window) so that every bin holds about the same number of
 // entries and ~1-2k workgroups accumulate. edc_set_msm_shape's parts instead split the whole batch.
 // Any plan is an exact MSM: the hint and the split only affect speed.
-static MsmPlan batch_plan(const edc_ctx* ctx, size_t n, bool per_sig, bool split = false) {
+static MsmPlan batch_plan(edc_ctx* ctx, size_t n, bool per_sig, bool split = false) {
   const int c = ctx->win_bits ? ctx->win_bits : auto_window_bits(n);
   const bool few = !per_sig && ctx->have_key_ratio && ctx->last_key_ratio * 16.0 <= 1.0 && n >= 4096;
   MsmPlan P = make_plan(c, few ? 8 : c, 1, !split);
@@ -487,6 +504,7 @@ static MsmPlan batch_plan(const edc_ctx* ctx, size_t n, bool per_sig, bool split
     while (parts > 1 && P.bins_per_range * parts > MSM_MAX_BINS) parts /= 2;
     P.nranges = parts;
     P.sum_ranges = parts > 1;
+    note_plan(ctx, P, 0.0, per_sig, split, few, false);
     return P;
   }
   // expected entries per slice of each window: short terms (the z_i) use the short windows, full
@@ -513,6 +531,7 @@ static MsmPlan batch_plan(const edc_ctx* ctx, size_t n, bool per_sig, bool split
     if (P.bins_per_range <= MSM_MAX_BINS) break;
     target *= 2;
   }
+  note_plan(ctx, P, target, per_sig, split, few, false);
   return P;
 }
 
@@ -852,6 +871,7 @@ static int enqueue_multi(edc_ctx* ctx, Slot& s, uint32_t nb, size_t n_per, const
     plan_layout(P);
   }
   if (P.bins_per_range * nb > MSM_MAX_BINS) { ctx->err = "multi-batch: too many batches for the MSM plan"; return EDC_ERR_ARG; }
+  note_plan(ctx, P, ctx->last_plan.target, per_sig, false, ctx->last_plan.few != 0, false);   // as launched: nb ranges
   const size_t nx_max = (size_t)nb * kstride + nb;
   const size_t full_max = (N > (size_t)nb * kstride ? N : (size_t)nb * kstride) + nb;
   rc = ensure_msm(ctx, s, P, msm_entry_capacity(P, N, full_max));
@@ -3135,6 +3155,12 @@ int edc_set_msm_bin_entries(edc_ctx* ctx, int entries) {
   return 0;
 }
 
+int edc_debug_last_plan(const edc_ctx* ctx, edc_plan_info* out) {
+  if (!ctx || !out || !ctx->have_plan) return EDC_ERR_ARG;
+  *out = ctx->last_plan;
+  return 0;
+}
+
 int edc_reserve(edc_ctx* ctx, size_t n) {
   if (!ctx) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
@@ -3946,7 +3972,7 @@ static int verifier_msg_room(edc_verifier* v, size_t m, size_t mbytes) {
 // ---- eager mode (edc_vfy_begin_eager) ----
 // Plan of a fold: every term is a 128-bit z, so there are no windows above bit 128 (the layout of
 // the split plan), and the slices are split into sub-bins as batch_plan splits them.
-static MsmPlan fold_plan(const edc_ctx* ctx, size_t cnt) {
+static MsmPlan fold_plan(edc_ctx* ctx, size_t cnt) {
   const int c = ctx->win_bits ? ctx->win_bits : auto_window_bits(cnt);
   MsmPlan P = make_plan(c, c, 1, false);
   const double total = (double)cnt * P.nwin;
@@ -3957,6 +3983,7 @@ static MsmPlan fold_plan(const edc_ctx* ctx, size_t cnt) {
     if (P.bins_per_range <= MSM_MAX_BINS) break;
     target *= 2;
   }
+  note_plan(ctx, P, target, false, false, false, true);
   return P;
 }
 
@@ -3973,6 +4000,8 @@ static int verifier_fold(edc_verifier* v) {
   Slot& s = v->s;
   const uint32_t cnt = (uint32_t)(b - a);
   const MsmPlan P = fold_plan(ctx, cnt);
+  v->last_plan = ctx->last_plan;
+  v->have_plan = true;
   int rc = ensure_msm(ctx, s, P, msm_entry_capacity(P, cnt, 0));
   if (rc) return rc;
   uint32_t seed[8];
@@ -4218,6 +4247,8 @@ static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const
   const uint32_t N = (uint32_t)n;
   const bool split = verifier_split(v);
   const MsmPlan P = batch_plan(ctx, nl, false, split);
+  v->last_plan = ctx->last_plan;
+  v->have_plan = true;
   // (after a grouping overflow every signature has its own key term: n of them, n + 1 with B)
   int rc = ensure_msm(ctx, s, P, split ? msm_entry_capacity(P, 2 + nl + 2 * n, 0) : msm_entry_capacity(P, nl, n + 1));
   if (rc) return rc;
@@ -4400,6 +4431,12 @@ int edc_vfy_queue_templated(edc_verifier* v, const edc_templates* ts, size_t m, 
 }
 
 int edc_vfy_last_split(const edc_verifier* v) { return v && v->last_split >= 0 ? v->last_split : EDC_ERR_ARG; }
+
+int edc_vfy_last_plan(const edc_verifier* v, edc_plan_info* out) {
+  if (!v || !out || !v->have_plan) return EDC_ERR_ARG;
+  *out = v->last_plan;
+  return 0;
+}
 
 size_t edc_verifier_size(const edc_verifier* v) { return v ? v->n : 0; }
 

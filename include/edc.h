@@ -393,7 +393,8 @@ int edc_set_msm_shape(edc_ctx* ctx, int bits, int parts);
 /*
  * Target MSM entries per bin (tuning / measurement; >= 256, 0 = from the batch size, default):
  * with automatic parts, the slices of the densest windows are split into sub-bins of about this
- * many digits each, one workgroup per bin. Results never depend on it.
+ * many digits each, one workgroup per bin. Results never depend on it
+ * (tests/test_gpu_subbins.py).
  */
 int edc_set_msm_bin_entries(edc_ctx* ctx, int entries);
 
@@ -418,6 +419,34 @@ int edc_debug_sc_reduce_wide(edc_ctx* ctx, size_t n, const uint8_t* d_in, uint8_
  * assert that create / run / destroy leaked nothing on a device other processes allocate on.
  */
 int edc_debug_live_allocs(uint64_t out[2]);
+
+/*
+ * Test hook: the Pippenger plan of the last batch on this context, as the host chose it (a copy
+ * made where the plan is chosen: no device work, no synchronization). Lets a test assert which
+ * plan its batch ran instead of inferring it from the shape: window widths, slices and sub-bins
+ * per window, the bin count, and what the choice was made from. Replaces nothing in the reference
+ * (an MSM evaluation order, src/batch.rs:205-210).
+ *   nwin, nwin_short   windows in all / over the 128 bits of a z_i (the first nwin_short)
+ *   nranges            ranges of a multi-batch launch, or parts of one batch (sum_ranges = 1)
+ *   bins_per_range     sum over the windows of nslice[w] * nsub[w]
+ *   bits / nslice / nsub [w < nwin]   width, 256-bucket slices and sub-bins per slice of window w
+ *   target             entries per bin the split finally aimed at (edc_set_msm_bin_entries or the
+ *                      size-chosen default, doubled until the plan fits the MSM's 8192 bins);
+ *                      0 with explicit parts (edc_set_msm_shape), which are not split
+ *   per_sig, split, few   the inputs of the choice: one key term per signature, split
+ *                      coefficients, 8-bit high windows for few distinct keys
+ *   fold               1: the plan of an eager verifier's fold (R terms only)
+ * EDC_ERR_ARG before any plan was made on the context and for NULL.
+ */
+typedef struct edc_plan_info {
+  uint32_t nwin, nwin_short, nranges, sum_ranges, bins_per_range;
+  uint32_t per_sig, split, few, fold;
+  uint32_t reserved;
+  double target;
+  uint8_t bits[32], nsub[32];
+  uint16_t nslice[32];
+} edc_plan_info;
+int edc_debug_last_plan(const edc_ctx* ctx, edc_plan_info* out);
 
 /*
  * Shape of the grouped fallback's range MSM (tuning / measurement): about `ranges` contiguous
@@ -517,6 +546,8 @@ int edc_synchronize(edc_ctx* ctx);
  *   queue forms.
  * edc_vfy_last_split  1 if the last edc_verifier_verify / _verify_fallback on v ran the split
  *   plan, 0 if not; EDC_ERR_ARG before any verify and for NULL.
+ * edc_vfy_last_plan   test hook: edc_debug_last_plan for the plan of the last verify or eager fold
+ *   on v, whichever came last (a host copy, no device work); EDC_ERR_ARG before either and for NULL.
  *
  * Eager mode: the R terms are summed while the items arrive. z_i depends only on (z_seed, queue
  * index i), so a seed committed when the block starts lets every queue call add [z_i]R_i of its
@@ -613,6 +644,7 @@ int edc_verifier_reset(edc_verifier* v);
 int edc_vfy_queue_indexed(edc_verifier* v, size_t m, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
                           const uint64_t* msg_off, const uint8_t* k);
 int edc_vfy_last_split(const edc_verifier* v);
+int edc_vfy_last_plan(const edc_verifier* v, edc_plan_info* out);
 int edc_vfy_begin_eager(edc_verifier* v, const uint8_t z_seed[32]);
 int edc_vfy_set_fold(edc_verifier* v, size_t min_items);
 int edc_vfy_folded(const edc_verifier* v, uint64_t* items, uint64_t* folds);
