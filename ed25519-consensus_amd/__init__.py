@@ -75,6 +75,7 @@ ABI_SYMBOLS = [
     "edc_tmpl_commits_submit_device", "edc_debug_tmpl_commit_map_alt",
     "edc_debug_live_allocs", "edc_debug_last_plan",
     "edc_quorum_plan", "edc_quorum_verify_device", "edc_quorum_verify", "edc_debug_quorum_select",
+    "edc_tmpl_quorum_verify", "edc_tmpl_quorum_verify_device", "edc_debug_tmpl_quorum_last",
 ]
 
 
@@ -361,6 +362,16 @@ def load_library(path=None):
                                               c_u8p, c_u64p, ctypes.c_int, c_u8p, c_vp, c_vp, c_vp, c_ip, c_szp, c_vp]
             lib.edc_debug_quorum_select.argtypes = [c_vp, c_sz, c_u32p, c_u64p, c_u8p, c_u64p, ctypes.c_int,
                                                     ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+        if hasattr(lib, "edc_tmpl_quorum_verify"):           # absent from older A/B builds (tools/)
+            c_tsp, c_u16p = ctypes.POINTER(EdcTemplates), ctypes.POINTER(ctypes.c_uint16)
+            c_u32p, c_ip, c_szp = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(c_sz)
+            lib.edc_tmpl_quorum_verify.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, ctypes.c_uint32, c_vp, c_u8p, c_u32p,
+                                                   c_u8p, c_u8p, c_u32p, c_u64p, c_u8p, c_u64p, ctypes.c_int, c_u8p,
+                                                   c_vp, c_vp, c_vp, c_ip, c_szp, c_vp]
+            lib.edc_tmpl_quorum_verify_device.argtypes = [c_vp, c_tsp, c_sz, c_u32p, c_u16p, ctypes.c_uint32, c_vp, c_vp,
+                                                          c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_u64p, ctypes.c_int, c_u8p,
+                                                          c_vp, c_vp, c_vp, c_ip, c_szp, c_vp]
+            lib.edc_debug_tmpl_quorum_last.argtypes = [c_vp, c_u64p]
         if path is None:
             _lib = lib
         return lib
@@ -879,6 +890,61 @@ class Engine:
                                                    out[1], out[2], ctypes.byref(out[3]), ctypes.byref(out[4]), out[5])
         self._check(rc)
         return self._quorum_result(rc, nc, n, out)
+
+    # ---- templated quorum commit sets (edc_tmpl_quorum_*): select first, hash only the checked votes ----
+    def quorum_verify_templated(self, templates, commit_off, commit_tpl, sigs, holes, powers, flags, thresholds, z_seed,
+                                light=True, alt_span=1, item_alt=None, vks=None, key_idx=None, var_off=None):
+        """edc_tmpl_quorum_verify: host buffers, synchronous; templates, commit_tpl, alt_span, item_alt
+        and holes as commits_verify_templated_alt, powers / flags / thresholds as quorum_verify.
+        Exactly one of vks and key_idx. Returns the dict quorum_verify returns."""
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        ts, _keep = templates.struct()
+        _, var, voff = _tmpl_items([0] * n, holes, var_off)
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
+        out = self._quorum_out(nc, n)
+        with self._lock:
+            rc = self.lib.edc_tmpl_quorum_verify(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
+                                                 self._item_alt(item_alt), vkb, idx, b"".join(sigs) or b"\0", var, voff,
+                                                 pw, fl, th, int(bool(light)), bytes(z_seed), out[0], out[1], out[2],
+                                                 ctypes.byref(out[3]), ctypes.byref(out[4]), out[5])
+        self._check(rc)
+        return self._quorum_result(rc, nc, n, out)
+
+    def quorum_verify_templated_device(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
+                                       d_power, d_flag, thresholds, z_seed, light=True, alt_span=1, d_item_alt=None):
+        """edc_tmpl_quorum_verify_device: keys, signatures, holes, variant bytes, powers (uint64) and
+        flags (uint8) as torch tensors or device pointers (d_item_alt None: all zeros); commit_off,
+        commit_tpl, thresholds and the set on the host. Returns the dict quorum_verify returns."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        ts, _keep = templates.struct()
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        thresholds = [int(x) for x in thresholds]
+        if len(thresholds) != nc:
+            raise ValueError("one threshold per commit")
+        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
+        out = self._quorum_out(nc, n)
+        p = self._dev_ptr
+        with self._lock:
+            rc = self.lib.edc_tmpl_quorum_verify_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
+                                                        p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
+                                                        var_bytes, p(d_power), p(d_flag), th, int(bool(light)),
+                                                        bytes(z_seed), out[0], out[1], out[2], ctypes.byref(out[3]),
+                                                        ctypes.byref(out[4]), out[5])
+        self._check(rc)
+        return self._quorum_result(rc, nc, n, out)
+
+    def tmpl_quorum_last(self):
+        """edc_debug_tmpl_quorum_last: (n, n_checked, items expanded and hashed, arena bytes assembled)
+        of the last templated quorum call on this engine."""
+        out = (ctypes.c_uint64 * 4)()
+        with self._lock:
+            rc = self.lib.edc_debug_tmpl_quorum_last(self.ctx, out)
+        self._check(rc)
+        return tuple(out)
 
     def quorum_select_ms(self, commit_off, powers, flags, thresholds, light=True, reps=20):
         """edc_debug_quorum_select: mean time of the selection kernels alone, in milliseconds."""

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -255,6 +256,17 @@ struct edc_ctx {
   DevBuf<uint8_t> q_flag;
   DevBuf<int> q_err;
   PinnedBuf<uint32_t> q_h;
+  // templated quorum commit sets (edc_tmpl_quorum_*): the all-n template array and the staged
+  // commit_tpl, the tiles' hole bytes (+ their total, which comes back in q_h[2]), the gathered
+  // template indices / hole offsets / holes of the checked votes, the host form's staged
+  // var_off | item_alt | var, the pinned word the arena's size comes back in, and the host copy
+  // edc_debug_tmpl_quorum_last returns
+  DevBuf<uint16_t> tq_tpl, tq_ctpl, tq_gtpl;
+  DevBuf<uint32_t> tq_wgh, tq_gvoff;
+  DevBuf<uint8_t> tq_gvar, tq_in;
+  PinnedBuf<uint64_t> tq_harena;
+  uint64_t tq_last[4] = {};
+  bool tq_have = false;
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -3557,7 +3569,7 @@ static int ensure_quorum(edc_ctx* ctx, size_t n, size_t nc) {
                      sized(ctx->q_aggf, tiles), sized(ctx->q_carry, tiles));
   }));
   if (!ctx->q_err) CK(ctx->q_err.alloc(1));
-  if (!ctx->q_h) CK(ctx->q_h.alloc(2));
+  if (!ctx->q_h) CK(ctx->q_h.alloc(4));    // flag, checked count, checked hole bytes (templated form)
   return 0;
 }
 
@@ -3589,8 +3601,11 @@ static int quorum_check_votes(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
 // Workspace, the staged offsets and thresholds, then the selection and the scan of its workgroup
 // counts on device-resident power / flag. *n_checked = the size of the gathered list. A vote the
 // device checks refuse is EDC_ERR_ARG here, before anything is gathered or verified.
+// behind: what a templated form enqueues behind the selection, in front of the one read-back (its
+// all-n checks raise q_err too, bit 1 for the holes).
 static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
-                             int mode, const uint64_t* d_power, const uint8_t* d_flag, size_t* n_checked) {
+                             int mode, const uint64_t* d_power, const uint8_t* d_flag, size_t* n_checked,
+                             const std::function<int(hipStream_t)>* behind = nullptr) {
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
   hipStream_t st = ctx->st();
@@ -3606,10 +3621,19 @@ static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* 
                        ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->sc_hit, ctx->sc_wg, ctx->q_planned, ctx->q_err);
   launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
   CK(hipGetLastError());
-  ctx->q_h[0] = ctx->q_h[1] = 0;
+  ctx->q_h[0] = ctx->q_h[1] = ctx->q_h[2] = 0;
+  if (behind && (rc = (*behind)(st))) return rc;
   CK(hipMemcpyAsync(&ctx->q_h[0], ctx->q_err, sizeof(int), hipMemcpyDeviceToHost, st));
   CK(hipMemcpyAsync(&ctx->q_h[1], ctx->sc_wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
+  if (ctx->q_h[0] & 2) {
+    ctx->err = "templated items: hole offsets out of range";
+    return EDC_ERR_ARG;
+  }
+  if (ctx->q_h[0] && behind) {
+    ctx->err = "votes: a flag above 2, a power or a commit's counted power above 2^63 - 1, or an item_alt[i] >= alt_span";
+    return EDC_ERR_ARG;
+  }
   if (ctx->q_h[0]) {
     ctx->err = "votes: a flag above 2, a power above 2^63 - 1 or a commit whose counted power passes 2^63 - 1";
     return EDC_ERR_ARG;
@@ -3626,6 +3650,10 @@ struct QuorumOut {
   size_t* n_checked;
   uint8_t* check8;
 };
+
+static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, size_t m, const uint8_t* b_vk,
+                         const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx, const uint64_t* d_power,
+                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out);
 
 // A checked quorum commit set whose items (vk, sig, k, power, flag) are on the device.
 static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode, size_t n,
@@ -3649,6 +3677,15 @@ static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
     b_sig = g_sig;
     b_k = g_k;
   }
+  return quorum_finish(ctx, nc, threshold, n, m, b_vk, b_sig, b_k, idx, d_power, d_flag, z_seed, out);
+}
+
+// The gathered list (m items in queue order; idx their queue positions, null when m == n or m == 0)
+// through the batch and its fallback, then the tally and the verdicts of all n items / nc commits.
+static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, size_t m, const uint8_t* b_vk,
+                         const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx, const uint64_t* d_power,
+                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out) {
+  hipStream_t st = ctx->st();
   std::vector<uint8_t> mv(m ? m : 1);
   const int code = batch_with_fallback(ctx, m, b_vk, b_sig, nullptr, nullptr, b_k, z_seed, mv.data(), nullptr, out.check8);
   if (code < 0) return code;
@@ -3844,6 +3881,179 @@ int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
   float t = 0.f;
   CK(hipEventElapsedTime(&t, e0, e1));
   if (ms) *ms = t / (float)reps;
+  return EDC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- templated quorum commit sets
+// edc_tmpl_quorum_*: select first. The selection needs only power, flag and the offsets, so it runs
+// before any message exists; behind it, in front of the one read-back, the all-n template map
+// (k_tmpl_commit_map_alt, which checks the variant bytes) and k_tq_holes (which checks the hole
+// offsets and sums the checked holes per tile). The read-back then carries the flag, the checked
+// count m and the checked hole bytes. k_tq_gather packs the m checked votes (keys, signatures,
+// template indices, holes) in queue order, the expansion and SHA-512 run on those m items into an
+// arena sized from m, and quorum_finish does what it does for every quorum form. m == n: nothing is
+// gathered, the caller's arrays are the list. All on slot 0.
+struct TmplQuorumItems {       // device arrays of all n items
+  const uint8_t *vk, *sig, *item_alt, *var;
+  const uint32_t* var_off;
+  size_t var_bytes;
+  const uint64_t* power;
+  const uint8_t* flag;
+};
+
+static int tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
+                           const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span, size_t n,
+                           const TmplQuorumItems& it, const uint64_t* threshold, int mode, const uint8_t* z_seed,
+                           const QuorumOut& out) {
+  Slot& s = ctx->slot[0];
+  TmplWs& w = s.tw;
+  int rc = init_slot(ctx, s);
+  if (rc) return rc;
+  hipStream_t st = ctx->st();
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, w, st, ts, sh, &view))) return rc;
+  const uint32_t nwg = (uint32_t)quorum_tiles(n);
+  if ((rc = tmpl_room(ctx, st, ctx->tq_tpl, n)) || (rc = tmpl_room(ctx, st, ctx->tq_ctpl, nc)) ||
+      (rc = tmpl_room(ctx, st, ctx->tq_wgh, (size_t)nwg + 1)))
+    return rc;
+  if (!ctx->tq_harena) CK(ctx->tq_harena.alloc(1));
+  const std::function<int(hipStream_t)> behind = [&](hipStream_t q) -> int {
+    CK(hipMemcpyAsync(ctx->tq_ctpl, commit_tpl, nc * sizeof(uint16_t), hipMemcpyHostToDevice, q));
+    launch_tmpl_commit_map_alt(q, (uint32_t)n, (uint32_t)nc, ctx->q_coff, ctx->tq_ctpl, alt_span, it.item_alt, ctx->tq_tpl,
+                               ctx->q_err);
+    launch_tmpl_quorum_holes(q, (uint32_t)n, ctx->sc_hit, it.var_off, it.var_bytes, ctx->tq_wgh, ctx->q_err);
+    launch_sc_scan(q, nwg, ctx->tq_wgh, ctx->tq_wgh + nwg);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&ctx->q_h[2], ctx->tq_wgh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+    return 0;
+  };
+  size_t m = 0;
+  if ((rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, it.power, it.flag, &m, &behind))) return rc;
+  const size_t holes = m ? ctx->q_h[2] : 0;
+  if (holes > it.var_bytes) { ctx->err = "quorum selection: checked hole bytes out of range"; return EDC_ERR_HIP; }
+  ctx->tq_have = true;
+  ctx->tq_last[0] = n;
+  ctx->tq_last[1] = m;
+  ctx->tq_last[2] = ctx->tq_last[3] = 0;
+  const uint8_t *b_vk = it.vk, *b_sig = it.sig;
+  // an empty list still runs the n = 0 batch, whose k is never read
+  const uint32_t *b_k = reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), *idx = nullptr;
+  *ctx->tq_harena = 0;
+  if (m) {
+    const uint16_t* e_tpl = ctx->tq_tpl;
+    const uint8_t* e_var = it.var;
+    const uint32_t* e_voff = it.var_off;
+    size_t e_bytes = it.var_bytes;
+    if (m < n) {
+      if ((rc = tmpl_room(ctx, st, ctx->tq_gtpl, m)) || (rc = tmpl_room(ctx, st, ctx->tq_gvoff, m + 1)) ||
+          (rc = tmpl_room(ctx, st, ctx->tq_gvar, holes + 16)))
+        return rc;
+      uint8_t* g_vk = ctx->sc_g;
+      uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
+      launch_tmpl_quorum_gather(st, (uint32_t)n, (uint32_t)m, ctx->sc_hit, ctx->sc_wg, ctx->tq_wgh, it.vk, it.sig,
+                                ctx->tq_tpl, it.var, it.var_off, ctx->sc_idx, g_vk, g_sig, ctx->tq_gtpl, ctx->tq_gvar,
+                                ctx->tq_gvoff);
+      CK(hipGetLastError());
+      idx = ctx->sc_idx;
+      b_vk = g_vk;
+      b_sig = g_sig;
+      e_tpl = ctx->tq_gtpl;
+      e_var = ctx->tq_gvar;
+      e_voff = ctx->tq_gvoff;
+      e_bytes = holes;
+    }
+    // Item::from (src/batch.rs:82-94) for the m checked votes alone: the arena is sized from m
+    if ((rc = tmpl_arena_room(ctx, w, st, m, sh, holes)) || (rc = ensure_n(ctx, m)) ||
+        (rc = tmpl_expand(ctx, w, st, view, m, e_tpl, e_var, e_voff, e_bytes, w.arena, w.off)))
+      return rc;
+    // k_tmpl_len checks the gathered items again; its flag travels behind the expansion and the
+    // batch's wait reads it before it believes a verdict
+    CK(hipMemcpyAsync(w.h_flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(ctx->tq_harena.get(), w.off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    w.check = true;
+    launch_challenge(st, (uint32_t)m, b_vk, b_sig, w.arena, w.off, ctx->kbuf);
+    CK(hipGetLastError());
+    b_k = ctx->kbuf;
+    ctx->tq_last[2] = m;
+  }
+  rc = quorum_finish(ctx, nc, threshold, n, m, b_vk, b_sig, b_k, idx, it.power, it.flag, z_seed, out);
+  w.check = false;              // also when the batch never reached its wait
+  if (rc >= 0) ctx->tq_last[3] = *ctx->tq_harena;
+  return rc;
+}
+
+extern "C" {
+
+int edc_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                  const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                  const uint32_t* d_var_off, size_t var_bytes, const uint64_t* d_power,
+                                  const uint8_t* d_flag, const uint64_t* threshold, int mode, const uint8_t z_seed[32],
+                                  uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits,
+                                  size_t* n_checked, uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return quorum_none(out);
+  TmplShape sh;
+  size_t n;
+  int rc = commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
+                                     var_bytes, &sh, &n);
+  if (rc || (rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n))) return rc;
+  if (n && (!d_power || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (n && ((uintptr_t)d_power & 7u)) { ctx->err = "d_power must be 8-byte aligned"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  const TmplQuorumItems it{d_vk, d_sig, d_item_alt, d_var, d_var_off, var_bytes, d_power, d_flag};
+  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
+}
+
+int edc_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                           const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                           const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
+                           const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                           int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return quorum_none(out);
+  TmplShape sh;
+  size_t n;
+  int rc = commits_check_tmpl_alt(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
+                                  &sh, &n);
+  if (rc || (rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n)) ||
+      (rc = quorum_check_votes(ctx, nc, commit_off, power, flag)))
+    return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = quorum_stage_votes(ctx, n, nc, power, flag)) || (rc = ensure_n(ctx, n))) return rc;
+  hipStream_t st = ctx->st();
+  TmplQuorumItems it{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->q_power, ctx->q_flag};
+  if (n) {                  // staged in one piece: var_off | item_alt | var, each at a 16-byte boundary
+    const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t var_bytes = var_off[n], o_alt = up16(4 * (n + 1)), o_var = up16(o_alt + n);
+    if ((rc = tmpl_room(ctx, st, ctx->tq_in, o_var + var_bytes))) return rc;
+    if (key_idx) {          // 4 bytes per item over PCIe; q_cidx is free until the selection writes it
+      CK(hipMemcpyAsync(ctx->q_cidx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      launch_expand_keys(st, (uint32_t)n, ctx->q_cidx, ctx->kc_reg, ctx->kc_keys, ctx->vk);
+      CK(hipGetLastError());
+    } else {
+      CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
+    }
+    CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(ctx->tq_in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
+    if (item_alt) CK(hipMemcpyAsync(ctx->tq_in + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
+    if (var_bytes) CK(hipMemcpyAsync(ctx->tq_in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
+    it.item_alt = item_alt ? ctx->tq_in + o_alt : nullptr;
+    it.var = ctx->tq_in + o_var;
+    it.var_off = reinterpret_cast<const uint32_t*>(ctx->tq_in.get());
+    it.var_bytes = var_bytes;
+  }
+  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
+}
+
+int edc_debug_tmpl_quorum_last(const edc_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out || !ctx->tq_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->tq_last, sizeof(ctx->tq_last));
   return EDC_OK;
 }
 

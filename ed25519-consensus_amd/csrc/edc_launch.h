@@ -124,6 +124,20 @@ void launch_quorum_select(hipStream_t st, uint32_t n, uint32_t nc, int light, co
 // the checked flag-1 items with code 0, cor[c] |= the checked items' codes (both zeroed by the caller)
 void launch_quorum_tally(hipStream_t st, uint32_t n, const uint32_t* cidx, const uint64_t* power, const uint8_t* flag,
                          const uint8_t* code, uint64_t* tally, uint32_t* cor);
+// templated quorum commit sets (edc_tmpl_quorum_*): the gather of the checked votes with their
+// holes. launch_tmpl_quorum_holes runs behind the selection, on all n items: *err |= 2 unless
+// var_off[i] <= var_off[i+1] <= var_bytes for every item, wg_hole[t] = the hole bytes of tile t's
+// checked items (quorum_tiles(n) + 1 words: launch_sc_scan makes them the tiles' starts and the
+// total). launch_tmpl_quorum_gather runs once the flag is known clear and m, the checked count,
+// is known (0 < m): wg_off / wg_hole are the scanned counts and hole bytes, tpl the all-n template
+// array; checked vote j gets idx[j], g_vk / g_sig row j, g_tpl[j] and its hole at g_var_off[j] of
+// g_var (16-byte aligned, room for the scanned total), g_var_off[m] = that total.
+void launch_tmpl_quorum_holes(hipStream_t st, uint32_t n, const uint8_t* skip, const uint32_t* var_off,
+                              uint64_t var_bytes, uint32_t* wg_hole, int* err);
+void launch_tmpl_quorum_gather(hipStream_t st, uint32_t n, uint32_t m, const uint8_t* skip, const uint32_t* wg_off,
+                               const uint32_t* wg_hole, const uint8_t* vk, const uint8_t* sig, const uint16_t* tpl,
+                               const uint8_t* var, const uint32_t* var_off, uint32_t* idx, uint8_t* g_vk, uint8_t* g_sig,
+                               uint16_t* g_tpl, uint8_t* g_var, uint32_t* g_var_off);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

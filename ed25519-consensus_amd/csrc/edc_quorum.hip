@@ -217,9 +217,148 @@ __global__ void __launch_bounds__(QR_TILE) k_q_tally(uint32_t n, const uint32_t*
   else if (flag[i] == QUORUM_COMMIT && power[i]) atomicAdd(&tally[c], (unsigned long long)power[i]);
 }
 
+// Templated quorum commit sets (edc_tmpl_quorum_*): the selection runs first, and only the checked
+// votes are gathered, assembled and hashed. Two kernels around the read-back of the checked count:
+//   k_tq_holes   per tile, behind k_q_select: var_off[i] <= var_off[i+1] <= var_bytes for ALL n
+//                items (bit 1 of the error flag), and the tile's sum of the checked items' hole
+//                lengths, which launch_sc_scan turns into the tile's start in the packed holes
+//   k_tq_gather  per tile, once the host knows the checked count m and the flag is clear: checked
+//                vote j (queue order) gets idx[j], its key, signature and template index, and
+//                g_var_off[j]; the tile's holes are one contiguous span of g_var, written in whole
+//                aligned 16-byte stores (byte stores only in the span's two partial end chunks,
+//                which the neighbouring tiles share), as k_tmpl_expand writes its arena
+// Sums of 32-bit lengths: valid offsets make every sum at most var_off[n] - var_off[0] < 2^32, and
+// wrapping addition is associative and commutative, so the grouping does not matter.
+__global__ void __launch_bounds__(QR_TILE) k_tq_holes(uint32_t n, const uint8_t* __restrict__ skip,
+                                                      const uint32_t* __restrict__ var_off, uint64_t var_bytes,
+                                                      uint32_t* __restrict__ wg_hole, int* __restrict__ err) {
+  __shared__ uint32_t wsum[QR_WAVES];
+  const uint32_t i = blockIdx.x * QR_TILE + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t len = 0;
+  if (i < n) {
+    const uint32_t a = var_off[i], b = var_off[i + 1];
+    if (a > b || (uint64_t)b > var_bytes) atomicOr(err, 2);
+    else if (skip[i] == 0) len = b - a;
+  }
+#pragma unroll
+  for (uint32_t d = 32; d >= 1; d >>= 1) len += __shfl_xor(len, d);
+  if (lane == 0) wsum[wave] = len;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (uint32_t w = 0; w < QR_WAVES; ++w) s += wsum[w];
+    wg_hole[blockIdx.x] = s;
+  }
+}
+
+__global__ void __launch_bounds__(QR_TILE) k_tq_gather(uint32_t n, uint32_t m, const uint8_t* __restrict__ skip,
+                                                       const uint32_t* __restrict__ wg_off,
+                                                       const uint32_t* __restrict__ wg_hole,
+                                                       const uint8_t* __restrict__ vk, const uint8_t* __restrict__ sig,
+                                                       const uint16_t* __restrict__ tpl,
+                                                       const uint8_t* __restrict__ var,
+                                                       const uint32_t* __restrict__ var_off, uint32_t* __restrict__ idx,
+                                                       uint8_t* __restrict__ g_vk, uint8_t* __restrict__ g_sig,
+                                                       uint16_t* __restrict__ g_tpl, uint8_t* __restrict__ g_var,
+                                                       uint32_t* __restrict__ g_var_off) {
+  __shared__ uint32_t wcnt[QR_WAVES], wlen[QR_WAVES];
+  __shared__ uint32_t s_go[QR_TILE + 1];       // rank r of the tile: where its hole starts in g_var; [cnt] = the span's end
+  __shared__ uint32_t s_src[QR_TILE];          // and where it starts in var
+  const uint32_t i = blockIdx.x * QR_TILE + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool checked = i < n && skip[i] == 0;
+  uint32_t a = 0, len = 0;
+  if (checked) {
+    a = var_off[i];
+    len = var_off[i + 1] - a;
+  }
+  const uint64_t bal = __ballot(checked);
+  uint32_t incl = len;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t u = __shfl_up(incl, d);
+    if (lane >= d) incl += u;
+  }
+  if (lane == 0) wcnt[wave] = (uint32_t)__popcll(bal);
+  if (lane == 63) wlen[wave] = incl;
+  __syncthreads();
+  uint32_t r = (uint32_t)__popcll(bal & ((1ull << lane) - 1)), cnt = 0, excl = incl - len, tot = 0;
+  for (uint32_t w = 0; w < QR_WAVES; ++w) {
+    if (w < wave) {
+      r += wcnt[w];
+      excl += wlen[w];
+    }
+    cnt += wcnt[w];
+    tot += wlen[w];
+  }
+  const uint32_t B = wg_hole[blockIdx.x];
+  if (checked) {
+    s_go[r] = B + excl;
+    s_src[r] = a;
+  }
+  if (threadIdx.x == 0) s_go[cnt] = B + tot;
+  __syncthreads();
+  if (checked) {
+    const uint32_t j = wg_off[blockIdx.x] + r;
+    idx[j] = i;
+    const uint4* sa = reinterpret_cast<const uint4*>(vk + (size_t)i * 32);
+    const uint4* sb = reinterpret_cast<const uint4*>(sig + (size_t)i * 64);
+    uint4* da = reinterpret_cast<uint4*>(g_vk + (size_t)j * 32);
+    uint4* db = reinterpret_cast<uint4*>(g_sig + (size_t)j * 64);
+    const uint4 q0 = sa[0], q1 = sa[1], q2 = sb[0], q3 = sb[1], q4 = sb[2], q5 = sb[3];
+    da[0] = q0; da[1] = q1;
+    db[0] = q2; db[1] = q3; db[2] = q4; db[3] = q5;
+    g_tpl[j] = tpl[i];
+    g_var_off[j] = B + excl;
+    if (j == m - 1) g_var_off[m] = B + excl + len;
+  }
+  if (!tot) return;
+  const uint64_t E = (uint64_t)B + tot;
+  for (uint64_t c = (B >> 4) + threadIdx.x; c < ((E + 15) >> 4); c += QR_TILE) {
+    const uint64_t p0 = (c << 4) > B ? (c << 4) : B, p1 = (c << 4) + 16 < E ? (c << 4) + 16 : E;
+    // the hole holding byte p0: the first rank with s_go[rank + 1] > p0 (p0 < E = s_go[cnt], so there is one)
+    uint32_t lo = 0, hi = cnt - 1;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (s_go[mid + 1] > p0) hi = mid;
+      else lo = mid + 1;
+    }
+    uint32_t q = lo;
+    auto byte_at = [&](uint64_t p) -> uint32_t {
+      while (p >= s_go[q + 1]) ++q;      // empty holes in between are skipped; p < E ends it
+      return var[(size_t)s_src[q] + (size_t)(p - s_go[q])];
+    };
+    if (p1 - p0 == 16) {
+      uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 16; ++k) w[k >> 2] |= byte_at(p0 + k) << (8 * (k & 3));
+      *reinterpret_cast<uint4*>(g_var + p0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+      for (uint64_t p = p0; p < p1; ++p) g_var[p] = (uint8_t)byte_at(p);
+    }
+  }
+}
+
 }  // namespace
 
 size_t quorum_tiles(size_t n) { return (n + QR_TILE - 1) / QR_TILE; }
+
+void launch_tmpl_quorum_holes(hipStream_t st, uint32_t n, const uint8_t* skip, const uint32_t* var_off,
+                              uint64_t var_bytes, uint32_t* wg_hole, int* err) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_tq_holes, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, skip, var_off, var_bytes,
+                     wg_hole, err);
+}
+
+void launch_tmpl_quorum_gather(hipStream_t st, uint32_t n, uint32_t m, const uint8_t* skip, const uint32_t* wg_off,
+                               const uint32_t* wg_hole, const uint8_t* vk, const uint8_t* sig, const uint16_t* tpl,
+                               const uint8_t* var, const uint32_t* var_off, uint32_t* idx, uint8_t* g_vk, uint8_t* g_sig,
+                               uint16_t* g_tpl, uint8_t* g_var, uint32_t* g_var_off) {
+  if (!n || !m) return;
+  hipLaunchKernelGGL(k_tq_gather, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, m, skip, wg_off, wg_hole, vk,
+                     sig, tpl, var, var_off, idx, g_vk, g_sig, g_tpl, g_var, g_var_off);
+}
 
 void launch_quorum_select(hipStream_t st, uint32_t n, uint32_t nc, int light, const uint32_t* commit_off,
                           const uint64_t* threshold, const uint64_t* power, const uint8_t* flag, uint32_t* cidx,

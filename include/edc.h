@@ -959,8 +959,9 @@ int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commi
  *   entries need no verified-signature table on the context.
  * edc_debug_quorum_select  measurement hook: the selection kernels alone on host arrays (checked as
  *   edc_quorum_plan), run `reps` times between HIP events; *ms (nullable) = the mean time.
- * Out of scope: asynchronous submit / wait forms, templated forms, the incremental verifier and
- *   the multi-GPU engine have no quorum entries.
+ * Out of scope for these entries: asynchronous submit / wait forms; templated forms are the
+ *   edc_tmpl_quorum_* entries below; the incremental verifier and the multi-GPU engine have no
+ *   quorum entries.
  */
 #define EDC_QUORUM_SHORT 3           /* every checked vote verified, tally <= threshold */
 #define EDC_NOT_CHECKED 255          /* item_verdicts: the vote was not verified */
@@ -983,6 +984,70 @@ int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
                       int* n_bad_commits, size_t* n_checked, uint8_t check8[32]);
 int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power,
                             const uint8_t* flag, const uint64_t* threshold, int mode, int reps, float* ms);
+
+/*
+ * Templated quorum commit sets: hash only the votes that are checked. The two halves above meet
+ * here: the votes are templated (shared heads and tails plus a hole and a variant byte per vote,
+ * as edc_tmpl_commits_verify_alt / _device take them) and the verdict is a quorum verdict (power,
+ * flag, threshold and mode as edc_quorum_verify / _device take them). The template inputs (ts,
+ * commit_tpl, alt_span, item_alt, var, var_off, var_bytes) mean exactly what they mean for
+ * edc_tmpl_commits_verify_alt / edc_tmpl_commits_verify_device, the quorum inputs and all outputs
+ * exactly what they mean for edc_quorum_verify / edc_quorum_verify_device; commit_off, commit_tpl,
+ * threshold and the template set are host memory in both forms.
+ *
+ * Equality contract: for the same keys, powers, flags, thresholds, mode and z_seed every output
+ * (the return value, commit_verdicts, item_verdicts, tally, *n_bad_commits, *n_checked and check8)
+ * equals what edc_quorum_verify[_device] gives on the materialised messages
+ * head[t] || hole || tail[t]. Equivalently, the union verdict and check8 are those of
+ * edc_batch_verify_prehashed_device on the gathered checked list with z_base = 0. Every checked
+ * vote is one batch::Item (Item::from, src/batch.rs:82-94) in ONE batch::Verifier (queue and
+ * verify, src/batch.rs:127-137, :149-217), and its code is Item::verify_single's
+ * (src/batch.rs:104-107). Soundness and the requirement on z_seed are those of the quorum entries.
+ *
+ * Select first: the selection needs only power, flag and the offsets, so it runs before any
+ * message exists. Only the checked votes are gathered, in queue order (key, signature, template
+ * index and hole), only their messages are assembled and only they are hashed; the arena is sized
+ * after the read-back of the checked count, from n_checked and not from n. A vote that is not
+ * checked has its vk, sig and hole BYTES never interpreted: noise there changes no output (its
+ * variant byte and its hole offsets are still checked, see below). The call adds no stream
+ * synchronization to the one edc_quorum_verify_device has for the checked count. When every vote
+ * is checked nothing is gathered; when none is, the n = 0 batch runs.
+ *
+ * edc_tmpl_quorum_verify_device  the items in this GPU's memory: d_vk, d_sig, d_item_alt, d_var,
+ *   d_var_off, var_bytes as edc_tmpl_commits_verify_device, d_power and d_flag as
+ *   edc_quorum_verify_device. Synchronous, on slot 0 (EDC_ERR_ARG while a submitted batch is
+ *   pending there). The host checks the offsets, the set, alt_span and the windows (EDC_ERR_ARG,
+ *   nothing launched). The device checks the flags, the powers and the per-commit sums as the
+ *   quorum entries do, and, for ALL n items and not only the checked ones, d_item_alt[i] < alt_span
+ *   and var_off[i] <= var_off[i+1] <= var_bytes: so EDC_ERR_ARG does not depend on the mode or on
+ *   which votes the thresholds select. The flag travels in the read-back of the checked count; on a
+ *   violation nothing is gathered, no index outside the declared arrays is formed, and the call
+ *   returns EDC_ERR_ARG, never a verdict; the context stays usable.
+ * edc_tmpl_quorum_verify  host buffers: exactly one of vk and key_idx (positions in the list last
+ *   given to edc_keycache_load), staged in one piece beside power and flag. Everything is checked on
+ *   the host before anything is launched, the union of the checks of edc_tmpl_commits_verify_alt
+ *   and edc_quorum_verify: the one-of pair, an index outside the registered list, the set,
+ *   alt_span, the windows, item_alt[i] < alt_span, the hole offsets, the flags, the power bounds.
+ * nc = 0 returns EDC_OK (no array is read); a NULL ctx or z_seed is EDC_ERR_ARG.
+ * edc_debug_tmpl_quorum_last  test hook, a host copy (no device work): out = {n, n_checked, the
+ *   items the expansion and SHA-512 ran over, the arena bytes assembled} of the last templated
+ *   quorum call on the context that reached its selection. EDC_ERR_ARG before any such call and
+ *   for NULL.
+ */
+int edc_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                           const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                           const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
+                           const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                           int* n_bad_commits, size_t* n_checked, uint8_t check8[32]);
+int edc_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                  const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                  const uint32_t* d_var_off, size_t var_bytes, const uint64_t* d_power,
+                                  const uint8_t* d_flag, const uint64_t* threshold, int mode, const uint8_t z_seed[32],
+                                  uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits,
+                                  size_t* n_checked, uint8_t check8[32]);
+int edc_debug_tmpl_quorum_last(const edc_ctx* ctx, uint64_t out[4]);
 
 /*
  * Verified-signature cache: skip the items that already verified on this context. A consensus
