@@ -76,6 +76,8 @@ ABI_SYMBOLS = [
     "edc_debug_live_allocs", "edc_debug_last_plan",
     "edc_quorum_plan", "edc_quorum_verify_device", "edc_quorum_verify", "edc_debug_quorum_select",
     "edc_tmpl_quorum_verify", "edc_tmpl_quorum_verify_device", "edc_debug_tmpl_quorum_last",
+    "edc_cached_quorum_verify_device", "edc_cached_quorum_verify", "edc_cached_tmpl_quorum_verify_device",
+    "edc_cached_tmpl_quorum_verify", "edc_debug_cached_quorum_last",
 ]
 
 
@@ -372,6 +374,13 @@ def load_library(path=None):
                                                           c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_u64p, ctypes.c_int, c_u8p,
                                                           c_vp, c_vp, c_vp, c_ip, c_szp, c_vp]
             lib.edc_debug_tmpl_quorum_last.argtypes = [c_vp, c_u64p]
+        if hasattr(lib, "edc_cached_quorum_verify"):         # absent from older A/B builds (tools/)
+            # the uncached twins' arguments with n_miss in front of check8
+            for name in ("edc_quorum_verify_device", "edc_quorum_verify", "edc_tmpl_quorum_verify_device",
+                         "edc_tmpl_quorum_verify"):
+                a = list(getattr(lib, name).argtypes)
+                getattr(lib, name.replace("edc_", "edc_cached_", 1)).argtypes = a[:-1] + [ctypes.POINTER(c_sz), a[-1]]
+            lib.edc_debug_cached_quorum_last.argtypes = [c_vp, c_u64p]
         if path is None:
             _lib = lib
         return lib
@@ -936,6 +945,102 @@ class Engine:
                                                         ctypes.byref(out[4]), out[5])
         self._check(rc)
         return self._quorum_result(rc, nc, n, out)
+
+    # ---- cached quorum commit sets (edc_cached_*): checked votes that are live records of the
+    # verified-signature table (sigcache_create) are not verified again; the results gain n_miss ----
+    @staticmethod
+    def _cached_quorum_result(rc, nc, n, out, miss):
+        res = Engine._quorum_result(rc, nc, n, out)
+        res["n_miss"] = miss.value
+        return res
+
+    def quorum_verify_cached(self, commit_off, sigs, powers, flags, thresholds, z_seed, light=True, vks=None,
+                             key_idx=None, msgs=None, ks=None):
+        """edc_cached_quorum_verify: quorum_verify through the verified-signature table. Returns
+        quorum_verify's dict plus n_miss, the size of the list that was verified."""
+        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
+        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
+        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
+        with self._lock:
+            rc = self.lib.edc_cached_quorum_verify(self.ctx, nc, *b, pw, fl, th, int(bool(light)), bytes(z_seed), out[0],
+                                                   out[1], out[2], ctypes.byref(out[3]), ctypes.byref(out[4]),
+                                                   ctypes.byref(miss), out[5])
+        self._check(rc)
+        return self._cached_quorum_result(rc, nc, n, out, miss)
+
+    def quorum_verify_cached_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_power, d_flag, thresholds, z_seed,
+                                    light=True, d_k=None):
+        """edc_cached_quorum_verify_device: quorum_verify_device through the verified-signature table."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        thresholds = [int(x) for x in thresholds]
+        if len(thresholds) != nc:
+            raise ValueError("one threshold per commit")
+        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
+        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
+        p = self._dev_ptr
+        with self._lock:
+            rc = self.lib.edc_cached_quorum_verify_device(self.ctx, nc, off, p(d_vk), p(d_sig), p(d_msg), p(d_msg_off),
+                                                          p(d_k), p(d_power), p(d_flag), th, int(bool(light)),
+                                                          bytes(z_seed), out[0], out[1], out[2], ctypes.byref(out[3]),
+                                                          ctypes.byref(out[4]), ctypes.byref(miss), out[5])
+        self._check(rc)
+        return self._cached_quorum_result(rc, nc, n, out, miss)
+
+    def quorum_verify_templated_cached(self, templates, commit_off, commit_tpl, sigs, holes, powers, flags, thresholds,
+                                       z_seed, light=True, alt_span=1, item_alt=None, vks=None, key_idx=None,
+                                       var_off=None):
+        """edc_cached_tmpl_quorum_verify: quorum_verify_templated through the verified-signature table."""
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        ts, _keep = templates.struct()
+        _, var, voff = _tmpl_items([0] * n, holes, var_off)
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
+        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
+        with self._lock:
+            rc = self.lib.edc_cached_tmpl_quorum_verify(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
+                                                        self._item_alt(item_alt), vkb, idx, b"".join(sigs) or b"\0", var,
+                                                        voff, pw, fl, th, int(bool(light)), bytes(z_seed), out[0], out[1],
+                                                        out[2], ctypes.byref(out[3]), ctypes.byref(out[4]),
+                                                        ctypes.byref(miss), out[5])
+        self._check(rc)
+        return self._cached_quorum_result(rc, nc, n, out, miss)
+
+    def quorum_verify_templated_cached_device(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off,
+                                              var_bytes, d_power, d_flag, thresholds, z_seed, light=True, alt_span=1,
+                                              d_item_alt=None):
+        """edc_cached_tmpl_quorum_verify_device: quorum_verify_templated_device through the
+        verified-signature table."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        ts, _keep = templates.struct()
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        thresholds = [int(x) for x in thresholds]
+        if len(thresholds) != nc:
+            raise ValueError("one threshold per commit")
+        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
+        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
+        p = self._dev_ptr
+        with self._lock:
+            rc = self.lib.edc_cached_tmpl_quorum_verify_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
+                                                               p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
+                                                               var_bytes, p(d_power), p(d_flag), th, int(bool(light)),
+                                                               bytes(z_seed), out[0], out[1], out[2],
+                                                               ctypes.byref(out[3]), ctypes.byref(out[4]),
+                                                               ctypes.byref(miss), out[5])
+        self._check(rc)
+        return self._cached_quorum_result(rc, nc, n, out, miss)
+
+    def cached_quorum_last(self):
+        """edc_debug_cached_quorum_last: (n, n_checked, hits among the checked, n_miss, items SHA-512
+        ran over, records inserted) of the last cached quorum call on this engine."""
+        out = (ctypes.c_uint64 * 6)()
+        with self._lock:
+            rc = self.lib.edc_debug_cached_quorum_last(self.ctx, out)
+        self._check(rc)
+        return tuple(out)
 
     def tmpl_quorum_last(self):
         """edc_debug_tmpl_quorum_last: (n, n_checked, items expanded and hashed, arena bytes assembled)
@@ -1719,7 +1824,7 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         return [c == EDC_OK for c in res[1]]
 
     @staticmethod
-    def verify_quorum(verifiers, powers, flags, thresholds, light=True, z_seed=None, engine=None):
+    def verify_quorum(verifiers, powers, flags, thresholds, light=True, z_seed=None, engine=None, cached=False):
         """Quorum check of many commits in ONE launch (a quorum commit set, edc_quorum_verify; not an
         API of the reference). verifiers: one batch.Verifier per commit, holding an item for EVERY
         validator of its set (any bytes for an absent one); powers / flags: one list per verifier, one
@@ -1728,7 +1833,10 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         only until the threshold is passed (VerifyCommitLight), False every vote that carries a
         signature (VerifyCommit). Returns (commit verdicts, tallies, item codes per verifier): a
         verdict is EDC_OK, EDC_INVALID_SIGNATURE or EDC_QUORUM_SHORT, an item code Item::verify_single's
-        or NOT_CHECKED. z_seed as verify_many."""
+        or NOT_CHECKED. z_seed as verify_many. cached=True goes through the engine's verified-signature
+        table (Engine.sigcache_create; edc_cached_quorum_verify): checked votes that already verified
+        on the engine are not verified again and count as EDC_OK, and what this call proves valid is
+        remembered. The return value has the same form."""
         verifiers = list(verifiers)
         for v in verifiers:
             if not isinstance(v, batch.Verifier):
@@ -1754,8 +1862,9 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         sigs = [x for v in verifiers for x in v._sigs]
         msgs = [x for v in verifiers for x in v._msgs]
         pw, fl = [x for p in powers for x in p], [x for f in flags for x in f]
+        run = eng.quorum_verify_cached if cached else eng.quorum_verify
         if all(m is not None for m in msgs):
-            res = eng.quorum_verify(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, msgs=msgs)
+            res = run(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, msgs=msgs)
         else:                                    # some items carry only their k: hash the rest in one launch
             ks = [x for v in verifiers for x in v._ks]
             need = [i for i, k in enumerate(ks) if k is None]
@@ -1763,7 +1872,7 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
                 for i, k in zip(need, eng.challenge([vks[i] for i in need], [sigs[i] for i in need],
                                                     [msgs[i] for i in need])):
                     ks[i] = k
-            res = eng.quorum_verify(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, ks=ks)
+            res = run(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, ks=ks)
         codes = [res["item_verdicts"][off[c]:off[c + 1]] for c in range(len(verifiers))]
         return res["commit_verdicts"], res["tally"], codes
 

@@ -267,6 +267,15 @@ struct edc_ctx {
   PinnedBuf<uint64_t> tq_harena;
   uint64_t tq_last[4] = {};
   bool tq_have = false;
+  // cached quorum commit sets (edc_cached_*): the masked lookup's leave-out bytes and base codes,
+  // its workgroup counts (misses + total, then hits + total), and for the templated forms, whose
+  // first staging area holds the gathered checked list, the second one (miss positions in that
+  // list, the misses' vk | sig | k); the host copy edc_debug_cached_quorum_last returns
+  size_t cq_cap_n = 0, cq_cap_g = 0;
+  DevBuf<uint8_t> cq_leave, cq_code, cq_g;
+  DevBuf<uint32_t> cq_wg, cq_idx;
+  uint64_t cq_last[6] = {};
+  bool cq_have = false;
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -3569,7 +3578,8 @@ static int ensure_quorum(edc_ctx* ctx, size_t n, size_t nc) {
                      sized(ctx->q_aggf, tiles), sized(ctx->q_carry, tiles));
   }));
   if (!ctx->q_err) CK(ctx->q_err.alloc(1));
-  if (!ctx->q_h) CK(ctx->q_h.alloc(4));    // flag, checked count, checked hole bytes (templated form)
+  // flag, checked count, checked hole bytes (templated form), checked misses and hits (cached forms)
+  if (!ctx->q_h) CK(ctx->q_h.alloc(6));
   return 0;
 }
 
@@ -3602,10 +3612,11 @@ static int quorum_check_votes(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
 // counts on device-resident power / flag. *n_checked = the size of the gathered list. A vote the
 // device checks refuse is EDC_ERR_ARG here, before anything is gathered or verified.
 // behind: what a templated form enqueues behind the selection, in front of the one read-back (its
-// all-n checks raise q_err too, bit 1 for the holes).
+// all-n checks raise q_err too, bit 1 for the holes; behind_alt: it checks variant bytes), or a
+// cached plain form (the masked lookup, whose counts travel in the same read-back).
 static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                              int mode, const uint64_t* d_power, const uint8_t* d_flag, size_t* n_checked,
-                             const std::function<int(hipStream_t)>* behind = nullptr) {
+                             const std::function<int(hipStream_t)>* behind = nullptr, bool behind_alt = true) {
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
   hipStream_t st = ctx->st();
@@ -3630,7 +3641,7 @@ static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* 
     ctx->err = "templated items: hole offsets out of range";
     return EDC_ERR_ARG;
   }
-  if (ctx->q_h[0] && behind) {
+  if (ctx->q_h[0] && behind && behind_alt) {
     ctx->err = "votes: a flag above 2, a power or a commit's counted power above 2^63 - 1, or an item_alt[i] >= alt_span";
     return EDC_ERR_ARG;
   }
@@ -3651,9 +3662,24 @@ struct QuorumOut {
   uint8_t* check8;
 };
 
+// What a cached form (edc_cached_*) adds to quorum_finish. The list it hands over holds the checked
+// MISSES of a looked-up list of n_mid items: all n items in the plain forms, the gathered checked
+// votes in the templated ones. codes: the lookup's base codes of those n_mid items (device; 255 not
+// checked, else 0), mid_idx: their queue positions (null: they are the n items). o_*: the
+// looked-up list's arrays, which quorum_finish's idx indexes; the insert reads them.
+struct QuorumCached {
+  size_t n_checked, n_mid;
+  uint8_t* codes;
+  const uint32_t* mid_idx;
+  const uint8_t *o_vk, *o_sig;
+  const uint32_t* o_k;
+  size_t* n_miss;
+};
+
 static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, size_t m, const uint8_t* b_vk,
                          const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx, const uint64_t* d_power,
-                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out);
+                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
+                         const QuorumCached* cq = nullptr);
 
 // A checked quorum commit set whose items (vk, sig, k, power, flag) are on the device.
 static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode, size_t n,
@@ -3682,13 +3708,25 @@ static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
 
 // The gathered list (m items in queue order; idx their queue positions, null when m == n or m == 0)
 // through the batch and its fallback, then the tally and the verdicts of all n items / nc commits.
+// cq (a cached form): the list is the checked misses; what it proves valid is inserted (every miss
+// after a passing union, the misses with code 0 after a failed one) before the last
+// synchronization, and a failed union's codes go back over the lookup's base codes, through the
+// list's positions in the looked-up list and that list's positions in the queue.
 static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, size_t m, const uint8_t* b_vk,
                          const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx, const uint64_t* d_power,
-                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out) {
+                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out, const QuorumCached* cq) {
   hipStream_t st = ctx->st();
   std::vector<uint8_t> mv(m ? m : 1);
   const int code = batch_with_fallback(ctx, m, b_vk, b_sig, nullptr, nullptr, b_k, z_seed, mv.data(), nullptr, out.check8);
   if (code < 0) return code;
+  const unsigned long long ins0 = cq ? ctx->sc_hctr[0] : 0;
+  if (cq && m) {
+    if (code != EDC_OK) CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
+    launch_sc_insert(st, ctx->sc(), (uint32_t)m, idx, cq->o_vk, cq->o_sig, cq->o_k,
+                     code == EDC_OK ? nullptr : ctx->sc_mverd.get(), ctx->sc_ctr);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(ctx->sc_hctr, ctx->sc_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  }
   std::vector<uint64_t> tal(nc);
   std::vector<uint32_t> cor32;
   std::vector<uint8_t> cor;
@@ -3700,11 +3738,23 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
       for (size_t i = 0; i < n; ++i) out.item_verdicts[i] = out.item_verdicts[i] ? QUORUM_NOT_CHECKED : 0;
   } else {                              // m > 0: codes back to queue order, then the tally kernel
     const uint8_t* d_codes = ctx->sc_mverd;
-    CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
-    if (idx) {
-      CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
-      launch_sc_scatter(st, (uint32_t)m, idx, ctx->sc_mverd, ctx->sc_verd);
-      d_codes = ctx->sc_verd;
+    if (!cq) {
+      CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
+      if (idx) {
+        CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
+        launch_sc_scatter(st, (uint32_t)m, idx, ctx->sc_mverd, ctx->sc_verd);
+        d_codes = ctx->sc_verd;
+      }
+    } else {                            // sc_mverd holds the misses' codes already
+      if (idx) {                        // hits keep the base code 0
+        launch_sc_scatter(st, (uint32_t)m, idx, ctx->sc_mverd, cq->codes);
+        d_codes = cq->codes;
+      }
+      if (cq->mid_idx) {
+        CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
+        launch_sc_scatter(st, (uint32_t)cq->n_mid, cq->mid_idx, d_codes, ctx->sc_verd);
+        d_codes = ctx->sc_verd;
+      }
     }
     CK(hipMemsetAsync(ctx->q_tally, 0, nc * sizeof(uint64_t), st));
     CK(hipMemsetAsync(ctx->q_cor, 0, nc * sizeof(uint32_t), st));
@@ -3722,7 +3772,12 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
   const int res = quorum_reduce(nc, cor.empty() ? nullptr : cor.data(), tal.data(), threshold, out.commit_verdicts, &bad);
   if (out.tally) memcpy(out.tally, tal.data(), nc * sizeof(uint64_t));
   if (out.n_bad_commits) *out.n_bad_commits = (int)bad;
-  if (out.n_checked) *out.n_checked = m;
+  if (out.n_checked) *out.n_checked = cq ? cq->n_checked : m;
+  if (cq) {
+    if (cq->n_miss) *cq->n_miss = m;
+    ctx->cq_last[3] = m;
+    ctx->cq_last[5] = ctx->sc_hctr[0] - ins0;
+  }
   return res;
 }
 
@@ -3741,6 +3796,38 @@ static int quorum_stage_votes(edc_ctx* ctx, size_t n, size_t nc, const uint64_t*
   CK(hipMemcpyAsync(ctx->q_flag, flag, n, hipMemcpyHostToDevice, ctx->st()));
   return 0;
 }
+
+// The device form's host checks, then k: the caller's, or Item::from for every item, skipped votes
+// included (as sc_batch), into kbuf. Shared with edc_cached_quorum_verify_device.
+static int quorum_device_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off, const uint8_t* d_k,
+                                const uint64_t* d_power, const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                                size_t* n_out, const uint32_t** k_out) {
+  size_t n;
+  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
+  if (rc) return rc;
+  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off) || !d_power || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)) || ((uintptr_t)d_power & 7u))) {
+    ctx->err = "device vk / sig / k arrays must be 16-byte aligned, d_power 8-byte aligned";
+    return EDC_ERR_ARG;
+  }
+  CK(hipSetDevice(ctx->device));
+  const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
+  if (n && !k) {
+    if ((rc = init_slot(ctx, ctx->slot[0])) || (rc = ensure_n(ctx, n))) return rc;
+    launch_challenge(ctx->st(), (uint32_t)n, d_vk, d_sig, d_msg, d_msg_off, ctx->kbuf);
+    CK(hipGetLastError());
+    k = ctx->kbuf;
+  }
+  *n_out = n;
+  *k_out = k;
+  return 0;
+}
+
+static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                              const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                              const uint8_t* k, const uint64_t* power, const uint8_t* flag, const uint64_t* threshold,
+                              int mode, size_t* n_out);
 
 extern "C" {
 
@@ -3777,21 +3864,10 @@ int edc_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
   const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
   if (!nc) return quorum_none(out);
   size_t n;
-  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
+  const uint32_t* k;
+  int rc = quorum_device_inputs(ctx, nc, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k, d_power, d_flag, threshold, mode,
+                                &n, &k);
   if (rc) return rc;
-  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off) || !d_power || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)) || ((uintptr_t)d_power & 7u))) {
-    ctx->err = "device vk / sig / k arrays must be 16-byte aligned, d_power 8-byte aligned";
-    return EDC_ERR_ARG;
-  }
-  CK(hipSetDevice(ctx->device));
-  const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
-  if (n && !k) {            // Item::from for every item, skipped votes included (as sc_batch)
-    if ((rc = init_slot(ctx, ctx->slot[0])) || (rc = ensure_n(ctx, n))) return rc;
-    launch_challenge(ctx->st(), (uint32_t)n, d_vk, d_sig, d_msg, d_msg_off, ctx->kbuf);
-    CK(hipGetLastError());
-    k = ctx->kbuf;
-  }
   return quorum_run(ctx, nc, commit_off, threshold, mode, n, d_vk, d_sig, k, d_power, d_flag, z_seed, out);
 }
 
@@ -3803,6 +3879,21 @@ int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
   if (!ctx || !z_seed) return EDC_ERR_ARG;
   const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
   if (!nc) return quorum_none(out);
+  size_t n;
+  int rc = quorum_host_inputs(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, power, flag, threshold, mode, &n);
+  if (rc) return rc;
+  return quorum_run(ctx, nc, commit_off, threshold, mode, n, ctx->vk, ctx->sig, ctx->kbuf, ctx->q_power, ctx->q_flag,
+                    z_seed, out);
+}
+
+}  // extern "C"
+
+// The host form's checks and staging (keys, signatures, power, flag; k copied or hashed into kbuf,
+// all on slot 0's stream). Shared with edc_cached_quorum_verify.
+static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                              const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                              const uint8_t* k, const uint64_t* power, const uint8_t* flag, const uint64_t* threshold,
+                              int mode, size_t* n_out) {
   size_t n;
   int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
   if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
@@ -3849,9 +3940,11 @@ int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
       CK(hipGetLastError());
     }
   }
-  return quorum_run(ctx, nc, commit_off, threshold, mode, n, ctx->vk, ctx->sig, ctx->kbuf, ctx->q_power, ctx->q_flag,
-                    z_seed, out);
+  *n_out = n;
+  return 0;
 }
+
+extern "C" {
 
 int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power,
                             const uint8_t* flag, const uint64_t* threshold, int mode, int reps, float* ms) {
@@ -3895,6 +3988,8 @@ int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
 // template indices, holes) in queue order, the expansion and SHA-512 run on those m items into an
 // arena sized from m, and quorum_finish does what it does for every quorum form. m == n: nothing is
 // gathered, the caller's arrays are the list. All on slot 0.
+// The cached forms (edc_cached_tmpl_quorum_*, cached = true) look the hashed list up before the
+// batch: see cached_tmpl_finish below.
 struct TmplQuorumItems {       // device arrays of all n items
   const uint8_t *vk, *sig, *item_alt, *var;
   const uint32_t* var_off;
@@ -3903,10 +3998,15 @@ struct TmplQuorumItems {       // device arrays of all n items
   const uint8_t* flag;
 };
 
+static int cached_tmpl_finish(edc_ctx* ctx, TmplWs& w, size_t nc, const uint64_t* threshold, size_t n, size_t m,
+                              const uint8_t* b_vk, const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx,
+                              const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
+                              size_t* n_miss);
+
 static int tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
                            const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span, size_t n,
                            const TmplQuorumItems& it, const uint64_t* threshold, int mode, const uint8_t* z_seed,
-                           const QuorumOut& out) {
+                           const QuorumOut& out, bool cached = false, size_t* n_miss = nullptr) {
   Slot& s = ctx->slot[0];
   TmplWs& w = s.tw;
   int rc = init_slot(ctx, s);
@@ -3978,11 +4078,38 @@ static int tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShap
     b_k = ctx->kbuf;
     ctx->tq_last[2] = m;
   }
-  rc = quorum_finish(ctx, nc, threshold, n, m, b_vk, b_sig, b_k, idx, it.power, it.flag, z_seed, out);
+  if (cached)
+    rc = cached_tmpl_finish(ctx, w, nc, threshold, n, m, b_vk, b_sig, b_k, idx, it.power, it.flag, z_seed, out, n_miss);
+  else
+    rc = quorum_finish(ctx, nc, threshold, n, m, b_vk, b_sig, b_k, idx, it.power, it.flag, z_seed, out);
   w.check = false;              // also when the batch never reached its wait
   if (rc >= 0) ctx->tq_last[3] = *ctx->tq_harena;
   return rc;
 }
+
+// The device form's host checks, shared with edc_cached_tmpl_quorum_verify_device.
+static int tmpl_quorum_device_inputs(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                     const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                     const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                     const uint32_t* d_var_off, size_t var_bytes, const uint64_t* d_power,
+                                     const uint8_t* d_flag, const uint64_t* threshold, int mode, TmplShape* sh, size_t* n,
+                                     TmplQuorumItems* it) {
+  int rc = commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
+                                     var_bytes, sh, n);
+  if (rc || (rc = quorum_check(ctx, nc, commit_off, threshold, mode, n))) return rc;
+  if (*n && (!d_power || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (*n && ((uintptr_t)d_power & 7u)) { ctx->err = "d_power must be 8-byte aligned"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  *it = TmplQuorumItems{d_vk, d_sig, d_item_alt, d_var, d_var_off, var_bytes, d_power, d_flag};
+  return 0;
+}
+
+static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                   const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
+                                   const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var,
+                                   const uint32_t* var_off, const uint64_t* power, const uint8_t* flag,
+                                   const uint64_t* threshold, int mode, TmplShape* sh_out, size_t* n_out,
+                                   TmplQuorumItems* it_out);
 
 extern "C" {
 
@@ -3998,13 +4125,10 @@ int edc_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t 
   if (!nc) return quorum_none(out);
   TmplShape sh;
   size_t n;
-  int rc = commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
-                                     var_bytes, &sh, &n);
-  if (rc || (rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n))) return rc;
-  if (n && (!d_power || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  if (n && ((uintptr_t)d_power & 7u)) { ctx->err = "d_power must be 8-byte aligned"; return EDC_ERR_ARG; }
-  CK(hipSetDevice(ctx->device));
-  const TmplQuorumItems it{d_vk, d_sig, d_item_alt, d_var, d_var_off, var_bytes, d_power, d_flag};
+  TmplQuorumItems it;
+  int rc = tmpl_quorum_device_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                     d_var_off, var_bytes, d_power, d_flag, threshold, mode, &sh, &n, &it);
+  if (rc) return rc;
   return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
 }
 
@@ -4017,6 +4141,24 @@ int edc_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, con
   if (!ctx || !z_seed) return EDC_ERR_ARG;
   const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
   if (!nc) return quorum_none(out);
+  TmplShape sh;
+  size_t n;
+  TmplQuorumItems it;
+  int rc = tmpl_quorum_host_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
+                                   power, flag, threshold, mode, &sh, &n, &it);
+  if (rc) return rc;
+  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
+}
+
+}  // extern "C"
+
+// The host form's checks and staging, shared with edc_cached_tmpl_quorum_verify.
+static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                   const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
+                                   const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var,
+                                   const uint32_t* var_off, const uint64_t* power, const uint8_t* flag,
+                                   const uint64_t* threshold, int mode, TmplShape* sh_out, size_t* n_out,
+                                   TmplQuorumItems* it_out) {
   TmplShape sh;
   size_t n;
   int rc = commits_check_tmpl_alt(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
@@ -4048,12 +4190,245 @@ int edc_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, con
     it.var_off = reinterpret_cast<const uint32_t*>(ctx->tq_in.get());
     it.var_bytes = var_bytes;
   }
-  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
+  *sh_out = sh;
+  *n_out = n;
+  *it_out = it;
+  return 0;
 }
+
+extern "C" {
 
 int edc_debug_tmpl_quorum_last(const edc_ctx* ctx, uint64_t out[4]) {
   if (!ctx || !out || !ctx->tq_have) return EDC_ERR_ARG;
   memcpy(out, ctx->tq_last, sizeof(ctx->tq_last));
+  return EDC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- cached quorum commit sets
+// edc_cached_*: the quorum entries with the verified-signature table between the selection and the
+// batch. The selection never looks at the table. k_sc_lookup_masked probes the checked items only
+// and leaves a second leave-out byte per item (not checked, or a hit), so ONE compaction takes the
+// checked misses straight from the n-item arrays into the staging area, and quorum_finish runs the
+// batch on them, inserts what it proves valid and puts the codes back over the lookup's base codes
+// (255 not checked, 0 otherwise: a hit ends as 0 with no pass of its own).
+// Plain forms: k exists for all n items before the selection, so the lookup rides behind it and
+// its counts come back in the selection's one read-back. Templated forms: k exists only for the m
+// votes that were gathered and hashed after that read-back, so the lookup runs on the m-item list
+// and the miss count needs a second read-back; the misses are compacted into a second staging area
+// (the first still holds the gathered list, which the insert and the code scatter index).
+static int ensure_cq(edc_ctx* ctx, size_t n) {
+  CK(grow_group(ctx->cq_cap_n, n ? n : 1, item_cap, sync_of(ctx->st()), [&](size_t cap) {
+    return alloc_all(sized(ctx->cq_leave, cap), sized(ctx->cq_code, cap),
+                     sized(ctx->cq_wg, 2 * (cap / SC_BLOCK + 2)));    // misses + total, hits + total
+  }));
+  return 0;
+}
+
+// preconditions of every cached quorum entry beyond the uncached form's own
+static int cq_ready(edc_ctx* ctx) {
+  if (!ctx->sc_cap) { ctx->err = "no signature cache on this context (edc_sigcache_create)"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+// The lookup of a list of `count` items (skip: the selection's bytes, null: every item is checked)
+// and the scans of its workgroup counts; the miss and hit totals travel to q_h[3] / q_h[4].
+static int cq_lookup(edc_ctx* ctx, hipStream_t st, size_t count, const uint8_t* skip, const uint8_t* vk,
+                     const uint8_t* sig, const uint32_t* k) {
+  int rc = ensure_cq(ctx, count);
+  if (rc) return rc;
+  const uint32_t nwg = (uint32_t)((count + SC_BLOCK - 1) / SC_BLOCK);
+  uint32_t *wm = ctx->cq_wg, *wh = ctx->cq_wg + nwg + 1;
+  launch_sc_lookup_masked(st, ctx->sc(), (uint32_t)count, skip, vk, sig, k, ctx->cq_leave, ctx->cq_code, wm, wh);
+  launch_sc_scan(st, nwg, wm, wm + nwg);
+  launch_sc_scan(st, nwg, wh, wh + nwg);
+  CK(hipGetLastError());
+  ctx->q_h[3] = ctx->q_h[4] = 0;
+  CK(hipMemcpyAsync(&ctx->q_h[3], wm + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(&ctx->q_h[4], wh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  return 0;
+}
+
+// the counts of a lookup that has been read back: the statistics and the debug record
+static int cq_counts(edc_ctx* ctx, size_t n, size_t m, size_t hashed, size_t* miss) {
+  const size_t c = m ? ctx->q_h[3] : 0, h = m ? ctx->q_h[4] : 0;
+  if (c + h != m) { ctx->err = "cached quorum: hits and misses do not add up to the checked count"; return EDC_ERR_HIP; }
+  ctx->sc_hits += h;
+  ctx->sc_misses += c;
+  ctx->cq_have = true;
+  ctx->cq_last[0] = n;
+  ctx->cq_last[1] = m;
+  ctx->cq_last[2] = h;
+  ctx->cq_last[3] = c;
+  ctx->cq_last[4] = hashed;
+  ctx->cq_last[5] = 0;
+  *miss = c;
+  return 0;
+}
+
+// A checked cached quorum commit set whose items (vk, sig, k, power, flag) are on the device;
+// hashed: the items SHA-512 ran over for this call.
+static int cached_quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
+                             size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint32_t* d_k,
+                             const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
+                             size_t* n_miss, size_t hashed) {
+  const std::function<int(hipStream_t)> behind = [&](hipStream_t q) -> int {
+    return cq_lookup(ctx, q, n, ctx->sc_hit, d_vk, d_sig, d_k);
+  };
+  size_t m = 0, c = 0;
+  int rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag, &m, &behind, false);
+  if (rc || (rc = cq_counts(ctx, n, m, hashed, &c))) return rc;
+  hipStream_t st = ctx->st();
+  const uint8_t *b_vk = d_vk, *b_sig = d_sig;
+  // an empty list still runs the n = 0 batch, whose k is never read
+  const uint32_t *b_k = c ? d_k : reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), *idx = nullptr;
+  if (c && c < n) {
+    uint8_t* g_vk = ctx->sc_g;
+    uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
+    uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->sc_cap_n * 64);
+    launch_sc_compact(st, (uint32_t)n, ctx->cq_leave, ctx->cq_wg, d_vk, d_sig, d_k, ctx->sc_idx, g_vk, g_sig, g_k);
+    CK(hipGetLastError());
+    idx = ctx->sc_idx;
+    b_vk = g_vk;
+    b_sig = g_sig;
+    b_k = g_k;
+  }
+  const QuorumCached cq{m, n, ctx->cq_code, nullptr, d_vk, d_sig, d_k, n_miss};
+  return quorum_finish(ctx, nc, threshold, n, c, b_vk, b_sig, b_k, idx, d_power, d_flag, z_seed, out, &cq);
+}
+
+// tmpl_quorum_run's last step in a cached form: the m checked votes (b_*: gathered, or the caller's
+// arrays when m == n; idx: their queue positions) have their k in kbuf.
+static int cached_tmpl_finish(edc_ctx* ctx, TmplWs& w, size_t nc, const uint64_t* threshold, size_t n, size_t m,
+                              const uint8_t* b_vk, const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx,
+                              const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
+                              size_t* n_miss) {
+  hipStream_t st = ctx->st();
+  int rc;
+  if (m) {
+    if ((rc = cq_lookup(ctx, st, m, nullptr, b_vk, b_sig, b_k))) return rc;
+    CK(hipStreamSynchronize(st));       // the second read-back: the miss count sizes the batch
+    if (*w.h_flag) {                    // what the batch's wait would find, before anything is counted
+      ctx->err = "templated items: template index or hole offsets out of range";
+      return EDC_ERR_ARG;
+    }
+  }
+  size_t c = 0;
+  if ((rc = cq_counts(ctx, n, m, m, &c))) return rc;
+  const uint8_t *l_vk = b_vk, *l_sig = b_sig;
+  const uint32_t *l_k = b_k, *lidx = nullptr;
+  if (c && c < m) {
+    CK(grow_group(ctx->cq_cap_g, m, item_cap, sync_of(st), [&](size_t cap) {
+      return alloc_all(sized(ctx->cq_g, cap * 128), sized(ctx->cq_idx, cap));
+    }));
+    uint8_t* g_vk = ctx->cq_g;
+    uint8_t* g_sig = g_vk + ctx->cq_cap_g * 32;
+    uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->cq_cap_g * 64);
+    launch_sc_compact(st, (uint32_t)m, ctx->cq_leave, ctx->cq_wg, b_vk, b_sig, b_k, ctx->cq_idx, g_vk, g_sig, g_k);
+    CK(hipGetLastError());
+    lidx = ctx->cq_idx;
+    l_vk = g_vk;
+    l_sig = g_sig;
+    l_k = g_k;
+  }
+  const QuorumCached cq{m, m, ctx->cq_code, idx, b_vk, b_sig, b_k, n_miss};
+  return quorum_finish(ctx, nc, threshold, n, c, l_vk, l_sig, l_k, lidx, d_power, d_flag, z_seed, out, &cq);
+}
+
+// nc == 0: nothing to verify
+static int cached_quorum_none(const QuorumOut& out, size_t* n_miss) {
+  if (n_miss) *n_miss = 0;
+  return quorum_none(out);
+}
+
+extern "C" {
+
+int edc_cached_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                    const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                    const uint8_t* d_k, const uint64_t* d_power, const uint8_t* d_flag,
+                                    const uint64_t* threshold, int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts,
+                                    uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits, size_t* n_checked,
+                                    size_t* n_miss, uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  int rc = cq_ready(ctx);
+  if (rc) return rc;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return cached_quorum_none(out, n_miss);
+  size_t n;
+  const uint32_t* k;
+  if ((rc = quorum_device_inputs(ctx, nc, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k, d_power, d_flag, threshold, mode,
+                                 &n, &k)))
+    return rc;
+  return cached_quorum_run(ctx, nc, commit_off, threshold, mode, n, d_vk, d_sig, k, d_power, d_flag, z_seed, out, n_miss,
+                           d_k ? 0 : n);
+}
+
+int edc_cached_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                             const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                             const uint8_t* k, const uint64_t* power, const uint8_t* flag, const uint64_t* threshold,
+                             int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                             uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss, uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  int rc = cq_ready(ctx);
+  if (rc) return rc;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return cached_quorum_none(out, n_miss);
+  size_t n;
+  if ((rc = quorum_host_inputs(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, power, flag, threshold, mode, &n)))
+    return rc;
+  return cached_quorum_run(ctx, nc, commit_off, threshold, mode, n, ctx->vk, ctx->sig, ctx->kbuf, ctx->q_power,
+                           ctx->q_flag, z_seed, out, n_miss, k ? 0 : n);
+}
+
+int edc_cached_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                         const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                         const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                         const uint32_t* d_var_off, size_t var_bytes, const uint64_t* d_power,
+                                         const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                                         const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                                         uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss,
+                                         uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  int rc = cq_ready(ctx);
+  if (rc) return rc;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return cached_quorum_none(out, n_miss);
+  TmplShape sh;
+  size_t n;
+  TmplQuorumItems it;
+  if ((rc = tmpl_quorum_device_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                      d_var_off, var_bytes, d_power, d_flag, threshold, mode, &sh, &n, &it)))
+    return rc;
+  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out, true,
+                         n_miss);
+}
+
+int edc_cached_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, const uint8_t* vk,
+                                  const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                                  const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
+                                  const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                                  uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss,
+                                  uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  int rc = cq_ready(ctx);
+  if (rc) return rc;
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
+  if (!nc) return cached_quorum_none(out, n_miss);
+  TmplShape sh;
+  size_t n;
+  TmplQuorumItems it;
+  if ((rc = tmpl_quorum_host_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var,
+                                    var_off, power, flag, threshold, mode, &sh, &n, &it)))
+    return rc;
+  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out, true,
+                         n_miss);
+}
+
+int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
+  if (!ctx || !out || !ctx->cq_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->cq_last, sizeof(ctx->cq_last));
   return EDC_OK;
 }
 

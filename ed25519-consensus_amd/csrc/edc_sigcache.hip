@@ -1,7 +1,7 @@
 // Verified-signature cache kernels (sigcache.h): lookup, order-preserving compaction of the
 // misses (per-workgroup ballot counts, scan, scatter + gather; for a cached verifier's queued
 // range, gather into the retained arrays at an offset with the offered positions), insert, verdict
-// scatter.
+// scatter; the masked lookup of the cached quorum commit sets, which probes the checked items only.
 // One lane per item; items and records move as uint4.
 #include "sigcache.h"
 
@@ -67,6 +67,19 @@ __device__ __forceinline__ bool sc_equal(const uint4* __restrict__ r, const uint
   return eq;
 }
 
+// the probe behind every lookup: is the loaded item q a live record?
+__device__ __forceinline__ bool sc_probe(const SigCacheView& sc, const uint4 q[8]) {
+  const uint64_t h = sc_hash(q, sc.k0, sc.k1);
+  const uint32_t fp = (uint32_t)(h >> 32), home = (uint32_t)h & sc.mask;
+  for (uint32_t p = 0; p < SC_WINDOW; ++p) {
+    const uint32_t slot = sc_slot(home, p);
+    const unsigned long long hd = sc.hdr[slot];
+    if (hd == 0) break;       // never used: nothing of this item's probe order lies beyond
+    if ((uint32_t)(hd >> 32) == fp && sc_live(sc, hd) && sc_equal(sc.rec + (size_t)slot * 8, q)) return true;
+  }
+  return false;
+}
+
 __global__ void __launch_bounds__(SC_BLOCK) k_sc_lookup(SigCacheView sc, uint32_t n, const uint8_t* __restrict__ vk,
                                                         const uint8_t* __restrict__ sig,
                                                         const uint32_t* __restrict__ k, uint8_t* __restrict__ hit,
@@ -76,18 +89,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_lookup(SigCacheView sc, uint32_
   if (i < n) {
     uint4 q[8];
     sc_load_item(vk, sig, k, i, q);
-    const uint64_t h = sc_hash(q, sc.k0, sc.k1);
-    const uint32_t fp = (uint32_t)(h >> 32), home = (uint32_t)h & sc.mask;
-    bool found = false;
-    for (uint32_t p = 0; p < SC_WINDOW; ++p) {
-      const uint32_t slot = sc_slot(home, p);
-      const unsigned long long hd = sc.hdr[slot];
-      if (hd == 0) break;     // never used: nothing of this item's probe order lies beyond
-      if ((uint32_t)(hd >> 32) == fp && sc_live(sc, hd) && sc_equal(sc.rec + (size_t)slot * 8, q)) {
-        found = true;
-        break;
-      }
-    }
+    const bool found = sc_probe(sc, q);
     hit[i] = found ? 1 : 0;
     miss = !found;
   }
@@ -101,6 +103,46 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_lookup(SigCacheView sc, uint32_
       for (uint32_t w = 0; w < SC_BLOCK / 64; ++w) s += wsum[w];
       wg_miss[blockIdx.x] = s;
     }
+  }
+}
+
+// Cached quorum commit sets (edc_cached_*): the lookup of the checked items only. skip[i] != 0
+// (skip null: no item is left out) marks an item the selection did not check: its lane touches
+// neither the item's bytes nor the table. leave[i] = 1 for an item that is not checked or is a
+// live record, else 0 (the byte k_sc_compact reads: what stays is the checked misses, in queue
+// order); code[i] = 255 for an item that is not checked, else 0 (the codes of a failed union's
+// misses are scattered over it, so hits end as 0); the workgroup's misses and hits among the
+// checked. One LDS word per wave as in the kernels around it: both counts are at most 64 and
+// share the word (misses low half, hits high half).
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_lookup_masked(SigCacheView sc, uint32_t n,
+                                                               const uint8_t* __restrict__ skip,
+                                                               const uint8_t* __restrict__ vk,
+                                                               const uint8_t* __restrict__ sig,
+                                                               const uint32_t* __restrict__ k,
+                                                               uint8_t* __restrict__ leave, uint8_t* __restrict__ code,
+                                                               uint32_t* __restrict__ wg_miss,
+                                                               uint32_t* __restrict__ wg_hit) {
+  __shared__ uint32_t wsum[SC_BLOCK / 64];
+  const uint32_t i = blockIdx.x * SC_BLOCK + threadIdx.x;
+  const bool checked = i < n && (!skip || skip[i] == 0);
+  bool found = false;
+  if (checked) {
+    uint4 q[8];
+    sc_load_item(vk, sig, k, i, q);
+    found = sc_probe(sc, q);
+  }
+  if (i < n) {
+    leave[i] = (!checked || found) ? 1 : 0;
+    code[i] = checked ? 0 : 255;
+  }
+  const uint64_t bm = __ballot(checked && !found), bh = __ballot(checked && found);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(bm) | ((uint32_t)__popcll(bh) << 16);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (uint32_t w = 0; w < SC_BLOCK / 64; ++w) s += wsum[w];    // each half at most SC_BLOCK: no carry between them
+    wg_miss[blockIdx.x] = s & 0xFFFFu;
+    wg_hit[blockIdx.x] = s >> 16;
   }
 }
 
@@ -254,6 +296,14 @@ inline uint32_t sc_blocks(uint32_t n) { return (n + SC_BLOCK - 1) / SC_BLOCK; }
 void launch_sc_lookup(hipStream_t st, const SigCacheView& sc, uint32_t n, const uint8_t* vk, const uint8_t* sig,
                       const uint32_t* k, uint8_t* hit, uint32_t* wg_miss) {
   if (n) hipLaunchKernelGGL(k_sc_lookup, dim3(sc_blocks(n)), dim3(SC_BLOCK), 0, st, sc, n, vk, sig, k, hit, wg_miss);
+}
+
+void launch_sc_lookup_masked(hipStream_t st, const SigCacheView& sc, uint32_t n, const uint8_t* skip, const uint8_t* vk,
+                             const uint8_t* sig, const uint32_t* k, uint8_t* leave, uint8_t* code, uint32_t* wg_miss,
+                             uint32_t* wg_hit) {
+  if (n)
+    hipLaunchKernelGGL(k_sc_lookup_masked, dim3(sc_blocks(n)), dim3(SC_BLOCK), 0, st, sc, n, skip, vk, sig, k, leave, code,
+                       wg_miss, wg_hit);
 }
 
 void launch_sc_scan(hipStream_t st, uint32_t nwg, uint32_t* wg_miss, uint32_t* total) {

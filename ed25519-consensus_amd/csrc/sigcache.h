@@ -49,6 +49,13 @@ struct SigCacheView {
 // hit[i] = 1 iff item i is a live record. wg_miss (nullable): misses of each workgroup of SC_BLOCK items.
 void launch_sc_lookup(hipStream_t st, const SigCacheView& sc, uint32_t n, const uint8_t* vk, const uint8_t* sig,
                       const uint32_t* k, uint8_t* hit, uint32_t* wg_miss);
+// cached quorum commit sets: the lookup of the items with skip[i] == 0 only (skip null: all n); no
+// other item's bytes are read and no table access is made for it. leave[i] = 1 iff item i is not
+// checked or is a live record (launch_sc_compact's `hit`), code[i] = 255 iff it is not checked,
+// else 0; wg_miss / wg_hit: the checked misses / hits of each workgroup of SC_BLOCK items
+void launch_sc_lookup_masked(hipStream_t st, const SigCacheView& sc, uint32_t n, const uint8_t* skip, const uint8_t* vk,
+                             const uint8_t* sig, const uint32_t* k, uint8_t* leave, uint8_t* code, uint32_t* wg_miss,
+                             uint32_t* wg_hit);
 // exclusive scan of the nwg workgroup counts in place; total[0] = their sum
 void launch_sc_scan(hipStream_t st, uint32_t nwg, uint32_t* wg_miss, uint32_t* total);
 // order-preserving compaction of the misses: idx[j] = queue index of miss j, its vk / sig / k

@@ -1136,6 +1136,113 @@ int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const ui
                              const uint64_t* msg_off, const uint8_t* k, uint8_t* verdicts, size_t* n_miss);
 
 /*
+ * Cached quorum commit sets: skip checked votes that already verified. The quorum entries and the
+ * verified-signature cache are meant for the same moment: a live node has verified almost every
+ * precommit of a block at gossip time (edc_sigcache_verify_each), and when the block's commit
+ * arrives it runs VerifyCommit or VerifyCommitLight over those same votes; the same holds for the
+ * next block's last-commit and for block sync. The motivating flow is CometBFT's
+ * VerifyCommitLightWithCache / VerifyCommitLightTrustingWithCache, named here from memory and not
+ * checked against a source tree. The reference crate has no such API and none of its APIs changes
+ * meaning: every vote that is verified is one batch::Item (src/batch.rs:76-94) in ONE
+ * batch::Verifier (queue + verify, src/batch.rs:127-137, :149-217), and its code is
+ * Item::verify_single's (src/batch.rs:104-107).
+ *
+ * Inputs and outputs mean exactly what they mean for edc_quorum_verify[_device] and
+ * edc_tmpl_quorum_verify[_device]. The one new output, size_t* n_miss (nullable), receives the size
+ * of the list that was actually verified.
+ *
+ * Contract.
+ * Selection. checked[i] and *n_checked are those of edc_quorum_plan for the same powers, flags,
+ *   thresholds and mode, whatever the table holds: the selection never looks at the table. A hit
+ *   still counts towards the running sum of light mode, as CometBFT's loop tallies a cached vote
+ *   like any other.
+ * Hit. A checked item that is a live record (a live header and 128 equal bytes, as
+ *   edc_sigcache_lookup_device defines it) is a hit. A hit is not verified, its code is EDC_OK, and
+ *   its power counts if its flag is 1. Items that are not checked are never looked up, never
+ *   interpreted and never inserted.
+ * Miss list. The checked misses, in queue order, form ONE batch; miss j draws z at index j of
+ *   z_seed's stream. The union verdict and check8 are bit-identical to
+ *   edc_batch_verify_prehashed_device on that list with z_base = 0, and if the union fails the
+ *   grouped fallback runs on that list. n_miss = 0 runs the n = 0 batch.
+ * Outputs. item_verdicts[i] is EDC_NOT_CHECKED (255) for an item that is not checked, 0 for a hit
+ *   and Item::verify_single's code for a miss. tally, commit_verdicts, *n_bad_commits and the return
+ *   value are derived from those codes exactly as the quorum section defines.
+ * Inserts. Exactly the misses whose code is EDC_OK are inserted: all misses when the union passes,
+ *   only the OK misses when it fails. Valid nil votes of full mode are inserted too. The insert
+ *   finishes before the call returns.
+ * Statistics. edc_sigcache_stats hits and misses grow by the lookups of the checked items only.
+ * Equality contract. With a table in which no checked item is a record, every output equals the
+ *   uncached entry's on the same inputs, check8 included, and n_miss == n_checked. With any table
+ *   whose records were planted by verification on this context, every output except check8 and
+ *   n_miss equals the uncached entry's.
+ * Errors. No table on the context returns EDC_ERR_ARG with nothing written. Every argument check
+ *   of the uncached forms applies, on the host for the host forms and on the device for the device
+ *   forms; for the templated forms this means all n items, not only the checked ones. A violation
+ *   returns EDC_ERR_ARG: no verdict is given, nothing is inserted, no counter changes, no index
+ *   outside the declared arrays is formed, and the context stays usable. A prehashed k must be
+ *   canonical for the checked items, as today. nc = 0 returns EDC_OK with no array read; a NULL ctx
+ *   or z_seed is EDC_ERR_ARG. The calls are synchronous on slot 0, and EDC_ERR_ARG while a batch is
+ *   pending there.
+ * Soundness of a cached quorum. A hit lends its voting power to a quorum on the strength of an
+ *   earlier verification on this context, one by one or inside a batch whose equation held: it
+ *   carries the probability that batch verification itself gives, no more. z_seed must be fresh and
+ *   secret for every call, because a passing call plants records: with a predictable seed, crafted
+ *   votes that cancel inside one batch would be planted and would lend their power to every later
+ *   quorum. The table is per context and never shared. In the prehashed forms the caller vouches
+ *   for k.
+ *
+ * Stream synchronizations. In the plain forms k exists for all n items before the selection, so the
+ *   masked lookup runs behind the selection and its miss and hit counts travel in the selection's
+ *   one read-back: edc_cached_quorum_verify_device adds no stream synchronization to what
+ *   edc_quorum_verify_device has. In the templated forms k exists only for the votes that were
+ *   gathered and hashed after that read-back, so the lookup runs on the checked list and the miss
+ *   count needs a SECOND read-back and stream synchronization before the batch can be planned.
+ *
+ * edc_cached_quorum_verify_device  edc_quorum_verify_device through the table (src/batch.rs:76-94,
+ *   :104-107, :127-137, :149-217).
+ * edc_cached_quorum_verify  edc_quorum_verify through the table (src/batch.rs:76-94, :104-107,
+ *   :127-137, :149-217).
+ * edc_cached_tmpl_quorum_verify_device  edc_tmpl_quorum_verify_device through the table
+ *   (src/batch.rs:76-94, :104-107, :127-137, :149-217): SHA-512 runs over the n_checked gathered
+ *   votes, the batch over the n_miss of them that are no records.
+ * edc_cached_tmpl_quorum_verify  edc_tmpl_quorum_verify through the table (src/batch.rs:76-94,
+ *   :104-107, :127-137, :149-217).
+ * edc_debug_cached_quorum_last  test hook, a host copy (no device work): out = {n, n_checked, the
+ *   hits among the checked, n_miss, the items SHA-512 ran over, the records the call inserted} of
+ *   the last cached quorum call on the context that reached its selection. EDC_ERR_ARG before any
+ *   such call and for NULL.
+ * Not built: asynchronous submit / wait forms, the incremental verifier and the multi-GPU engine
+ *   have no cached quorum entries.
+ */
+int edc_cached_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                    const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                    const uint8_t* d_k, const uint64_t* d_power, const uint8_t* d_flag,
+                                    const uint64_t* threshold, int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts,
+                                    uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits, size_t* n_checked,
+                                    size_t* n_miss, uint8_t check8[32]);
+int edc_cached_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                             const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                             const uint8_t* k, const uint64_t* power, const uint8_t* flag, const uint64_t* threshold,
+                             int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                             uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss, uint8_t check8[32]);
+int edc_cached_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                         const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                         const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                         const uint32_t* d_var_off, size_t var_bytes, const uint64_t* d_power,
+                                         const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                                         const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                                         uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss,
+                                         uint8_t check8[32]);
+int edc_cached_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, const uint8_t* vk,
+                                  const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                                  const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
+                                  const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                                  uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss,
+                                  uint8_t check8[32]);
+int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]);
+
+/*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
  * one batch::Verifier::verify (reference src/batch.rs:149-217) split into contiguous shards, one
  * per listed device (a device may be listed more than once: several contexts on one GPU). Shard g
