@@ -857,48 +857,90 @@ class Engine:
         self._check(rc)
         return list(checked.raw[:n]), list(planned[:nc]), cnt.value
 
-    def _quorum_out(self, nc, n):
-        return (ctypes.create_string_buffer(max(nc, 1)), ctypes.create_string_buffer(max(n, 1)),
-                (ctypes.c_uint64 * max(nc, 1))(), ctypes.c_int(0), ctypes.c_size_t(0), ctypes.create_string_buffer(32))
+    @staticmethod
+    def _quorum_thresholds(nc, thresholds):
+        thresholds = [int(x) for x in thresholds]
+        if len(thresholds) != nc:
+            raise ValueError("one threshold per commit")
+        return (ctypes.c_uint64 * max(nc, 1))(*thresholds)
 
     @staticmethod
-    def _quorum_result(rc, nc, n, out):
-        return {"code": rc, "commit_verdicts": list(out[0].raw[:nc]), "item_verdicts": list(out[1].raw[:n]),
-                "tally": list(out[2][:nc]), "n_bad_commits": out[3].value, "n_checked": out[4].value,
-                "check8": out[5].raw}
+    def _quorum_result(rc, nc, n, out, cached):
+        res = {"code": rc, "commit_verdicts": list(out[0].raw[:nc]), "item_verdicts": list(out[1].raw[:n]),
+               "tally": list(out[2][:nc]), "n_bad_commits": out[3].value, "n_checked": out[4].value,
+               "check8": out[6].raw}
+        if cached:
+            res["n_miss"] = out[5].value
+        return res
+
+    def _quorum_call(self, fn, cached, form, votes, z_seed, light):
+        """fn(ctx, *form's arguments, power, flag, threshold, mode, z_seed, <out-parameters>) -> the
+        result dict. form: (nc, n, the arguments, whatever they point into); votes: (power, flag,
+        threshold) as fn takes them. A cached fn has the miss out-parameter and its dict the n_miss key."""
+        nc, n, args = form[:3]
+        out = (ctypes.create_string_buffer(max(nc, 1)), ctypes.create_string_buffer(max(n, 1)),
+               (ctypes.c_uint64 * max(nc, 1))(), ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0),
+               ctypes.create_string_buffer(32))
+        counts = [ctypes.byref(x) for x in out[3:6 if cached else 5]]
+        with self._lock:
+            rc = fn(self.ctx, *args, *votes, int(bool(light)), bytes(z_seed), out[0], out[1], out[2], *counts, out[6])
+        self._check(rc)
+        return self._quorum_result(rc, nc, n, out, cached)
+
+    def _quorum_host(self, fn, cached, form, powers, flags, thresholds, z_seed, light):
+        """The host call shape: powers, flags and thresholds are sequences."""
+        return self._quorum_call(fn, cached, form, self._quorum_votes(form[1], form[0], powers, flags, thresholds), z_seed,
+                                 light)
+
+    def _quorum_device(self, fn, cached, form, d_power, d_flag, thresholds, z_seed, light):
+        """The device call shape: powers and flags are on the device, thresholds a sequence."""
+        votes = self._dev_ptr(d_power), self._dev_ptr(d_flag), self._quorum_thresholds(form[0], thresholds)
+        return self._quorum_call(fn, cached, form, votes, z_seed, light)
+
+    # the forms' own arguments, as _quorum_call takes them
+    def _quorum_host_form(self, commit_off, sigs, vks, key_idx, msgs, ks):
+        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
+        return nc, n, (nc,) + b
+
+    def _quorum_device_form(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k):
+        nc, off = self._commit_offsets(commit_off)
+        p = self._dev_ptr
+        return nc, off[nc] if nc else 0, (nc, off, p(d_vk), p(d_sig), p(d_msg), p(d_msg_off), p(d_k))
+
+    def _tmpl_quorum_host_form(self, templates, commit_off, commit_tpl, sigs, holes, alt_span, item_alt, vks, key_idx,
+                               var_off):
+        n = len(sigs)
+        nc, off = self._commit_offsets(commit_off)
+        ts, keep = templates.struct()
+        _, var, voff = _tmpl_items([0] * n, holes, var_off)
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        return nc, n, (ctypes.byref(ts), nc, off, ctpl, alt_span, self._item_alt(item_alt), vkb, idx,
+                       b"".join(sigs) or b"\0", var, voff), keep
+
+    def _tmpl_quorum_device_form(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
+                                 alt_span, d_item_alt):
+        nc, off = self._commit_offsets(commit_off)
+        ts, keep = templates.struct()
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        p = self._dev_ptr
+        return nc, off[nc] if nc else 0, (ctypes.byref(ts), nc, off, ctpl, alt_span, p(d_item_alt), p(d_vk), p(d_sig),
+                                          p(d_var), p(d_var_off), var_bytes), keep
 
     def quorum_verify(self, commit_off, sigs, powers, flags, thresholds, z_seed, light=True, vks=None, key_idx=None,
                       msgs=None, ks=None):
         """edc_quorum_verify: host buffers, synchronous. Exactly one of vks and key_idx, exactly one
         of msgs and ks, as commits_verify. Returns a dict: code, commit_verdicts, item_verdicts
         (NOT_CHECKED for the votes left out), tally, n_bad_commits, n_checked, check8."""
-        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
-        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
-        out = self._quorum_out(nc, n)
-        with self._lock:
-            rc = self.lib.edc_quorum_verify(self.ctx, nc, *b, pw, fl, th, int(bool(light)), bytes(z_seed), out[0],
-                                            out[1], out[2], ctypes.byref(out[3]), ctypes.byref(out[4]), out[5])
-        self._check(rc)
-        return self._quorum_result(rc, nc, n, out)
+        form = self._quorum_host_form(commit_off, sigs, vks, key_idx, msgs, ks)
+        return self._quorum_host(self.lib.edc_quorum_verify, False, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_power, d_flag, thresholds, z_seed,
                              light=True, d_k=None):
         """edc_quorum_verify_device: the items, powers (uint64) and flags (uint8) as torch tensors or
         device pointers; commit_off and thresholds on the host. d_k given: the messages are not read."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        thresholds = [int(x) for x in thresholds]
-        if len(thresholds) != nc:
-            raise ValueError("one threshold per commit")
-        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
-        out = self._quorum_out(nc, n)
-        p = self._dev_ptr
-        with self._lock:
-            rc = self.lib.edc_quorum_verify_device(self.ctx, nc, off, p(d_vk), p(d_sig), p(d_msg), p(d_msg_off), p(d_k),
-                                                   p(d_power), p(d_flag), th, int(bool(light)), bytes(z_seed), out[0],
-                                                   out[1], out[2], ctypes.byref(out[3]), ctypes.byref(out[4]), out[5])
-        self._check(rc)
-        return self._quorum_result(rc, nc, n, out)
+        form = self._quorum_device_form(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k)
+        return self._quorum_device(self.lib.edc_quorum_verify_device, False, form, d_power, d_flag, thresholds, z_seed, light)
 
     # ---- templated quorum commit sets (edc_tmpl_quorum_*): select first, hash only the checked votes ----
     def quorum_verify_templated(self, templates, commit_off, commit_tpl, sigs, holes, powers, flags, thresholds, z_seed,
@@ -906,132 +948,53 @@ class Engine:
         """edc_tmpl_quorum_verify: host buffers, synchronous; templates, commit_tpl, alt_span, item_alt
         and holes as commits_verify_templated_alt, powers / flags / thresholds as quorum_verify.
         Exactly one of vks and key_idx. Returns the dict quorum_verify returns."""
-        n = len(sigs)
-        nc, off = self._commit_offsets(commit_off)
-        ts, _keep = templates.struct()
-        _, var, voff = _tmpl_items([0] * n, holes, var_off)
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
-        out = self._quorum_out(nc, n)
-        with self._lock:
-            rc = self.lib.edc_tmpl_quorum_verify(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
-                                                 self._item_alt(item_alt), vkb, idx, b"".join(sigs) or b"\0", var, voff,
-                                                 pw, fl, th, int(bool(light)), bytes(z_seed), out[0], out[1], out[2],
-                                                 ctypes.byref(out[3]), ctypes.byref(out[4]), out[5])
-        self._check(rc)
-        return self._quorum_result(rc, nc, n, out)
+        form = self._tmpl_quorum_host_form(templates, commit_off, commit_tpl, sigs, holes, alt_span, item_alt, vks, key_idx,
+                                           var_off)
+        return self._quorum_host(self.lib.edc_tmpl_quorum_verify, False, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_templated_device(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
                                        d_power, d_flag, thresholds, z_seed, light=True, alt_span=1, d_item_alt=None):
         """edc_tmpl_quorum_verify_device: keys, signatures, holes, variant bytes, powers (uint64) and
         flags (uint8) as torch tensors or device pointers (d_item_alt None: all zeros); commit_off,
         commit_tpl, thresholds and the set on the host. Returns the dict quorum_verify returns."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        ts, _keep = templates.struct()
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        thresholds = [int(x) for x in thresholds]
-        if len(thresholds) != nc:
-            raise ValueError("one threshold per commit")
-        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
-        out = self._quorum_out(nc, n)
-        p = self._dev_ptr
-        with self._lock:
-            rc = self.lib.edc_tmpl_quorum_verify_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
-                                                        p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
-                                                        var_bytes, p(d_power), p(d_flag), th, int(bool(light)),
-                                                        bytes(z_seed), out[0], out[1], out[2], ctypes.byref(out[3]),
-                                                        ctypes.byref(out[4]), out[5])
-        self._check(rc)
-        return self._quorum_result(rc, nc, n, out)
+        form = self._tmpl_quorum_device_form(templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
+                                             alt_span, d_item_alt)
+        return self._quorum_device(self.lib.edc_tmpl_quorum_verify_device, False, form, d_power, d_flag, thresholds, z_seed,
+                                   light)
 
     # ---- cached quorum commit sets (edc_cached_*): checked votes that are live records of the
     # verified-signature table (sigcache_create) are not verified again; the results gain n_miss ----
-    @staticmethod
-    def _cached_quorum_result(rc, nc, n, out, miss):
-        res = Engine._quorum_result(rc, nc, n, out)
-        res["n_miss"] = miss.value
-        return res
-
     def quorum_verify_cached(self, commit_off, sigs, powers, flags, thresholds, z_seed, light=True, vks=None,
                              key_idx=None, msgs=None, ks=None):
         """edc_cached_quorum_verify: quorum_verify through the verified-signature table. Returns
         quorum_verify's dict plus n_miss, the size of the list that was verified."""
-        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
-        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
-        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
-        with self._lock:
-            rc = self.lib.edc_cached_quorum_verify(self.ctx, nc, *b, pw, fl, th, int(bool(light)), bytes(z_seed), out[0],
-                                                   out[1], out[2], ctypes.byref(out[3]), ctypes.byref(out[4]),
-                                                   ctypes.byref(miss), out[5])
-        self._check(rc)
-        return self._cached_quorum_result(rc, nc, n, out, miss)
+        form = self._quorum_host_form(commit_off, sigs, vks, key_idx, msgs, ks)
+        return self._quorum_host(self.lib.edc_cached_quorum_verify, True, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_cached_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_power, d_flag, thresholds, z_seed,
                                     light=True, d_k=None):
         """edc_cached_quorum_verify_device: quorum_verify_device through the verified-signature table."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        thresholds = [int(x) for x in thresholds]
-        if len(thresholds) != nc:
-            raise ValueError("one threshold per commit")
-        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
-        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
-        p = self._dev_ptr
-        with self._lock:
-            rc = self.lib.edc_cached_quorum_verify_device(self.ctx, nc, off, p(d_vk), p(d_sig), p(d_msg), p(d_msg_off),
-                                                          p(d_k), p(d_power), p(d_flag), th, int(bool(light)),
-                                                          bytes(z_seed), out[0], out[1], out[2], ctypes.byref(out[3]),
-                                                          ctypes.byref(out[4]), ctypes.byref(miss), out[5])
-        self._check(rc)
-        return self._cached_quorum_result(rc, nc, n, out, miss)
+        form = self._quorum_device_form(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k)
+        return self._quorum_device(self.lib.edc_cached_quorum_verify_device, True, form, d_power, d_flag, thresholds, z_seed,
+                                   light)
 
     def quorum_verify_templated_cached(self, templates, commit_off, commit_tpl, sigs, holes, powers, flags, thresholds,
                                        z_seed, light=True, alt_span=1, item_alt=None, vks=None, key_idx=None,
                                        var_off=None):
         """edc_cached_tmpl_quorum_verify: quorum_verify_templated through the verified-signature table."""
-        n = len(sigs)
-        nc, off = self._commit_offsets(commit_off)
-        ts, _keep = templates.struct()
-        _, var, voff = _tmpl_items([0] * n, holes, var_off)
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        pw, fl, th = self._quorum_votes(n, nc, powers, flags, thresholds)
-        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
-        with self._lock:
-            rc = self.lib.edc_cached_tmpl_quorum_verify(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
-                                                        self._item_alt(item_alt), vkb, idx, b"".join(sigs) or b"\0", var,
-                                                        voff, pw, fl, th, int(bool(light)), bytes(z_seed), out[0], out[1],
-                                                        out[2], ctypes.byref(out[3]), ctypes.byref(out[4]),
-                                                        ctypes.byref(miss), out[5])
-        self._check(rc)
-        return self._cached_quorum_result(rc, nc, n, out, miss)
+        form = self._tmpl_quorum_host_form(templates, commit_off, commit_tpl, sigs, holes, alt_span, item_alt, vks, key_idx,
+                                           var_off)
+        return self._quorum_host(self.lib.edc_cached_tmpl_quorum_verify, True, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_templated_cached_device(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off,
                                               var_bytes, d_power, d_flag, thresholds, z_seed, light=True, alt_span=1,
                                               d_item_alt=None):
         """edc_cached_tmpl_quorum_verify_device: quorum_verify_templated_device through the
         verified-signature table."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        ts, _keep = templates.struct()
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        thresholds = [int(x) for x in thresholds]
-        if len(thresholds) != nc:
-            raise ValueError("one threshold per commit")
-        th = (ctypes.c_uint64 * max(nc, 1))(*thresholds)
-        out, miss = self._quorum_out(nc, n), ctypes.c_size_t(0)
-        p = self._dev_ptr
-        with self._lock:
-            rc = self.lib.edc_cached_tmpl_quorum_verify_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
-                                                               p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
-                                                               var_bytes, p(d_power), p(d_flag), th, int(bool(light)),
-                                                               bytes(z_seed), out[0], out[1], out[2],
-                                                               ctypes.byref(out[3]), ctypes.byref(out[4]),
-                                                               ctypes.byref(miss), out[5])
-        self._check(rc)
-        return self._cached_quorum_result(rc, nc, n, out, miss)
+        form = self._tmpl_quorum_device_form(templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
+                                             alt_span, d_item_alt)
+        return self._quorum_device(self.lib.edc_cached_tmpl_quorum_verify_device, True, form, d_power, d_flag, thresholds,
+                                   z_seed, light)
 
     def cached_quorum_last(self):
         """edc_debug_cached_quorum_last: (n, n_checked, hits among the checked, n_miss, items SHA-512

@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
-#include <functional>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -643,6 +642,22 @@ static int ensure_slot_inputs(edc_ctx* ctx, Slot& s, size_t n, size_t mbytes) {
   return 0;
 }
 
+// Keys and signatures of n > 0 host items onto the device: key_idx given, 4 bytes per item over
+// PCIe instead of 32 (d_idx) and the registered keys expanded from them, else the keys themselves;
+// then the signatures.
+static int stage_keys_sigs(edc_ctx* ctx, hipStream_t st, size_t n, const uint8_t* vk, const uint32_t* key_idx,
+                           const uint8_t* sig, uint32_t* d_idx, uint8_t* d_vk, uint8_t* d_sig) {
+  if (key_idx) {
+    CK(hipMemcpyAsync(d_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    launch_expand_keys(st, (uint32_t)n, d_idx, ctx->kc_reg, ctx->kc_keys, d_vk);
+    CK(hipGetLastError());
+  } else {
+    CK(hipMemcpyAsync(d_vk, vk, n * 32, hipMemcpyHostToDevice, st));
+  }
+  CK(hipMemcpyAsync(d_sig, sig, n * 64, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
 static int upload_slot(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                        const uint64_t* msg_off, const uint32_t* key_idx = nullptr) {
   if (n && ((!vk && !key_idx) || !sig || !msg_off)) { ctx->err = "null input"; return EDC_ERR_ARG; }
@@ -660,15 +675,7 @@ static int upload_slot(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* vk, const
   }
   CK(hipMemcpyAsync(s.in_off, off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   if (mbytes) CK(hipMemcpyAsync(s.in_msg, msg + msg_off[0], mbytes, hipMemcpyHostToDevice, st));
-  if (key_idx) {                     // 4 bytes per item over PCIe instead of 32
-    CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    launch_expand_keys(st, (uint32_t)n, s.in_idx, ctx->kc_reg, ctx->kc_keys, s.in_vk);
-    CK(hipGetLastError());
-  } else {
-    CK(hipMemcpyAsync(s.in_vk, vk, n * 32, hipMemcpyHostToDevice, st));
-  }
-  CK(hipMemcpyAsync(s.in_sig, sig, n * 64, hipMemcpyHostToDevice, st));
-  return 0;
+  return stage_keys_sigs(ctx, st, n, vk, key_idx, sig, s.in_idx, s.in_vk, s.in_sig);
 }
 
 // Prehashed host submissions (reference Item = {vk_bytes, sig, k}, src/batch.rs:76-80): keys and
@@ -681,20 +688,16 @@ static int upload_slot_prehashed(edc_ctx* ctx, Slot& s, size_t n, const uint8_t*
   if (rc) return rc;
   rc = ensure_slot(ctx, s, n);
   if (rc || !n) return rc;
-  if (key_idx) {                     // 4 bytes per item over PCIe instead of 32: 100 B per item
-    CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.st));
-    launch_expand_keys(s.st, (uint32_t)n, s.in_idx, ctx->kc_reg, ctx->kc_keys, s.in_vk);
-    CK(hipGetLastError());
-  } else {
-    CK(hipMemcpyAsync(s.in_vk, vk, n * 32, hipMemcpyHostToDevice, s.st));
-  }
-  CK(hipMemcpyAsync(s.in_sig, sig, n * 64, hipMemcpyHostToDevice, s.st));
+  // with key_idx, 100 B per item
+  if ((rc = stage_keys_sigs(ctx, s.st, n, vk, key_idx, sig, s.in_idx, s.in_vk, s.in_sig))) return rc;
   CK(hipMemcpyAsync(s.k, k, n * 32, hipMemcpyHostToDevice, s.st));
   return 0;
 }
 
 // caller-supplied device k arrays are read with 16-byte loads
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// sub-arrays of one staged piece start at 16-byte boundaries
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 static uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -1507,14 +1510,7 @@ static int tmpl_upload_slot(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* vk, 
   if ((rc = tmpl_upload_set(ctx, s.tw, s.st, it.ts, sh, &view))) return rc;
   if (!n) return 0;
   if ((rc = tmpl_arena_room(ctx, s.tw, s.st, n, sh, it.var_off[n]))) return rc;
-  if (key_idx) {
-    CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.st));
-    launch_expand_keys(s.st, (uint32_t)n, s.in_idx, ctx->kc_reg, ctx->kc_keys, s.in_vk);
-    CK(hipGetLastError());
-  } else {
-    CK(hipMemcpyAsync(s.in_vk, vk, n * 32, hipMemcpyHostToDevice, s.st));
-  }
-  CK(hipMemcpyAsync(s.in_sig, sig, n * 64, hipMemcpyHostToDevice, s.st));
+  if ((rc = stage_keys_sigs(ctx, s.st, n, vk, key_idx, sig, s.in_idx, s.in_vk, s.in_sig))) return rc;
   return tmpl_expand_host(ctx, s.tw, s.st, view, n, it, s.tw.arena, s.tw.off);
 }
 
@@ -2326,6 +2322,14 @@ static int commits_check_keys(edc_ctx* ctx, size_t n, const uint8_t* vk, const u
   return 0;
 }
 
+// messages of n > 0 host items: (msg, msg_off), or the prehashed k (its values are the caller's to check)
+static int commits_check_msg_or_k(edc_ctx* ctx, size_t n, const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k) {
+  if (!msg_off == !k || (msg && k)) { ctx->err = "exactly one of (msg, msg_off) and k"; return EDC_ERR_ARG; }
+  if (msg_off && msg_off[n] < msg_off[0]) { ctx->err = "message offsets decrease"; return EDC_ERR_ARG; }
+  if (msg_off && msg_off[n] > msg_off[0] && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
+  return 0;
+}
+
 // the host checks of edc_commits_verify / _submit (nothing is launched before they pass)
 static int commits_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
                               const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
@@ -2334,11 +2338,8 @@ static int commits_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   if (rc || !*n) return rc;
   if ((rc = commits_check_keys(ctx, *n, vk, key_idx))) return rc;
   if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  if (!msg_off == !k || (msg && k)) { ctx->err = "exactly one of (msg, msg_off) and k"; return EDC_ERR_ARG; }
-  if (msg_off) {
-    if (msg_off[*n] < msg_off[0]) { ctx->err = "message offsets decrease"; return EDC_ERR_ARG; }
-    if (msg_off[*n] > msg_off[0] && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
-  } else {
+  if ((rc = commits_check_msg_or_k(ctx, *n, msg, msg_off, k))) return rc;
+  if (k) {
     for (size_t i = 0; i < *n; ++i) {      // Scalar::from_hash never yields k >= l
       uint32_t w[8];
       memcpy(w, k + 32 * i, 32);
@@ -2463,20 +2464,12 @@ static int commits_enqueue_tmpl(edc_ctx* ctx, Slot& s, const edc_templates* ts, 
     TmplWs& w = s.tw;
     hipStream_t st = s.st;
     const size_t var_bytes = var_off[n];
-    const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_tpl = up16(4 * (n + 1)), o_var = up16(o_tpl + 2 * n), o_coff = up16(o_var + var_bytes),
                  o_ctpl = up16(o_coff + 4 * (nc + 1)), o_alt = up16(o_ctpl + 2 * nc);
     if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) ||
         (rc = tmpl_room(ctx, st, w.in, item_alt ? o_alt + n : o_ctpl + 2 * nc)))
       return rc;
-    if (key_idx) {
-      CK(hipMemcpyAsync(s.in_idx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      launch_expand_keys(st, (uint32_t)n, s.in_idx, ctx->kc_reg, ctx->kc_keys, s.in_vk);
-      CK(hipGetLastError());
-    } else {
-      CK(hipMemcpyAsync(s.in_vk, vk, n * 32, hipMemcpyHostToDevice, st));
-    }
-    CK(hipMemcpyAsync(s.in_sig, sig, n * 64, hipMemcpyHostToDevice, st));
+    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, s.in_idx, s.in_vk, s.in_sig))) return rc;
     CK(hipMemcpyAsync(w.in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
     if (var_bytes) CK(hipMemcpyAsync(w.in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(w.in + o_coff, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
@@ -2517,7 +2510,6 @@ static int commits_enqueue_tmpl_device(edc_ctx* ctx, Slot& s, const edc_template
   if (n) {
     TmplWs& w = s.tw;
     hipStream_t st = s.st;
-    const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_coff = up16(2 * n), o_ctpl = up16(o_coff + 4 * (nc + 1));
     if ((rc = tmpl_arena_room(ctx, w, st, n, sh, var_bytes)) || (rc = tmpl_room(ctx, st, w.in, o_ctpl + 2 * nc)))
       return rc;
@@ -2804,7 +2796,6 @@ int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   Slot& s = ctx->slot[0];
   if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
-  const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t o_ctpl = up16(4 * (nc + 1)), o_tpl = up16(o_ctpl + 2 * nc);
   if ((rc = init_slot(ctx, s)) || (rc = ensure_aux(ctx, o_tpl + 2 * n))) return rc;
   hipStream_t st = s.st;
@@ -2843,7 +2834,6 @@ int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commi
   CK(hipSetDevice(ctx->device));
   // the device copies of item_alt and tpl_out start at the host pointers' offsets from a 16-byte
   // boundary, so a caller picks the kernel's wide or narrow access paths by how it places its arrays
-  const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t o_ctpl = up16(4 * (nc + 1)), o_alt = up16(o_ctpl + 2 * nc) + ((uintptr_t)item_alt & 15u),
                o_flag = up16(o_alt + n), o_tpl = o_flag + 16 + ((uintptr_t)tpl_out & 14u);
   if ((rc = init_slot(ctx, s)) || (rc = ensure_aux(ctx, o_tpl + 2 * n))) return rc;
@@ -3566,6 +3556,8 @@ int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const ui
 // device-to-host copy (with the device checks' flag) and a stream synchronization before the MSM
 // can be planned. A passing union's tally is planned[]; a failed one scatters the codes back and
 // runs the tally kernel. All on slot 0.
+// Every form is its checks and staging (*_inputs), then quorum_select_enqueue, what the form adds
+// behind the selection, quorum_select_read, quorum_gather and quorum_finish.
 static int ensure_quorum(edc_ctx* ctx, size_t n, size_t nc) {
   hipStream_t st = ctx->st();
   CK(grow_group(ctx->q_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
@@ -3608,49 +3600,9 @@ static int quorum_check_votes(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   return 0;
 }
 
-// Workspace, the staged offsets and thresholds, then the selection and the scan of its workgroup
-// counts on device-resident power / flag. *n_checked = the size of the gathered list. A vote the
-// device checks refuse is EDC_ERR_ARG here, before anything is gathered or verified.
-// behind: what a templated form enqueues behind the selection, in front of the one read-back (its
-// all-n checks raise q_err too, bit 1 for the holes; behind_alt: it checks variant bytes), or a
-// cached plain form (the masked lookup, whose counts travel in the same read-back).
-static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
-                             int mode, const uint64_t* d_power, const uint8_t* d_flag, size_t* n_checked,
-                             const std::function<int(hipStream_t)>* behind = nullptr, bool behind_alt = true) {
-  int rc = init_slot(ctx, ctx->slot[0]);
-  if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
-  hipStream_t st = ctx->st();
-  if ((rc = sc_order_after_inserts(ctx, st))) return rc;
-  CK(hipMemsetAsync(ctx->q_planned, 0, nc * sizeof(uint64_t), st));
-  *n_checked = 0;
-  if (!n) return 0;
-  const uint32_t N = (uint32_t)n, nwg = (uint32_t)quorum_tiles(n);
-  CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(ctx->q_thr, threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  CK(hipMemsetAsync(ctx->q_err, 0, sizeof(int), st));
-  launch_quorum_select(st, N, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, d_power, d_flag, ctx->q_cidx,
-                       ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->sc_hit, ctx->sc_wg, ctx->q_planned, ctx->q_err);
-  launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
-  CK(hipGetLastError());
-  ctx->q_h[0] = ctx->q_h[1] = ctx->q_h[2] = 0;
-  if (behind && (rc = (*behind)(st))) return rc;
-  CK(hipMemcpyAsync(&ctx->q_h[0], ctx->q_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  CK(hipMemcpyAsync(&ctx->q_h[1], ctx->sc_wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  if (ctx->q_h[0] & 2) {
-    ctx->err = "templated items: hole offsets out of range";
-    return EDC_ERR_ARG;
-  }
-  if (ctx->q_h[0] && behind && behind_alt) {
-    ctx->err = "votes: a flag above 2, a power or a commit's counted power above 2^63 - 1, or an item_alt[i] >= alt_span";
-    return EDC_ERR_ARG;
-  }
-  if (ctx->q_h[0]) {
-    ctx->err = "votes: a flag above 2, a power above 2^63 - 1 or a commit whose counted power passes 2^63 - 1";
-    return EDC_ERR_ARG;
-  }
-  if (ctx->q_h[1] > n) { ctx->err = "quorum selection: checked count out of range"; return EDC_ERR_HIP; }
-  *n_checked = ctx->q_h[1];
+// preconditions of every cached quorum entry (edc_cached_*) beyond the uncached form's own
+static int cq_ready(edc_ctx* ctx) {
+  if (!ctx->sc_cap) { ctx->err = "no signature cache on this context (edc_sigcache_create)"; return EDC_ERR_ARG; }
   return 0;
 }
 
@@ -3658,134 +3610,25 @@ struct QuorumOut {
   uint8_t *commit_verdicts, *item_verdicts;
   uint64_t* tally;
   int* n_bad_commits;
-  size_t* n_checked;
+  size_t *n_checked, *n_miss;   // n_miss: the cached entries' (null in the uncached ones)
   uint8_t* check8;
 };
-
-// What a cached form (edc_cached_*) adds to quorum_finish. The list it hands over holds the checked
-// MISSES of a looked-up list of n_mid items: all n items in the plain forms, the gathered checked
-// votes in the templated ones. codes: the lookup's base codes of those n_mid items (device; 255 not
-// checked, else 0), mid_idx: their queue positions (null: they are the n items). o_*: the
-// looked-up list's arrays, which quorum_finish's idx indexes; the insert reads them.
-struct QuorumCached {
-  size_t n_checked, n_mid;
-  uint8_t* codes;
-  const uint32_t* mid_idx;
-  const uint8_t *o_vk, *o_sig;
-  const uint32_t* o_k;
-  size_t* n_miss;
-};
-
-static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, size_t m, const uint8_t* b_vk,
-                         const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx, const uint64_t* d_power,
-                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
-                         const QuorumCached* cq = nullptr);
-
-// A checked quorum commit set whose items (vk, sig, k, power, flag) are on the device.
-static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode, size_t n,
-                      const uint8_t* d_vk, const uint8_t* d_sig, const uint32_t* d_k, const uint64_t* d_power,
-                      const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out) {
-  size_t m = 0;
-  int rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag, &m);
-  if (rc) return rc;
-  hipStream_t st = ctx->st();
-  const uint8_t *b_vk = d_vk, *b_sig = d_sig;
-  // an empty list still runs the n = 0 batch, whose k is never read
-  const uint32_t *b_k = m ? d_k : reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), *idx = nullptr;
-  if (m && m < n) {
-    uint8_t* g_vk = ctx->sc_g;
-    uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
-    uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->sc_cap_n * 64);
-    launch_sc_compact(st, (uint32_t)n, ctx->sc_hit, ctx->sc_wg, d_vk, d_sig, d_k, ctx->sc_idx, g_vk, g_sig, g_k);
-    CK(hipGetLastError());
-    idx = ctx->sc_idx;
-    b_vk = g_vk;
-    b_sig = g_sig;
-    b_k = g_k;
-  }
-  return quorum_finish(ctx, nc, threshold, n, m, b_vk, b_sig, b_k, idx, d_power, d_flag, z_seed, out);
-}
-
-// The gathered list (m items in queue order; idx their queue positions, null when m == n or m == 0)
-// through the batch and its fallback, then the tally and the verdicts of all n items / nc commits.
-// cq (a cached form): the list is the checked misses; what it proves valid is inserted (every miss
-// after a passing union, the misses with code 0 after a failed one) before the last
-// synchronization, and a failed union's codes go back over the lookup's base codes, through the
-// list's positions in the looked-up list and that list's positions in the queue.
-static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, size_t m, const uint8_t* b_vk,
-                         const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx, const uint64_t* d_power,
-                         const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out, const QuorumCached* cq) {
-  hipStream_t st = ctx->st();
-  std::vector<uint8_t> mv(m ? m : 1);
-  const int code = batch_with_fallback(ctx, m, b_vk, b_sig, nullptr, nullptr, b_k, z_seed, mv.data(), nullptr, out.check8);
-  if (code < 0) return code;
-  const unsigned long long ins0 = cq ? ctx->sc_hctr[0] : 0;
-  if (cq && m) {
-    if (code != EDC_OK) CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
-    launch_sc_insert(st, ctx->sc(), (uint32_t)m, idx, cq->o_vk, cq->o_sig, cq->o_k,
-                     code == EDC_OK ? nullptr : ctx->sc_mverd.get(), ctx->sc_ctr);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(ctx->sc_hctr, ctx->sc_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  }
-  std::vector<uint64_t> tal(nc);
-  std::vector<uint32_t> cor32;
-  std::vector<uint8_t> cor;
-  if (code == EDC_OK) {                 // every checked item verified: the tally is the plan
-    CK(hipMemcpyAsync(tal.data(), ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (out.item_verdicts && n) CK(hipMemcpyAsync(out.item_verdicts, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    if (out.item_verdicts)
-      for (size_t i = 0; i < n; ++i) out.item_verdicts[i] = out.item_verdicts[i] ? QUORUM_NOT_CHECKED : 0;
-  } else {                              // m > 0: codes back to queue order, then the tally kernel
-    const uint8_t* d_codes = ctx->sc_mverd;
-    if (!cq) {
-      CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
-      if (idx) {
-        CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
-        launch_sc_scatter(st, (uint32_t)m, idx, ctx->sc_mverd, ctx->sc_verd);
-        d_codes = ctx->sc_verd;
-      }
-    } else {                            // sc_mverd holds the misses' codes already
-      if (idx) {                        // hits keep the base code 0
-        launch_sc_scatter(st, (uint32_t)m, idx, ctx->sc_mverd, cq->codes);
-        d_codes = cq->codes;
-      }
-      if (cq->mid_idx) {
-        CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
-        launch_sc_scatter(st, (uint32_t)cq->n_mid, cq->mid_idx, d_codes, ctx->sc_verd);
-        d_codes = ctx->sc_verd;
-      }
-    }
-    CK(hipMemsetAsync(ctx->q_tally, 0, nc * sizeof(uint64_t), st));
-    CK(hipMemsetAsync(ctx->q_cor, 0, nc * sizeof(uint32_t), st));
-    launch_quorum_tally(st, (uint32_t)n, ctx->q_cidx, d_power, d_flag, d_codes, ctx->q_tally, ctx->q_cor);
-    CK(hipGetLastError());
-    cor32.resize(nc);
-    CK(hipMemcpyAsync(tal.data(), ctx->q_tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(cor32.data(), ctx->q_cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (out.item_verdicts) CK(hipMemcpyAsync(out.item_verdicts, d_codes, n, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    cor.resize(nc);
-    for (size_t c = 0; c < nc; ++c) cor[c] = cor32[c] ? 1 : 0;
-  }
-  size_t bad = 0;
-  const int res = quorum_reduce(nc, cor.empty() ? nullptr : cor.data(), tal.data(), threshold, out.commit_verdicts, &bad);
-  if (out.tally) memcpy(out.tally, tal.data(), nc * sizeof(uint64_t));
-  if (out.n_bad_commits) *out.n_bad_commits = (int)bad;
-  if (out.n_checked) *out.n_checked = cq ? cq->n_checked : m;
-  if (cq) {
-    if (cq->n_miss) *cq->n_miss = m;
-    ctx->cq_last[3] = m;
-    ctx->cq_last[5] = ctx->sc_hctr[0] - ins0;
-  }
-  return res;
-}
 
 // nc == 0: nothing to verify
 static int quorum_none(const QuorumOut& out) {
   if (out.n_bad_commits) *out.n_bad_commits = 0;
   if (out.n_checked) *out.n_checked = 0;
+  if (out.n_miss) *out.n_miss = 0;
   return EDC_OK;
+}
+
+// What every verify entry does first. True: *rc is the entry's result (a null argument, a cached
+// entry without a table, or nc == 0).
+static bool quorum_entry_done(edc_ctx* ctx, const uint8_t* z_seed, bool cached, size_t nc, const QuorumOut& out, int* rc) {
+  if (!ctx || !z_seed) { *rc = EDC_ERR_ARG; return true; }
+  if (cached && (*rc = cq_ready(ctx))) return true;
+  if (!nc) { *rc = quorum_none(out); return true; }
+  return false;
 }
 
 // power and flag of a host form beside the other staged inputs (slot 0's stream)
@@ -3824,10 +3667,238 @@ static int quorum_device_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_
   return 0;
 }
 
+// The host form's checks and staging (keys, signatures, power, flag; k copied or hashed into kbuf,
+// all on slot 0's stream). Shared with edc_cached_quorum_verify.
 static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
                               const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
                               const uint8_t* k, const uint64_t* power, const uint8_t* flag, const uint64_t* threshold,
-                              int mode, size_t* n_out);
+                              int mode, size_t* n_out) {
+  size_t n;
+  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
+  if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
+  if (n) {
+    if ((rc = commits_check_keys(ctx, n, vk, key_idx))) return rc;
+    if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
+    if ((rc = commits_check_msg_or_k(ctx, n, msg, msg_off, k))) return rc;
+    if (k) {                // only a checked vote's k reaches the batch (Scalar::from_hash never yields k >= l)
+      std::vector<uint8_t> chk(n);
+      quorum_select(nc, commit_off, power, flag, threshold, mode, chk.data(), nullptr);
+      for (size_t i = 0; i < n; ++i) {
+        uint32_t w[8];
+        memcpy(w, k + 32 * i, 32);
+        if (chk[i] && w[7] >= 0x10000000u && !sc_is_canonical(w)) {
+          ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
+          return EDC_ERR_ARG;
+        }
+      }
+    }
+  }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = quorum_stage_votes(ctx, n, nc, power, flag))) return rc;
+  hipStream_t st = ctx->st();
+  if (k) {
+    if ((rc = ensure_n(ctx, n))) return rc;
+    if (n) CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
+  } else if ((rc = upload_msgs(ctx, n, msg, n ? msg_off : nullptr))) {
+    return rc;
+  }
+  if (n) {                  // key indices into q_cidx, which is free until the selection writes it
+    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->q_cidx, ctx->vk, ctx->sig))) return rc;
+    if (!k) {
+      launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
+      CK(hipGetLastError());
+    }
+  }
+  *n_out = n;
+  return 0;
+}
+
+// Workspace, the staged offsets and thresholds, then the selection and the scan of its workgroup
+// counts on device-resident power / flag, all enqueued. A form with work of its own behind the
+// selection (n > 0 only) enqueues it between this and quorum_select_read.
+static int quorum_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                                 int mode, const uint64_t* d_power, const uint8_t* d_flag) {
+  int rc = init_slot(ctx, ctx->slot[0]);
+  if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
+  hipStream_t st = ctx->st();
+  if ((rc = sc_order_after_inserts(ctx, st))) return rc;
+  CK(hipMemsetAsync(ctx->q_planned, 0, nc * sizeof(uint64_t), st));
+  if (!n) return 0;
+  const uint32_t N = (uint32_t)n, nwg = (uint32_t)quorum_tiles(n);
+  CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->q_thr, threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  CK(hipMemsetAsync(ctx->q_err, 0, sizeof(int), st));
+  launch_quorum_select(st, N, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, d_power, d_flag, ctx->q_cidx,
+                       ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->sc_hit, ctx->sc_wg, ctx->q_planned, ctx->q_err);
+  launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
+  CK(hipGetLastError());
+  ctx->q_h[0] = ctx->q_h[1] = ctx->q_h[2] = 0;
+  return 0;
+}
+
+// The one read-back behind quorum_select_enqueue: the device checks' flag and the checked count
+// (*n_checked, the size of the gathered list), with whatever else the form sent to q_h. A vote the
+// device checks refuse is EDC_ERR_ARG here, before anything is gathered or verified. flag_msg: a
+// templated form's all-n checks raise q_err too (bit 1 for the holes), so it words bit 0 itself.
+static int quorum_select_read(edc_ctx* ctx, size_t n, size_t* n_checked, const char* flag_msg = nullptr) {
+  *n_checked = 0;
+  if (!n) return 0;
+  hipStream_t st = ctx->st();
+  const uint32_t nwg = (uint32_t)quorum_tiles(n);
+  CK(hipMemcpyAsync(&ctx->q_h[0], ctx->q_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(&ctx->q_h[1], ctx->sc_wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  if (ctx->q_h[0] & 2) {
+    ctx->err = "templated items: hole offsets out of range";
+    return EDC_ERR_ARG;
+  }
+  if (ctx->q_h[0]) {
+    ctx->err = "votes: a flag above 2, a power above 2^63 - 1 or a commit whose counted power passes 2^63 - 1";
+    if (flag_msg) ctx->err = flag_msg;
+    return EDC_ERR_ARG;
+  }
+  if (ctx->q_h[1] > n) { ctx->err = "quorum selection: checked count out of range"; return EDC_ERR_HIP; }
+  *n_checked = ctx->q_h[1];
+  return 0;
+}
+
+// the selection with nothing behind it
+static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                             int mode, const uint64_t* d_power, const uint8_t* d_flag, size_t* n_checked) {
+  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag);
+  return rc ? rc : quorum_select_read(ctx, n, n_checked);
+}
+
+// Device arrays of `count` items (keys, signatures, k). idx: where each stands in the list it was
+// gathered from; null: it is that list.
+struct ItemList {
+  const uint8_t *vk, *sig;
+  const uint32_t *k, *idx;
+  size_t count;
+};
+
+// where a gather puts what it keeps: vk | sig | k of cap items each, and the positions
+struct GatherArea {
+  uint8_t* g;
+  size_t cap;
+  uint32_t* idx;
+};
+
+static GatherArea sc_area(edc_ctx* ctx) { return GatherArea{ctx->sc_g, ctx->sc_cap_n, ctx->sc_idx}; }
+
+// The `keep` items of `in` that leave[] does not mark (wg: its scanned workgroup counts), packed
+// into `to` in list order. All kept: `in` itself, nothing moves. None kept: an empty list still
+// runs the n = 0 batch, whose k is never read.
+static int quorum_gather(edc_ctx* ctx, const ItemList& in, size_t keep, const uint8_t* leave, const uint32_t* wg,
+                         const GatherArea& to, ItemList* out) {
+  *out = ItemList{in.vk, in.sig, keep ? in.k : reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), nullptr, keep};
+  if (!keep || keep == in.count) return 0;
+  uint8_t* g_sig = to.g + to.cap * 32;
+  uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + to.cap * 64);
+  launch_sc_compact(ctx->st(), (uint32_t)in.count, leave, wg, in.vk, in.sig, in.k, to.idx, to.g, g_sig, g_k);
+  CK(hipGetLastError());
+  *out = ItemList{to.g, g_sig, g_k, to.idx, keep};
+  return 0;
+}
+
+// What a cached form (edc_cached_*) adds to quorum_finish. The list it hands over holds the checked
+// MISSES of a looked-up list `mid`: all n items in the plain forms (mid.idx null), the gathered
+// checked votes in the templated ones (mid.idx: their queue positions). quorum_finish's list
+// indexes mid's arrays, and the insert reads them. codes: the lookup's base codes of mid's items
+// (device; 255 not checked, else 0).
+struct QuorumCached {
+  size_t n_checked;
+  uint8_t* codes;
+  ItemList mid;
+};
+
+// The gathered list (in queue order; list.idx null when it holds all n items or none) through the
+// batch and its fallback, then the tally and the verdicts of all n items / nc commits.
+// cq (a cached form): the list is the checked misses; what it proves valid is inserted (every miss
+// after a passing union, the misses with code 0 after a failed one) before the last
+// synchronization, and a failed union's codes go back over the lookup's base codes, through the
+// list's positions in the looked-up list and that list's positions in the queue.
+static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, const ItemList& list,
+                         const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
+                         const QuorumCached* cq = nullptr) {
+  hipStream_t st = ctx->st();
+  const size_t m = list.count;
+  std::vector<uint8_t> mv(m ? m : 1);
+  const int code = batch_with_fallback(ctx, m, list.vk, list.sig, nullptr, nullptr, list.k, z_seed, mv.data(), nullptr,
+                                       out.check8);
+  if (code < 0) return code;
+  const unsigned long long ins0 = cq ? ctx->sc_hctr[0] : 0;
+  if (cq && m) {
+    if (code != EDC_OK) CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
+    launch_sc_insert(st, ctx->sc(), (uint32_t)m, list.idx, cq->mid.vk, cq->mid.sig, cq->mid.k,
+                     code == EDC_OK ? nullptr : ctx->sc_mverd.get(), ctx->sc_ctr);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(ctx->sc_hctr, ctx->sc_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  }
+  std::vector<uint64_t> tal(nc);
+  std::vector<uint32_t> cor32;
+  std::vector<uint8_t> cor;
+  if (code == EDC_OK) {                 // every checked item verified: the tally is the plan
+    CK(hipMemcpyAsync(tal.data(), ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (out.item_verdicts && n) CK(hipMemcpyAsync(out.item_verdicts, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    if (out.item_verdicts)
+      for (size_t i = 0; i < n; ++i) out.item_verdicts[i] = out.item_verdicts[i] ? QUORUM_NOT_CHECKED : 0;
+  } else {                              // m > 0: codes back to queue order, then the tally kernel
+    const uint8_t* d_codes = ctx->sc_mverd;
+    if (!cq) {
+      CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), m, hipMemcpyHostToDevice, st));
+      if (list.idx) {
+        CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
+        launch_sc_scatter(st, (uint32_t)m, list.idx, ctx->sc_mverd, ctx->sc_verd);
+        d_codes = ctx->sc_verd;
+      }
+    } else {                            // sc_mverd holds the misses' codes already
+      if (list.idx) {                   // hits keep the base code 0
+        launch_sc_scatter(st, (uint32_t)m, list.idx, ctx->sc_mverd, cq->codes);
+        d_codes = cq->codes;
+      }
+      if (cq->mid.idx) {
+        CK(hipMemsetAsync(ctx->sc_verd, QUORUM_NOT_CHECKED, n, st));
+        launch_sc_scatter(st, (uint32_t)cq->mid.count, cq->mid.idx, d_codes, ctx->sc_verd);
+        d_codes = ctx->sc_verd;
+      }
+    }
+    CK(hipMemsetAsync(ctx->q_tally, 0, nc * sizeof(uint64_t), st));
+    CK(hipMemsetAsync(ctx->q_cor, 0, nc * sizeof(uint32_t), st));
+    launch_quorum_tally(st, (uint32_t)n, ctx->q_cidx, d_power, d_flag, d_codes, ctx->q_tally, ctx->q_cor);
+    CK(hipGetLastError());
+    cor32.resize(nc);
+    CK(hipMemcpyAsync(tal.data(), ctx->q_tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(cor32.data(), ctx->q_cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (out.item_verdicts) CK(hipMemcpyAsync(out.item_verdicts, d_codes, n, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    cor.resize(nc);
+    for (size_t c = 0; c < nc; ++c) cor[c] = cor32[c] ? 1 : 0;
+  }
+  size_t bad = 0;
+  const int res = quorum_reduce(nc, cor.empty() ? nullptr : cor.data(), tal.data(), threshold, out.commit_verdicts, &bad);
+  if (out.tally) memcpy(out.tally, tal.data(), nc * sizeof(uint64_t));
+  if (out.n_bad_commits) *out.n_bad_commits = (int)bad;
+  if (out.n_checked) *out.n_checked = cq ? cq->n_checked : m;
+  if (cq) {
+    if (out.n_miss) *out.n_miss = m;
+    ctx->cq_last[3] = m;
+    ctx->cq_last[5] = ctx->sc_hctr[0] - ins0;
+  }
+  return res;
+}
+
+// A checked quorum commit set whose items (all: vk, sig, k of the n votes; power, flag) are on the device.
+static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
+                      const ItemList& all, const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
+                      const QuorumOut& out) {
+  size_t m = 0;
+  ItemList list;
+  int rc = quorum_select_run(ctx, all.count, nc, commit_off, threshold, mode, d_power, d_flag, &m);
+  if (rc || (rc = quorum_gather(ctx, all, m, ctx->sc_hit, ctx->sc_wg, sc_area(ctx), &list))) return rc;
+  return quorum_finish(ctx, nc, threshold, all.count, list, d_power, d_flag, z_seed, out);
+}
 
 extern "C" {
 
@@ -3860,15 +3931,16 @@ int edc_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
                              const uint64_t* d_power, const uint8_t* d_flag, const uint64_t* threshold, int mode,
                              const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
                              int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return quorum_none(out);
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
   size_t n;
   const uint32_t* k;
-  int rc = quorum_device_inputs(ctx, nc, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k, d_power, d_flag, threshold, mode,
-                                &n, &k);
-  if (rc) return rc;
-  return quorum_run(ctx, nc, commit_off, threshold, mode, n, d_vk, d_sig, k, d_power, d_flag, z_seed, out);
+  if ((rc = quorum_device_inputs(ctx, nc, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k, d_power, d_flag, threshold, mode,
+                                 &n, &k)))
+    return rc;
+  return quorum_run(ctx, nc, commit_off, threshold, mode, ItemList{d_vk, d_sig, k, nullptr, n}, d_power, d_flag, z_seed,
+                    out);
 }
 
 int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
@@ -3876,75 +3948,15 @@ int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
                       const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
                       const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
                       int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return quorum_none(out);
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
   size_t n;
-  int rc = quorum_host_inputs(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, power, flag, threshold, mode, &n);
-  if (rc) return rc;
-  return quorum_run(ctx, nc, commit_off, threshold, mode, n, ctx->vk, ctx->sig, ctx->kbuf, ctx->q_power, ctx->q_flag,
-                    z_seed, out);
-}
-
-}  // extern "C"
-
-// The host form's checks and staging (keys, signatures, power, flag; k copied or hashed into kbuf,
-// all on slot 0's stream). Shared with edc_cached_quorum_verify.
-static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
-                              const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
-                              const uint8_t* k, const uint64_t* power, const uint8_t* flag, const uint64_t* threshold,
-                              int mode, size_t* n_out) {
-  size_t n;
-  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n);
-  if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
-  if (n) {
-    if ((rc = commits_check_keys(ctx, n, vk, key_idx))) return rc;
-    if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
-    if (!msg_off == !k || (msg && k)) { ctx->err = "exactly one of (msg, msg_off) and k"; return EDC_ERR_ARG; }
-    if (msg_off) {
-      if (msg_off[n] < msg_off[0]) { ctx->err = "message offsets decrease"; return EDC_ERR_ARG; }
-      if (msg_off[n] > msg_off[0] && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
-    } else {                // only a checked vote's k reaches the batch (Scalar::from_hash never yields k >= l)
-      std::vector<uint8_t> chk(n);
-      quorum_select(nc, commit_off, power, flag, threshold, mode, chk.data(), nullptr);
-      for (size_t i = 0; i < n; ++i) {
-        uint32_t w[8];
-        memcpy(w, k + 32 * i, 32);
-        if (chk[i] && w[7] >= 0x10000000u && !sc_is_canonical(w)) {
-          ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
-          return EDC_ERR_ARG;
-        }
-      }
-    }
-  }
-  CK(hipSetDevice(ctx->device));
-  if ((rc = quorum_stage_votes(ctx, n, nc, power, flag))) return rc;
-  hipStream_t st = ctx->st();
-  if (k) {
-    if ((rc = ensure_n(ctx, n))) return rc;
-    if (n) CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
-  } else if ((rc = upload_msgs(ctx, n, msg, n ? msg_off : nullptr))) {
+  if ((rc = quorum_host_inputs(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, power, flag, threshold, mode, &n)))
     return rc;
-  }
-  if (n) {
-    if (key_idx) {          // 4 bytes per item over PCIe; q_cidx is free until the selection writes it
-      CK(hipMemcpyAsync(ctx->q_cidx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      launch_expand_keys(st, (uint32_t)n, ctx->q_cidx, ctx->kc_reg, ctx->kc_keys, ctx->vk);
-      CK(hipGetLastError());
-    } else {
-      CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
-    }
-    CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
-    if (!k) {
-      launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
-      CK(hipGetLastError());
-    }
-  }
-  *n_out = n;
-  return 0;
+  return quorum_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n}, ctx->q_power,
+                    ctx->q_flag, z_seed, out);
 }
-
-extern "C" {
 
 int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power,
                             const uint8_t* flag, const uint64_t* threshold, int mode, int reps, float* ms) {
@@ -3986,10 +3998,10 @@ int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
 // offsets and sums the checked holes per tile). The read-back then carries the flag, the checked
 // count m and the checked hole bytes. k_tq_gather packs the m checked votes (keys, signatures,
 // template indices, holes) in queue order, the expansion and SHA-512 run on those m items into an
-// arena sized from m, and quorum_finish does what it does for every quorum form. m == n: nothing is
-// gathered, the caller's arrays are the list. All on slot 0.
-// The cached forms (edc_cached_tmpl_quorum_*, cached = true) look the hashed list up before the
-// batch: see cached_tmpl_finish below.
+// arena sized from m (tmpl_quorum_list), and quorum_finish does what it does for every quorum form.
+// m == n: nothing is gathered, the caller's arrays are the list. All on slot 0.
+// The cached forms (edc_cached_tmpl_quorum_*) look the hashed list up before the batch: see
+// cached_tmpl_finish below.
 struct TmplQuorumItems {       // device arrays of all n items
   const uint8_t *vk, *sig, *item_alt, *var;
   const uint32_t* var_off;
@@ -3997,95 +4009,6 @@ struct TmplQuorumItems {       // device arrays of all n items
   const uint64_t* power;
   const uint8_t* flag;
 };
-
-static int cached_tmpl_finish(edc_ctx* ctx, TmplWs& w, size_t nc, const uint64_t* threshold, size_t n, size_t m,
-                              const uint8_t* b_vk, const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx,
-                              const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
-                              size_t* n_miss);
-
-static int tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
-                           const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span, size_t n,
-                           const TmplQuorumItems& it, const uint64_t* threshold, int mode, const uint8_t* z_seed,
-                           const QuorumOut& out, bool cached = false, size_t* n_miss = nullptr) {
-  Slot& s = ctx->slot[0];
-  TmplWs& w = s.tw;
-  int rc = init_slot(ctx, s);
-  if (rc) return rc;
-  hipStream_t st = ctx->st();
-  TmplView view;
-  if ((rc = tmpl_upload_set(ctx, w, st, ts, sh, &view))) return rc;
-  const uint32_t nwg = (uint32_t)quorum_tiles(n);
-  if ((rc = tmpl_room(ctx, st, ctx->tq_tpl, n)) || (rc = tmpl_room(ctx, st, ctx->tq_ctpl, nc)) ||
-      (rc = tmpl_room(ctx, st, ctx->tq_wgh, (size_t)nwg + 1)))
-    return rc;
-  if (!ctx->tq_harena) CK(ctx->tq_harena.alloc(1));
-  const std::function<int(hipStream_t)> behind = [&](hipStream_t q) -> int {
-    CK(hipMemcpyAsync(ctx->tq_ctpl, commit_tpl, nc * sizeof(uint16_t), hipMemcpyHostToDevice, q));
-    launch_tmpl_commit_map_alt(q, (uint32_t)n, (uint32_t)nc, ctx->q_coff, ctx->tq_ctpl, alt_span, it.item_alt, ctx->tq_tpl,
-                               ctx->q_err);
-    launch_tmpl_quorum_holes(q, (uint32_t)n, ctx->sc_hit, it.var_off, it.var_bytes, ctx->tq_wgh, ctx->q_err);
-    launch_sc_scan(q, nwg, ctx->tq_wgh, ctx->tq_wgh + nwg);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(&ctx->q_h[2], ctx->tq_wgh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
-    return 0;
-  };
-  size_t m = 0;
-  if ((rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, it.power, it.flag, &m, &behind))) return rc;
-  const size_t holes = m ? ctx->q_h[2] : 0;
-  if (holes > it.var_bytes) { ctx->err = "quorum selection: checked hole bytes out of range"; return EDC_ERR_HIP; }
-  ctx->tq_have = true;
-  ctx->tq_last[0] = n;
-  ctx->tq_last[1] = m;
-  ctx->tq_last[2] = ctx->tq_last[3] = 0;
-  const uint8_t *b_vk = it.vk, *b_sig = it.sig;
-  // an empty list still runs the n = 0 batch, whose k is never read
-  const uint32_t *b_k = reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), *idx = nullptr;
-  *ctx->tq_harena = 0;
-  if (m) {
-    const uint16_t* e_tpl = ctx->tq_tpl;
-    const uint8_t* e_var = it.var;
-    const uint32_t* e_voff = it.var_off;
-    size_t e_bytes = it.var_bytes;
-    if (m < n) {
-      if ((rc = tmpl_room(ctx, st, ctx->tq_gtpl, m)) || (rc = tmpl_room(ctx, st, ctx->tq_gvoff, m + 1)) ||
-          (rc = tmpl_room(ctx, st, ctx->tq_gvar, holes + 16)))
-        return rc;
-      uint8_t* g_vk = ctx->sc_g;
-      uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
-      launch_tmpl_quorum_gather(st, (uint32_t)n, (uint32_t)m, ctx->sc_hit, ctx->sc_wg, ctx->tq_wgh, it.vk, it.sig,
-                                ctx->tq_tpl, it.var, it.var_off, ctx->sc_idx, g_vk, g_sig, ctx->tq_gtpl, ctx->tq_gvar,
-                                ctx->tq_gvoff);
-      CK(hipGetLastError());
-      idx = ctx->sc_idx;
-      b_vk = g_vk;
-      b_sig = g_sig;
-      e_tpl = ctx->tq_gtpl;
-      e_var = ctx->tq_gvar;
-      e_voff = ctx->tq_gvoff;
-      e_bytes = holes;
-    }
-    // Item::from (src/batch.rs:82-94) for the m checked votes alone: the arena is sized from m
-    if ((rc = tmpl_arena_room(ctx, w, st, m, sh, holes)) || (rc = ensure_n(ctx, m)) ||
-        (rc = tmpl_expand(ctx, w, st, view, m, e_tpl, e_var, e_voff, e_bytes, w.arena, w.off)))
-      return rc;
-    // k_tmpl_len checks the gathered items again; its flag travels behind the expansion and the
-    // batch's wait reads it before it believes a verdict
-    CK(hipMemcpyAsync(w.h_flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(ctx->tq_harena.get(), w.off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    w.check = true;
-    launch_challenge(st, (uint32_t)m, b_vk, b_sig, w.arena, w.off, ctx->kbuf);
-    CK(hipGetLastError());
-    b_k = ctx->kbuf;
-    ctx->tq_last[2] = m;
-  }
-  if (cached)
-    rc = cached_tmpl_finish(ctx, w, nc, threshold, n, m, b_vk, b_sig, b_k, idx, it.power, it.flag, z_seed, out, n_miss);
-  else
-    rc = quorum_finish(ctx, nc, threshold, n, m, b_vk, b_sig, b_k, idx, it.power, it.flag, z_seed, out);
-  w.check = false;              // also when the batch never reached its wait
-  if (rc >= 0) ctx->tq_last[3] = *ctx->tq_harena;
-  return rc;
-}
 
 // The device form's host checks, shared with edc_cached_tmpl_quorum_verify_device.
 static int tmpl_quorum_device_inputs(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -4103,54 +4026,6 @@ static int tmpl_quorum_device_inputs(edc_ctx* ctx, const edc_templates* ts, size
   *it = TmplQuorumItems{d_vk, d_sig, d_item_alt, d_var, d_var_off, var_bytes, d_power, d_flag};
   return 0;
 }
-
-static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
-                                   const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
-                                   const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var,
-                                   const uint32_t* var_off, const uint64_t* power, const uint8_t* flag,
-                                   const uint64_t* threshold, int mode, TmplShape* sh_out, size_t* n_out,
-                                   TmplQuorumItems* it_out);
-
-extern "C" {
-
-int edc_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
-                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
-                                  const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
-                                  const uint32_t* d_var_off, size_t var_bytes, const uint64_t* d_power,
-                                  const uint8_t* d_flag, const uint64_t* threshold, int mode, const uint8_t z_seed[32],
-                                  uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits,
-                                  size_t* n_checked, uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return quorum_none(out);
-  TmplShape sh;
-  size_t n;
-  TmplQuorumItems it;
-  int rc = tmpl_quorum_device_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
-                                     d_var_off, var_bytes, d_power, d_flag, threshold, mode, &sh, &n, &it);
-  if (rc) return rc;
-  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
-}
-
-int edc_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
-                           const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, const uint8_t* vk,
-                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
-                           const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
-                           const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
-                           int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return quorum_none(out);
-  TmplShape sh;
-  size_t n;
-  TmplQuorumItems it;
-  int rc = tmpl_quorum_host_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
-                                   power, flag, threshold, mode, &sh, &n, &it);
-  if (rc) return rc;
-  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
-}
-
-}  // extern "C"
 
 // The host form's checks and staging, shared with edc_cached_tmpl_quorum_verify.
 static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -4171,17 +4046,10 @@ static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t
   hipStream_t st = ctx->st();
   TmplQuorumItems it{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->q_power, ctx->q_flag};
   if (n) {                  // staged in one piece: var_off | item_alt | var, each at a 16-byte boundary
-    const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t var_bytes = var_off[n], o_alt = up16(4 * (n + 1)), o_var = up16(o_alt + n);
     if ((rc = tmpl_room(ctx, st, ctx->tq_in, o_var + var_bytes))) return rc;
-    if (key_idx) {          // 4 bytes per item over PCIe; q_cidx is free until the selection writes it
-      CK(hipMemcpyAsync(ctx->q_cidx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      launch_expand_keys(st, (uint32_t)n, ctx->q_cidx, ctx->kc_reg, ctx->kc_keys, ctx->vk);
-      CK(hipGetLastError());
-    } else {
-      CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
-    }
-    CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
+    // key indices into q_cidx, which is free until the selection writes it
+    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->q_cidx, ctx->vk, ctx->sig))) return rc;
     CK(hipMemcpyAsync(ctx->tq_in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
     if (item_alt) CK(hipMemcpyAsync(ctx->tq_in + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
     if (var_bytes) CK(hipMemcpyAsync(ctx->tq_in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
@@ -4196,7 +4064,142 @@ static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t
   return 0;
 }
 
+// The selection, then the m checked votes gathered and hashed: *list holds them with their k in
+// kbuf. From the expansion on, the slot's template workspace is armed (w.check): whoever runs the
+// batch on the list ends with tmpl_quorum_done.
+static int tmpl_quorum_list(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
+                            const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span, size_t n,
+                            const TmplQuorumItems& it, const uint64_t* threshold, int mode, ItemList* list) {
+  Slot& s = ctx->slot[0];
+  TmplWs& w = s.tw;
+  int rc = init_slot(ctx, s);
+  if (rc) return rc;
+  hipStream_t st = ctx->st();
+  TmplView view;
+  if ((rc = tmpl_upload_set(ctx, w, st, ts, sh, &view))) return rc;
+  const uint32_t nwg = (uint32_t)quorum_tiles(n);
+  if ((rc = tmpl_room(ctx, st, ctx->tq_tpl, n)) || (rc = tmpl_room(ctx, st, ctx->tq_ctpl, nc)) ||
+      (rc = tmpl_room(ctx, st, ctx->tq_wgh, (size_t)nwg + 1)))
+    return rc;
+  if (!ctx->tq_harena) CK(ctx->tq_harena.alloc(1));
+  if ((rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, it.power, it.flag))) return rc;
+  if (n) {                      // behind the selection: the all-n checks and the checked hole bytes
+    CK(hipMemcpyAsync(ctx->tq_ctpl, commit_tpl, nc * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, ctx->q_coff, ctx->tq_ctpl, alt_span, it.item_alt, ctx->tq_tpl,
+                               ctx->q_err);
+    launch_tmpl_quorum_holes(st, (uint32_t)n, ctx->sc_hit, it.var_off, it.var_bytes, ctx->tq_wgh, ctx->q_err);
+    launch_sc_scan(st, nwg, ctx->tq_wgh, ctx->tq_wgh + nwg);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(&ctx->q_h[2], ctx->tq_wgh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  }
+  size_t m = 0;
+  rc = quorum_select_read(
+      ctx, n, &m,
+      "votes: a flag above 2, a power or a commit's counted power above 2^63 - 1, or an item_alt[i] >= alt_span");
+  if (rc) return rc;
+  const size_t holes = m ? ctx->q_h[2] : 0;
+  if (holes > it.var_bytes) { ctx->err = "quorum selection: checked hole bytes out of range"; return EDC_ERR_HIP; }
+  ctx->tq_have = true;
+  ctx->tq_last[0] = n;
+  ctx->tq_last[1] = m;
+  ctx->tq_last[2] = ctx->tq_last[3] = 0;
+  // an empty list still runs the n = 0 batch, whose k is never read
+  *list = ItemList{it.vk, it.sig, reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), nullptr, m};
+  *ctx->tq_harena = 0;
+  if (!m) return 0;
+  const uint16_t* e_tpl = ctx->tq_tpl;
+  const uint8_t* e_var = it.var;
+  const uint32_t* e_voff = it.var_off;
+  size_t e_bytes = it.var_bytes;
+  if (m < n) {
+    if ((rc = tmpl_room(ctx, st, ctx->tq_gtpl, m)) || (rc = tmpl_room(ctx, st, ctx->tq_gvoff, m + 1)) ||
+        (rc = tmpl_room(ctx, st, ctx->tq_gvar, holes + 16)))
+      return rc;
+    uint8_t* g_vk = ctx->sc_g;
+    uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
+    launch_tmpl_quorum_gather(st, (uint32_t)n, (uint32_t)m, ctx->sc_hit, ctx->sc_wg, ctx->tq_wgh, it.vk, it.sig,
+                              ctx->tq_tpl, it.var, it.var_off, ctx->sc_idx, g_vk, g_sig, ctx->tq_gtpl, ctx->tq_gvar,
+                              ctx->tq_gvoff);
+    CK(hipGetLastError());
+    list->vk = g_vk;
+    list->sig = g_sig;
+    list->idx = ctx->sc_idx;
+    e_tpl = ctx->tq_gtpl;
+    e_var = ctx->tq_gvar;
+    e_voff = ctx->tq_gvoff;
+    e_bytes = holes;
+  }
+  // Item::from (src/batch.rs:82-94) for the m checked votes alone: the arena is sized from m
+  if ((rc = tmpl_arena_room(ctx, w, st, m, sh, holes)) || (rc = ensure_n(ctx, m)) ||
+      (rc = tmpl_expand(ctx, w, st, view, m, e_tpl, e_var, e_voff, e_bytes, w.arena, w.off)))
+    return rc;
+  // k_tmpl_len checks the gathered items again; its flag travels behind the expansion and the
+  // batch's wait reads it before it believes a verdict
+  CK(hipMemcpyAsync(w.h_flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(ctx->tq_harena.get(), w.off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  w.check = true;
+  launch_challenge(st, (uint32_t)m, list->vk, list->sig, w.arena, w.off, ctx->kbuf);
+  CK(hipGetLastError());
+  list->k = ctx->kbuf;
+  ctx->tq_last[2] = m;
+  return 0;
+}
+
+// behind the batch on tmpl_quorum_list's list; rc: what it returned
+static int tmpl_quorum_done(edc_ctx* ctx, int rc) {
+  ctx->slot[0].tw.check = false;        // also when the batch never reached its wait
+  if (rc >= 0) ctx->tq_last[3] = *ctx->tq_harena;
+  return rc;
+}
+
+static int tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
+                           const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span, size_t n,
+                           const TmplQuorumItems& it, const uint64_t* threshold, int mode, const uint8_t* z_seed,
+                           const QuorumOut& out) {
+  ItemList list;
+  int rc = tmpl_quorum_list(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, &list);
+  if (rc) return rc;
+  return tmpl_quorum_done(ctx, quorum_finish(ctx, nc, threshold, n, list, it.power, it.flag, z_seed, out));
+}
+
 extern "C" {
+
+int edc_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* d_item_alt,
+                                  const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
+                                  const uint32_t* d_var_off, size_t var_bytes, const uint64_t* d_power,
+                                  const uint8_t* d_flag, const uint64_t* threshold, int mode, const uint8_t z_seed[32],
+                                  uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits,
+                                  size_t* n_checked, uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
+  TmplShape sh;
+  size_t n;
+  TmplQuorumItems it;
+  if ((rc = tmpl_quorum_device_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                      d_var_off, var_bytes, d_power, d_flag, threshold, mode, &sh, &n, &it)))
+    return rc;
+  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
+}
+
+int edc_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                           const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
+                           const uint64_t* power, const uint8_t* flag, const uint64_t* threshold, int mode,
+                           const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                           int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
+  TmplShape sh;
+  size_t n;
+  TmplQuorumItems it;
+  if ((rc = tmpl_quorum_host_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
+                                    power, flag, threshold, mode, &sh, &n, &it)))
+    return rc;
+  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
+}
 
 int edc_debug_tmpl_quorum_last(const edc_ctx* ctx, uint64_t out[4]) {
   if (!ctx || !out || !ctx->tq_have) return EDC_ERR_ARG;
@@ -4226,21 +4229,16 @@ static int ensure_cq(edc_ctx* ctx, size_t n) {
   return 0;
 }
 
-// preconditions of every cached quorum entry beyond the uncached form's own
-static int cq_ready(edc_ctx* ctx) {
-  if (!ctx->sc_cap) { ctx->err = "no signature cache on this context (edc_sigcache_create)"; return EDC_ERR_ARG; }
-  return 0;
-}
-
-// The lookup of a list of `count` items (skip: the selection's bytes, null: every item is checked)
-// and the scans of its workgroup counts; the miss and hit totals travel to q_h[3] / q_h[4].
-static int cq_lookup(edc_ctx* ctx, hipStream_t st, size_t count, const uint8_t* skip, const uint8_t* vk,
-                     const uint8_t* sig, const uint32_t* k) {
-  int rc = ensure_cq(ctx, count);
+// The lookup of a list (skip: the selection's bytes, null: every item is checked) and the scans of
+// its workgroup counts; the miss and hit totals travel to q_h[3] / q_h[4].
+static int cq_lookup(edc_ctx* ctx, const ItemList& list, const uint8_t* skip) {
+  int rc = ensure_cq(ctx, list.count);
   if (rc) return rc;
-  const uint32_t nwg = (uint32_t)((count + SC_BLOCK - 1) / SC_BLOCK);
+  hipStream_t st = ctx->st();
+  const uint32_t nwg = (uint32_t)((list.count + SC_BLOCK - 1) / SC_BLOCK);
   uint32_t *wm = ctx->cq_wg, *wh = ctx->cq_wg + nwg + 1;
-  launch_sc_lookup_masked(st, ctx->sc(), (uint32_t)count, skip, vk, sig, k, ctx->cq_leave, ctx->cq_code, wm, wh);
+  launch_sc_lookup_masked(st, ctx->sc(), (uint32_t)list.count, skip, list.vk, list.sig, list.k, ctx->cq_leave, ctx->cq_code,
+                          wm, wh);
   launch_sc_scan(st, nwg, wm, wm + nwg);
   launch_sc_scan(st, nwg, wh, wh + nwg);
   CK(hipGetLastError());
@@ -4267,79 +4265,62 @@ static int cq_counts(edc_ctx* ctx, size_t n, size_t m, size_t hashed, size_t* mi
   return 0;
 }
 
-// A checked cached quorum commit set whose items (vk, sig, k, power, flag) are on the device;
-// hashed: the items SHA-512 ran over for this call.
+// A checked cached quorum commit set whose items (all: vk, sig, k of the n votes; power, flag) are
+// on the device; hashed: the items SHA-512 ran over for this call.
 static int cached_quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
-                             size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint32_t* d_k,
-                             const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
-                             size_t* n_miss, size_t hashed) {
-  const std::function<int(hipStream_t)> behind = [&](hipStream_t q) -> int {
-    return cq_lookup(ctx, q, n, ctx->sc_hit, d_vk, d_sig, d_k);
-  };
+                             const ItemList& all, const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
+                             const QuorumOut& out, size_t hashed) {
+  const size_t n = all.count;
   size_t m = 0, c = 0;
-  int rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag, &m, &behind, false);
-  if (rc || (rc = cq_counts(ctx, n, m, hashed, &c))) return rc;
-  hipStream_t st = ctx->st();
-  const uint8_t *b_vk = d_vk, *b_sig = d_sig;
-  // an empty list still runs the n = 0 batch, whose k is never read
-  const uint32_t *b_k = c ? d_k : reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), *idx = nullptr;
-  if (c && c < n) {
-    uint8_t* g_vk = ctx->sc_g;
-    uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
-    uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->sc_cap_n * 64);
-    launch_sc_compact(st, (uint32_t)n, ctx->cq_leave, ctx->cq_wg, d_vk, d_sig, d_k, ctx->sc_idx, g_vk, g_sig, g_k);
-    CK(hipGetLastError());
-    idx = ctx->sc_idx;
-    b_vk = g_vk;
-    b_sig = g_sig;
-    b_k = g_k;
-  }
-  const QuorumCached cq{m, n, ctx->cq_code, nullptr, d_vk, d_sig, d_k, n_miss};
-  return quorum_finish(ctx, nc, threshold, n, c, b_vk, b_sig, b_k, idx, d_power, d_flag, z_seed, out, &cq);
+  ItemList miss;
+  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag);
+  if (rc) return rc;
+  // behind the selection: the masked lookup, whose counts travel in the same read-back
+  if (n && (rc = cq_lookup(ctx, all, ctx->sc_hit))) return rc;
+  if ((rc = quorum_select_read(ctx, n, &m)) || (rc = cq_counts(ctx, n, m, hashed, &c))) return rc;
+  if ((rc = quorum_gather(ctx, all, c, ctx->cq_leave, ctx->cq_wg, sc_area(ctx), &miss))) return rc;
+  const QuorumCached cq{m, ctx->cq_code, all};
+  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq);
 }
 
-// tmpl_quorum_run's last step in a cached form: the m checked votes (b_*: gathered, or the caller's
-// arrays when m == n; idx: their queue positions) have their k in kbuf.
-static int cached_tmpl_finish(edc_ctx* ctx, TmplWs& w, size_t nc, const uint64_t* threshold, size_t n, size_t m,
-                              const uint8_t* b_vk, const uint8_t* b_sig, const uint32_t* b_k, const uint32_t* idx,
-                              const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
-                              size_t* n_miss) {
+// tmpl_quorum_list's list (the m checked votes, their k in kbuf) through the table and the batch:
+// the lookup, the second read-back, the counts, the misses gathered, quorum_finish.
+static int cached_tmpl_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, const ItemList& list,
+                              const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
+                              const QuorumOut& out) {
   hipStream_t st = ctx->st();
+  const size_t m = list.count;
   int rc;
   if (m) {
-    if ((rc = cq_lookup(ctx, st, m, nullptr, b_vk, b_sig, b_k))) return rc;
+    if ((rc = cq_lookup(ctx, list, nullptr))) return rc;
     CK(hipStreamSynchronize(st));       // the second read-back: the miss count sizes the batch
-    if (*w.h_flag) {                    // what the batch's wait would find, before anything is counted
+    if (*ctx->slot[0].tw.h_flag) {      // what the batch's wait would find, before anything is counted
       ctx->err = "templated items: template index or hole offsets out of range";
       return EDC_ERR_ARG;
     }
   }
   size_t c = 0;
   if ((rc = cq_counts(ctx, n, m, m, &c))) return rc;
-  const uint8_t *l_vk = b_vk, *l_sig = b_sig;
-  const uint32_t *l_k = b_k, *lidx = nullptr;
-  if (c && c < m) {
+  if (c && c < m) {                     // the second staging area, when something is gathered
     CK(grow_group(ctx->cq_cap_g, m, item_cap, sync_of(st), [&](size_t cap) {
       return alloc_all(sized(ctx->cq_g, cap * 128), sized(ctx->cq_idx, cap));
     }));
-    uint8_t* g_vk = ctx->cq_g;
-    uint8_t* g_sig = g_vk + ctx->cq_cap_g * 32;
-    uint32_t* g_k = reinterpret_cast<uint32_t*>(g_sig + ctx->cq_cap_g * 64);
-    launch_sc_compact(st, (uint32_t)m, ctx->cq_leave, ctx->cq_wg, b_vk, b_sig, b_k, ctx->cq_idx, g_vk, g_sig, g_k);
-    CK(hipGetLastError());
-    lidx = ctx->cq_idx;
-    l_vk = g_vk;
-    l_sig = g_sig;
-    l_k = g_k;
   }
-  const QuorumCached cq{m, m, ctx->cq_code, idx, b_vk, b_sig, b_k, n_miss};
-  return quorum_finish(ctx, nc, threshold, n, c, l_vk, l_sig, l_k, lidx, d_power, d_flag, z_seed, out, &cq);
+  ItemList miss;
+  if ((rc = quorum_gather(ctx, list, c, ctx->cq_leave, ctx->cq_wg, GatherArea{ctx->cq_g, ctx->cq_cap_g, ctx->cq_idx}, &miss)))
+    return rc;
+  const QuorumCached cq{m, ctx->cq_code, list};
+  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq);
 }
 
-// nc == 0: nothing to verify
-static int cached_quorum_none(const QuorumOut& out, size_t* n_miss) {
-  if (n_miss) *n_miss = 0;
-  return quorum_none(out);
+static int cached_tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
+                                  const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span, size_t n,
+                                  const TmplQuorumItems& it, const uint64_t* threshold, int mode, const uint8_t* z_seed,
+                                  const QuorumOut& out) {
+  ItemList list;
+  int rc = tmpl_quorum_list(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, &list);
+  if (rc) return rc;
+  return tmpl_quorum_done(ctx, cached_tmpl_finish(ctx, nc, threshold, n, list, it.power, it.flag, z_seed, out));
 }
 
 extern "C" {
@@ -4350,18 +4331,16 @@ int edc_cached_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* com
                                     const uint64_t* threshold, int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts,
                                     uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits, size_t* n_checked,
                                     size_t* n_miss, uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  int rc = cq_ready(ctx);
-  if (rc) return rc;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return cached_quorum_none(out, n_miss);
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, n_miss, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, true, nc, out, &rc)) return rc;
   size_t n;
   const uint32_t* k;
   if ((rc = quorum_device_inputs(ctx, nc, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k, d_power, d_flag, threshold, mode,
                                  &n, &k)))
     return rc;
-  return cached_quorum_run(ctx, nc, commit_off, threshold, mode, n, d_vk, d_sig, k, d_power, d_flag, z_seed, out, n_miss,
-                           d_k ? 0 : n);
+  return cached_quorum_run(ctx, nc, commit_off, threshold, mode, ItemList{d_vk, d_sig, k, nullptr, n}, d_power, d_flag,
+                           z_seed, out, d_k ? 0 : n);
 }
 
 int edc_cached_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
@@ -4369,16 +4348,14 @@ int edc_cached_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
                              const uint8_t* k, const uint64_t* power, const uint8_t* flag, const uint64_t* threshold,
                              int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
                              uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss, uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  int rc = cq_ready(ctx);
-  if (rc) return rc;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return cached_quorum_none(out, n_miss);
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, n_miss, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, true, nc, out, &rc)) return rc;
   size_t n;
   if ((rc = quorum_host_inputs(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, power, flag, threshold, mode, &n)))
     return rc;
-  return cached_quorum_run(ctx, nc, commit_off, threshold, mode, n, ctx->vk, ctx->sig, ctx->kbuf, ctx->q_power,
-                           ctx->q_flag, z_seed, out, n_miss, k ? 0 : n);
+  return cached_quorum_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n},
+                           ctx->q_power, ctx->q_flag, z_seed, out, k ? 0 : n);
 }
 
 int edc_cached_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -4389,19 +4366,16 @@ int edc_cached_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, 
                                          const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
                                          uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss,
                                          uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  int rc = cq_ready(ctx);
-  if (rc) return rc;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return cached_quorum_none(out, n_miss);
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, n_miss, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, true, nc, out, &rc)) return rc;
   TmplShape sh;
   size_t n;
   TmplQuorumItems it;
   if ((rc = tmpl_quorum_device_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
                                       d_var_off, var_bytes, d_power, d_flag, threshold, mode, &sh, &n, &it)))
     return rc;
-  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out, true,
-                         n_miss);
+  return cached_tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
 }
 
 int edc_cached_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -4411,19 +4385,16 @@ int edc_cached_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t 
                                   const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
                                   uint64_t* tally, int* n_bad_commits, size_t* n_checked, size_t* n_miss,
                                   uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  int rc = cq_ready(ctx);
-  if (rc) return rc;
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, check8};
-  if (!nc) return cached_quorum_none(out, n_miss);
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, n_miss, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, true, nc, out, &rc)) return rc;
   TmplShape sh;
   size_t n;
   TmplQuorumItems it;
   if ((rc = tmpl_quorum_host_inputs(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var,
                                     var_off, power, flag, threshold, mode, &sh, &n, &it)))
     return rc;
-  return tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out, true,
-                         n_miss);
+  return cached_tmpl_quorum_run(ctx, ts, sh, nc, commit_off, commit_tpl, alt_span, n, it, threshold, mode, z_seed, out);
 }
 
 int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
@@ -4772,16 +4743,9 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
     if (rc) return rc;
     if (v->chal_pending) CK(hipStreamWaitEvent(v->cs, v->ev_chal, 0));
   }
-  if (key_idx) {
-    // (the previous indexed append's expansion reads v->idx on the copy stream)
-    CK(grow(v->idx, m, item_cap, sync_of(v->cs)));
-    CK(hipMemcpyAsync(v->idx, key_idx, m * sizeof(uint32_t), hipMemcpyHostToDevice, v->cs));
-    launch_expand_keys(v->cs, (uint32_t)m, v->idx, ctx->kc_reg, ctx->kc_keys, r_vk);
-    CK(hipGetLastError());
-  } else {
-    CK(hipMemcpyAsync(r_vk, vk, m * 32, hipMemcpyHostToDevice, v->cs));
-  }
-  CK(hipMemcpyAsync(r_sig, sig, m * 64, hipMemcpyHostToDevice, v->cs));
+  // (the previous indexed append's expansion reads v->idx on the copy stream)
+  if (key_idx) CK(grow(v->idx, m, item_cap, sync_of(v->cs)));
+  if ((rc = stage_keys_sigs(ctx, v->cs, m, vk, key_idx, sig, v->idx, r_vk, r_sig))) return rc;
   if (k) {
     CK(hipMemcpyAsync(r_k, k, m * 32, hipMemcpyHostToDevice, v->cs));
   } else if (tm) {

@@ -410,3 +410,37 @@ def test_python_batch_surface(ceng, edc, g, qsets):
         assert [c for per in codes for c in per] == j["item_verdicts"]
         assert ceng.cached_quorum_last()[3] == expect_miss
     assert edc.batch.verify_quorum(vs, powers, flags, Q.thr, light=True, engine=ceng) == (verdicts, tally, codes)
+
+
+# ---- 10: the host form with registered keys ----
+
+@pytest.mark.parametrize("light", [False, True], ids=["full", "light"])
+def test_host_form_with_key_idx(ceng, qsets, light):
+    """quorum_verify_cached(key_idx=...) after keycache_load, cold and then warm: all eight fields are
+    those of the same call with vks= at the same table state, and everything but n_miss is
+    quorum_verify(key_idx=...)'s. check8 belongs to the list that was verified, so the warm call's,
+    whose list is empty, is held to the vks= call's alone."""
+    Q = qsets("valid")
+    keys = list(dict.fromkeys(Q.vks))
+    pos = {k: i for i, k in enumerate(keys)}
+    idx = [pos[k] for k in Q.vks]
+    seed = random.Random("hostidx%d" % light).randbytes(32)
+    ceng.keycache_load(keys)
+    try:
+        want = ceng.quorum_verify(Q.off, Q.sigs, Q.power, Q.flag, Q.thr, seed, light=light, key_idx=idx, msgs=Q.msgs)
+        runs = {}
+        for how, kw in (("vks", dict(vks=Q.vks)), ("key_idx", dict(key_idx=idx))):
+            ceng.sigcache_clear()
+            runs[how] = [ceng.quorum_verify_cached(Q.off, Q.sigs, Q.power, Q.flag, Q.thr, seed, light=light, msgs=Q.msgs, **kw)
+                         for _ in ("cold", "warm")]
+    finally:
+        ceng.keycache_clear()
+    for got, same in zip(runs["key_idx"], runs["vks"]):
+        assert sorted(got) == sorted(KEYS + ("n_miss",))
+        assert got == same
+    cold, warm = runs["key_idx"]
+    for key in KEYS:
+        assert cold[key] == want[key], key
+    for key in KEYS[:-1]:
+        assert warm[key] == want[key], key
+    assert cold["n_miss"] == cold["n_checked"] > 0 and warm["n_miss"] == 0      # every vote of this set is valid

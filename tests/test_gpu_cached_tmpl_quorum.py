@@ -209,3 +209,35 @@ def test_argument_errors_cover_all_items(ceng, edc, g, qsets):
         assert (got["code"], got["n_checked"], got["n_miss"]) == (0, 0, 0)
     finally:
         eng.close()
+
+
+def test_host_form_with_key_idx(ceng, qsets):
+    """quorum_verify_templated_cached(key_idx=...) after keycache_load, cold and then warm: all eight
+    fields are those of the same call with vks= at the same table state, and everything but n_miss
+    is quorum_verify_templated(key_idx=...)'s. check8 belongs to the list that was verified, so the
+    warm call's, whose list is empty, is held to the vks= call's alone."""
+    Q, T = qsets("valid"), qsets.templates
+    S = Q.S
+    keys = list(dict.fromkeys(Q.vks))
+    pos = {k: i for i, k in enumerate(keys)}
+    idx = [pos[k] for k in Q.vks]
+    seed = random.Random("tmplhostidx").randbytes(32)
+    ceng.keycache_load(keys)
+    try:
+        want = ceng.quorum_verify_templated(T, Q.off, S.commit_tpl, Q.sigs, S.holes, Q.power, Q.flag, Q.thr, seed, key_idx=idx)
+        runs = {}
+        for how, kw in (("vks", dict(vks=Q.vks)), ("key_idx", dict(key_idx=idx))):
+            ceng.sigcache_clear()
+            runs[how] = [ceng.quorum_verify_templated_cached(T, Q.off, S.commit_tpl, Q.sigs, S.holes, Q.power, Q.flag, Q.thr,
+                                                             seed, **kw) for _ in ("cold", "warm")]
+    finally:
+        ceng.keycache_clear()
+    for got, same in zip(runs["key_idx"], runs["vks"]):
+        assert sorted(got) == sorted(KEYS + ("n_miss",))
+        assert got == same
+    cold, warm = runs["key_idx"]
+    for key in KEYS:
+        assert cold[key] == want[key], key
+    for key in KEYS[:-1]:
+        assert warm[key] == want[key], key
+    assert cold["n_miss"] == cold["n_checked"] > 0 and warm["n_miss"] == 0      # every vote of this set is valid
