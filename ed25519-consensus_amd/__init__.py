@@ -448,7 +448,7 @@ class Engine:
         self._lock = threading.Lock()
         self._kc_keys = set()          # host mirror of the key cache's key bytes (keycache_missing)
         self._host_inflight = {}        # ticket -> host buffers borrowed by edc_batch_submit
-        self._commits_inflight = {}     # ticket -> (nc, n, host buffers) of a submitted commit set
+        self._commits_inflight = {}     # ticket -> (nc, n, keep) of a submitted commit set (_commits_call)
         self._verifiers = weakref.WeakSet()   # open batch.StreamVerifier objects (destroyed before the context)
 
     def close(self):
@@ -645,70 +645,20 @@ class Engine:
     def _commits_result(rc, nc, n, out):
         return rc, list(out[0].raw[:nc]), list(out[1].raw[:n]), out[2].value
 
+    # The forms' own arguments as _commits_call and _quorum_call take them: (nc, n, the arguments
+    # between ctx and z_seed, whatever else they point into).
     def _commits_host(self, commit_off, sigs, vks, key_idx, msgs, ks):
         n = len(sigs)
         nc, off = self._commit_offsets(commit_off)
         vkb, idx = _tmpl_keys(n, vks, key_idx)
         arena, moff = _arena(msgs) if msgs is not None else (None, None)
         kb = None if ks is None else (b"".join(ks) or b"\0")
-        return nc, n, (off, vkb, idx, b"".join(sigs) or b"\0", arena, moff, kb)
+        return nc, n, (nc, off, vkb, idx, b"".join(sigs) or b"\0", arena, moff, kb)
 
-    def commits_verify(self, commit_off, sigs, z_seed, vks=None, key_idx=None, msgs=None, ks=None):
-        """edc_commits_verify: host buffers, synchronous. Exactly one of vks and key_idx (positions
-        in the last keycache_load list), exactly one of msgs and ks (prehashed)."""
-        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
-        out = self._commits_out(nc, n)
-        with self._lock:
-            rc = self.lib.edc_commits_verify(self.ctx, nc, *b, bytes(z_seed), out[0], out[1], ctypes.byref(out[2]))
-        self._check(rc)
-        return self._commits_result(rc, nc, n, out)
-
-    def commits_submit(self, commit_off, sigs, z_seed, vks=None, key_idx=None, msgs=None, ks=None):
-        """edc_commits_submit: a ticket for commits_wait; the host buffers are kept alive here until then."""
-        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
-        seed = bytes(z_seed)
-        with self._lock:
-            t = self.lib.edc_commits_submit(self.ctx, nc, *b, seed)
-            if t < 0:
-                self._check(t)
-            self._commits_inflight[t] = (nc, n, b, seed)
-        return t
-
-    def commits_verify_templated(self, templates, commit_off, commit_tpl, sigs, holes, z_seed, vks=None, key_idx=None,
-                                 var_off=None):
-        """edc_tmpl_commits_verify: one template per commit (commit_tpl[c]); the items carry their
-        signature, hole and key or key index."""
-        n = len(sigs)
+    def _commits_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k):
         nc, off = self._commit_offsets(commit_off)
-        ts, _keep = templates.struct()
-        _, var, voff = _tmpl_items([0] * n, holes, var_off)
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        out = self._commits_out(nc, n)
-        with self._lock:
-            rc = self.lib.edc_tmpl_commits_verify(self.ctx, ctypes.byref(ts), nc, off, ctpl, vkb, idx,
-                                                  b"".join(sigs) or b"\0", var, voff, bytes(z_seed), out[0], out[1],
-                                                  ctypes.byref(out[2]))
-        self._check(rc)
-        return self._commits_result(rc, nc, n, out)
-
-    def commits_submit_templated(self, templates, commit_off, commit_tpl, sigs, holes, z_seed, vks=None, key_idx=None,
-                                 var_off=None):
-        """edc_tmpl_commits_submit: a ticket for commits_wait."""
-        n = len(sigs)
-        nc, off = self._commit_offsets(commit_off)
-        ts, keep = templates.struct()
-        _, var, voff = _tmpl_items([0] * n, holes, var_off)
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        bufs = (ts, keep, off, ctpl, vkb, idx, b"".join(sigs) or b"\0", var, voff, bytes(z_seed))
-        with self._lock:
-            t = self.lib.edc_tmpl_commits_submit(self.ctx, ctypes.byref(ts), nc, off, ctpl, vkb, idx, bufs[6], var, voff,
-                                                 bufs[9])
-            if t < 0:
-                self._check(t)
-            self._commits_inflight[t] = (nc, n, bufs, None)
-        return t
+        p = self._dev_ptr
+        return nc, off[nc] if nc else 0, (nc, off, p(d_vk), p(d_sig), p(d_msg), p(d_msg_off), p(d_k))
 
     # Template variants: every commit owns the window [commit_tpl[c], commit_tpl[c] + alt_span) of the
     # set and item i takes template commit_tpl[c] + item_alt[i] (item_alt None: all zeros).
@@ -720,103 +670,114 @@ class Engine:
             raise ValueError("item_alt entries are uint8")
         return bytes(bytearray(int(a) for a in item_alt)) or b"\0"
 
-    def commits_verify_templated_alt(self, templates, commit_off, commit_tpl, alt_span, item_alt, sigs, holes, z_seed,
-                                     vks=None, key_idx=None, var_off=None):
-        """edc_tmpl_commits_verify_alt: commits_verify_templated with a variant byte per item."""
-        n = len(sigs)
-        nc, off = self._commit_offsets(commit_off)
-        ts, _keep = templates.struct()
-        _, var, voff = _tmpl_items([0] * n, holes, var_off)
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        out = self._commits_out(nc, n)
-        with self._lock:
-            rc = self.lib.edc_tmpl_commits_verify_alt(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
-                                                      self._item_alt(item_alt), vkb, idx, b"".join(sigs) or b"\0", var,
-                                                      voff, bytes(z_seed), out[0], out[1], ctypes.byref(out[2]))
-        self._check(rc)
-        return self._commits_result(rc, nc, n, out)
-
-    def commits_submit_templated_alt(self, templates, commit_off, commit_tpl, alt_span, item_alt, sigs, holes, z_seed,
-                                     vks=None, key_idx=None, var_off=None):
-        """edc_tmpl_commits_submit_alt: a ticket for commits_wait."""
+    def _commits_tmpl_host(self, templates, commit_off, commit_tpl, sigs, holes, vks, key_idx, var_off, alt=None):
+        """alt: None for the one-template forms, (alt_span, item_alt) for the forms with variants."""
         n = len(sigs)
         nc, off = self._commit_offsets(commit_off)
         ts, keep = templates.struct()
         _, var, voff = _tmpl_items([0] * n, holes, var_off)
         ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
         vkb, idx = _tmpl_keys(n, vks, key_idx)
-        bufs = (ts, keep, off, ctpl, vkb, idx, b"".join(sigs) or b"\0", var, voff, bytes(z_seed), self._item_alt(item_alt))
-        with self._lock:
-            t = self.lib.edc_tmpl_commits_submit_alt(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span, bufs[10], vkb,
-                                                     idx, bufs[6], var, voff, bufs[9])
-            if t < 0:
-                self._check(t)
-            self._commits_inflight[t] = (nc, n, bufs, None)
-        return t
+        variants = () if alt is None else (alt[0], self._item_alt(alt[1]))
+        return nc, n, (ctypes.byref(ts), nc, off, ctpl, *variants, vkb, idx, b"".join(sigs) or b"\0", var, voff), keep
 
     @staticmethod
     def _dev_ptr(x):
         """A device pointer given as an int, None, or a torch tensor (its data_ptr())."""
         return x.data_ptr() if hasattr(x, "data_ptr") else x
 
+    def _commits_tmpl_device(self, templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var, d_var_off,
+                             var_bytes):
+        nc, off = self._commit_offsets(commit_off)
+        ts, keep = templates.struct()
+        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+        p = self._dev_ptr
+        return nc, off[nc] if nc else 0, (ctypes.byref(ts), nc, off, ctpl, alt_span, p(d_item_alt), p(d_vk), p(d_sig),
+                                          p(d_var), p(d_var_off), var_bytes), (keep, d_item_alt, d_vk, d_sig, d_var, d_var_off)
+
+    def _commits_call(self, fn, form, z_seed, submit=False):
+        """A verify fn(ctx, *form's arguments, z_seed, <the three outputs>) -> the result tuple, or a
+        submit fn(ctx, *form's arguments, z_seed) -> its ticket, recorded as (nc, n, keep) until
+        commits_wait: keep is the form and the seed, all the entry may still read. A refused submit
+        records nothing."""
+        nc, n, args = form[:3]
+        seed = bytes(z_seed)
+        if submit:
+            with self._lock:
+                t = fn(self.ctx, *args, seed)
+                if t < 0:
+                    self._check(t)
+                self._commits_inflight[t] = (nc, n, (form, seed))
+            return t
+        out = self._commits_out(nc, n)
+        with self._lock:
+            rc = fn(self.ctx, *args, seed, out[0], out[1], ctypes.byref(out[2]))
+        self._check(rc)
+        return self._commits_result(rc, nc, n, out)
+
+    def commits_verify(self, commit_off, sigs, z_seed, vks=None, key_idx=None, msgs=None, ks=None):
+        """edc_commits_verify: host buffers, synchronous. Exactly one of vks and key_idx (positions
+        in the last keycache_load list), exactly one of msgs and ks (prehashed)."""
+        return self._commits_call(self.lib.edc_commits_verify, self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks),
+                                  z_seed)
+
+    def commits_submit(self, commit_off, sigs, z_seed, vks=None, key_idx=None, msgs=None, ks=None):
+        """edc_commits_submit: a ticket for commits_wait; the host buffers are kept alive here until then."""
+        return self._commits_call(self.lib.edc_commits_submit, self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks),
+                                  z_seed, submit=True)
+
+    def commits_verify_templated(self, templates, commit_off, commit_tpl, sigs, holes, z_seed, vks=None, key_idx=None,
+                                 var_off=None):
+        """edc_tmpl_commits_verify: one template per commit (commit_tpl[c]); the items carry their
+        signature, hole and key or key index."""
+        form = self._commits_tmpl_host(templates, commit_off, commit_tpl, sigs, holes, vks, key_idx, var_off)
+        return self._commits_call(self.lib.edc_tmpl_commits_verify, form, z_seed)
+
+    def commits_submit_templated(self, templates, commit_off, commit_tpl, sigs, holes, z_seed, vks=None, key_idx=None,
+                                 var_off=None):
+        """edc_tmpl_commits_submit: a ticket for commits_wait."""
+        form = self._commits_tmpl_host(templates, commit_off, commit_tpl, sigs, holes, vks, key_idx, var_off)
+        return self._commits_call(self.lib.edc_tmpl_commits_submit, form, z_seed, submit=True)
+
+    def commits_verify_templated_alt(self, templates, commit_off, commit_tpl, alt_span, item_alt, sigs, holes, z_seed,
+                                     vks=None, key_idx=None, var_off=None):
+        """edc_tmpl_commits_verify_alt: commits_verify_templated with a variant byte per item."""
+        form = self._commits_tmpl_host(templates, commit_off, commit_tpl, sigs, holes, vks, key_idx, var_off,
+                                       (alt_span, item_alt))
+        return self._commits_call(self.lib.edc_tmpl_commits_verify_alt, form, z_seed)
+
+    def commits_submit_templated_alt(self, templates, commit_off, commit_tpl, alt_span, item_alt, sigs, holes, z_seed,
+                                     vks=None, key_idx=None, var_off=None):
+        """edc_tmpl_commits_submit_alt: a ticket for commits_wait."""
+        form = self._commits_tmpl_host(templates, commit_off, commit_tpl, sigs, holes, vks, key_idx, var_off,
+                                       (alt_span, item_alt))
+        return self._commits_call(self.lib.edc_tmpl_commits_submit_alt, form, z_seed, submit=True)
+
     def commits_verify_templated_device(self, templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig,
                                         d_var, d_var_off, var_bytes, z_seed):
         """edc_tmpl_commits_verify_device: keys, signatures, holes and variant bytes as torch tensors
         or device pointers (ints; d_item_alt None: all zeros); commit_off, commit_tpl and the set on the host."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        ts, _keep = templates.struct()
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        out = self._commits_out(nc, n)
-        p = self._dev_ptr
-        with self._lock:
-            rc = self.lib.edc_tmpl_commits_verify_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
-                                                         p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
-                                                         var_bytes, bytes(z_seed), out[0], out[1], ctypes.byref(out[2]))
-        self._check(rc)
-        return self._commits_result(rc, nc, n, out)
+        form = self._commits_tmpl_device(templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                         d_var_off, var_bytes)
+        return self._commits_call(self.lib.edc_tmpl_commits_verify_device, form, z_seed)
 
     def commits_submit_templated_device(self, templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig,
                                         d_var, d_var_off, var_bytes, z_seed):
         """edc_tmpl_commits_submit_device: a ticket for commits_wait; the device arrays (kept alive
         here when given as tensors) stay the caller's until then."""
-        nc, off = self._commit_offsets(commit_off)
-        ts, keep = templates.struct()
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        seed = bytes(z_seed)
-        p = self._dev_ptr
-        bufs = (ts, keep, off, ctpl, seed, d_item_alt, d_vk, d_sig, d_var, d_var_off)
-        with self._lock:
-            t = self.lib.edc_tmpl_commits_submit_device(self.ctx, ctypes.byref(ts), nc, off, ctpl, alt_span,
-                                                        p(d_item_alt), p(d_vk), p(d_sig), p(d_var), p(d_var_off),
-                                                        var_bytes, seed)
-            if t < 0:
-                self._check(t)
-            self._commits_inflight[t] = (nc, off[nc] if nc else 0, bufs, None)
-        return t
+        form = self._commits_tmpl_device(templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                         d_var_off, var_bytes)
+        return self._commits_call(self.lib.edc_tmpl_commits_submit_device, form, z_seed, submit=True)
 
     def commits_verify_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, z_seed, d_k=None):
         """edc_commits_verify_device (device pointers as ints; d_k given: the messages are not read)."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        out = self._commits_out(nc, n)
-        with self._lock:
-            rc = self.lib.edc_commits_verify_device(self.ctx, nc, off, d_vk, d_sig, d_msg, d_msg_off, d_k, bytes(z_seed),
-                                                    out[0], out[1], ctypes.byref(out[2]))
-        self._check(rc)
-        return self._commits_result(rc, nc, n, out)
+        return self._commits_call(self.lib.edc_commits_verify_device,
+                                  self._commits_device(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k), z_seed)
 
     def commits_submit_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, z_seed, d_k=None):
         """edc_commits_submit_device: a ticket for commits_wait; the device arrays stay the caller's."""
-        nc, off = self._commit_offsets(commit_off)
-        seed = bytes(z_seed)
-        with self._lock:
-            t = self.lib.edc_commits_submit_device(self.ctx, nc, off, d_vk, d_sig, d_msg, d_msg_off, d_k, seed)
-            if t < 0:
-                self._check(t)
-            self._commits_inflight[t] = (nc, off[nc] if nc else 0, (off,), seed)
-        return t
+        return self._commits_call(self.lib.edc_commits_submit_device,
+                                  self._commits_device(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k), z_seed, submit=True)
 
     def commits_wait(self, ticket):
         """edc_commits_wait: the results of a submitted commit set; a failed union runs its
@@ -897,49 +858,19 @@ class Engine:
         votes = self._dev_ptr(d_power), self._dev_ptr(d_flag), self._quorum_thresholds(form[0], thresholds)
         return self._quorum_call(fn, cached, form, votes, z_seed, light)
 
-    # the forms' own arguments, as _quorum_call takes them
-    def _quorum_host_form(self, commit_off, sigs, vks, key_idx, msgs, ks):
-        nc, n, b = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
-        return nc, n, (nc,) + b
-
-    def _quorum_device_form(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k):
-        nc, off = self._commit_offsets(commit_off)
-        p = self._dev_ptr
-        return nc, off[nc] if nc else 0, (nc, off, p(d_vk), p(d_sig), p(d_msg), p(d_msg_off), p(d_k))
-
-    def _tmpl_quorum_host_form(self, templates, commit_off, commit_tpl, sigs, holes, alt_span, item_alt, vks, key_idx,
-                               var_off):
-        n = len(sigs)
-        nc, off = self._commit_offsets(commit_off)
-        ts, keep = templates.struct()
-        _, var, voff = _tmpl_items([0] * n, holes, var_off)
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        return nc, n, (ctypes.byref(ts), nc, off, ctpl, alt_span, self._item_alt(item_alt), vkb, idx,
-                       b"".join(sigs) or b"\0", var, voff), keep
-
-    def _tmpl_quorum_device_form(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
-                                 alt_span, d_item_alt):
-        nc, off = self._commit_offsets(commit_off)
-        ts, keep = templates.struct()
-        ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
-        p = self._dev_ptr
-        return nc, off[nc] if nc else 0, (ctypes.byref(ts), nc, off, ctpl, alt_span, p(d_item_alt), p(d_vk), p(d_sig),
-                                          p(d_var), p(d_var_off), var_bytes), keep
-
     def quorum_verify(self, commit_off, sigs, powers, flags, thresholds, z_seed, light=True, vks=None, key_idx=None,
                       msgs=None, ks=None):
         """edc_quorum_verify: host buffers, synchronous. Exactly one of vks and key_idx, exactly one
         of msgs and ks, as commits_verify. Returns a dict: code, commit_verdicts, item_verdicts
         (NOT_CHECKED for the votes left out), tally, n_bad_commits, n_checked, check8."""
-        form = self._quorum_host_form(commit_off, sigs, vks, key_idx, msgs, ks)
+        form = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
         return self._quorum_host(self.lib.edc_quorum_verify, False, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_power, d_flag, thresholds, z_seed,
                              light=True, d_k=None):
         """edc_quorum_verify_device: the items, powers (uint64) and flags (uint8) as torch tensors or
         device pointers; commit_off and thresholds on the host. d_k given: the messages are not read."""
-        form = self._quorum_device_form(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k)
+        form = self._commits_device(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k)
         return self._quorum_device(self.lib.edc_quorum_verify_device, False, form, d_power, d_flag, thresholds, z_seed, light)
 
     # ---- templated quorum commit sets (edc_tmpl_quorum_*): select first, hash only the checked votes ----
@@ -948,8 +879,8 @@ class Engine:
         """edc_tmpl_quorum_verify: host buffers, synchronous; templates, commit_tpl, alt_span, item_alt
         and holes as commits_verify_templated_alt, powers / flags / thresholds as quorum_verify.
         Exactly one of vks and key_idx. Returns the dict quorum_verify returns."""
-        form = self._tmpl_quorum_host_form(templates, commit_off, commit_tpl, sigs, holes, alt_span, item_alt, vks, key_idx,
-                                           var_off)
+        form = self._commits_tmpl_host(templates, commit_off, commit_tpl, sigs, holes, vks, key_idx, var_off,
+                                       (alt_span, item_alt))
         return self._quorum_host(self.lib.edc_tmpl_quorum_verify, False, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_templated_device(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
@@ -957,8 +888,8 @@ class Engine:
         """edc_tmpl_quorum_verify_device: keys, signatures, holes, variant bytes, powers (uint64) and
         flags (uint8) as torch tensors or device pointers (d_item_alt None: all zeros); commit_off,
         commit_tpl, thresholds and the set on the host. Returns the dict quorum_verify returns."""
-        form = self._tmpl_quorum_device_form(templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
-                                             alt_span, d_item_alt)
+        form = self._commits_tmpl_device(templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                         d_var_off, var_bytes)
         return self._quorum_device(self.lib.edc_tmpl_quorum_verify_device, False, form, d_power, d_flag, thresholds, z_seed,
                                    light)
 
@@ -968,13 +899,13 @@ class Engine:
                              key_idx=None, msgs=None, ks=None):
         """edc_cached_quorum_verify: quorum_verify through the verified-signature table. Returns
         quorum_verify's dict plus n_miss, the size of the list that was verified."""
-        form = self._quorum_host_form(commit_off, sigs, vks, key_idx, msgs, ks)
+        form = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
         return self._quorum_host(self.lib.edc_cached_quorum_verify, True, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_cached_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_power, d_flag, thresholds, z_seed,
                                     light=True, d_k=None):
         """edc_cached_quorum_verify_device: quorum_verify_device through the verified-signature table."""
-        form = self._quorum_device_form(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k)
+        form = self._commits_device(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k)
         return self._quorum_device(self.lib.edc_cached_quorum_verify_device, True, form, d_power, d_flag, thresholds, z_seed,
                                    light)
 
@@ -982,8 +913,8 @@ class Engine:
                                        z_seed, light=True, alt_span=1, item_alt=None, vks=None, key_idx=None,
                                        var_off=None):
         """edc_cached_tmpl_quorum_verify: quorum_verify_templated through the verified-signature table."""
-        form = self._tmpl_quorum_host_form(templates, commit_off, commit_tpl, sigs, holes, alt_span, item_alt, vks, key_idx,
-                                           var_off)
+        form = self._commits_tmpl_host(templates, commit_off, commit_tpl, sigs, holes, vks, key_idx, var_off,
+                                       (alt_span, item_alt))
         return self._quorum_host(self.lib.edc_cached_tmpl_quorum_verify, True, form, powers, flags, thresholds, z_seed, light)
 
     def quorum_verify_templated_cached_device(self, templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off,
@@ -991,8 +922,8 @@ class Engine:
                                               d_item_alt=None):
         """edc_cached_tmpl_quorum_verify_device: quorum_verify_templated_device through the
         verified-signature table."""
-        form = self._tmpl_quorum_device_form(templates, commit_off, commit_tpl, d_vk, d_sig, d_var, d_var_off, var_bytes,
-                                             alt_span, d_item_alt)
+        form = self._commits_tmpl_device(templates, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                         d_var_off, var_bytes)
         return self._quorum_device(self.lib.edc_cached_tmpl_quorum_verify_device, True, form, d_power, d_flag, thresholds,
                                    z_seed, light)
 

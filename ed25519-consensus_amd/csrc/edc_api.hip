@@ -382,6 +382,36 @@ static int init_slot(edc_ctx* ctx, Slot& s) {
   return 0;
 }
 
+// The slot claims. A synchronous call runs on slot 0 and a submission on the slot of the next
+// ticket; each refuses a slot whose batch has not been waited for (null, ctx->err says why). The
+// ticket is taken only once the enqueue has succeeded, so a refused or failed submission leaves
+// next_ticket where it was.
+static const char kAllSlotsInFlight[] = "all slots in flight: wait for the oldest ticket first";
+
+static Slot* claim_slot0(edc_ctx* ctx) {
+  if (ctx->slot[0].pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return nullptr; }
+  return &ctx->slot[0];
+}
+
+static Slot* claim_next_slot(edc_ctx* ctx) {
+  Slot& s = ctx->slot[ctx->next_ticket % ctx->nslots];
+  if (s.pending) { ctx->err = kAllSlotsInFlight; return nullptr; }
+  return &s;
+}
+
+static int64_t take_ticket(edc_ctx* ctx, Slot& s) {
+  s.ticket = ctx->next_ticket;
+  return ctx->next_ticket++;
+}
+
+// key indices of a host form: every one a position in the registered key list (kc_reg)
+static int check_key_idx(edc_ctx* ctx, size_t n, const uint32_t* key_idx) {
+  uint32_t mx = 0;
+  for (size_t i = 0; i < n; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
+  if (n && mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
+  return 0;
+}
+
 static int ensure_slot(edc_ctx* ctx, Slot& s, size_t n) {
   int rc = init_slot(ctx, s);
   if (rc) return rc;
@@ -1113,13 +1143,13 @@ static int finish_batch(edc_ctx* ctx, Slot& s, uint8_t check8[32], uint8_t parti
 static int run_batch_sync(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
                           const uint64_t* d_off, const uint8_t* z_seed, uint64_t z_base, const uint8_t* d_z,
                           uint8_t check8[32], uint8_t partial[128], int* bad, const uint32_t* d_k = nullptr) {
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  Slot* s = claim_slot0(ctx);
+  if (!s) return EDC_ERR_ARG;
   // a synchronous call is one batch on an otherwise idle GPU: latency-shaped kernels (see
   // launch_msm_bucket); pipelined submissions keep the work-minimal ones
-  int rc = enqueue_batch(ctx, s, n, d_vk, d_sig, d_msg, d_off, z_seed, z_base, d_z, check8 != nullptr, d_k, true);
+  int rc = enqueue_batch(ctx, *s, n, d_vk, d_sig, d_msg, d_off, z_seed, z_base, d_z, check8 != nullptr, d_k, true);
   if (rc) return rc;
-  return finish_batch(ctx, s, check8, partial, bad);
+  return finish_batch(ctx, *s, check8, partial, bad);
 }
 
 // ---- synchronous host-buffer calls, copy overlapped with compute ----
@@ -1362,8 +1392,8 @@ static int enqueue_host_chunked(edc_ctx* ctx, size_t n, const uint8_t* vk, const
 static int run_host_sync(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                          const uint64_t* msg_off, const uint8_t* k, const uint8_t* z, const uint8_t* z_seed,
                          uint8_t check8[32]) {
+  if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   if (n && (!vk || !sig || (k ? false : !msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
   if (n && !k && msg_off[n] > msg_off[0] && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
   if (!host_chunked_ok(ctx, n)) {
@@ -1619,33 +1649,29 @@ int64_t edc_batch_submit_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, con
                                 uint64_t z_base, const uint8_t* d_z, int want_check8) {
   if (!ctx || (!z_seed && !d_z)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  Slot* sp = claim_next_slot(ctx);
+  if (!sp) return EDC_ERR_ARG;
+  Slot& s = *sp;
 #ifdef EDC_BATCH_STAMPS
   s.t_submit_us = host_us();
 #endif
   int rc = enqueue_batch(ctx, s, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, z_base, d_z, want_check8 != 0);
   if (rc) return rc;
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return take_ticket(ctx, s);
 }
 
 int64_t edc_batch_submit(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                          const uint64_t* msg_off, const uint8_t z_seed[32], uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  Slot* sp = claim_next_slot(ctx);
+  if (!sp) return EDC_ERR_ARG;
+  Slot& s = *sp;
   int rc = upload_slot(ctx, s, n, vk, sig, msg, msg_off);
   if (rc) return rc;
   rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.in_msg, s.in_off, z_seed, z_base, nullptr, want_check8 != 0);
   if (rc) return rc;
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return take_ticket(ctx, s);
 }
 
 int64_t edc_batch_submit_indexed(edc_ctx* ctx, size_t n, const uint32_t* key_idx, const uint8_t* sig,
@@ -1653,19 +1679,15 @@ int64_t edc_batch_submit_indexed(edc_ctx* ctx, size_t n, const uint32_t* key_idx
                                  uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed || (n && !key_idx)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  uint32_t mx = 0;
-  for (size_t i = 0; i < n; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
-  if (n && mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  if (check_key_idx(ctx, n, key_idx)) return EDC_ERR_ARG;
+  Slot* sp = claim_next_slot(ctx);
+  if (!sp) return EDC_ERR_ARG;
+  Slot& s = *sp;
   int rc = upload_slot(ctx, s, n, nullptr, sig, msg, msg_off, key_idx);
   if (rc) return rc;
   rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.in_msg, s.in_off, z_seed, z_base, nullptr, want_check8 != 0);
   if (rc) return rc;
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return take_ticket(ctx, s);
 }
 
 int edc_batch_wait(edc_ctx* ctx, int64_t ticket, uint8_t check8[32], uint8_t partial[128], int* bad) {
@@ -1681,9 +1703,9 @@ int64_t edc_batch_submit_multi_device(edc_ctx* ctx, size_t nb, size_t n_per, con
                                       const uint8_t z_seed[32], uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  Slot* sp = claim_next_slot(ctx);
+  if (!sp) return EDC_ERR_ARG;
+  Slot& s = *sp;
   const uint32_t nbv = (uint32_t)(nb <= kMultiMax ? nb : 0);
   const uint32_t* dk = reinterpret_cast<const uint32_t*>(d_k);
   int rc;
@@ -1707,9 +1729,7 @@ int64_t edc_batch_submit_multi_device(edc_ctx* ctx, size_t nb, size_t n_per, con
     if (rc) return rc;
     s.mu_union = false;
   }
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return take_ticket(ctx, s);
 }
 
 int edc_batch_wait_multi(edc_ctx* ctx, int64_t ticket, size_t nb, int* verdicts, uint8_t* check8, uint8_t* partials,
@@ -1837,8 +1857,8 @@ int edc_tmpl_expand_device(edc_ctx* ctx, const edc_templates* ts, size_t n, cons
     return EDC_ERR_ARG;
   }
   if (n && !aligned16(d_msg_out)) { ctx->err = "the message arena must be 16-byte aligned"; return EDC_ERR_ARG; }
+  if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
   if ((rc = init_slot(ctx, s))) return rc;
   if (!n) {
@@ -1863,8 +1883,8 @@ int edc_tmpl_challenge(edc_ctx* ctx, const edc_templates* ts, size_t n, const ui
   TmplShape sh;
   int rc = tmpl_check_host(ctx, n, vk, nullptr, sig, it, &sh);
   if (rc) return rc;
+  if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
   if ((rc = init_slot(ctx, s)) || (rc = ensure_n(ctx, n))) return rc;
   if (!n) return 0;
@@ -1882,22 +1902,31 @@ int edc_tmpl_challenge(edc_ctx* ctx, const edc_templates* ts, size_t n, const ui
   return 0;
 }
 
-int edc_tmpl_batch_verify(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint32_t* key_idx,
-                          const uint8_t* sig, const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off,
-                          const uint8_t z_seed[32], uint8_t check8[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
+// edc_tmpl_batch_verify (sync: slot 0, latency-shaped kernels, waits into check8) and
+// edc_tmpl_batch_submit (the next ticket's slot, returns the ticket)
+static int64_t tmpl_batch_run(edc_ctx* ctx, bool sync, const edc_templates* ts, size_t n, const uint8_t* vk,
+                              const uint32_t* key_idx, const uint8_t* sig, const uint16_t* tpl, const uint8_t* var,
+                              const uint32_t* var_off, const uint8_t* z_seed, uint64_t z_base, bool compress,
+                              uint8_t* check8) {
   const TmplItems it{ts, tpl, var, var_off};
   TmplShape sh;
   int rc = tmpl_check_host(ctx, n, vk, key_idx, sig, it, &sh);
   if (rc) return rc;
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
+  Slot* s = sync ? claim_slot0(ctx) : claim_next_slot(ctx);
+  if (!s) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  if ((rc = tmpl_upload_slot(ctx, s, n, vk, key_idx, sig, it, sh))) return rc;
-  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.tw.arena, s.tw.off, z_seed, 0, nullptr, check8 != nullptr, nullptr,
-                     true);
+  if ((rc = tmpl_upload_slot(ctx, *s, n, vk, key_idx, sig, it, sh))) return rc;
+  rc = enqueue_batch(ctx, *s, n, s->in_vk, s->in_sig, s->tw.arena, s->tw.off, z_seed, z_base, nullptr, compress, nullptr,
+                     sync);
   if (rc) return rc;
-  return finish_batch(ctx, s, check8, nullptr, nullptr);
+  return sync ? finish_batch(ctx, *s, check8, nullptr, nullptr) : take_ticket(ctx, *s);
+}
+
+int edc_tmpl_batch_verify(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint32_t* key_idx,
+                          const uint8_t* sig, const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off,
+                          const uint8_t z_seed[32], uint8_t check8[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  return (int)tmpl_batch_run(ctx, true, ts, n, vk, key_idx, sig, tpl, var, var_off, z_seed, 0, check8 != nullptr, check8);
 }
 
 int edc_tmpl_batch_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* d_vk,
@@ -1908,8 +1937,8 @@ int edc_tmpl_batch_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t n
   TmplShape sh;
   int rc = tmpl_check_device(ctx, n, ts, d_tpl, d_var, d_var_off, var_bytes, &sh);
   if (rc) return rc;
+  if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
   if ((rc = init_slot(ctx, s))) return rc;
   TmplView view;
@@ -1931,20 +1960,7 @@ int64_t edc_tmpl_batch_submit(edc_ctx* ctx, const edc_templates* ts, size_t n, c
                               const uint8_t* sig, const uint16_t* tpl, const uint8_t* var, const uint32_t* var_off,
                               const uint8_t z_seed[32], uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  const TmplItems it{ts, tpl, var, var_off};
-  TmplShape sh;
-  int rc = tmpl_check_host(ctx, n, vk, key_idx, sig, it, &sh);
-  if (rc) return rc;
-  CK(hipSetDevice(ctx->device));
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
-  if ((rc = tmpl_upload_slot(ctx, s, n, vk, key_idx, sig, it, sh))) return rc;
-  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.tw.arena, s.tw.off, z_seed, z_base, nullptr, want_check8 != 0);
-  if (rc) return rc;
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return tmpl_batch_run(ctx, false, ts, n, vk, key_idx, sig, tpl, var, var_off, z_seed, z_base, want_check8 != 0, nullptr);
 }
 
 int edc_verify_prehashed_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* k,
@@ -2132,8 +2148,8 @@ int edc_find_invalid_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const u
   (void)leaf;
   if (!ctx || !z_seed || (n && (!d_vk || !d_sig || !d_msg_off || !verdicts))) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
+  if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   if (!n) return 0;
   int rc = enqueue_prefix(ctx, s, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, 0, nullptr, false, nullptr);
   if (rc) return rc;
@@ -2205,35 +2221,29 @@ int64_t edc_batch_submit_prehashed_indexed(edc_ctx* ctx, size_t n, const uint32_
                                            int want_check8) {
   if (!ctx || !z_seed || (n && !key_idx)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  uint32_t mx = 0;
-  for (size_t i = 0; i < n; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
-  if (n && mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  if (check_key_idx(ctx, n, key_idx)) return EDC_ERR_ARG;
+  Slot* sp = claim_next_slot(ctx);
+  if (!sp) return EDC_ERR_ARG;
+  Slot& s = *sp;
   int rc = upload_slot_prehashed(ctx, s, n, nullptr, sig, k, key_idx);
   if (rc) return rc;
   rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, nullptr, nullptr, z_seed, z_base, nullptr, want_check8 != 0, s.k);
   if (rc) return rc;
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return take_ticket(ctx, s);
 }
 
 int64_t edc_batch_submit_prehashed(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* k,
                                    const uint8_t z_seed[32], uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  Slot* sp = claim_next_slot(ctx);
+  if (!sp) return EDC_ERR_ARG;
+  Slot& s = *sp;
   int rc = upload_slot_prehashed(ctx, s, n, vk, sig, k);
   if (rc) return rc;
   rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, nullptr, nullptr, z_seed, z_base, nullptr, want_check8 != 0, s.k);
   if (rc) return rc;
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return take_ticket(ctx, s);
 }
 
 int64_t edc_batch_submit_prehashed_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
@@ -2242,15 +2252,13 @@ int64_t edc_batch_submit_prehashed_device(edc_ctx* ctx, size_t n, const uint8_t*
   if (!ctx || (!z_seed && !d_z) || (n && (!d_vk || !d_sig || !d_k))) return EDC_ERR_ARG;
   if (!aligned16(d_k) || (d_z && !aligned16(d_z))) { ctx->err = "d_k / d_z must be 16-byte aligned"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
-  const int64_t ticket = ctx->next_ticket;
-  Slot& s = ctx->slot[ticket % ctx->nslots];
-  if (s.pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  Slot* sp = claim_next_slot(ctx);
+  if (!sp) return EDC_ERR_ARG;
+  Slot& s = *sp;
   int rc = enqueue_batch(ctx, s, n, d_vk, d_sig, nullptr, nullptr, z_seed, z_base, d_z, want_check8 != 0,
                          reinterpret_cast<const uint32_t*>(d_k));
   if (rc) return rc;
-  s.ticket = ticket;
-  ctx->next_ticket++;
-  return ticket;
+  return take_ticket(ctx, s);
 }
 
 int edc_batch_verify_prehashed_fallback(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig,
@@ -2258,8 +2266,8 @@ int edc_batch_verify_prehashed_fallback(edc_ctx* ctx, size_t n, const uint8_t* v
                                         int* n_invalid, uint8_t check8[32]) {
   if (!ctx || !z_seed || (n && (!vk || !sig || !k || !verdicts))) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
+  if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   int rc = ensure_n(ctx, n);
   if (rc) return rc;
   rc = ensure_slot(ctx, s, n);
@@ -2314,12 +2322,7 @@ static int commits_check(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, si
 // keys of a host form: exactly one of vk and key_idx, every index inside the registered list
 static int commits_check_keys(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint32_t* key_idx) {
   if (!vk == !key_idx) { ctx->err = "exactly one of vk and key_idx"; return EDC_ERR_ARG; }
-  if (key_idx) {
-    uint32_t mx = 0;
-    for (size_t i = 0; i < n; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
-    if (mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
-  }
-  return 0;
+  return key_idx ? check_key_idx(ctx, n, key_idx) : 0;
 }
 
 // messages of n > 0 host items: (msg, msg_off), or the prehashed k (its values are the caller's to check)
@@ -2352,25 +2355,6 @@ static int commits_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   return 0;
 }
 
-static int commits_check_tmpl(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
-                              const uint16_t* commit_tpl, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
-                              const uint8_t* var, const uint32_t* var_off, TmplShape* sh, size_t* n) {
-  int rc = tmpl_check(ctx, ts, sh);
-  if (rc || (rc = commits_check(ctx, nc, commit_off, n))) return rc;
-  if (!commits_check_tpl(ts->count, nc, commit_tpl)) {
-    ctx->err = "commit templates: one index below the set's count per commit";
-    return EDC_ERR_ARG;
-  }
-  if (!*n) return 0;
-  if ((rc = commits_check_keys(ctx, *n, vk, key_idx))) return rc;
-  if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  if (!commits_check_holes(*n, var_off) || (var_off[*n] && !var)) {
-    ctx->err = "templated items: hole offsets out of range";
-    return EDC_ERR_ARG;
-  }
-  return 0;
-}
-
 // Template variants: every commit's window [commit_tpl[c], commit_tpl[c] + alt_span) inside the set.
 static int commits_check_windows(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint16_t* commit_tpl,
                                  uint32_t alt_span) {
@@ -2381,16 +2365,43 @@ static int commits_check_windows(edc_ctx* ctx, const edc_templates* ts, size_t n
   return 0;
 }
 
-// the host checks of edc_tmpl_commits_verify_alt / _submit_alt: those of the one-template form,
-// then the windows and the variant bytes
-static int commits_check_tmpl_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
-                                  const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
-                                  const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var,
-                                  const uint32_t* var_off, TmplShape* sh, size_t* n) {
-  int rc = commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, vk, key_idx, sig, var, var_off, sh, n);
-  if (rc || (rc = commits_check_windows(ctx, ts, nc, commit_tpl, alt_span))) return rc;
+// The host checks of a templated host form. variants: the caller passed alt_span and item_alt
+// (edc_tmpl_commits_*_alt, the templated quorum forms), so the windows and the variant bytes are
+// checked too, and alt_span = 0 is refused there, never read as "one template per commit".
+static int commits_check_tmpl(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
+                              const uint16_t* commit_tpl, bool variants, uint32_t alt_span, const uint8_t* item_alt,
+                              const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* var,
+                              const uint32_t* var_off, TmplShape* sh, size_t* n) {
+  int rc = tmpl_check(ctx, ts, sh);
+  if (rc || (rc = commits_check(ctx, nc, commit_off, n))) return rc;
+  if (!commits_check_tpl(ts->count, nc, commit_tpl)) {
+    ctx->err = "commit templates: one index below the set's count per commit";
+    return EDC_ERR_ARG;
+  }
+  if (*n) {
+    if ((rc = commits_check_keys(ctx, *n, vk, key_idx))) return rc;
+    if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
+    if (!commits_check_holes(*n, var_off) || (var_off[*n] && !var)) {
+      ctx->err = "templated items: hole offsets out of range";
+      return EDC_ERR_ARG;
+    }
+  }
+  if (!variants) return 0;
+  if ((rc = commits_check_windows(ctx, ts, nc, commit_tpl, alt_span))) return rc;
   if (!commits_check_item_alt(*n, item_alt, alt_span)) {
     ctx->err = "template variants: item_alt[i] < alt_span for every item";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
+// What a templated submit of no commits still checks: the set, and with variants the span's range.
+static int commits_check_tmpl_empty(edc_ctx* ctx, const edc_templates* ts, bool variants, uint32_t alt_span,
+                                    TmplShape* sh) {
+  int rc = tmpl_check(ctx, ts, sh);
+  if (rc) return rc;
+  if (variants && (alt_span < 1 || alt_span > COMMITS_MAX_ALT_SPAN)) {
+    ctx->err = "template variants: alt_span in 1..256";
     return EDC_ERR_ARG;
   }
   return 0;
@@ -2563,22 +2574,111 @@ static int commits_finish(edc_ctx* ctx, Slot& s, uint8_t* commit_verdicts, uint8
   return bad ? EDC_INVALID_SIGNATURE : EDC_OK;
 }
 
-// the slot of the next ticket, or the reason there is none
-static int commits_next_slot(edc_ctx* ctx, Slot** s) {
-  *s = &ctx->slot[ctx->next_ticket % ctx->nslots];
-  if ((*s)->pending) { ctx->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
-  return 0;
+// Where a commit-set call's result goes: the three outputs of a synchronous call (verify), or
+// null for "enqueue and return a ticket" (submit). One body per form serves both; the three
+// helpers below are every place where the two modes part, on purpose:
+//  - a verify of nc == 0 is EDC_OK with *n_bad = 0 before anything else is looked at, a null or
+//    refused template set included; a submit of nc == 0 still checks the set, and with variants
+//    that alt_span is in 1..256 (commits_check_tmpl_empty), then takes a ticket whose wait gives
+//    no verdicts;
+//  - a verify claims slot 0 and a submit the next ticket's slot, both after the argument checks,
+//    so an argument error is reported before a busy slot;
+//  - a verify enqueues latency-shaped kernels (latency = true: one batch on an idle GPU) and waits;
+//    a submit enqueues the work-minimal ones and takes its ticket, only after the enqueue succeeded.
+struct CommitsOut {
+  uint8_t *commit_verdicts, *item_verdicts;
+  int* n_bad;
+};
+
+static bool commits_nothing(const CommitsOut* out, size_t nc) {
+  if (!out || nc) return false;
+  if (out->n_bad) *out->n_bad = 0;
+  return true;
 }
 
-static int64_t commits_ticket(edc_ctx* ctx, Slot& s) {
-  s.ticket = ctx->next_ticket;
-  return ctx->next_ticket++;
+static Slot* commits_claim(edc_ctx* ctx, const CommitsOut* out) { return out ? claim_slot0(ctx) : claim_next_slot(ctx); }
+
+static int64_t commits_done(edc_ctx* ctx, Slot& s, const CommitsOut* out) {
+  if (out) return commits_finish(ctx, s, out->commit_verdicts, out->item_verdicts, out->n_bad);
+  return take_ticket(ctx, s);
 }
 
-// nc == 0 of a synchronous form: nothing to verify
-static int commits_none(int* n_bad) {
-  if (n_bad) *n_bad = 0;
-  return EDC_OK;
+// edc_commits_verify_device / _submit_device
+static int64_t commits_run_device(edc_ctx* ctx, const CommitsOut* out, size_t nc, const uint32_t* commit_off,
+                                  const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
+                                  const uint64_t* d_msg_off, const uint8_t* d_k, const uint8_t* z_seed) {
+  if (commits_nothing(out, nc)) return EDC_OK;
+  size_t n = 0;
+  int rc = nc ? commits_check(ctx, nc, commit_off, &n) : 0;
+  if (rc) return rc;
+  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  Slot* s = commits_claim(ctx, out);
+  if (!s) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  rc = commits_enqueue(ctx, *s, nc, commit_off, n, d_vk, d_sig, d_k ? nullptr : d_msg, d_k ? nullptr : d_msg_off,
+                       reinterpret_cast<const uint32_t*>(d_k), z_seed, out != nullptr);
+  if (rc) return rc;
+  return commits_done(ctx, *s, out);
+}
+
+// edc_commits_verify / _submit
+static int64_t commits_run_host(edc_ctx* ctx, const CommitsOut* out, size_t nc, const uint32_t* commit_off,
+                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
+                                const uint64_t* msg_off, const uint8_t* k, const uint8_t* z_seed) {
+  if (commits_nothing(out, nc)) return EDC_OK;
+  size_t n = 0;
+  int rc = nc ? commits_check_host(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, &n) : 0;
+  if (rc) return rc;
+  Slot* s = commits_claim(ctx, out);
+  if (!s) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  rc = commits_enqueue_host(ctx, *s, nc, commit_off, n, vk, key_idx, sig, msg, msg_off, k, z_seed, out != nullptr);
+  if (rc) return rc;
+  return commits_done(ctx, *s, out);
+}
+
+// edc_tmpl_commits_verify / _submit (variants = false: alt_span and item_alt are not looked at)
+// and edc_tmpl_commits_verify_alt / _submit_alt (variants = true: the caller's alt_span, checked)
+static int64_t commits_run_tmpl(edc_ctx* ctx, const CommitsOut* out, const edc_templates* ts, size_t nc,
+                                const uint32_t* commit_off, const uint16_t* commit_tpl, bool variants, uint32_t alt_span,
+                                const uint8_t* item_alt, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                                const uint8_t* var, const uint32_t* var_off, const uint8_t* z_seed) {
+  if (commits_nothing(out, nc)) return EDC_OK;
+  size_t n = 0;
+  TmplShape sh;
+  int rc = nc ? commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, variants, alt_span, item_alt, vk, key_idx, sig, var,
+                                   var_off, &sh, &n)
+              : commits_check_tmpl_empty(ctx, ts, variants, alt_span, &sh);
+  if (rc) return rc;
+  Slot* s = commits_claim(ctx, out);
+  if (!s) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  rc = commits_enqueue_tmpl(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
+                            out != nullptr, variants ? alt_span : 0, item_alt);
+  if (rc) return rc;
+  return commits_done(ctx, *s, out);
+}
+
+// edc_tmpl_commits_verify_device / _submit_device (always with variants)
+static int64_t commits_run_tmpl_device(edc_ctx* ctx, const CommitsOut* out, const edc_templates* ts, size_t nc,
+                                       const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span,
+                                       const uint8_t* d_item_alt, const uint8_t* d_vk, const uint8_t* d_sig,
+                                       const uint8_t* d_var, const uint32_t* d_var_off, size_t var_bytes,
+                                       const uint8_t* z_seed) {
+  if (commits_nothing(out, nc)) return EDC_OK;
+  size_t n = 0;
+  TmplShape sh;
+  int rc = nc ? commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
+                                          var_bytes, &sh, &n)
+              : commits_check_tmpl_empty(ctx, ts, true, alt_span, &sh);
+  if (rc) return rc;
+  Slot* s = commits_claim(ctx, out);
+  if (!s) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  rc = commits_enqueue_tmpl_device(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                   d_var_off, var_bytes, z_seed, out != nullptr);
+  if (rc) return rc;
+  return commits_done(ctx, *s, out);
 }
 
 extern "C" {
@@ -2588,33 +2688,30 @@ int edc_commits_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
                               const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
                               int* n_bad_commits) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  if (!nc) return commits_none(n_bad_commits);
-  size_t n;
-  int rc = commits_check(ctx, nc, commit_off, &n);
-  if (rc) return rc;
-  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  CK(hipSetDevice(ctx->device));
-  rc = commits_enqueue(ctx, s, nc, commit_off, n, d_vk, d_sig, d_k ? nullptr : d_msg, d_k ? nullptr : d_msg_off,
-                       reinterpret_cast<const uint32_t*>(d_k), z_seed, true);
-  if (rc) return rc;
-  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+  const CommitsOut out{commit_verdicts, item_verdicts, n_bad_commits};
+  return (int)commits_run_device(ctx, &out, nc, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k, z_seed);
+}
+
+int64_t edc_commits_submit_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                  const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                  const uint8_t* d_k, const uint8_t z_seed[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  return commits_run_device(ctx, nullptr, nc, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k, z_seed);
 }
 
 int edc_commits_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
                        const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k,
                        const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  if (!nc) return commits_none(n_bad_commits);
-  size_t n;
-  int rc = commits_check_host(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, &n);
-  if (rc) return rc;
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_host(ctx, s, nc, commit_off, n, vk, key_idx, sig, msg, msg_off, k, z_seed, true))) return rc;
-  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+  const CommitsOut out{commit_verdicts, item_verdicts, n_bad_commits};
+  return (int)commits_run_host(ctx, &out, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, z_seed);
+}
+
+int64_t edc_commits_submit(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                           const uint8_t* k, const uint8_t z_seed[32]) {
+  if (!ctx || !z_seed) return EDC_ERR_ARG;
+  return commits_run_host(ctx, nullptr, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, z_seed);
 }
 
 int edc_tmpl_commits_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -2622,49 +2719,9 @@ int edc_tmpl_commits_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, co
                             const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32],
                             uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  if (!nc) return commits_none(n_bad_commits);
-  size_t n;
-  TmplShape sh;
-  int rc = commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, vk, key_idx, sig, var, var_off, &sh, &n);
-  if (rc) return rc;
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_tmpl(ctx, s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
-                                 true)))
-    return rc;
-  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
-}
-
-int64_t edc_commits_submit_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
-                                  const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
-                                  const uint8_t* d_k, const uint8_t z_seed[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  size_t n = 0;
-  int rc = nc ? commits_check(ctx, nc, commit_off, &n) : 0;
-  if (rc) return rc;
-  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  Slot* s;
-  if ((rc = commits_next_slot(ctx, &s))) return rc;
-  CK(hipSetDevice(ctx->device));
-  rc = commits_enqueue(ctx, *s, nc, commit_off, n, d_vk, d_sig, d_k ? nullptr : d_msg, d_k ? nullptr : d_msg_off,
-                       reinterpret_cast<const uint32_t*>(d_k), z_seed, false);
-  if (rc) return rc;
-  return commits_ticket(ctx, *s);
-}
-
-int64_t edc_commits_submit(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
-                           const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
-                           const uint8_t* k, const uint8_t z_seed[32]) {
-  if (!ctx || !z_seed) return EDC_ERR_ARG;
-  size_t n = 0;
-  int rc = nc ? commits_check_host(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, &n) : 0;
-  if (rc) return rc;
-  Slot* s;
-  if ((rc = commits_next_slot(ctx, &s))) return rc;
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_host(ctx, *s, nc, commit_off, n, vk, key_idx, sig, msg, msg_off, k, z_seed, false))) return rc;
-  return commits_ticket(ctx, *s);
+  const CommitsOut out{commit_verdicts, item_verdicts, n_bad_commits};
+  return (int)commits_run_tmpl(ctx, &out, ts, nc, commit_off, commit_tpl, false, 0, nullptr, vk, key_idx, sig, var, var_off,
+                               z_seed);
 }
 
 int64_t edc_tmpl_commits_submit(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -2672,18 +2729,8 @@ int64_t edc_tmpl_commits_submit(edc_ctx* ctx, const edc_templates* ts, size_t nc
                                 const uint8_t* sig, const uint8_t* var, const uint32_t* var_off,
                                 const uint8_t z_seed[32]) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  size_t n = 0;
-  TmplShape sh;
-  int rc = nc ? commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, vk, key_idx, sig, var, var_off, &sh, &n)
-              : tmpl_check(ctx, ts, &sh);
-  if (rc) return rc;
-  Slot* s;
-  if ((rc = commits_next_slot(ctx, &s))) return rc;
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_tmpl(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
-                                 false)))
-    return rc;
-  return commits_ticket(ctx, *s);
+  return commits_run_tmpl(ctx, nullptr, ts, nc, commit_off, commit_tpl, false, 0, nullptr, vk, key_idx, sig, var, var_off,
+                          z_seed);
 }
 
 int edc_tmpl_commits_verify_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -2692,19 +2739,9 @@ int edc_tmpl_commits_verify_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc
                                 const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32],
                                 uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  if (!nc) return commits_none(n_bad_commits);
-  size_t n;
-  TmplShape sh;
-  int rc = commits_check_tmpl_alt(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
-                                  &sh, &n);
-  if (rc) return rc;
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_tmpl(ctx, s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
-                                 true, alt_span, item_alt)))
-    return rc;
-  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+  const CommitsOut out{commit_verdicts, item_verdicts, n_bad_commits};
+  return (int)commits_run_tmpl(ctx, &out, ts, nc, commit_off, commit_tpl, true, alt_span, item_alt, vk, key_idx, sig, var,
+                               var_off, z_seed);
 }
 
 int64_t edc_tmpl_commits_submit_alt(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -2712,23 +2749,8 @@ int64_t edc_tmpl_commits_submit_alt(edc_ctx* ctx, const edc_templates* ts, size_
                                     const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
                                     const uint8_t* var, const uint32_t* var_off, const uint8_t z_seed[32]) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  size_t n = 0;
-  TmplShape sh;
-  int rc = nc ? commits_check_tmpl_alt(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var,
-                                       var_off, &sh, &n)
-              : tmpl_check(ctx, ts, &sh);
-  if (rc) return rc;
-  if (!nc && (alt_span < 1 || alt_span > COMMITS_MAX_ALT_SPAN)) {
-    ctx->err = "template variants: alt_span in 1..256";
-    return EDC_ERR_ARG;
-  }
-  Slot* s;
-  if ((rc = commits_next_slot(ctx, &s))) return rc;
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_tmpl(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, vk, key_idx, sig, var, var_off, z_seed,
-                                 false, alt_span, item_alt)))
-    return rc;
-  return commits_ticket(ctx, *s);
+  return commits_run_tmpl(ctx, nullptr, ts, nc, commit_off, commit_tpl, true, alt_span, item_alt, vk, key_idx, sig, var,
+                          var_off, z_seed);
 }
 
 int edc_tmpl_commits_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -2737,19 +2759,9 @@ int edc_tmpl_commits_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t
                                    const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32],
                                    uint8_t* commit_verdicts, uint8_t* item_verdicts, int* n_bad_commits) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  if (!nc) return commits_none(n_bad_commits);
-  size_t n;
-  TmplShape sh;
-  int rc = commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
-                                     var_bytes, &sh, &n);
-  if (rc) return rc;
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_tmpl_device(ctx, s, ts, sh, nc, commit_off, commit_tpl, n, alt_span, d_item_alt, d_vk, d_sig,
-                                        d_var, d_var_off, var_bytes, z_seed, true)))
-    return rc;
-  return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
+  const CommitsOut out{commit_verdicts, item_verdicts, n_bad_commits};
+  return (int)commits_run_tmpl_device(ctx, &out, ts, nc, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                      d_var_off, var_bytes, z_seed);
 }
 
 int64_t edc_tmpl_commits_submit_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -2757,23 +2769,8 @@ int64_t edc_tmpl_commits_submit_device(edc_ctx* ctx, const edc_templates* ts, si
                                        const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_var,
                                        const uint32_t* d_var_off, size_t var_bytes, const uint8_t z_seed[32]) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
-  size_t n = 0;
-  TmplShape sh;
-  int rc = nc ? commits_check_tmpl_device(ctx, ts, nc, commit_off, commit_tpl, alt_span, d_vk, d_sig, d_var, d_var_off,
-                                          var_bytes, &sh, &n)
-              : tmpl_check(ctx, ts, &sh);
-  if (rc) return rc;
-  if (!nc && (alt_span < 1 || alt_span > COMMITS_MAX_ALT_SPAN)) {
-    ctx->err = "template variants: alt_span in 1..256";
-    return EDC_ERR_ARG;
-  }
-  Slot* s;
-  if ((rc = commits_next_slot(ctx, &s))) return rc;
-  CK(hipSetDevice(ctx->device));
-  if ((rc = commits_enqueue_tmpl_device(ctx, *s, ts, sh, nc, commit_off, commit_tpl, n, alt_span, d_item_alt, d_vk, d_sig,
-                                        d_var, d_var_off, var_bytes, z_seed, false)))
-    return rc;
-  return commits_ticket(ctx, *s);
+  return commits_run_tmpl_device(ctx, nullptr, ts, nc, commit_off, commit_tpl, alt_span, d_item_alt, d_vk, d_sig, d_var,
+                                 d_var_off, var_bytes, z_seed);
 }
 
 int edc_commits_wait(edc_ctx* ctx, int64_t ticket, uint8_t* commit_verdicts, uint8_t* item_verdicts,
@@ -2786,73 +2783,56 @@ int edc_commits_wait(edc_ctx* ctx, int64_t ticket, uint8_t* commit_verdicts, uin
   return commits_finish(ctx, s, commit_verdicts, item_verdicts, n_bad_commits);
 }
 
-int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
-                              uint16_t* tpl_out, int reps, float* ms) {
-  if (!ctx || !nc || !commit_tpl || reps < 1) return EDC_ERR_ARG;
+// One of the two map kernels alone: stage the offsets and templates, time `reps` launches between
+// two events, read the map back. variants = false: k_tmpl_commit_map over commit_off | commit_tpl |
+// tpl, no flag word. variants = true: k_tmpl_commit_map_alt, with the flag word and the device
+// copies of item_alt and tpl_out at the host pointers' offsets from a 16-byte boundary, so a caller
+// picks the kernel's wide or narrow access paths by how it places its arrays.
+static int debug_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl, bool variants,
+                            uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl_out, int* flagged, int reps,
+                            float* ms) {
   size_t n;
   int rc = commits_check(ctx, nc, commit_off, &n);
   if (rc) return rc;
-  if (n && !tpl_out) { ctx->err = "null output"; return EDC_ERR_ARG; }
-  Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  CK(hipSetDevice(ctx->device));
-  const size_t o_ctpl = up16(4 * (nc + 1)), o_tpl = up16(o_ctpl + 2 * nc);
-  if ((rc = init_slot(ctx, s)) || (rc = ensure_aux(ctx, o_tpl + 2 * n))) return rc;
-  hipStream_t st = s.st;
-  CK(hipMemcpyAsync(ctx->aux, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(ctx->aux + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
-  CK(hipEventRecord(s.ev[0], st));
-  for (int r = 0; r < reps; ++r)
-    launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(ctx->aux.get()),
-                           reinterpret_cast<const uint16_t*>(ctx->aux + o_ctpl),
-                           reinterpret_cast<uint16_t*>(ctx->aux + o_tpl));
-  CK(hipGetLastError());
-  CK(hipEventRecord(s.ev[1], st));
-  if (n) CK(hipMemcpyAsync(tpl_out, ctx->aux + o_tpl, 2 * n, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  if (ms) {
-    CK(hipEventElapsedTime(ms, s.ev[0], s.ev[1]));
-    *ms /= (float)reps;
-  }
-  return 0;
-}
-
-int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
-                                  uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl_out, int* flagged,
-                                  int reps, float* ms) {
-  if (!ctx || !nc || !commit_tpl || reps < 1) return EDC_ERR_ARG;
-  size_t n;
-  int rc = commits_check(ctx, nc, commit_off, &n);
-  if (rc) return rc;
-  if (!commits_check_alt_span(65535, nc, commit_tpl, alt_span)) {      // the windows inside the largest set there is
+  if (variants && !commits_check_alt_span(65535, nc, commit_tpl, alt_span)) {      // the windows inside the largest set there is
     ctx->err = "template variants: alt_span in 1..256 and commit_tpl[c] + alt_span <= 65535";
     return EDC_ERR_ARG;
   }
   if (n && !tpl_out) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
-  if (s.pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
-  // the device copies of item_alt and tpl_out start at the host pointers' offsets from a 16-byte
-  // boundary, so a caller picks the kernel's wide or narrow access paths by how it places its arrays
-  const size_t o_ctpl = up16(4 * (nc + 1)), o_alt = up16(o_ctpl + 2 * nc) + ((uintptr_t)item_alt & 15u),
-               o_flag = up16(o_alt + n), o_tpl = o_flag + 16 + ((uintptr_t)tpl_out & 14u);
+  const size_t o_ctpl = up16(4 * (nc + 1));
+  size_t o_alt = 0, o_flag = 0, o_tpl = up16(o_ctpl + 2 * nc);
+  if (variants) {
+    o_alt = o_tpl + ((uintptr_t)item_alt & 15u);
+    o_flag = up16(o_alt + n);
+    o_tpl = o_flag + 16 + ((uintptr_t)tpl_out & 14u);
+  }
   if ((rc = init_slot(ctx, s)) || (rc = ensure_aux(ctx, o_tpl + 2 * n))) return rc;
   hipStream_t st = s.st;
+  const uint32_t* d_off = reinterpret_cast<const uint32_t*>(ctx->aux.get());
+  const uint16_t* d_ctpl = reinterpret_cast<const uint16_t*>(ctx->aux + o_ctpl);
+  uint16_t* d_tpl = reinterpret_cast<uint16_t*>(ctx->aux + o_tpl);
   int* d_flag = reinterpret_cast<int*>(ctx->aux + o_flag);
   CK(hipMemcpyAsync(ctx->aux, commit_off, 4 * (nc + 1), hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(ctx->aux + o_ctpl, commit_tpl, 2 * nc, hipMemcpyHostToDevice, st));
-  if (item_alt && n) CK(hipMemcpyAsync(ctx->aux + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
-  CK(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  if (variants) {
+    if (item_alt && n) CK(hipMemcpyAsync(ctx->aux + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
+    CK(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  }
   CK(hipEventRecord(s.ev[0], st));
   for (int r = 0; r < reps; ++r)
-    launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, reinterpret_cast<const uint32_t*>(ctx->aux.get()),
-                               reinterpret_cast<const uint16_t*>(ctx->aux + o_ctpl), alt_span,
-                               item_alt ? ctx->aux + o_alt : nullptr, reinterpret_cast<uint16_t*>(ctx->aux + o_tpl), d_flag);
+    if (variants)
+      launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, d_off, d_ctpl, alt_span, item_alt ? ctx->aux + o_alt : nullptr,
+                                 d_tpl, d_flag);
+    else
+      launch_tmpl_commit_map(st, (uint32_t)n, (uint32_t)nc, d_off, d_ctpl, d_tpl);
   CK(hipGetLastError());
   CK(hipEventRecord(s.ev[1], st));
   int flag = 0;
-  if (n) CK(hipMemcpyAsync(tpl_out, ctx->aux + o_tpl, 2 * n, hipMemcpyDeviceToHost, st));
-  CK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (n) CK(hipMemcpyAsync(tpl_out, d_tpl, 2 * n, hipMemcpyDeviceToHost, st));
+  if (variants) CK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
   if (flagged) *flagged = flag != 0;
   if (ms) {
@@ -2860,6 +2840,19 @@ int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commi
     *ms /= (float)reps;
   }
   return 0;
+}
+
+int edc_debug_tmpl_commit_map(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
+                              uint16_t* tpl_out, int reps, float* ms) {
+  if (!ctx || !nc || !commit_tpl || reps < 1) return EDC_ERR_ARG;
+  return debug_commit_map(ctx, nc, commit_off, commit_tpl, false, 0, nullptr, tpl_out, nullptr, reps, ms);
+}
+
+int edc_debug_tmpl_commit_map_alt(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint16_t* commit_tpl,
+                                  uint32_t alt_span, const uint8_t* item_alt, uint16_t* tpl_out, int* flagged,
+                                  int reps, float* ms) {
+  if (!ctx || !nc || !commit_tpl || reps < 1) return EDC_ERR_ARG;
+  return debug_commit_map(ctx, nc, commit_off, commit_tpl, true, alt_span, item_alt, tpl_out, flagged, reps, ms);
 }
 
 int edc_decompress(edc_ctx* ctx, size_t n, const uint8_t* enc, uint8_t* xy, uint8_t* ok) {
@@ -3234,8 +3227,7 @@ int edc_synchronize(edc_ctx* ctx) {
 // preconditions of every cached entry: a table, and slot 0 (their stream and workspace) idle
 static int sc_ready(edc_ctx* ctx) {
   if (!ctx->sc_cap) { ctx->err = "no signature cache on this context (edc_sigcache_create)"; return EDC_ERR_ARG; }
-  if (ctx->slot[0].pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  return 0;
+  return claim_slot0(ctx) ? 0 : EDC_ERR_ARG;
 }
 
 // Ordering against the deferred inserts of cached verifiers (edc_ctx::sc_ev): work enqueued on st
@@ -3582,8 +3574,7 @@ static int quorum_check(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, con
   if (rc) return rc;
   if (!threshold) { ctx->err = "null threshold"; return EDC_ERR_ARG; }
   if (!quorum_check_mode(mode)) { ctx->err = "mode is EDC_QUORUM_FULL or EDC_QUORUM_LIGHT"; return EDC_ERR_ARG; }
-  if (ctx->slot[0].pending) { ctx->err = "slot 0 busy: wait for submitted batches first"; return EDC_ERR_ARG; }
-  return 0;
+  return claim_slot0(ctx) ? 0 : EDC_ERR_ARG;
 }
 
 // the votes of a host form
@@ -4036,8 +4027,8 @@ static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t
                                    TmplQuorumItems* it_out) {
   TmplShape sh;
   size_t n;
-  int rc = commits_check_tmpl_alt(ctx, ts, nc, commit_off, commit_tpl, alt_span, item_alt, vk, key_idx, sig, var, var_off,
-                                  &sh, &n);
+  int rc = commits_check_tmpl(ctx, ts, nc, commit_off, commit_tpl, true, alt_span, item_alt, vk, key_idx, sig, var, var_off,
+                              &sh, &n);
   if (rc || (rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n)) ||
       (rc = quorum_check_votes(ctx, nc, commit_off, power, flag)))
     return rc;
@@ -5416,7 +5407,7 @@ int64_t edc_multi_submit(edc_multi* M, size_t n, const uint8_t* vk, const uint8_
   if (!M || !z_seed || (n && (!vk || !sig || !msg_off))) return EDC_ERR_ARG;
   const int64_t ticket = M->next_ticket;
   MultiSlot& ms = M->ms[ticket % M->ring];
-  if (ms.pending) { M->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  if (ms.pending) { M->err = kAllSlotsInFlight; return EDC_ERR_ARG; }      // a MultiSlot: the claim's message, not its slot
   int rc = multi_slot_init(M, ms);
   if (rc) return rc;
   std::vector<Shard> sh;
@@ -5440,7 +5431,7 @@ int64_t edc_multi_submit_device(edc_multi* M, const size_t* n, const uint8_t* co
   if (!M || !z_seed || !n || !d_vk || !d_sig || !d_msg || !d_msg_off) return EDC_ERR_ARG;
   const int64_t ticket = M->next_ticket;
   MultiSlot& ms = M->ms[ticket % M->ring];
-  if (ms.pending) { M->err = "all slots in flight: wait for the oldest ticket first"; return EDC_ERR_ARG; }
+  if (ms.pending) { M->err = kAllSlotsInFlight; return EDC_ERR_ARG; }      // a MultiSlot: the claim's message, not its slot
   int rc = multi_slot_init(M, ms);
   if (rc) return rc;
   const size_t G = M->ctx.size();
