@@ -40,6 +40,9 @@ EDC_QUORUM_SHORT = 3
 NOT_CHECKED = 255
 VOTE_ABSENT, VOTE_COMMIT, VOTE_NIL = 0, 1, 2
 QUORUM_FULL, QUORUM_LIGHT = 0, 1
+# validator-set quorum commit sets (include/edc.h, edc_valset_*)
+EDC_DOUBLE_VOTE = 4
+NO_POS = 0xFFFFFFFF
 
 # every symbol include/edc.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -78,6 +81,8 @@ ABI_SYMBOLS = [
     "edc_tmpl_quorum_verify", "edc_tmpl_quorum_verify_device", "edc_debug_tmpl_quorum_last",
     "edc_cached_quorum_verify_device", "edc_cached_quorum_verify", "edc_cached_tmpl_quorum_verify_device",
     "edc_cached_tmpl_quorum_verify", "edc_debug_cached_quorum_last",
+    "edc_valset_set_powers", "edc_valset_size", "edc_valset_resolve", "edc_valset_quorum_verify_device",
+    "edc_valset_quorum_verify", "edc_debug_valset_select",
 ]
 
 
@@ -128,6 +133,11 @@ class InvalidSliceLength(Error):
 class QuorumShort(Error):
     """Every checked vote of the commit verified, but its tally is not above the threshold
     (EDC_QUORUM_SHORT; CometBFT's ErrNotEnoughVotingPowerSigned). Not an error of the reference crate."""
+
+
+class DoubleVote(Error):
+    """Two checked votes of one commit come from the same member of the validator set
+    (EDC_DOUBLE_VOTE; CometBFT's double-vote error). Not an error of the reference crate."""
 
 
 class EngineError(RuntimeError):
@@ -381,6 +391,18 @@ def load_library(path=None):
                 a = list(getattr(lib, name).argtypes)
                 getattr(lib, name.replace("edc_", "edc_cached_", 1)).argtypes = a[:-1] + [ctypes.POINTER(c_sz), a[-1]]
             lib.edc_debug_cached_quorum_last.argtypes = [c_vp, c_u64p]
+        if hasattr(lib, "edc_valset_quorum_verify"):         # absent from older A/B builds (tools/)
+            # the quorum twins' arguments without the power array
+            a = list(lib.edc_quorum_verify_device.argtypes)
+            lib.edc_valset_quorum_verify_device.argtypes = a[:8] + a[9:]
+            a = list(lib.edc_quorum_verify.argtypes)
+            lib.edc_valset_quorum_verify.argtypes = a[:9] + a[10:]
+            lib.edc_valset_set_powers.argtypes = [c_vp, c_sz, c_u64p]
+            lib.edc_valset_size.argtypes = [c_vp]
+            lib.edc_valset_resolve.argtypes = [c_vp, c_sz, c_u32p, c_u8p, c_u32p, c_u8p, c_u64p, ctypes.c_int, c_vp, c_vp,
+                                               c_vp, c_vp, c_vp, c_szp, c_vp]
+            lib.edc_debug_valset_select.argtypes = [c_vp, c_sz, c_u32p, c_u8p, c_u32p, c_u8p, c_u64p, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         if path is None:
             _lib = lib
         return lib
@@ -944,6 +966,78 @@ class Engine:
             rc = self.lib.edc_debug_tmpl_quorum_last(self.ctx, out)
         self._check(rc)
         return tuple(out)
+
+    # ---- validator-set quorum commit sets (edc_valset_*): the powers are the registered list's, the
+    # join of the votes against it and the double-vote check run on the GPU ----
+    def valset_set_powers(self, powers):
+        """edc_valset_set_powers: one power per position of the last keycache_load list; None or []
+        clears them. Returns the member count."""
+        powers = [int(x) for x in (powers or [])]
+        if any(x < 0 or x >= 1 << 64 for x in powers):
+            raise ValueError("powers are uint64")
+        pw = (ctypes.c_uint64 * len(powers))(*powers) if powers else None
+        with self._lock:
+            self._check(self.lib.edc_valset_set_powers(self.ctx, len(powers), pw))
+        return self.valset_size()
+
+    def valset_size(self):
+        return int(self.lib.edc_valset_size(self.ctx))
+
+    @staticmethod
+    def _valset_flags(n, flags):
+        flags = [int(x) for x in flags]
+        if len(flags) != n:
+            raise ValueError("one flag per item")
+        if any(x < 0 or x > 255 for x in flags):
+            raise ValueError("flags are uint8")
+        return bytes(flags) or b"\0"
+
+    def valset_resolve(self, commit_off, flags, thresholds, light=True, vks=None, key_idx=None):
+        """edc_valset_resolve: the join, the selection and the double-vote scan alone -> a dict: pos
+        (NO_POS for a signer that is no member), power, flag, checked, planned, n_checked, dv."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        fl, th = self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds)
+        pos, power = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))()
+        flag_out, checked = ctypes.create_string_buffer(max(n, 1)), ctypes.create_string_buffer(max(n, 1))
+        planned, dv = (ctypes.c_uint64 * max(nc, 1))(), ctypes.create_string_buffer(max(nc, 1))
+        cnt = ctypes.c_size_t(0)
+        with self._lock:
+            rc = self.lib.edc_valset_resolve(self.ctx, nc, off, vkb, idx, fl, th, int(bool(light)), pos, power, flag_out,
+                                             checked, planned, ctypes.byref(cnt), dv)
+        self._check(rc)
+        return {"pos": list(pos[:n]), "power": list(power[:n]), "flag": list(flag_out.raw[:n]),
+                "checked": list(checked.raw[:n]), "planned": list(planned[:nc]), "n_checked": cnt.value,
+                "dv": list(dv.raw[:nc])}
+
+    def quorum_verify_valset(self, commit_off, sigs, flags, thresholds, z_seed, light=True, vks=None, key_idx=None,
+                             msgs=None, ks=None):
+        """edc_valset_quorum_verify: quorum_verify with the powers of the registered validator set
+        (valset_set_powers). A commit with two checked votes of one member is EDC_DOUBLE_VOTE.
+        Returns the dict quorum_verify returns."""
+        form = self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks)
+        votes = self._valset_flags(form[1], flags), self._quorum_thresholds(form[0], thresholds)
+        return self._quorum_call(self.lib.edc_valset_quorum_verify, False, form, votes, z_seed, light)
+
+    def quorum_verify_valset_device(self, commit_off, d_vk, d_sig, d_msg, d_msg_off, d_flag, thresholds, z_seed,
+                                    light=True, d_k=None):
+        """edc_valset_quorum_verify_device: quorum_verify_device without d_power."""
+        form = self._commits_device(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k)
+        votes = self._dev_ptr(d_flag), self._quorum_thresholds(form[0], thresholds)
+        return self._quorum_call(self.lib.edc_valset_quorum_verify_device, False, form, votes, z_seed, light)
+
+    def valset_select_ms(self, commit_off, flags, thresholds, light=True, vks=None, key_idx=None, reps=20):
+        """edc_debug_valset_select: mean times of the join kernel and of the double-vote scan, in milliseconds."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        fl, th = self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds)
+        ms = (ctypes.c_float * 2)()
+        with self._lock:
+            rc = self.lib.edc_debug_valset_select(self.ctx, nc, off, vkb, idx, fl, th, int(bool(light)), reps, ms)
+        self._check(rc)
+        return ms[0], ms[1]
 
     def quorum_select_ms(self, commit_off, powers, flags, thresholds, light=True, reps=20):
         """edc_debug_quorum_select: mean time of the selection kernels alone, in milliseconds."""
@@ -1730,8 +1824,18 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         or NOT_CHECKED. z_seed as verify_many. cached=True goes through the engine's verified-signature
         table (Engine.sigcache_create; edc_cached_quorum_verify): checked votes that already verified
         on the engine are not verified again and count as EDC_OK, and what this call proves valid is
-        remembered. The return value has the same form."""
+        remembered. The return value has the same form.
+        powers=None takes the powers from the engine's registered validator set
+        (Engine.valset_set_powers; edc_valset_quorum_verify): a vote whose key is no member of it
+        counts as absent, and a commit with two checked votes of one member gets EDC_DOUBLE_VOTE."""
         verifiers = list(verifiers)
+        if powers is None:
+            if cached:
+                raise ValueError("verify_quorum: the registered validator set has no cached form")
+            powers = [[0] * v.batch_size if isinstance(v, batch.Verifier) else [] for v in verifiers]
+            from_set = True
+        else:
+            from_set = False
         for v in verifiers:
             if not isinstance(v, batch.Verifier):
                 raise TypeError("verify_quorum takes batch.Verifier objects")
@@ -1756,7 +1860,11 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         sigs = [x for v in verifiers for x in v._sigs]
         msgs = [x for v in verifiers for x in v._msgs]
         pw, fl = [x for p in powers for x in p], [x for f in flags for x in f]
-        run = eng.quorum_verify_cached if cached else eng.quorum_verify
+        if from_set:
+            def run(off, sigs, pw, fl, thresholds, z_seed, **kw):
+                return eng.quorum_verify_valset(off, sigs, fl, thresholds, z_seed, **kw)
+        else:
+            run = eng.quorum_verify_cached if cached else eng.quorum_verify
         if all(m is not None for m in msgs):
             res = run(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, msgs=msgs)
         else:                                    # some items carry only their k: hash the rest in one launch

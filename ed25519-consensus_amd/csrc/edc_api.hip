@@ -22,6 +22,7 @@
 #include "tmpl.h"
 #include "commits.h"
 #include "quorum.h"
+#include "valset.h"
 #include "sigcache.h"
 #include "devbuf.h"
 
@@ -275,6 +276,24 @@ struct edc_ctx {
   DevBuf<uint32_t> cq_wg, cq_idx;
   uint64_t cq_last[6] = {};
   bool cq_have = false;
+  // validator-set quorum commit sets (valset.h; edc_valset_*). The powers of the registered list
+  // (edc_valset_set_powers), by cache index: power, member byte and position on the device for the
+  // vs_count keys the cache held then, the positions on the host too (vs_posh) beside the host copy
+  // of kc_reg; vs_m members. Per call, on slot 0's stream: the staged flags and key positions of
+  // the host forms and the members' cache indices (vs_cap_n items), the pair set of the double-vote
+  // scan (2 words per item), the commits' double-vote bytes and the pinned bytes they come back in
+  // (vs_cap_c commits)
+  std::vector<uint32_t> kc_regh, vs_posh;
+  DevBuf<uint64_t> vs_power;
+  DevBuf<uint8_t> vs_member;
+  DevBuf<uint32_t> vs_pos;
+  uint32_t vs_count = 0, vs_m = 0;
+  size_t vs_cap_n = 0, vs_cap_c = 0;
+  DevBuf<uint32_t> vs_who, vs_kidx;
+  DevBuf<uint64_t> vs_set;
+  DevBuf<uint8_t> vs_flag, vs_dv;
+  PinnedBuf<uint8_t> vs_hdv;
+  ValsetView vs() const { return ValsetView{vs_power, vs_member, vs_pos, vs_count}; }
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -1591,9 +1610,18 @@ edc_ctx* edc_create(int device) {
   return ctx;
 }
 
+// the powers of the registered list (edc_valset_set_powers)
+static void free_valset(edc_ctx* ctx) {
+  reset_all(ctx->vs_power, ctx->vs_member, ctx->vs_pos);
+  ctx->vs_count = ctx->vs_m = 0;
+  ctx->vs_posh.clear();
+}
+
 static void free_keycache(edc_ctx* ctx) {
   reset_all(ctx->kc_table, ctx->kc_keys, ctx->kc_comb, ctx->kc_ok, ctx->kc_reg);
   ctx->kc_reg_m = 0;
+  ctx->kc_regh.clear();
+  free_valset(ctx);             // the powers belong to the list
   ctx->kc_m = ctx->kc_tmask = ctx->kc_cap = 0;
   ctx->kc_gen++;
   ctx->kc_words.clear();
@@ -3013,6 +3041,7 @@ int64_t edc_keycache_load(edc_ctx* ctx, size_t m, const uint8_t* vk, uint8_t* ok
   CK(ctx->kc_reg.alloc(m));
   CK(hipMemcpy(ctx->kc_reg, of.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
   ctx->kc_reg_m = (uint32_t)m;
+  ctx->kc_regh = of;
   if (ok)
     for (size_t i = 0; i < m; ++i) ok[i] = ctx->kc_okh[of[i]];
   return ctx->kc_m;
@@ -3809,9 +3838,10 @@ struct QuorumCached {
 // after a passing union, the misses with code 0 after a failed one) before the last
 // synchronization, and a failed union's codes go back over the lookup's base codes, through the
 // list's positions in the looked-up list and that list's positions in the queue.
+// dv (a validator-set form, host, nc bytes): the commits that hold a double vote (valset_reduce).
 static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, const ItemList& list,
                          const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
-                         const QuorumCached* cq = nullptr) {
+                         const QuorumCached* cq = nullptr, const uint8_t* dv = nullptr) {
   hipStream_t st = ctx->st();
   const size_t m = list.count;
   std::vector<uint8_t> mv(m ? m : 1);
@@ -3868,7 +3898,9 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
     for (size_t c = 0; c < nc; ++c) cor[c] = cor32[c] ? 1 : 0;
   }
   size_t bad = 0;
-  const int res = quorum_reduce(nc, cor.empty() ? nullptr : cor.data(), tal.data(), threshold, out.commit_verdicts, &bad);
+  const uint8_t* corp = cor.empty() ? nullptr : cor.data();
+  const int res = dv ? valset_reduce(nc, corp, tal.data(), threshold, dv, out.commit_verdicts, &bad)
+                     : quorum_reduce(nc, corp, tal.data(), threshold, out.commit_verdicts, &bad);
   if (out.tally) memcpy(out.tally, tal.data(), nc * sizeof(uint64_t));
   if (out.n_bad_commits) *out.n_bad_commits = (int)bad;
   if (out.n_checked) *out.n_checked = cq ? cq->n_checked : m;
@@ -4391,6 +4423,301 @@ int edc_cached_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t 
 int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
   if (!ctx || !out || !ctx->cq_have) return EDC_ERR_ARG;
   memcpy(out, ctx->cq_last, sizeof(ctx->cq_last));
+  return EDC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- validator-set quorum commit sets
+// edc_valset_*: the quorum entries with the join on the device. The registered list carries its
+// powers (edc_valset_set_powers); the resolve kernel turns every vote's key bytes (or position)
+// into the power and flag the selection reads, in q_power / q_flag where a host form of the quorum
+// entries stages them; the double-vote scan runs behind the selection on its skip bytes, and its
+// per-commit bytes come back with the selection's one read-back. Everything after that is the
+// quorum entries' own: quorum_gather, then quorum_finish with the double-vote bytes.
+static int ensure_valset(edc_ctx* ctx, size_t n, size_t nc) {
+  hipStream_t st = ctx->st();
+  CK(grow_group(ctx->vs_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
+    return alloc_all(sized(ctx->vs_who, cap), sized(ctx->vs_kidx, cap), sized(ctx->vs_flag, cap), sized(ctx->vs_set, 2 * cap));
+  }));
+  CK(grow_group(ctx->vs_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
+    hipError_t e = ctx->vs_dv.alloc(cap);
+    return e != hipSuccess ? e : ctx->vs_hdv.alloc(cap);
+  }));
+  return 0;
+}
+
+static int valset_ready(edc_ctx* ctx) {
+  if (!ctx->vs_m) { ctx->err = "no voting powers on the registered list (edc_valset_set_powers)"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+// Workspace for n items in nc commits on slot 0; everything the selection allocates is allocated
+// here, so that nothing the resolve kernel has written moves afterwards.
+static int valset_room(edc_ctx* ctx, size_t n, size_t nc) {
+  int rc = init_slot(ctx, ctx->slot[0]);
+  if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
+  return ensure_valset(ctx, n, nc);
+}
+
+// The join, the selection and the double-vote scan of n votes whose keys (d_vk, or d_kidx with
+// d_vk null) and flags are on the device, with one read-back: *n_checked, the commits'
+// double-vote bytes in vs_hdv and, if h_skip is given, the n skip bytes. valset_room has run.
+static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                         int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag, uint8_t* h_skip,
+                         size_t* n_checked) {
+  hipStream_t st = ctx->st();
+  launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, d_kidx, ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag,
+                        ctx->vs_who);
+  CK(hipGetLastError());
+  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag);
+  if (rc) return rc;
+  memset(ctx->vs_hdv, 0, nc);
+  if (n) {
+    CK(hipMemsetAsync(ctx->vs_dv, 0, nc, st));
+    CK(hipMemsetAsync(ctx->vs_set, 0, 2 * n * sizeof(uint64_t), st));
+    launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, ctx->sc_hit, ctx->vs_who, ctx->vs_set, ctx->vs_dv);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(ctx->vs_hdv, ctx->vs_dv, nc, hipMemcpyDeviceToHost, st));
+    if (h_skip) CK(hipMemcpyAsync(h_skip, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
+  }
+  return quorum_select_read(ctx, n, n_checked,
+                            "votes: a flag above 2 or a commit whose counted power passes 2^63 - 1");
+}
+
+// keys (bytes into ctx->vk, or positions into vs_kidx) and flags (vs_flag) of n > 0 host votes
+static int valset_stage_votes(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag) {
+  hipStream_t st = ctx->st();
+  if (key_idx) {
+    CK(hipMemcpyAsync(ctx->vs_kidx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  } else {
+    int rc = ensure_n(ctx, n);
+    if (rc) return rc;
+    CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
+  }
+  CK(hipMemcpyAsync(ctx->vs_flag, flag, n, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// what the host checks of a call on host keys and flags without signatures (resolve, the hook)
+static int valset_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                             const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, size_t* n) {
+  int rc = quorum_check(ctx, nc, commit_off, threshold, mode, n);
+  if (rc || (rc = valset_ready(ctx))) return rc;
+  if (*n) {
+    if ((rc = commits_check_keys(ctx, *n, vk, key_idx))) return rc;
+    if (!flag) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  }
+  return 0;
+}
+
+// A checked validator-set commit set whose items (all: vk, sig, k) are on the device and whose keys
+// or positions and flags are where valset_select reads them. host_k: a host form's prehashed k,
+// which must be canonical for the checked votes (the skip bytes come back with the read-back).
+static int valset_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
+                      const ItemList& all, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
+                      const uint8_t* host_k, const uint8_t* z_seed, const QuorumOut& out) {
+  const size_t n = all.count;
+  size_t m = 0;
+  ItemList list;
+  std::vector<uint8_t> skip(host_k ? n : 0);
+  int rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, host_k && n ? skip.data() : nullptr, &m);
+  if (rc) return rc;
+  for (size_t i = 0; i < skip.size(); ++i) {      // Scalar::from_hash never yields k >= l
+    uint32_t w[8];
+    memcpy(w, host_k + 32 * i, 32);
+    if (!skip[i] && w[7] >= 0x10000000u && !sc_is_canonical(w)) {
+      ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
+      return EDC_ERR_ARG;
+    }
+  }
+  if ((rc = quorum_gather(ctx, all, m, ctx->sc_hit, ctx->sc_wg, sc_area(ctx), &list))) return rc;
+  return quorum_finish(ctx, nc, threshold, n, list, ctx->q_power, ctx->q_flag, z_seed, out, nullptr, ctx->vs_hdv);
+}
+
+extern "C" {
+
+int edc_valset_set_powers(edc_ctx* ctx, size_t m, const uint64_t* power) {
+  if (!ctx) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  for (Slot& s : ctx->slot)
+    if (s.pending) { ctx->err = "voting powers change with a batch in flight"; return EDC_ERR_ARG; }
+  int rc = sync_all(ctx);
+  if (rc) return rc;
+  if (!m && !power) {
+    free_valset(ctx);
+    return EDC_OK;
+  }
+  if (!ctx->kc_reg_m) { ctx->err = "no registered key list (edc_keycache_load)"; return EDC_ERR_ARG; }
+  if (m != ctx->kc_reg_m || !power) { ctx->err = "one power per position of the registered key list"; return EDC_ERR_ARG; }
+  const uint32_t u = ctx->kc_m;
+  std::vector<uint64_t> pw(u, 0);
+  std::vector<uint8_t> mem(u, 0);
+  std::vector<uint32_t> pos(u, VALSET_NO_POS);
+  for (size_t p = 0; p < m; ++p) {
+    const uint32_t c = ctx->kc_regh[p];
+    if (mem[c]) { ctx->err = "the registered key list holds a key twice: not a validator set"; return EDC_ERR_ARG; }
+    mem[c] = 1;
+    pw[c] = power[p];
+    pos[c] = (uint32_t)p;
+  }
+  if (!valset_check_powers(m, power)) {
+    ctx->err = "voting power: every power and their sum at most 2^63 - 1";
+    return EDC_ERR_ARG;
+  }
+  DevBuf<uint64_t> d_pw;          // committed to the context only on success
+  DevBuf<uint8_t> d_mem;
+  DevBuf<uint32_t> d_pos;
+  CK(alloc_all(sized(d_pw, u), sized(d_mem, u), sized(d_pos, u)));
+  CK(hipMemcpy(d_pw, pw.data(), u * sizeof(uint64_t), hipMemcpyHostToDevice));
+  CK(hipMemcpy(d_mem, mem.data(), u, hipMemcpyHostToDevice));
+  CK(hipMemcpy(d_pos, pos.data(), u * sizeof(uint32_t), hipMemcpyHostToDevice));
+  ctx->vs_power = std::move(d_pw);
+  ctx->vs_member = std::move(d_mem);
+  ctx->vs_pos = std::move(d_pos);
+  ctx->vs_posh.swap(pos);
+  ctx->vs_count = u;
+  ctx->vs_m = (uint32_t)m;
+  return EDC_OK;
+}
+
+int edc_valset_size(const edc_ctx* ctx) { return ctx ? (int)ctx->vs_m : 0; }
+
+int edc_valset_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
+                       const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos, uint64_t* power,
+                       uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked, uint8_t* dv) {
+  if (!ctx) return EDC_ERR_ARG;
+  if (!nc) {
+    if (n_checked) *n_checked = 0;
+    return EDC_OK;
+  }
+  size_t n, m = 0;
+  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n);
+  if (rc) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = valset_room(ctx, n, nc)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
+  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx,
+                          ctx->vs_flag, nullptr, &m)))
+    return rc;
+  hipStream_t st = ctx->st();
+  std::vector<uint32_t> who(pos ? n : 0);
+  if (pos && n) CK(hipMemcpyAsync(who.data(), ctx->vs_who, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (power && n) CK(hipMemcpyAsync(power, ctx->q_power, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (flag_out && n) CK(hipMemcpyAsync(flag_out, ctx->q_flag, n, hipMemcpyDeviceToHost, st));
+  if (planned) CK(hipMemcpyAsync(planned, ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (checked && n) CK(hipMemcpyAsync(checked, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  for (size_t i = 0; i < who.size(); ++i) pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : ctx->vs_posh[who[i]];
+  if (checked)
+    for (size_t i = 0; i < n; ++i) checked[i] = checked[i] ? 0 : 1;      // the kernel writes the skip byte
+  if (dv) memcpy(dv, ctx->vs_hdv, nc);
+  if (n_checked) *n_checked = m;
+  return EDC_OK;
+}
+
+int edc_valset_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                    const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                    const uint8_t* d_k, const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                                    const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                                    uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
+  size_t n;
+  if ((rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n)) || (rc = valset_ready(ctx))) return rc;
+  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off) || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)))) {
+    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
+    return EDC_ERR_ARG;
+  }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = valset_room(ctx, n, nc))) return rc;
+  const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
+  if (n && !k) {
+    if ((rc = ensure_n(ctx, n))) return rc;
+    launch_challenge(ctx->st(), (uint32_t)n, d_vk, d_sig, d_msg, d_msg_off, ctx->kbuf);
+    CK(hipGetLastError());
+    k = ctx->kbuf;
+  }
+  return valset_run(ctx, nc, commit_off, threshold, mode, ItemList{d_vk, d_sig, k, nullptr, n}, d_vk, nullptr, d_flag,
+                    nullptr, z_seed, out);
+}
+
+int edc_valset_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                             const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                             const uint8_t* k, const uint8_t* flag, const uint64_t* threshold, int mode,
+                             const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                             int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
+  size_t n;
+  if ((rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n))) return rc;
+  if (n) {
+    if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
+    if ((rc = commits_check_msg_or_k(ctx, n, msg, msg_off, k))) return rc;
+  }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = valset_room(ctx, n, nc))) return rc;
+  hipStream_t st = ctx->st();
+  if (k) {
+    if ((rc = ensure_n(ctx, n))) return rc;
+    if (n) CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
+  } else if ((rc = upload_msgs(ctx, n, msg, n ? msg_off : nullptr))) {
+    return rc;
+  }
+  if (n) {                  // 4 + 64 + 1 bytes per vote in the key_idx form: the keys are expanded on the device
+    CK(hipMemcpyAsync(ctx->vs_flag, flag, n, hipMemcpyHostToDevice, st));
+    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->vs_kidx, ctx->vk, ctx->sig))) return rc;
+    if (!k) {
+      launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
+      CK(hipGetLastError());
+    }
+  }
+  return valset_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n},
+                    key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, n ? k : nullptr, z_seed, out);
+}
+
+int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                            const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, int reps,
+                            float ms[2]) {
+  if (!ctx || reps < 1) return EDC_ERR_ARG;
+  if (ms) ms[0] = ms[1] = 0.f;
+  if (!nc) return EDC_OK;
+  size_t n, m = 0;
+  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n);
+  if (rc) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = valset_room(ctx, n, nc)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
+  const uint8_t* d_vk = key_idx ? nullptr : ctx->vk.get();
+  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, ctx->vs_kidx, ctx->vs_flag, nullptr, &m))) return rc;
+  if (!n) return EDC_OK;
+  hipStream_t st = ctx->st();
+  Event e0, e1, e2;
+  CK(e0.create());
+  CK(e1.create());
+  CK(e2.create());
+  CK(hipEventRecord(e0, st));
+  for (int r = 0; r < reps; ++r)        // the resolve kernel rewrites the same values
+    launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, ctx->vs_kidx, ctx->kc_reg, ctx->vs_flag, ctx->q_power,
+                          ctx->q_flag, ctx->vs_who);
+  CK(hipGetLastError());
+  CK(hipEventRecord(e1, st));
+  for (int r = 0; r < reps; ++r) {      // the scan with the clearing of its set and bytes, as every call runs it
+    CK(hipMemsetAsync(ctx->vs_dv, 0, nc, st));
+    CK(hipMemsetAsync(ctx->vs_set, 0, 2 * n * sizeof(uint64_t), st));
+    launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, ctx->sc_hit, ctx->vs_who, ctx->vs_set, ctx->vs_dv);
+  }
+  CK(hipGetLastError());
+  CK(hipEventRecord(e2, st));
+  CK(hipEventSynchronize(e2));
+  float t0 = 0.f, t1 = 0.f;
+  CK(hipEventElapsedTime(&t0, e0, e1));
+  CK(hipEventElapsedTime(&t1, e1, e2));
+  if (ms) {
+    ms[0] = t0 / (float)reps;
+    ms[1] = t1 / (float)reps;
+  }
   return EDC_OK;
 }
 

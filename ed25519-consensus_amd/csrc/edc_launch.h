@@ -138,6 +138,27 @@ void launch_tmpl_quorum_gather(hipStream_t st, uint32_t n, uint32_t m, const uin
                                const uint32_t* wg_hole, const uint8_t* vk, const uint8_t* sig, const uint16_t* tpl,
                                const uint8_t* var, const uint32_t* var_off, uint32_t* idx, uint8_t* g_vk, uint8_t* g_sig,
                                uint16_t* g_tpl, uint8_t* g_var, uint32_t* g_var_off);
+// validator-set quorum commit sets (valset.h; edc_valset_*). The powers of the registered list,
+// indexed by cache index (count entries; a cache index at or past count is no member): power[c],
+// member[c] = 1 iff key c is a member, pos[c] = its position in the list.
+struct ValsetView {
+  const uint64_t* power;
+  const uint8_t* member;
+  const uint32_t* pos;
+  uint32_t count;
+};
+// launch_valset_resolve runs before the selection, on all n items: item i's signer is looked up by
+// its key bytes (vk, 16-byte aligned) or by its position (key_idx into reg, every entry checked by
+// the caller; vk null); power[i] / flag_out[i] are the selection's inputs (a flag above 2 is kept
+// so that the selection's checks refuse it), who[i] the member's cache index or KC_EMPTY.
+// launch_valset_pairs runs behind the selection, on its skip bytes and commit indices: dv[c] (nc
+// bytes, zeroed by the caller) = 1 iff two checked items of commit c have the same who; set: 2 n
+// words, zeroed by the caller.
+void launch_valset_resolve(hipStream_t st, uint32_t n, const KeyCacheView& kc, const ValsetView& vs, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag, uint64_t* power,
+                           uint8_t* flag_out, uint32_t* who);
+void launch_valset_pairs(hipStream_t st, uint32_t n, const uint32_t* commit_off, const uint32_t* cidx, const uint8_t* skip,
+                         const uint32_t* who, uint64_t* set, uint8_t* dv);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

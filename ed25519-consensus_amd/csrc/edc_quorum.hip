@@ -340,6 +340,74 @@ __global__ void __launch_bounds__(QR_TILE) k_tq_gather(uint32_t n, uint32_t m, c
   }
 }
 
+// Validator-set quorum commit sets (valset.h; edc_valset_*): the powers are the registered list's,
+// and a commit in which one validator has two checked votes is refused. Two kernels around the
+// selection above:
+//   k_vs_resolve  before it, one lane per item: the signer's cache index (kc_lookup on the key
+//                 bytes, or kc_reg on a position), then power / flag as the selection reads them
+//                 (a member's power and its flag; 0 and EDC_VOTE_ABSENT for anyone else) and
+//                 who[i] = the member's cache index or KC_EMPTY. A flag above 2 is passed through
+//                 whoever signed, so that k_q_tile raises the error flag on it. Reads the hash
+//                 table, the key words and the per-index power / member bytes, never a comb table.
+//   k_vs_pairs    behind it, one lane per checked item: the pair (commit, member) goes into an
+//                 open-addressing set by a 64-bit compare-and-swap on an empty slot. A lane that
+//                 meets its own pair in the set raises dv[c]. Commit c owns the slots
+//                 [2 off[c], 2 off[c+1]) of the set, twice its items, so a probe never leaves the
+//                 commit's span, never meets a full span and the set is 16 bytes per item.
+// Of two lanes with the same pair exactly one wins the empty slot and the other then finds it there
+// (nothing is ever removed and both walk the same slots), so dv[c] = 1 iff some pair occurs twice,
+// whatever the order of the lanes; the stores to dv[c] all write 1.
+__global__ void __launch_bounds__(QR_TILE) k_vs_resolve(uint32_t n, KeyCacheView kc, ValsetView vs,
+                                                        const uint8_t* __restrict__ vk,
+                                                        const uint32_t* __restrict__ key_idx,
+                                                        const uint32_t* __restrict__ reg,
+                                                        const uint8_t* __restrict__ flag, uint64_t* __restrict__ power,
+                                                        uint8_t* __restrict__ flag_out, uint32_t* __restrict__ who) {
+  const uint32_t i = blockIdx.x * QR_TILE + threadIdx.x;
+  if (i >= n) return;
+  uint32_t c;
+  if (vk) {
+    const uint4* q = reinterpret_cast<const uint4*>(vk + (size_t)i * 32);
+    const uint4 a = q[0], b = q[1];
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const int r = kc_lookup(kc, w);
+    c = r < 0 ? KC_EMPTY : (uint32_t)r;
+  } else {
+    c = reg[key_idx[i]];                // the host checked key_idx[i] against the list's length
+  }
+  const bool member = c < vs.count && vs.member[c];
+  const uint8_t fl = flag[i];
+  power[i] = member ? vs.power[c] : 0;
+  flag_out[i] = (member || fl > QUORUM_NIL) ? fl : QUORUM_ABSENT;
+  who[i] = member ? c : KC_EMPTY;
+}
+
+__global__ void __launch_bounds__(QR_TILE) k_vs_pairs(uint32_t n, const uint32_t* __restrict__ commit_off,
+                                                      const uint32_t* __restrict__ cidx,
+                                                      const uint8_t* __restrict__ skip,
+                                                      const uint32_t* __restrict__ who,
+                                                      unsigned long long* __restrict__ set, uint8_t* __restrict__ dv) {
+  const uint32_t i = blockIdx.x * QR_TILE + threadIdx.x;
+  if (i >= n || skip[i]) return;
+  const uint32_t m = who[i];
+  if (m == KC_EMPTY) return;
+  const uint32_t c = cidx[i];
+  const uint32_t a = commit_off[c], slots = 2 * (commit_off[c + 1] - a);      // item i is one of them: slots >= 2
+  if (!slots) return;
+  unsigned long long* span = set + 2 * (size_t)a;
+  const unsigned long long pair = ((unsigned long long)c << 32) | (m + 1);   // never 0, the empty slot
+  uint32_t h = (uint32_t)(((uint64_t)(m * 0x9E3779B1u) * slots) >> 32);
+  for (uint32_t probe = 0; probe < slots; ++probe) {
+    const unsigned long long old = atomicCAS(&span[h], 0ull, pair);
+    if (old == 0) return;
+    if (old == pair) {
+      dv[c] = 1;
+      return;
+    }
+    h = h + 1 == slots ? 0 : h + 1;
+  }
+}
+
 }  // namespace
 
 size_t quorum_tiles(size_t n) { return (n + QR_TILE - 1) / QR_TILE; }
@@ -377,6 +445,21 @@ void launch_quorum_tally(hipStream_t st, uint32_t n, const uint32_t* cidx, const
   if (!n) return;
   hipLaunchKernelGGL(k_q_tally, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, cidx, power, flag, code,
                      reinterpret_cast<unsigned long long*>(tally), cor);
+}
+
+void launch_valset_resolve(hipStream_t st, uint32_t n, const KeyCacheView& kc, const ValsetView& vs, const uint8_t* vk,
+                           const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag, uint64_t* power,
+                           uint8_t* flag_out, uint32_t* who) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_vs_resolve, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, kc, vs, vk, key_idx, reg, flag,
+                     power, flag_out, who);
+}
+
+void launch_valset_pairs(hipStream_t st, uint32_t n, const uint32_t* commit_off, const uint32_t* cidx, const uint8_t* skip,
+                         const uint32_t* who, uint64_t* set, uint8_t* dv) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_vs_pairs, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, commit_off, cidx, skip, who,
+                     reinterpret_cast<unsigned long long*>(set), dv);
 }
 
 }  // namespace edc

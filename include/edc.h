@@ -1243,6 +1243,104 @@ int edc_cached_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t 
 int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]);
 
 /*
+ * Validator-set quorum commit sets: powers and double votes resolved on the GPU. The quorum entries
+ * take a power and a flag per vote, which the caller has to work out before every call: for
+ * VerifyCommit a copy of the set's powers, for VerifyCommitLightTrusting a join of every signer's
+ * key against the trusted set ("EDC_VOTE_ABSENT for the signers that set does not know") and, in
+ * the same loop, CometBFT's check that no validator of the trusted set is seen twice in one commit
+ * (named here from memory, as the calls above are, and not checked against a source tree). These
+ * entries keep the powers with the registered key list and do the join and that check on the
+ * device. The reference crate has no such API and none of its APIs changes meaning: every vote
+ * that is checked is one batch::Item (src/batch.rs:76-94) in ONE batch::Verifier (queue + verify,
+ * src/batch.rs:127-137, :149-217), and its code is Item::verify_single's (src/batch.rs:104-107).
+ *
+ * edc_valset_set_powers  power[p] (uint64_t, m entries, host) is the voting power of position p of
+ *   the list last given to edc_keycache_load; the keys of that list are from then on the MEMBERS of
+ *   the validator set. EDC_ERR_ARG with nothing changed if m differs from that list's length, if
+ *   there is no list, if two positions of the list hold the same key (a validator set has distinct
+ *   keys), if a power is above 2^63 - 1 or if the powers sum to more than 2^63 - 1; refused while
+ *   batches are in flight, as edc_keycache_load is. The powers live on the device, indexed by cache
+ *   index, beside a member byte and the inverse map from cache index to position.
+ *   edc_keycache_load and edc_keycache_clear drop them; edc_keycache_add keeps them, and a key it
+ *   adds is not a member. m = 0 with a NULL power clears them.
+ * edc_valset_size  the member count; 0 when no powers are set (and for NULL).
+ *
+ * The join. Item i's signer is given by its key bytes or, in the host forms, by its position
+ * key_idx[i] in the registered list. With the powers set,
+ *   pos[i]       the registered position of the signer, 0xFFFFFFFF when its key is not a member;
+ *   power[i]     the member's power, 0 for anyone else;
+ *   flag_out[i]  flag[i] for a member, EDC_VOTE_ABSENT for anyone else.
+ * checked[i], planned[c] and *n_checked are exactly edc_quorum_plan's for (power, flag_out) with the
+ * same offsets, thresholds and mode.
+ * Double-vote rule. dv[c] = 1 iff two CHECKED items of commit c resolve to the same member. It is
+ *   the loop's own rule: in light mode a second vote that arrives after the quorum is not checked
+ *   and raises nothing, one that is checked does; in full mode every signed vote is checked, and a
+ *   commit vote and a nil vote from one validator are a double vote too. The same validator in two
+ *   different commits is none, and two non-members never are.
+ * edc_valset_resolve  the join, the selection and the double-vote scan alone, on host arrays (no
+ *   signatures): exactly one of vk (n x 32) and key_idx; outputs pos (uint32_t, n), power (n),
+ *   flag_out (n), checked (n bytes, 0 / 1), planned (nc), *n_checked and dv (nc bytes), all
+ *   nullable. It is to these entries what edc_quorum_plan is to the quorum entries and runs the
+ *   kernels they run.
+ *
+ * edc_valset_quorum_verify_device / edc_valset_quorum_verify  the arguments of
+ *   edc_quorum_verify_device / edc_quorum_verify without d_power / power. Inputs and outputs keep
+ *   their meaning, with three changes:
+ *   - item i's power and flag are the joined power[i] and flag_out[i]. A non-member's vk, sig and
+ *     message bytes are never interpreted and its code is EDC_NOT_CHECKED (without d_k its message
+ *     is hashed with every other and must be mapped like any other);
+ *   - a commit with dv[c] = 1 has the verdict EDC_DOUBLE_VOTE whatever else holds for it. Its
+ *     checked items are still verified and still get their codes, so the gathered list does not
+ *     depend on dv; its tally is the sum as defined and carries no meaning;
+ *   - the return value is EDC_OK iff every commit is EDC_OK; else EDC_INVALID_SIGNATURE if any
+ *     commit is EDC_INVALID_SIGNATURE; else EDC_DOUBLE_VOTE if any commit is EDC_DOUBLE_VOTE; else
+ *     EDC_QUORUM_SHORT. *n_bad_commits counts every commit that is not EDC_OK.
+ * Equality contract. On a set with no double vote every output, check8 included, equals what
+ *   edc_quorum_verify[_device] gives for the same keys, z_seed, thresholds and mode when it is
+ *   handed the joined power / flag_out. With double votes every output except the verdicts of those
+ *   commits, *n_bad_commits and the return value still equals it.
+ * Stream synchronizations. The join runs before the selection, the double-vote scan behind it on
+ *   its skip bytes and commit indices, and dv travels in the selection's one read-back:
+ *   edc_valset_quorum_verify_device adds no stream synchronization to what edc_quorum_verify_device
+ *   has. The scan's workspace is 16 bytes per item and a byte per commit, grow-only.
+ * Argument checks. The host checks the offsets, the mode, the one-of pairs, that the key indices
+ *   lie inside the registered list and that powers are set (without powers: EDC_ERR_ARG). The device
+ *   checks a flag above 2, for members and non-members alike, and the bound on a commit's counted
+ *   sum: duplicates can push one commit past 2^63 - 1, which is EDC_ERR_ARG for the call. Both forms
+ *   rely on the device for these, because the powers exist only there. On a violation nothing is
+ *   gathered, no output is written, no index outside the declared arrays is formed and the context
+ *   stays usable. A host form's prehashed k must be canonical for the checked items only. nc = 0
+ *   returns EDC_OK (no array is read); a NULL ctx or z_seed is EDC_ERR_ARG. The calls are synchronous
+ *   on slot 0 (EDC_ERR_ARG while a submitted batch is pending there). The key_idx host form
+ *   resolves by position, with no hash lookup, and stages 4 + 64 + 1 bytes per vote plus k or the
+ *   message.
+ * edc_debug_valset_select  measurement hook: on host arrays checked as edc_valset_resolve, the join
+ *   kernel and the double-vote scan (with the clearing of its workspace) alone, each run `reps`
+ *   times between HIP events; ms (nullable) = {the join's mean time, the scan's}.
+ * Not built: templated, cached, asynchronous submit / wait, incremental-verifier and multi-GPU
+ *   forms of these entries.
+ */
+#define EDC_DOUBLE_VOTE 4            /* two checked votes of one commit from the same member */
+int edc_valset_set_powers(edc_ctx* ctx, size_t m, const uint64_t* power);
+int edc_valset_size(const edc_ctx* ctx);
+int edc_valset_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
+                       const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos, uint64_t* power,
+                       uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked, uint8_t* dv);
+int edc_valset_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                    const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                    const uint8_t* d_k, const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                                    const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                                    uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]);
+int edc_valset_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                             const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                             const uint8_t* k, const uint8_t* flag, const uint64_t* threshold, int mode,
+                             const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                             int* n_bad_commits, size_t* n_checked, uint8_t check8[32]);
+int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                            const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, int reps,
+                            float ms[2]);
+
+/*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
  * one batch::Verifier::verify (reference src/batch.rs:149-217) split into contiguous shards, one
  * per listed device (a device may be listed more than once: several contexts on one GPU). Shard g
