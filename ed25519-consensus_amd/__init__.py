@@ -43,6 +43,8 @@ QUORUM_FULL, QUORUM_LIGHT = 0, 1
 # validator-set quorum commit sets (include/edc.h, edc_valset_*)
 EDC_DOUBLE_VOTE = 4
 NO_POS = 0xFFFFFFFF
+# validator-set history (edc_vhist_*): the power of a position that is not a member
+VHIST_NOT_MEMBER = 0xFFFFFFFFFFFFFFFF
 
 # every symbol include/edc.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -83,6 +85,8 @@ ABI_SYMBOLS = [
     "edc_cached_tmpl_quorum_verify", "edc_debug_cached_quorum_last",
     "edc_valset_set_powers", "edc_valset_size", "edc_valset_resolve", "edc_valset_quorum_verify_device",
     "edc_valset_quorum_verify", "edc_debug_valset_select",
+    "edc_vhist_set", "edc_vhist_versions", "edc_vhist_totals", "edc_vhist_resolve", "edc_vhist_quorum_verify_device",
+    "edc_vhist_quorum_verify", "edc_debug_vhist_select",
 ]
 
 
@@ -403,6 +407,15 @@ def load_library(path=None):
                                                c_vp, c_vp, c_vp, c_szp, c_vp]
             lib.edc_debug_valset_select.argtypes = [c_vp, c_sz, c_u32p, c_u8p, c_u32p, c_u8p, c_u64p, ctypes.c_int,
                                                     ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+        if hasattr(lib, "edc_vhist_quorum_verify"):          # absent from older A/B builds (tools/)
+            # the validator-set twins' arguments with the commits' versions behind the offsets
+            for name in ("edc_valset_resolve", "edc_valset_quorum_verify_device", "edc_valset_quorum_verify",
+                         "edc_debug_valset_select"):
+                a = list(getattr(lib, name).argtypes)
+                getattr(lib, name.replace("valset", "vhist")).argtypes = a[:3] + [c_u32p] + a[3:]
+            lib.edc_vhist_set.argtypes = [c_vp, c_sz, c_u64p, c_sz, c_u32p, c_u32p, c_u64p]
+            lib.edc_vhist_versions.argtypes = [c_vp]
+            lib.edc_vhist_totals.argtypes = [c_vp, ctypes.c_uint32, c_sz, c_u64p, c_u32p]
         if path is None:
             _lib = lib
         return lib
@@ -995,8 +1008,13 @@ class Engine:
     def valset_resolve(self, commit_off, flags, thresholds, light=True, vks=None, key_idx=None):
         """edc_valset_resolve: the join, the selection and the double-vote scan alone -> a dict: pos
         (NO_POS for a signer that is no member), power, flag, checked, planned, n_checked, dv."""
+        return self._valset_resolve(self.lib.edc_valset_resolve, commit_off, None, flags, thresholds, light, vks, key_idx)
+
+    def _valset_resolve(self, fn, commit_off, versions, flags, thresholds, light, vks, key_idx):
+        """fn: edc_valset_resolve (versions None) or edc_vhist_resolve, which takes them behind the offsets"""
         nc, off = self._commit_offsets(commit_off)
         n = off[nc] if nc else 0
+        ver = () if versions is None else (self._vhist_versions_arg(nc, versions),)
         vkb, idx = _tmpl_keys(n, vks, key_idx)
         fl, th = self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds)
         pos, power = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))()
@@ -1004,8 +1022,8 @@ class Engine:
         planned, dv = (ctypes.c_uint64 * max(nc, 1))(), ctypes.create_string_buffer(max(nc, 1))
         cnt = ctypes.c_size_t(0)
         with self._lock:
-            rc = self.lib.edc_valset_resolve(self.ctx, nc, off, vkb, idx, fl, th, int(bool(light)), pos, power, flag_out,
-                                             checked, planned, ctypes.byref(cnt), dv)
+            rc = fn(self.ctx, nc, off, *ver, vkb, idx, fl, th, int(bool(light)), pos, power, flag_out, checked, planned,
+                    ctypes.byref(cnt), dv)
         self._check(rc)
         return {"pos": list(pos[:n]), "power": list(power[:n]), "flag": list(flag_out.raw[:n]),
                 "checked": list(checked.raw[:n]), "planned": list(planned[:nc]), "n_checked": cnt.value,
@@ -1036,6 +1054,97 @@ class Engine:
         ms = (ctypes.c_float * 2)()
         with self._lock:
             rc = self.lib.edc_debug_valset_select(self.ctx, nc, off, vkb, idx, fl, th, int(bool(light)), reps, ms)
+        self._check(rc)
+        return ms[0], ms[1]
+
+    # ---- validator-set history (edc_vhist_*): a base set plus per-version updates; every commit is
+    # judged by the set of the version it names ----
+    def vhist_set(self, base_powers, updates=()):
+        """edc_vhist_set: base_powers, one per position of the last keycache_load list (VHIST_NOT_MEMBER
+        or None: no member), and updates, one list of (position, power) pairs per version 1..nv.
+        base_powers None or []: clears the history. Returns the number of versions."""
+        def u64(x):
+            x = VHIST_NOT_MEMBER if x is None else int(x)
+            if x < 0 or x >= 1 << 64:
+                raise ValueError("powers are uint64")
+            return x
+        base = [u64(x) for x in (base_powers or [])]
+        updates = [[(int(p), u64(w)) for p, w in u] for u in updates]
+        flat = [x for u in updates for x in u]
+        if any(p < 0 or p >= 1 << 32 for p, _ in flat) or len(flat) >= 1 << 32:
+            raise ValueError("update positions and their count are uint32")
+        if not base:
+            if updates:
+                raise ValueError("updates without a base set")
+            args = (0, None, 0, None, None, None)
+        else:
+            off = [0]
+            for u in updates:
+                off.append(off[-1] + len(u))
+            args = (len(base), (ctypes.c_uint64 * len(base))(*base), len(updates), (ctypes.c_uint32 * len(off))(*off),
+                    (ctypes.c_uint32 * max(len(flat), 1))(*[p for p, _ in flat]),
+                    (ctypes.c_uint64 * max(len(flat), 1))(*[w for _, w in flat]))
+        with self._lock:
+            self._check(self.lib.edc_vhist_set(self.ctx, *args))
+        return self.vhist_versions()
+
+    def vhist_versions(self):
+        return int(self.lib.edc_vhist_versions(self.ctx))
+
+    def vhist_totals(self, v0=0, count=None):
+        """edc_vhist_totals -> (totals, member counts) of the versions v0 .. v0 + count - 1 (count None:
+        up to the last)."""
+        if count is None:
+            count = max(self.vhist_versions() - v0, 0)
+        total, members = (ctypes.c_uint64 * max(count, 1))(), (ctypes.c_uint32 * max(count, 1))()
+        self._check(self.lib.edc_vhist_totals(self.ctx, v0, count, total, members))
+        return list(total[:count]), list(members[:count])
+
+    @staticmethod
+    def _vhist_versions_arg(nc, versions):
+        versions = [int(v) for v in versions]
+        if len(versions) != nc:
+            raise ValueError("one version per commit")
+        if any(v < 0 or v >= 1 << 32 for v in versions):
+            raise ValueError("versions are uint32")
+        return (ctypes.c_uint32 * max(nc, 1))(*versions)
+
+    def _vhist_form(self, form, versions):
+        """form with the commits' versions behind the offsets, as the edc_vhist_* entries take them"""
+        nc, n, args = form
+        return nc, n, args[:2] + (self._vhist_versions_arg(nc, versions),) + args[2:]
+
+    def vhist_resolve(self, commit_off, versions, flags, thresholds, light=True, vks=None, key_idx=None):
+        """edc_vhist_resolve: valset_resolve with every commit judged at its own version."""
+        return self._valset_resolve(self.lib.edc_vhist_resolve, commit_off, versions, flags, thresholds, light, vks,
+                                    key_idx)
+
+    def quorum_verify_vhist(self, commit_off, versions, sigs, flags, thresholds, z_seed, light=True, vks=None,
+                            key_idx=None, msgs=None, ks=None):
+        """edc_vhist_quorum_verify: quorum_verify_valset with commit c judged by version versions[c] of
+        the validator-set history (vhist_set). Returns the dict quorum_verify returns."""
+        form = self._vhist_form(self._commits_host(commit_off, sigs, vks, key_idx, msgs, ks), versions)
+        votes = self._valset_flags(form[1], flags), self._quorum_thresholds(form[0], thresholds)
+        return self._quorum_call(self.lib.edc_vhist_quorum_verify, False, form, votes, z_seed, light)
+
+    def quorum_verify_vhist_device(self, commit_off, versions, d_vk, d_sig, d_msg, d_msg_off, d_flag, thresholds, z_seed,
+                                   light=True, d_k=None):
+        """edc_vhist_quorum_verify_device: quorum_verify_valset_device with the commits' versions (host)."""
+        form = self._vhist_form(self._commits_device(commit_off, d_vk, d_sig, d_msg, d_msg_off, d_k), versions)
+        votes = self._dev_ptr(d_flag), self._quorum_thresholds(form[0], thresholds)
+        return self._quorum_call(self.lib.edc_vhist_quorum_verify_device, False, form, votes, z_seed, light)
+
+    def vhist_select_ms(self, commit_off, versions, flags, thresholds, light=True, vks=None, key_idx=None, reps=20):
+        """edc_debug_vhist_select: mean times of the history's join kernel and of the double-vote scan,
+        in milliseconds."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        ver = self._vhist_versions_arg(nc, versions)
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        fl, th = self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds)
+        ms = (ctypes.c_float * 2)()
+        with self._lock:
+            rc = self.lib.edc_debug_vhist_select(self.ctx, nc, off, ver, vkb, idx, fl, th, int(bool(light)), reps, ms)
         self._check(rc)
         return ms[0], ms[1]
 
@@ -1812,7 +1921,8 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         return [c == EDC_OK for c in res[1]]
 
     @staticmethod
-    def verify_quorum(verifiers, powers, flags, thresholds, light=True, z_seed=None, engine=None, cached=False):
+    def verify_quorum(verifiers, powers, flags, thresholds, light=True, z_seed=None, engine=None, cached=False,
+                      versions=None):
         """Quorum check of many commits in ONE launch (a quorum commit set, edc_quorum_verify; not an
         API of the reference). verifiers: one batch.Verifier per commit, holding an item for EVERY
         validator of its set (any bytes for an absent one); powers / flags: one list per verifier, one
@@ -1827,8 +1937,16 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         remembered. The return value has the same form.
         powers=None takes the powers from the engine's registered validator set
         (Engine.valset_set_powers; edc_valset_quorum_verify): a vote whose key is no member of it
-        counts as absent, and a commit with two checked votes of one member gets EDC_DOUBLE_VOTE."""
+        counts as absent, and a commit with two checked votes of one member gets EDC_DOUBLE_VOTE.
+        versions (one per verifier, with powers=None only) judges every commit by that version of the
+        engine's validator-set history (Engine.vhist_set; edc_vhist_quorum_verify) instead."""
         verifiers = list(verifiers)
+        if versions is not None:
+            if powers is not None or cached:
+                raise ValueError("verify_quorum: versions go with powers=None and have no cached form")
+            versions = [int(v) for v in versions]
+            if len(versions) != len(verifiers):
+                raise ValueError("verify_quorum: one version per verifier")
         if powers is None:
             if cached:
                 raise ValueError("verify_quorum: the registered validator set has no cached form")
@@ -1862,6 +1980,8 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         pw, fl = [x for p in powers for x in p], [x for f in flags for x in f]
         if from_set:
             def run(off, sigs, pw, fl, thresholds, z_seed, **kw):
+                if versions is not None:
+                    return eng.quorum_verify_vhist(off, versions, sigs, fl, thresholds, z_seed, **kw)
                 return eng.quorum_verify_valset(off, sigs, fl, thresholds, z_seed, **kw)
         else:
             run = eng.quorum_verify_cached if cached else eng.quorum_verify

@@ -23,6 +23,7 @@
 #include "commits.h"
 #include "quorum.h"
 #include "valset.h"
+#include "vhist.h"
 #include "sigcache.h"
 #include "devbuf.h"
 
@@ -294,6 +295,18 @@ struct edc_ctx {
   DevBuf<uint8_t> vs_flag, vs_dv;
   PinnedBuf<uint8_t> vs_hdv;
   ValsetView vs() const { return ValsetView{vs_power, vs_member, vs_pos, vs_count}; }
+  // validator-set history (vhist.h; edc_vhist_*), independent of the powers above: the change
+  // lists by cache index on the device (vh_count keys the cache held at edc_vhist_set), the
+  // history by position (totals, the reference lists) and each cache index's position on the host;
+  // vh.m = 0: none. Per call the commits' versions (vh_cap_c commits); the rest of the per-call
+  // workspace is the vs_* one.
+  VHist vh;
+  std::vector<uint32_t> vh_posh;
+  DevBuf<uint32_t> vh_off, vh_ver, vh_cver;
+  DevBuf<uint64_t> vh_pow;
+  uint32_t vh_count = 0;
+  size_t vh_cap_c = 0;
+  VhistView vhv() const { return VhistView{vh_off, vh_ver, vh_pow, vh_count}; }
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -1617,11 +1630,20 @@ static void free_valset(edc_ctx* ctx) {
   ctx->vs_posh.clear();
 }
 
+// the history of the registered list (edc_vhist_set)
+static void free_vhist(edc_ctx* ctx) {
+  reset_all(ctx->vh_off, ctx->vh_ver, ctx->vh_pow);
+  ctx->vh_count = 0;
+  ctx->vh = VHist();
+  ctx->vh_posh.clear();
+}
+
 static void free_keycache(edc_ctx* ctx) {
   reset_all(ctx->kc_table, ctx->kc_keys, ctx->kc_comb, ctx->kc_ok, ctx->kc_reg);
   ctx->kc_reg_m = 0;
   ctx->kc_regh.clear();
-  free_valset(ctx);             // the powers belong to the list
+  free_valset(ctx);             // the powers and the history belong to the list
+  free_vhist(ctx);
   ctx->kc_m = ctx->kc_tmask = ctx->kc_cap = 0;
   ctx->kc_gen++;
   ctx->kc_words.clear();
@@ -4435,6 +4457,10 @@ int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
 // entries stages them; the double-vote scan runs behind the selection on its skip bytes, and its
 // per-commit bytes come back with the selection's one read-back. Everything after that is the
 // quorum entries' own: quorum_gather, then quorum_finish with the double-vote bytes.
+// edc_vhist_*: the same entries with every commit judged by the set of its own version (cver, the
+// commits' versions on the host; null in this section: the one set of edc_valset_set_powers). Only
+// the join differs: the offsets and versions go to the device in front of it, and k_vh_resolve
+// stands where k_vs_resolve does.
 static int ensure_valset(edc_ctx* ctx, size_t n, size_t nc) {
   hipStream_t st = ctx->st();
   CK(grow_group(ctx->vs_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
@@ -4452,11 +4478,20 @@ static int valset_ready(edc_ctx* ctx) {
   return 0;
 }
 
+// a history is set and every commit names one of its versions
+static int vhist_ready(edc_ctx* ctx, size_t nc, const uint32_t* cver) {
+  if (!ctx->vh.m) { ctx->err = "no validator-set history on the registered list (edc_vhist_set)"; return EDC_ERR_ARG; }
+  for (size_t c = 0; c < nc; ++c)
+    if (cver[c] > ctx->vh.nv) { ctx->err = "commit_ver: a version past the history's last"; return EDC_ERR_ARG; }
+  return 0;
+}
+
 // Workspace for n items in nc commits on slot 0; everything the selection allocates is allocated
 // here, so that nothing the resolve kernel has written moves afterwards.
-static int valset_room(edc_ctx* ctx, size_t n, size_t nc) {
+static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false) {
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
+  if (hist) CK(grow_group(ctx->vh_cap_c, nc, off_cap, sync_of(ctx->st()), [&](size_t cap) { return ctx->vh_cver.alloc(cap); }));
   return ensure_valset(ctx, n, nc);
 }
 
@@ -4465,10 +4500,17 @@ static int valset_room(edc_ctx* ctx, size_t n, size_t nc) {
 // double-vote bytes in vs_hdv and, if h_skip is given, the n skip bytes. valset_room has run.
 static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                          int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag, uint8_t* h_skip,
-                         size_t* n_checked) {
+                         size_t* n_checked, const uint32_t* cver = nullptr) {
   hipStream_t st = ctx->st();
-  launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, d_kidx, ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag,
-                        ctx->vs_who);
+  if (cver && n) {      // the history's join reads the offsets, which the selection stages (again) only behind it
+    CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(ctx->vh_cver, cver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    launch_vhist_resolve(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, d_vk, d_kidx,
+                         ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
+  } else {
+    launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, d_kidx, ctx->kc_reg, d_flag, ctx->q_power,
+                          ctx->q_flag, ctx->vs_who);
+  }
   CK(hipGetLastError());
   int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag);
   if (rc) return rc;
@@ -4501,9 +4543,10 @@ static int valset_stage_votes(edc_ctx* ctx, size_t n, const uint8_t* vk, const u
 
 // what the host checks of a call on host keys and flags without signatures (resolve, the hook)
 static int valset_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
-                             const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, size_t* n) {
+                             const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, size_t* n,
+                             const uint32_t* cver = nullptr) {
   int rc = quorum_check(ctx, nc, commit_off, threshold, mode, n);
-  if (rc || (rc = valset_ready(ctx))) return rc;
+  if (rc || (rc = cver ? vhist_ready(ctx, nc, cver) : valset_ready(ctx))) return rc;
   if (*n) {
     if ((rc = commits_check_keys(ctx, *n, vk, key_idx))) return rc;
     if (!flag) { ctx->err = "null input"; return EDC_ERR_ARG; }
@@ -4516,12 +4559,13 @@ static int valset_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
 // which must be canonical for the checked votes (the skip bytes come back with the read-back).
 static int valset_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
                       const ItemList& all, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
-                      const uint8_t* host_k, const uint8_t* z_seed, const QuorumOut& out) {
+                      const uint8_t* host_k, const uint8_t* z_seed, const QuorumOut& out, const uint32_t* cver) {
   const size_t n = all.count;
   size_t m = 0;
   ItemList list;
   std::vector<uint8_t> skip(host_k ? n : 0);
-  int rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, host_k && n ? skip.data() : nullptr, &m);
+  int rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, host_k && n ? skip.data() : nullptr, &m,
+                         cver);
   if (rc) return rc;
   for (size_t i = 0; i < skip.size(); ++i) {      // Scalar::from_hash never yields k >= l
     uint32_t w[8];
@@ -4583,22 +4627,33 @@ int edc_valset_set_powers(edc_ctx* ctx, size_t m, const uint64_t* power) {
 
 int edc_valset_size(const edc_ctx* ctx) { return ctx ? (int)ctx->vs_m : 0; }
 
-int edc_valset_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
-                       const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos, uint64_t* power,
-                       uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked, uint8_t* dv) {
+}  // extern "C"
+
+// The bodies of the entries, for both sections. hist: an edc_vhist_* entry, which needs cver.
+static bool vhist_ver_missing(edc_ctx* ctx, bool hist, const uint32_t* cver) {
+  if (hist && !cver) ctx->err = "null commit_ver";
+  return hist && !cver;
+}
+
+static int valset_resolve_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
+                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
+                                int mode, uint32_t* pos, uint64_t* power, uint8_t* flag_out, uint8_t* checked,
+                                uint64_t* planned, size_t* n_checked, uint8_t* dv) {
   if (!ctx) return EDC_ERR_ARG;
   if (!nc) {
     if (n_checked) *n_checked = 0;
     return EDC_OK;
   }
+  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
   size_t n, m = 0;
-  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n);
+  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, cver);
   if (rc) return rc;
   CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
+  if ((rc = valset_room(ctx, n, nc, hist)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
   if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx,
-                          ctx->vs_flag, nullptr, &m)))
+                          ctx->vs_flag, nullptr, &m, cver)))
     return rc;
+  const std::vector<uint32_t>& posh = hist ? ctx->vh_posh : ctx->vs_posh;
   hipStream_t st = ctx->st();
   std::vector<uint32_t> who(pos ? n : 0);
   if (pos && n) CK(hipMemcpyAsync(who.data(), ctx->vs_who, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -4607,7 +4662,7 @@ int edc_valset_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, cons
   if (planned) CK(hipMemcpyAsync(planned, ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (checked && n) CK(hipMemcpyAsync(checked, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
-  for (size_t i = 0; i < who.size(); ++i) pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : ctx->vs_posh[who[i]];
+  for (size_t i = 0; i < who.size(); ++i) pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : posh[who[i]];
   if (checked)
     for (size_t i = 0; i < n; ++i) checked[i] = checked[i] ? 0 : 1;      // the kernel writes the skip byte
   if (dv) memcpy(dv, ctx->vs_hdv, nc);
@@ -4615,23 +4670,24 @@ int edc_valset_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, cons
   return EDC_OK;
 }
 
-int edc_valset_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
-                                    const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
-                                    const uint8_t* d_k, const uint8_t* d_flag, const uint64_t* threshold, int mode,
-                                    const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
-                                    uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+static int valset_verify_device_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
+                                      const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
+                                      const uint64_t* d_msg_off, const uint8_t* d_k, const uint8_t* d_flag,
+                                      const uint64_t* threshold, int mode, const uint8_t z_seed[32], const QuorumOut& out) {
   int rc;
   if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
+  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
   size_t n;
-  if ((rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n)) || (rc = valset_ready(ctx))) return rc;
+  if ((rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n)) ||
+      (rc = hist ? vhist_ready(ctx, nc, cver) : valset_ready(ctx)))
+    return rc;
   if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off) || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
   if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)))) {
     ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
     return EDC_ERR_ARG;
   }
   CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc))) return rc;
+  if ((rc = valset_room(ctx, n, nc, hist))) return rc;
   const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
   if (n && !k) {
     if ((rc = ensure_n(ctx, n))) return rc;
@@ -4640,25 +4696,24 @@ int edc_valset_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* com
     k = ctx->kbuf;
   }
   return valset_run(ctx, nc, commit_off, threshold, mode, ItemList{d_vk, d_sig, k, nullptr, n}, d_vk, nullptr, d_flag,
-                    nullptr, z_seed, out);
+                    nullptr, z_seed, out, cver);
 }
 
-int edc_valset_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
-                             const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
-                             const uint8_t* k, const uint8_t* flag, const uint64_t* threshold, int mode,
-                             const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
-                             int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
-  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+static int valset_verify_host_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
+                                    const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
+                                    const uint64_t* msg_off, const uint8_t* k, const uint8_t* flag,
+                                    const uint64_t* threshold, int mode, const uint8_t z_seed[32], const QuorumOut& out) {
   int rc;
   if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
+  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
   size_t n;
-  if ((rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n))) return rc;
+  if ((rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, cver))) return rc;
   if (n) {
     if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
     if ((rc = commits_check_msg_or_k(ctx, n, msg, msg_off, k))) return rc;
   }
   CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc))) return rc;
+  if ((rc = valset_room(ctx, n, nc, hist))) return rc;
   hipStream_t st = ctx->st();
   if (k) {
     if ((rc = ensure_n(ctx, n))) return rc;
@@ -4675,22 +4730,24 @@ int edc_valset_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
     }
   }
   return valset_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n},
-                    key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, n ? k : nullptr, z_seed, out);
+                    key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, n ? k : nullptr, z_seed, out, cver);
 }
 
-int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
-                            const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, int reps,
-                            float ms[2]) {
+static int valset_debug_select_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
+                                     const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
+                                     const uint64_t* threshold, int mode, int reps, float ms[2]) {
   if (!ctx || reps < 1) return EDC_ERR_ARG;
   if (ms) ms[0] = ms[1] = 0.f;
   if (!nc) return EDC_OK;
+  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
   size_t n, m = 0;
-  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n);
+  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, cver);
   if (rc) return rc;
   CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
+  if ((rc = valset_room(ctx, n, nc, hist)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
   const uint8_t* d_vk = key_idx ? nullptr : ctx->vk.get();
-  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, ctx->vs_kidx, ctx->vs_flag, nullptr, &m))) return rc;
+  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, ctx->vs_kidx, ctx->vs_flag, nullptr, &m, cver)))
+    return rc;
   if (!n) return EDC_OK;
   hipStream_t st = ctx->st();
   Event e0, e1, e2;
@@ -4698,9 +4755,14 @@ int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
   CK(e1.create());
   CK(e2.create());
   CK(hipEventRecord(e0, st));
-  for (int r = 0; r < reps; ++r)        // the resolve kernel rewrites the same values
-    launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, ctx->vs_kidx, ctx->kc_reg, ctx->vs_flag, ctx->q_power,
-                          ctx->q_flag, ctx->vs_who);
+  for (int r = 0; r < reps; ++r) {      // the resolve kernel rewrites the same values
+    if (hist)                           // the offsets and versions are where valset_select left them
+      launch_vhist_resolve(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, d_vk, ctx->vs_kidx,
+                           ctx->kc_reg, ctx->vs_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
+    else
+      launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, ctx->vs_kidx, ctx->kc_reg, ctx->vs_flag,
+                            ctx->q_power, ctx->q_flag, ctx->vs_who);
+  }
   CK(hipGetLastError());
   CK(hipEventRecord(e1, st));
   for (int r = 0; r < reps; ++r) {      // the scan with the clearing of its set and bytes, as every call runs it
@@ -4719,6 +4781,137 @@ int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
     ms[1] = t1 / (float)reps;
   }
   return EDC_OK;
+}
+
+extern "C" {
+
+int edc_valset_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
+                       const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos, uint64_t* power,
+                       uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked, uint8_t* dv) {
+  return valset_resolve_entry(ctx, false, nc, commit_off, nullptr, vk, key_idx, flag, threshold, mode, pos, power, flag_out,
+                              checked, planned, n_checked, dv);
+}
+
+int edc_valset_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
+                                    const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_msg_off,
+                                    const uint8_t* d_k, const uint8_t* d_flag, const uint64_t* threshold, int mode,
+                                    const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                                    uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  return valset_verify_device_entry(ctx, false, nc, commit_off, nullptr, d_vk, d_sig, d_msg, d_msg_off, d_k, d_flag,
+                                    threshold, mode, z_seed, out);
+}
+
+int edc_valset_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                             const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
+                             const uint8_t* k, const uint8_t* flag, const uint64_t* threshold, int mode,
+                             const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
+                             int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  return valset_verify_host_entry(ctx, false, nc, commit_off, nullptr, vk, key_idx, sig, msg, msg_off, k, flag, threshold,
+                                  mode, z_seed, out);
+}
+
+int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
+                            const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, int reps,
+                            float ms[2]) {
+  return valset_debug_select_entry(ctx, false, nc, commit_off, nullptr, vk, key_idx, flag, threshold, mode, reps, ms);
+}
+
+// ---------------------------------------------------------------- validator-set history
+// edc_vhist_set checks the history and builds its change lists by position (vhist_build), then
+// re-indexes them from position to cache index, as edc_valset_set_powers re-indexes its arrays: key
+// s of the cache owns the list of its position, every other key an empty one.
+int edc_vhist_set(edc_ctx* ctx, size_t m, const uint64_t* base_power, size_t nv, const uint32_t* upd_off,
+                  const uint32_t* upd_pos, const uint64_t* upd_power) {
+  if (!ctx) return EDC_ERR_ARG;
+  CK(hipSetDevice(ctx->device));
+  for (Slot& s : ctx->slot)
+    if (s.pending) { ctx->err = "validator-set history changes with a batch in flight"; return EDC_ERR_ARG; }
+  int rc = sync_all(ctx);
+  if (rc) return rc;
+  if (!m && !base_power && !upd_off && !upd_pos && !upd_power) {
+    free_vhist(ctx);
+    return EDC_OK;
+  }
+  VHist h;
+  const char* why = nullptr;
+  if (!vhist_build(ctx->kc_reg_m, ctx->kc_regh.data(), m, base_power, nv, upd_off, upd_pos, upd_power, &h, &why)) {
+    ctx->err = why;
+    return EDC_ERR_ARG;
+  }
+  const uint32_t u = ctx->kc_m;
+  std::vector<uint32_t> pos(u, VALSET_NO_POS), off(u + 1, 0), ver(h.ver.size());
+  std::vector<uint64_t> pw(h.pow.size());
+  for (size_t p = 0; p < m; ++p) pos[ctx->kc_regh[p]] = (uint32_t)p;
+  for (uint32_t s = 0; s < u; ++s) {
+    const uint32_t p = pos[s];
+    const uint32_t a = p == VALSET_NO_POS ? 0 : h.off[p], len = p == VALSET_NO_POS ? 0 : h.off[p + 1] - a;
+    std::copy_n(h.ver.begin() + a, len, ver.begin() + off[s]);
+    std::copy_n(h.pow.begin() + a, len, pw.begin() + off[s]);
+    off[s + 1] = off[s] + len;
+  }
+  DevBuf<uint32_t> d_off, d_ver;          // committed to the context only on success
+  DevBuf<uint64_t> d_pw;
+  CK(alloc_all(sized(d_off, off.size()), sized(d_ver, ver.size()), sized(d_pw, pw.size())));
+  CK(hipMemcpy(d_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CK(hipMemcpy(d_ver, ver.data(), ver.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CK(hipMemcpy(d_pw, pw.data(), pw.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  ctx->vh_off = std::move(d_off);
+  ctx->vh_ver = std::move(d_ver);
+  ctx->vh_pow = std::move(d_pw);
+  ctx->vh_posh.swap(pos);
+  ctx->vh_count = u;
+  ctx->vh = std::move(h);
+  return EDC_OK;
+}
+
+int edc_vhist_versions(const edc_ctx* ctx) { return ctx && ctx->vh.m ? (int)ctx->vh.nv + 1 : 0; }
+
+int edc_vhist_totals(const edc_ctx* ctx, uint32_t v0, size_t count, uint64_t* total, uint32_t* members) {
+  if (!ctx) return EDC_ERR_ARG;
+  const size_t nver = ctx->vh.m ? (size_t)ctx->vh.nv + 1 : 0;
+  if (v0 > nver || count > nver - v0) return EDC_ERR_ARG;
+  for (size_t j = 0; j < count; ++j) {
+    if (total) total[j] = ctx->vh.total[v0 + j];
+    if (members) members[j] = ctx->vh.members[v0 + j];
+  }
+  return EDC_OK;
+}
+
+int edc_vhist_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver, const uint8_t* vk,
+                      const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos,
+                      uint64_t* power, uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked,
+                      uint8_t* dv) {
+  return valset_resolve_entry(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, pos, power,
+                              flag_out, checked, planned, n_checked, dv);
+}
+
+int edc_vhist_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                                   const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
+                                   const uint64_t* d_msg_off, const uint8_t* d_k, const uint8_t* d_flag,
+                                   const uint64_t* threshold, int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts,
+                                   uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits, size_t* n_checked,
+                                   uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  return valset_verify_device_entry(ctx, true, nc, commit_off, commit_ver, d_vk, d_sig, d_msg, d_msg_off, d_k, d_flag,
+                                    threshold, mode, z_seed, out);
+}
+
+int edc_vhist_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                            const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
+                            const uint64_t* msg_off, const uint8_t* k, const uint8_t* flag, const uint64_t* threshold,
+                            int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                            uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
+  const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
+  return valset_verify_host_entry(ctx, true, nc, commit_off, commit_ver, vk, key_idx, sig, msg, msg_off, k, flag, threshold,
+                                  mode, z_seed, out);
+}
+
+int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                           const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
+                           int mode, int reps, float ms[2]) {
+  return valset_debug_select_entry(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, reps, ms);
 }
 
 }  // extern "C"

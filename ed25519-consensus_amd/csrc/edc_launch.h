@@ -159,6 +159,23 @@ void launch_valset_resolve(hipStream_t st, uint32_t n, const KeyCacheView& kc, c
                            uint8_t* flag_out, uint32_t* who);
 void launch_valset_pairs(hipStream_t st, uint32_t n, const uint32_t* commit_off, const uint32_t* cidx, const uint8_t* skip,
                          const uint32_t* who, uint64_t* set, uint8_t* dv);
+// validator-set history (vhist.h; edc_vhist_*). The change lists by cache index: key s owns the
+// entries [off[s], off[s+1]) (count + 1 offsets; empty for a key outside the list, and a cache
+// index at or past count is no member at any version), ver[] ascending from the base's 0, pow[]
+// the power from that version on or VHIST_NOT_MEMBER.
+struct VhistView {
+  const uint32_t* off;
+  const uint32_t* ver;
+  const uint64_t* pow;
+  uint32_t count;
+};
+// launch_vhist_resolve stands where launch_valset_resolve does and writes the same three arrays,
+// with item i judged at commit_ver[c], c the commit of i by commit_off (nc + 1 offsets and nc
+// versions on the device, every version checked by the caller against the history).
+void launch_vhist_resolve(hipStream_t st, uint32_t n, uint32_t nc, const KeyCacheView& kc, const VhistView& vh,
+                          const uint32_t* commit_off, const uint32_t* commit_ver, const uint8_t* vk,
+                          const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag, uint64_t* power,
+                          uint8_t* flag_out, uint32_t* who);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

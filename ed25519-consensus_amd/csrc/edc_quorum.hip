@@ -26,6 +26,7 @@
 #include "edc_launch.h"
 #include "quorum.h"
 #include "sigcache.h"
+#include "vhist.h"
 
 namespace edc {
 
@@ -357,6 +358,19 @@ __global__ void __launch_bounds__(QR_TILE) k_tq_gather(uint32_t n, uint32_t m, c
 // Of two lanes with the same pair exactly one wins the empty slot and the other then finds it there
 // (nothing is ever removed and both walk the same slots), so dv[c] = 1 iff some pair occurs twice,
 // whatever the order of the lanes; the stores to dv[c] all write 1.
+// the cache index of item i's signer: by its key bytes (KC_EMPTY for a key the cache does not hold)
+// or, with vk null, by its position in the registered list
+__device__ __forceinline__ uint32_t signer_index(const KeyCacheView& kc, const uint8_t* __restrict__ vk,
+                                                 const uint32_t* __restrict__ key_idx,
+                                                 const uint32_t* __restrict__ reg, uint32_t i) {
+  if (!vk) return reg[key_idx[i]];      // the host checked key_idx[i] against the list's length
+  const uint4* q = reinterpret_cast<const uint4*>(vk + (size_t)i * 32);
+  const uint4 a = q[0], b = q[1];
+  const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  const int r = kc_lookup(kc, w);
+  return r < 0 ? KC_EMPTY : (uint32_t)r;
+}
+
 __global__ void __launch_bounds__(QR_TILE) k_vs_resolve(uint32_t n, KeyCacheView kc, ValsetView vs,
                                                         const uint8_t* __restrict__ vk,
                                                         const uint32_t* __restrict__ key_idx,
@@ -365,21 +379,58 @@ __global__ void __launch_bounds__(QR_TILE) k_vs_resolve(uint32_t n, KeyCacheView
                                                         uint8_t* __restrict__ flag_out, uint32_t* __restrict__ who) {
   const uint32_t i = blockIdx.x * QR_TILE + threadIdx.x;
   if (i >= n) return;
-  uint32_t c;
-  if (vk) {
-    const uint4* q = reinterpret_cast<const uint4*>(vk + (size_t)i * 32);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const int r = kc_lookup(kc, w);
-    c = r < 0 ? KC_EMPTY : (uint32_t)r;
-  } else {
-    c = reg[key_idx[i]];                // the host checked key_idx[i] against the list's length
-  }
+  const uint32_t c = signer_index(kc, vk, key_idx, reg, i);
   const bool member = c < vs.count && vs.member[c];
   const uint8_t fl = flag[i];
   power[i] = member ? vs.power[c] : 0;
   flag_out[i] = (member || fl > QUORUM_NIL) ? fl : QUORUM_ABSENT;
   who[i] = member ? c : KC_EMPTY;
+}
+
+// Validator-set history (vhist.h; edc_vhist_*): the join of k_vs_resolve with every commit judged
+// by the set of its own version. One lane per item, in front of the selection: the signer's cache
+// index as above; the item's commit by the search k_q_tile makes, bounded by the commits of the
+// tile's first and last item, so that an empty commit resolves here as it does there and the
+// version read is that of the commit k_q_tile then writes to cidx[i]; the signer's change list
+// [off[s], off[s+1]) searched for the last entry with ver <= commit_ver[c] (the base entry has
+// version 0, so a list of one entry is not searched at all); its pow, or no member for
+// VHIST_NOT_MEMBER, an empty list or a cache index past the history. Writes what k_vs_resolve
+// writes, so the selection and k_vs_pairs run unchanged behind it. The loads depend on each other
+// (key -> index -> offsets -> versions -> power); the searched array is 32-bit versions only.
+__global__ void __launch_bounds__(QR_TILE) k_vh_resolve(uint32_t n, uint32_t nc, KeyCacheView kc, VhistView vh,
+                                                        const uint32_t* __restrict__ commit_off,
+                                                        const uint32_t* __restrict__ commit_ver,
+                                                        const uint8_t* __restrict__ vk,
+                                                        const uint32_t* __restrict__ key_idx,
+                                                        const uint32_t* __restrict__ reg,
+                                                        const uint8_t* __restrict__ flag, uint64_t* __restrict__ power,
+                                                        uint8_t* __restrict__ flag_out, uint32_t* __restrict__ who) {
+  const uint32_t g0 = blockIdx.x * QR_TILE;
+  const uint32_t g1 = (n - g0 < QR_TILE ? n : g0 + QR_TILE) - 1;
+  const uint32_t clo = commit_of(commit_off, 0, nc - 1, g0), chi = commit_of(commit_off, clo, nc - 1, g1);
+  const uint32_t i = g0 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = signer_index(kc, vk, key_idx, reg, i);
+  const uint32_t v = commit_ver[commit_of(commit_off, clo, chi, i)];
+  uint64_t pw = VHIST_NOT_MEMBER;
+  if (s < vh.count) {
+    uint32_t lo = vh.off[s];
+    const uint32_t end = vh.off[s + 1];
+    if (lo < end) {
+      uint32_t hi = end - 1;              // ver[lo] = 0 <= v
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+        if (vh.ver[mid] <= v) lo = mid;
+        else hi = mid - 1;
+      }
+      pw = vh.pow[lo];
+    }
+  }
+  const bool member = pw != VHIST_NOT_MEMBER;
+  const uint8_t fl = flag[i];
+  power[i] = member ? pw : 0;
+  flag_out[i] = (member || fl > QUORUM_NIL) ? fl : QUORUM_ABSENT;
+  who[i] = member ? s : KC_EMPTY;
 }
 
 __global__ void __launch_bounds__(QR_TILE) k_vs_pairs(uint32_t n, const uint32_t* __restrict__ commit_off,
@@ -453,6 +504,15 @@ void launch_valset_resolve(hipStream_t st, uint32_t n, const KeyCacheView& kc, c
   if (!n) return;
   hipLaunchKernelGGL(k_vs_resolve, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, kc, vs, vk, key_idx, reg, flag,
                      power, flag_out, who);
+}
+
+void launch_vhist_resolve(hipStream_t st, uint32_t n, uint32_t nc, const KeyCacheView& kc, const VhistView& vh,
+                          const uint32_t* commit_off, const uint32_t* commit_ver, const uint8_t* vk,
+                          const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag, uint64_t* power,
+                          uint8_t* flag_out, uint32_t* who) {
+  if (!n || !nc) return;
+  hipLaunchKernelGGL(k_vh_resolve, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, nc, kc, vh, commit_off,
+                     commit_ver, vk, key_idx, reg, flag, power, flag_out, who);
 }
 
 void launch_valset_pairs(hipStream_t st, uint32_t n, const uint32_t* commit_off, const uint32_t* cidx, const uint8_t* skip,

@@ -1341,6 +1341,91 @@ int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
                             float ms[2]);
 
 /*
+ * Validator-set history: every commit judged by the set of its own height. edc_valset_set_powers
+ * holds one set, and a call judges every commit against it; on a chain the set moves with almost
+ * every block (CometBFT's validator updates, named from memory as above), and a commit set that
+ * spans many heights would have to be cut at every change. These entries keep the HISTORY of the
+ * set with the registered key list: a base set plus per-version updates. Every commit names the
+ * version it is judged by, and the device resolves each vote's membership and power at that
+ * version. Selection, double-vote scan, gather, batch and tally are the validator-set entries' own
+ * and run behind the join unchanged; the reference crate's APIs keep their meaning as stated there.
+ *
+ * Versions. Positions are those of the list last given to edc_keycache_load, which is the union of
+ *   every key that is a member at any version. Version 0 is base_power[p] for p < m. Version v
+ *   (1..nv) is version v-1 with the updates [upd_off[v-1], upd_off[v]) applied: position upd_pos[j]
+ *   gets the power upd_power[j]. EDC_VHIST_NOT_MEMBER, in the base or in an update, means the
+ *   position is not a member from that version on, until a later update gives it a power. A power
+ *   of 0 is a member without weight: its flag counts and it can double-vote. An update that
+ *   restates the current state is allowed and changes no version's set (it is one more entry in
+ *   that position's change list).
+ * edc_vhist_set  sets the history (m base powers; nv versions of updates: upd_off has nv + 1
+ *   entries, upd_pos / upd_power upd_off[nv]; all host). It is independent of
+ *   edc_valset_set_powers: both may be set, and the edc_valset_* entries never read the history.
+ *   edc_keycache_load and edc_keycache_clear drop it; edc_keycache_add keeps it, and a key it adds
+ *   is not a member at any version. m = 0 with NULL arrays clears it. Refused while batches are in
+ *   flight, as edc_valset_set_powers is. EDC_ERR_ARG with nothing changed if m differs from the
+ *   registered list's length or there is no list, if a key occurs twice in the list, if upd_off is
+ *   not monotone from 0, if an update position is >= m, if a position occurs twice inside one
+ *   version's slice, if a power other than the sentinel is above 2^63 - 1, if the member powers of
+ *   any version sum to more than 2^63 - 1, or if m plus the update count reaches 2^32. On the
+ *   device the history is one change list per key in CSR form, indexed by cache index: 32-bit
+ *   versions (ascending, the base as version 0) and, apart from them, 64-bit powers; 12 bytes per
+ *   position and per update.
+ * edc_vhist_versions  nv + 1; 0 when no history is set (and for NULL).
+ * edc_vhist_totals  for the versions v0 .. v0 + count - 1: total[j] = the sum of the member powers,
+ *   members[j] = the member count (both nullable) -- what a caller derives thresholds from
+ *   (floor(2T/3), or floor(T/3) for the trusting check). Computed on the host when the history is
+ *   set. A range outside the history is EDC_ERR_ARG.
+ *
+ * The join. With c the commit of item i and v = commit_ver[c] (uint32_t, nc entries, host):
+ *   pos[i]       the signer's registered position if it is a member at version v, else 0xFFFFFFFF;
+ *   power[i]     its power at v, else 0;
+ *   flag_out[i]  flag[i] for a member at v, else EDC_VOTE_ABSENT.
+ *   A flag above 2 is passed through whoever signed, so that the selection's check raises it.
+ *   commit_ver[c] > nv is EDC_ERR_ARG, checked on the host; versions may repeat and come in any
+ *   order across commits. checked, planned and *n_checked are edc_quorum_plan's on
+ *   (power, flag_out); dv[c] is the double-vote rule above over the members of commit c's version.
+ * edc_vhist_resolve  edc_valset_resolve with the history's join.
+ * edc_vhist_quorum_verify_device / edc_vhist_quorum_verify  the arguments of
+ *   edc_valset_quorum_verify_device / edc_valset_quorum_verify with commit_ver after commit_off.
+ *   Verdicts, the order of the return value (1 over 4 over 3), argument checks (a missing history
+ *   where those name missing powers), the canonical-k rule of the host form and the stream
+ *   synchronizations are theirs: the offsets and versions are copied to the device in front of the
+ *   join kernel, and no stream synchronization is added.
+ * Equality contract. Apart from the verdicts of double-vote commits, *n_bad_commits and the return
+ *   value, every output, check8 included, equals what edc_quorum_verify[_device] gives when handed
+ *   the joined power / flag_out. With nv = 0 and no sentinel in the base every output, the
+ *   EDC_DOUBLE_VOTE verdicts included, equals what edc_valset_quorum_verify[_device] gives after
+ *   edc_valset_set_powers(base_power).
+ * edc_debug_vhist_select  edc_debug_valset_select with the history's join kernel in ms[0].
+ * Not built: templated, cached, asynchronous submit / wait, incremental-verifier and multi-GPU
+ *   forms of these entries.
+ */
+#define EDC_VHIST_NOT_MEMBER 0xFFFFFFFFFFFFFFFFull
+int edc_vhist_set(edc_ctx* ctx, size_t m, const uint64_t* base_power, size_t nv, const uint32_t* upd_off,
+                  const uint32_t* upd_pos, const uint64_t* upd_power);
+int edc_vhist_versions(const edc_ctx* ctx);
+int edc_vhist_totals(const edc_ctx* ctx, uint32_t v0, size_t count, uint64_t* total, uint32_t* members);
+int edc_vhist_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver, const uint8_t* vk,
+                      const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos,
+                      uint64_t* power, uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked,
+                      uint8_t* dv);
+int edc_vhist_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                                   const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
+                                   const uint64_t* d_msg_off, const uint8_t* d_k, const uint8_t* d_flag,
+                                   const uint64_t* threshold, int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts,
+                                   uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits, size_t* n_checked,
+                                   uint8_t check8[32]);
+int edc_vhist_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                            const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
+                            const uint64_t* msg_off, const uint8_t* k, const uint8_t* flag, const uint64_t* threshold,
+                            int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
+                            uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]);
+int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                           const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
+                           int mode, int reps, float ms[2]);
+
+/*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
  * one batch::Verifier::verify (reference src/batch.rs:149-217) split into contiguous shards, one
  * per listed device (a device may be listed more than once: several contexts on one GPU). Shard g
