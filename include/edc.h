@@ -73,7 +73,10 @@ int edc_batch_verify(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* s
                      const uint8_t* msg, const uint64_t* msg_off, const uint8_t z_seed[32],
                      uint8_t check8[32]);
 
-/* Same, with caller-drawn z (n*16 bytes, LE u128 per item) for RNGs other than ChaCha20. */
+/* Same, with caller-drawn z (n*16 bytes, LE u128 per item) for RNGs other than ChaCha20. Any z is
+ * accepted, here and through the d_z arguments below: how full the MSM's bins and buckets are is
+ * then whatever the caller makes it (every item in one bucket, empty windows, z = 0), and results
+ * do not depend on it (tests/test_gpu_bucket_shapes.py). */
 int edc_batch_verify_z(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig,
                        const uint8_t* msg, const uint64_t* msg_off, const uint8_t* z,
                        uint8_t check8[32]);
