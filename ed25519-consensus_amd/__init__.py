@@ -87,6 +87,7 @@ ABI_SYMBOLS = [
     "edc_valset_quorum_verify", "edc_debug_valset_select",
     "edc_vhist_set", "edc_vhist_versions", "edc_vhist_totals", "edc_vhist_resolve", "edc_vhist_quorum_verify_device",
     "edc_vhist_quorum_verify", "edc_debug_vhist_select",
+    "edc_vq_verify", "edc_debug_vq_last",
 ]
 
 
@@ -95,6 +96,26 @@ class EdcTemplates(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint32),
                 ("head", ctypes.c_char_p), ("head_off", ctypes.POINTER(ctypes.c_uint32)),
                 ("tail", ctypes.c_char_p), ("tail_off", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class EdcVqRequest(ctypes.Structure):
+    """struct edc_vq_request (include/edc.h): one validator-set request. Pointers are plain addresses:
+    host buffers for device = 0, device addresses for device = 1."""
+    _fields_ = [("size", ctypes.c_uint32), ("device", ctypes.c_uint32), ("mode", ctypes.c_int32),
+                ("cached", ctypes.c_uint32), ("alt_span", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("nc", ctypes.c_size_t), ("commit_off", ctypes.c_void_p), ("commit_ver", ctypes.c_void_p),
+                ("threshold", ctypes.c_void_p), ("z_seed", ctypes.c_void_p), ("vk", ctypes.c_void_p),
+                ("key_idx", ctypes.c_void_p), ("sig", ctypes.c_void_p), ("flag", ctypes.c_void_p),
+                ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p), ("k", ctypes.c_void_p),
+                ("ts", ctypes.c_void_p), ("commit_tpl", ctypes.c_void_p), ("item_alt", ctypes.c_void_p),
+                ("var", ctypes.c_void_p), ("var_off", ctypes.c_void_p), ("var_bytes", ctypes.c_size_t)]
+
+
+class EdcVqResult(ctypes.Structure):
+    """struct edc_vq_result (include/edc.h): where a validator-set request writes; all nullable."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("commit_verdicts", ctypes.c_void_p),
+                ("item_verdicts", ctypes.c_void_p), ("tally", ctypes.c_void_p), ("n_bad_commits", ctypes.c_void_p),
+                ("n_checked", ctypes.c_void_p), ("n_miss", ctypes.c_void_p), ("check8", ctypes.c_void_p)]
 
 
 class EdcPlanInfo(ctypes.Structure):
@@ -416,6 +437,9 @@ def load_library(path=None):
             lib.edc_vhist_set.argtypes = [c_vp, c_sz, c_u64p, c_sz, c_u32p, c_u32p, c_u64p]
             lib.edc_vhist_versions.argtypes = [c_vp]
             lib.edc_vhist_totals.argtypes = [c_vp, ctypes.c_uint32, c_sz, c_u64p, c_u32p]
+        if hasattr(lib, "edc_vq_verify"):                    # absent from older A/B builds (tools/)
+            lib.edc_vq_verify.argtypes = [c_vp, ctypes.POINTER(EdcVqRequest), ctypes.POINTER(EdcVqResult)]
+            lib.edc_debug_vq_last.argtypes = [c_vp, c_u64p]
         if path is None:
             _lib = lib
         return lib
@@ -1147,6 +1171,85 @@ class Engine:
             rc = self.lib.edc_debug_vhist_select(self.ctx, nc, off, ver, vkb, idx, fl, th, int(bool(light)), reps, ms)
         self._check(rc)
         return ms[0], ms[1]
+
+    # ---- validator-set requests (edc_vq_verify): the validator-set and history entries, templates and
+    # the verified-signature table behind one request ----
+    def vq_verify(self, commit_off, flags, thresholds, z_seed, light=True, versions=None, cached=False, device=False,
+                  vks=None, key_idx=None, sigs=None, msgs=None, ks=None, msg_off=None, templates=None, commit_tpl=None,
+                  alt_span=1, item_alt=None, holes=None, var_off=None, var_bytes=None, raw=None):
+        """edc_vq_verify. device=False: vks / sigs / msgs / ks / holes are sequences of bytes, key_idx /
+        flags / item_alt sequences of ints, as the sibling host methods take them. device=True: vks,
+        sigs, flags, msgs (the arena, with msg_off), ks, item_alt, holes (the hole bytes) and var_off
+        are torch tensors or device pointers, and var_bytes is given. commit_off, versions (None: the
+        one set of valset_set_powers), thresholds, commit_tpl and templates are host values in both.
+        Exactly one of vks and key_idx; exactly one of msgs, ks and templates. Returns the dict
+        quorum_verify returns, with n_miss when cached. raw: a dict of request field -> value that
+        overrides what was built (tests of the refusals)."""
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        th = self._quorum_thresholds(nc, thresholds)
+        ver = None if versions is None else self._vhist_versions_arg(nc, versions)
+        seed = bytes(z_seed)
+        keep = [off, th, ver, seed]
+        rq = EdcVqRequest(size=ctypes.sizeof(EdcVqRequest), device=int(bool(device)), mode=int(bool(light)),
+                          cached=int(bool(cached)), nc=nc)
+
+        def addr(x):
+            if x is None:
+                return None
+            if device:
+                return self._dev_ptr(x)
+            keep.append(x)
+            return ctypes.cast(x, ctypes.c_void_p).value if isinstance(x, bytes) else ctypes.addressof(x)
+
+        rq.commit_off, rq.threshold, rq.z_seed = ctypes.addressof(off), ctypes.addressof(th), \
+            ctypes.cast(seed, ctypes.c_void_p).value
+        rq.commit_ver = None if ver is None else ctypes.addressof(ver)
+        if device:
+            rq.vk, rq.sig, rq.flag, rq.msg, rq.msg_off, rq.k = (addr(x) for x in (vks, sigs, flags, msgs, msg_off, ks))
+            if templates is not None:
+                rq.item_alt, rq.var, rq.var_off, rq.var_bytes = addr(item_alt), addr(holes), addr(var_off), int(var_bytes)
+            keep += [vks, sigs, flags, msgs, msg_off, ks, item_alt, holes, var_off]
+        else:
+            vkb, idx = _tmpl_keys(n, vks, key_idx)
+            rq.vk, rq.key_idx = addr(vkb), addr(idx)
+            rq.sig = addr(None if sigs is None else (b"".join(sigs) or b"\0"))
+            rq.flag = addr(None if flags is None else self._valset_flags(n, flags))
+            if msgs is not None:
+                arena, moff = _arena(msgs)
+                rq.msg, rq.msg_off = addr(arena), addr(moff)
+            if ks is not None:
+                rq.k = addr(b"".join(ks) or b"\0")
+            if templates is not None:
+                _, var, voff = _tmpl_items([0] * n, holes, var_off)
+                rq.item_alt, rq.var, rq.var_off = addr(self._item_alt(item_alt)), addr(var), addr(voff)
+        if templates is not None:
+            ts, tkeep = templates.struct()
+            ctpl = (ctypes.c_uint16 * max(nc, 1))(*commit_tpl)
+            keep += [ts, tkeep, ctpl]
+            rq.ts, rq.commit_tpl, rq.alt_span = ctypes.addressof(ts), ctypes.addressof(ctpl), int(alt_span)
+        for name, value in (raw or {}).items():
+            if name != "result_size":
+                setattr(rq, name, value)
+        out = (ctypes.create_string_buffer(max(nc, 1)), ctypes.create_string_buffer(max(n, 1)),
+               (ctypes.c_uint64 * max(nc, 1))(), ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0),
+               ctypes.create_string_buffer(32))
+        rs = EdcVqResult(ctypes.sizeof(EdcVqResult), 0, *(ctypes.addressof(x) for x in out))
+        if raw and "result_size" in raw:
+            rs.size = raw["result_size"]
+        with self._lock:
+            rc = self.lib.edc_vq_verify(self.ctx, ctypes.byref(rq), ctypes.byref(rs))
+        self._check(rc)
+        return self._quorum_result(rc, nc, n, out, bool(cached))
+
+    def vq_last(self):
+        """edc_debug_vq_last: (n, n_checked, hits, n_miss, items SHA-512 ran over, records inserted, 0
+        (reserved), arena bytes) of the last validator-set request on this engine."""
+        out = (ctypes.c_uint64 * 8)()
+        with self._lock:
+            rc = self.lib.edc_debug_vq_last(self.ctx, out)
+        self._check(rc)
+        return tuple(out)
 
     def quorum_select_ms(self, commit_off, powers, flags, thresholds, light=True, reps=20):
         """edc_debug_quorum_select: mean time of the selection kernels alone, in milliseconds."""

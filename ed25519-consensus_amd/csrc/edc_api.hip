@@ -307,6 +307,9 @@ struct edc_ctx {
   uint32_t vh_count = 0;
   size_t vh_cap_c = 0;
   VhistView vhv() const { return VhistView{vh_off, vh_ver, vh_pow, vh_count}; }
+  // validator-set requests (edc_vq_verify): the host copy edc_debug_vq_last returns
+  uint64_t vq_last[8] = {};
+  bool vq_have = false;
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -3811,6 +3814,50 @@ static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* 
   return rc ? rc : quorum_select_read(ctx, n, n_checked);
 }
 
+// Optional stages around the selection (edc_vq_verify): the validator-set join in front of it,
+// writing q_power / q_flag, and the double-vote scan behind it, whose bytes travel to vs_hdv in the
+// selection's read-back. d_vk: the n keys on the device, or null with d_kidx their positions;
+// d_flag: the caller's flags; cver (host): the commits' versions, null for the one set;
+// host_k: a host form's prehashed k, canonical for the checked votes (quorum_join_check_k).
+// valset_room has run.
+struct QuorumJoin {
+  const uint8_t* d_vk;
+  const uint32_t* d_kidx;
+  const uint8_t* d_flag;
+  const uint32_t* cver;
+  const uint8_t* host_k;
+  std::vector<uint8_t> skip;    // host_k: the skip bytes, read back with the selection
+};
+
+static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                                 int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
+                                 uint8_t* h_skip, const uint32_t* cver);
+
+// quorum_select_enqueue, with the join in front and the double-vote scan behind it when jn is given
+// (d_power / d_flag are then q_power / q_flag, which the join writes)
+static int quorum_front_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                                int mode, const uint64_t* d_power, const uint8_t* d_flag, QuorumJoin* jn) {
+  if (!jn) return quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag);
+  jn->skip.assign(jn->host_k ? n : 0, 0);
+  return valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, jn->d_vk, jn->d_kidx, jn->d_flag,
+                               jn->skip.empty() ? nullptr : jn->skip.data(), jn->cver);
+}
+
+static const char kJoinFlagMsg[] = "votes: a flag above 2 or a commit whose counted power passes 2^63 - 1";
+
+// behind the read-back: Scalar::from_hash never yields k >= l, so a checked vote's k must be canonical
+static int quorum_join_check_k(edc_ctx* ctx, const QuorumJoin* jn) {
+  for (size_t i = 0; jn && i < jn->skip.size(); ++i) {
+    uint32_t w[8];
+    memcpy(w, jn->host_k + 32 * i, 32);
+    if (!jn->skip[i] && w[7] >= 0x10000000u && !sc_is_canonical(w)) {
+      ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
+      return EDC_ERR_ARG;
+    }
+  }
+  return 0;
+}
+
 // Device arrays of `count` items (keys, signatures, k). idx: where each stands in the list it was
 // gathered from; null: it is that list.
 struct ItemList {
@@ -4072,6 +4119,23 @@ static int tmpl_quorum_device_inputs(edc_ctx* ctx, const edc_templates* ts, size
   return 0;
 }
 
+// var_off | item_alt | var of n > 0 host items staged in one piece, each at a 16-byte boundary
+static int tmpl_quorum_stage_holes(edc_ctx* ctx, size_t n, const uint8_t* item_alt, const uint8_t* var,
+                                   const uint32_t* var_off, TmplQuorumItems* it) {
+  hipStream_t st = ctx->st();
+  const size_t var_bytes = var_off[n], o_alt = up16(4 * (n + 1)), o_var = up16(o_alt + n);
+  int rc = tmpl_room(ctx, st, ctx->tq_in, o_var + var_bytes);
+  if (rc) return rc;
+  CK(hipMemcpyAsync(ctx->tq_in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
+  if (item_alt) CK(hipMemcpyAsync(ctx->tq_in + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
+  if (var_bytes) CK(hipMemcpyAsync(ctx->tq_in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
+  it->item_alt = item_alt ? ctx->tq_in + o_alt : nullptr;
+  it->var = ctx->tq_in + o_var;
+  it->var_off = reinterpret_cast<const uint32_t*>(ctx->tq_in.get());
+  it->var_bytes = var_bytes;
+  return 0;
+}
+
 // The host form's checks and staging, shared with edc_cached_tmpl_quorum_verify.
 static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
                                    const uint16_t* commit_tpl, uint32_t alt_span, const uint8_t* item_alt,
@@ -4090,18 +4154,11 @@ static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t
   if ((rc = quorum_stage_votes(ctx, n, nc, power, flag)) || (rc = ensure_n(ctx, n))) return rc;
   hipStream_t st = ctx->st();
   TmplQuorumItems it{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->q_power, ctx->q_flag};
-  if (n) {                  // staged in one piece: var_off | item_alt | var, each at a 16-byte boundary
-    const size_t var_bytes = var_off[n], o_alt = up16(4 * (n + 1)), o_var = up16(o_alt + n);
-    if ((rc = tmpl_room(ctx, st, ctx->tq_in, o_var + var_bytes))) return rc;
+  if (n) {
     // key indices into q_cidx, which is free until the selection writes it
-    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->q_cidx, ctx->vk, ctx->sig))) return rc;
-    CK(hipMemcpyAsync(ctx->tq_in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
-    if (item_alt) CK(hipMemcpyAsync(ctx->tq_in + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
-    if (var_bytes) CK(hipMemcpyAsync(ctx->tq_in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
-    it.item_alt = item_alt ? ctx->tq_in + o_alt : nullptr;
-    it.var = ctx->tq_in + o_var;
-    it.var_off = reinterpret_cast<const uint32_t*>(ctx->tq_in.get());
-    it.var_bytes = var_bytes;
+    if ((rc = tmpl_quorum_stage_holes(ctx, n, item_alt, var, var_off, &it)) ||
+        (rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->q_cidx, ctx->vk, ctx->sig)))
+      return rc;
   }
   *sh_out = sh;
   *n_out = n;
@@ -4111,10 +4168,12 @@ static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t
 
 // The selection, then the m checked votes gathered and hashed: *list holds them with their k in
 // kbuf. From the expansion on, the slot's template workspace is armed (w.check): whoever runs the
-// batch on the list ends with tmpl_quorum_done.
+// batch on the list ends with tmpl_quorum_done. jn (a validator-set request): the join runs in front
+// of the selection and the double-vote scan behind it, in front of the template map.
 static int tmpl_quorum_list(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
                             const uint32_t* commit_off, const uint16_t* commit_tpl, uint32_t alt_span, size_t n,
-                            const TmplQuorumItems& it, const uint64_t* threshold, int mode, ItemList* list) {
+                            const TmplQuorumItems& it, const uint64_t* threshold, int mode, ItemList* list,
+                            QuorumJoin* jn = nullptr) {
   Slot& s = ctx->slot[0];
   TmplWs& w = s.tw;
   int rc = init_slot(ctx, s);
@@ -4127,7 +4186,7 @@ static int tmpl_quorum_list(edc_ctx* ctx, const edc_templates* ts, const TmplSha
       (rc = tmpl_room(ctx, st, ctx->tq_wgh, (size_t)nwg + 1)))
     return rc;
   if (!ctx->tq_harena) CK(ctx->tq_harena.alloc(1));
-  if ((rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, it.power, it.flag))) return rc;
+  if ((rc = quorum_front_enqueue(ctx, n, nc, commit_off, threshold, mode, it.power, it.flag, jn))) return rc;
   if (n) {                      // behind the selection: the all-n checks and the checked hole bytes
     CK(hipMemcpyAsync(ctx->tq_ctpl, commit_tpl, nc * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, ctx->q_coff, ctx->tq_ctpl, alt_span, it.item_alt, ctx->tq_tpl,
@@ -4314,25 +4373,28 @@ static int cq_counts(edc_ctx* ctx, size_t n, size_t m, size_t hashed, size_t* mi
 // on the device; hashed: the items SHA-512 ran over for this call.
 static int cached_quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
                              const ItemList& all, const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
-                             const QuorumOut& out, size_t hashed) {
+                             const QuorumOut& out, size_t hashed, QuorumJoin* jn = nullptr) {
   const size_t n = all.count;
   size_t m = 0, c = 0;
   ItemList miss;
-  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag);
+  int rc = quorum_front_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag, jn);
   if (rc) return rc;
-  // behind the selection: the masked lookup, whose counts travel in the same read-back
+  // behind the selection (and a request's double-vote scan, which reads the selection's skip bytes
+  // alone): the masked lookup, whose counts travel in the same read-back
   if (n && (rc = cq_lookup(ctx, all, ctx->sc_hit))) return rc;
-  if ((rc = quorum_select_read(ctx, n, &m)) || (rc = cq_counts(ctx, n, m, hashed, &c))) return rc;
+  if ((rc = quorum_select_read(ctx, n, &m, jn ? kJoinFlagMsg : nullptr)) || (rc = quorum_join_check_k(ctx, jn)) ||
+      (rc = cq_counts(ctx, n, m, hashed, &c)))
+    return rc;
   if ((rc = quorum_gather(ctx, all, c, ctx->cq_leave, ctx->cq_wg, sc_area(ctx), &miss))) return rc;
   const QuorumCached cq{m, ctx->cq_code, all};
-  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq);
+  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, jn ? ctx->vs_hdv.get() : nullptr);
 }
 
 // tmpl_quorum_list's list (the m checked votes, their k in kbuf) through the table and the batch:
 // the lookup, the second read-back, the counts, the misses gathered, quorum_finish.
 static int cached_tmpl_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, const ItemList& list,
                               const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
-                              const QuorumOut& out) {
+                              const QuorumOut& out, const uint8_t* dv = nullptr) {
   hipStream_t st = ctx->st();
   const size_t m = list.count;
   int rc;
@@ -4355,7 +4417,7 @@ static int cached_tmpl_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold
   if ((rc = quorum_gather(ctx, list, c, ctx->cq_leave, ctx->cq_wg, GatherArea{ctx->cq_g, ctx->cq_cap_g, ctx->cq_idx}, &miss)))
     return rc;
   const QuorumCached cq{m, ctx->cq_code, list};
-  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq);
+  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, dv);
 }
 
 static int cached_tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
@@ -4496,11 +4558,12 @@ static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false) {
 }
 
 // The join, the selection and the double-vote scan of n votes whose keys (d_vk, or d_kidx with
-// d_vk null) and flags are on the device, with one read-back: *n_checked, the commits'
-// double-vote bytes in vs_hdv and, if h_skip is given, the n skip bytes. valset_room has run.
-static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
-                         int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag, uint8_t* h_skip,
-                         size_t* n_checked, const uint32_t* cver = nullptr) {
+// d_vk null) and flags are on the device, enqueued with the copies quorum_select_read's one
+// read-back then brings: the commits' double-vote bytes in vs_hdv and, if h_skip is given, the n
+// skip bytes. valset_room has run.
+static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                                 int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
+                                 uint8_t* h_skip, const uint32_t* cver) {
   hipStream_t st = ctx->st();
   if (cver && n) {      // the history's join reads the offsets, which the selection stages (again) only behind it
     CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -4523,8 +4586,15 @@ static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* comm
     CK(hipMemcpyAsync(ctx->vs_hdv, ctx->vs_dv, nc, hipMemcpyDeviceToHost, st));
     if (h_skip) CK(hipMemcpyAsync(h_skip, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
   }
-  return quorum_select_read(ctx, n, n_checked,
-                            "votes: a flag above 2 or a commit whose counted power passes 2^63 - 1");
+  return 0;
+}
+
+// valset_select_enqueue and its read-back: *n_checked
+static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                         int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag, uint8_t* h_skip,
+                         size_t* n_checked, const uint32_t* cver = nullptr) {
+  int rc = valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, h_skip, cver);
+  return rc ? rc : quorum_select_read(ctx, n, n_checked, kJoinFlagMsg);
 }
 
 // keys (bytes into ctx->vk, or positions into vs_kidx) and flags (vs_flag) of n > 0 host votes
@@ -4912,6 +4982,191 @@ int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, 
                            const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
                            int mode, int reps, float ms[2]) {
   return valset_debug_select_entry(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, reps, ms);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- validator-set requests
+// edc_vq_verify: the stages above composed behind one request. Every form is the request's checks
+// and staging, then the join (QuorumJoin) in front of the selection the form's pipeline already
+// enqueues and the double-vote scan behind it:
+//   plain            valset_run: join, selection, scan, one read-back, gather, quorum_finish
+//   plain cached     cached_quorum_run with the join: ... scan, masked lookup, one read-back, ...
+//   templated        tmpl_quorum_list with the join, then quorum_finish
+//   templated cached tmpl_quorum_list with the join, then cached_tmpl_finish
+// A host request by key position (key_idx) stages 4 bytes per key and expands the keys on the
+// device (stage_keys_sigs), as every host form does; the join still resolves by position. Gathers
+// that take the kept keys by position instead were measured level with this (DESIGN.md,
+// "Validator-set requests") and are not kept.
+struct VqForm {
+  bool hist, tmpl, dev;
+  size_t n;
+};
+
+// the checks that read no array, then nc == 0; true: *rc is the entry's result
+static bool vq_entry_done(edc_ctx* ctx, const edc_vq_request* rq, const edc_vq_result* rs, const QuorumOut& out, int* rc) {
+  *rc = EDC_ERR_ARG;
+  if (!ctx || !rq || !rs) return true;
+  if (rq->size != sizeof(edc_vq_request) || rs->size != sizeof(edc_vq_result)) {
+    ctx->err = "edc_vq_verify: size is the caller's sizeof of the structure";
+    return true;
+  }
+  if (rq->reserved || rs->reserved || rq->device > 1) { ctx->err = "edc_vq_verify: reserved fields are 0, device is 0 or 1"; return true; }
+  if (!rq->z_seed) { ctx->err = "null z_seed"; return true; }
+  if (!rq->vk == !rq->key_idx) { ctx->err = "exactly one of vk and key_idx"; return true; }
+  if (rq->device && rq->key_idx) { ctx->err = "key_idx is a host form's: a device request passes vk"; return true; }
+  if ((rq->msg_off ? 1 : 0) + (rq->k ? 1 : 0) + (rq->ts ? 1 : 0) != 1 || (rq->msg && !rq->msg_off)) {
+    ctx->err = "exactly one of (msg, msg_off), k and a template description";
+    return true;
+  }
+  if (!rq->ts && (rq->commit_tpl || rq->alt_span || rq->item_alt || rq->var || rq->var_off || rq->var_bytes)) {
+    ctx->err = "template fields without a template set";
+    return true;
+  }
+  if (rq->cached && (*rc = cq_ready(ctx))) return true;
+  if (!rq->nc) { *rc = quorum_none(out); return true; }
+  return false;
+}
+
+// the templated forms: checks, staging, tmpl_quorum_list with the join, the finish
+static int vq_run_tmpl(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out) {
+  const size_t nc = rq->nc;
+  TmplShape sh;
+  size_t n;
+  int rc;
+  if (rq->device)
+    rc = commits_check_tmpl_device(ctx, rq->ts, nc, rq->commit_off, rq->commit_tpl, rq->alt_span, rq->vk, rq->sig, rq->var,
+                                   rq->var_off, rq->var_bytes, &sh, &n);
+  else
+    rc = commits_check_tmpl(ctx, rq->ts, nc, rq->commit_off, rq->commit_tpl, true, rq->alt_span, rq->item_alt, rq->vk,
+                            rq->key_idx, rq->sig, rq->var, rq->var_off, &sh, &n);
+  if (rc || (rc = quorum_check(ctx, nc, rq->commit_off, rq->threshold, rq->mode, &n)) ||
+      (rc = rq->commit_ver ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx)))
+    return rc;
+  if (n && !rq->flag) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  CK(hipSetDevice(ctx->device));
+  if ((rc = valset_room(ctx, n, nc, rq->commit_ver != nullptr))) return rc;
+  hipStream_t st = ctx->st();
+  TmplQuorumItems it{rq->vk, rq->sig, rq->item_alt, rq->var, rq->var_off, rq->var_bytes, ctx->q_power, ctx->q_flag};
+  QuorumJoin jn{rq->vk, nullptr, rq->flag, rq->commit_ver, nullptr, {}};
+  if (!rq->device) {
+    if ((rc = ensure_n(ctx, n))) return rc;
+    it = TmplQuorumItems{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->q_power, ctx->q_flag};
+    if (n) {                    // 4 + 64 + 1 bytes per vote and its hole in the key_idx form
+      CK(hipMemcpyAsync(ctx->vs_flag, rq->flag, n, hipMemcpyHostToDevice, st));
+      if ((rc = tmpl_quorum_stage_holes(ctx, n, rq->item_alt, rq->var, rq->var_off, &it)) ||
+          (rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->vs_kidx, ctx->vk, ctx->sig)))
+        return rc;
+    }
+    jn.d_vk = rq->key_idx ? nullptr : ctx->vk.get();
+    jn.d_kidx = ctx->vs_kidx;
+    jn.d_flag = ctx->vs_flag;
+  }
+  ItemList list;
+  if ((rc = tmpl_quorum_list(ctx, rq->ts, sh, nc, rq->commit_off, rq->commit_tpl, rq->alt_span, n, it, rq->threshold,
+                             rq->mode, &list, &jn)))
+    return rc;
+  return tmpl_quorum_done(ctx, rq->cached ? cached_tmpl_finish(ctx, nc, rq->threshold, n, list, it.power, it.flag,
+                                                               rq->z_seed, out, ctx->vs_hdv)
+                                          : quorum_finish(ctx, nc, rq->threshold, n, list, it.power, it.flag, rq->z_seed,
+                                                          out, nullptr, ctx->vs_hdv));
+}
+
+// the forms on messages or k: the checks and staging of valset_verify_*_entry, then valset_run or
+// cached_quorum_run with the join; *hashed: the items SHA-512 runs over
+static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out, size_t* hashed) {
+  const size_t nc = rq->nc;
+  const bool hist = rq->commit_ver != nullptr;
+  size_t n;
+  int rc = quorum_check(ctx, nc, rq->commit_off, rq->threshold, rq->mode, &n);
+  if (rc || (rc = hist ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx))) return rc;
+  if (n && (!rq->sig || !rq->flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  ItemList all;
+  QuorumJoin jn{nullptr, nullptr, nullptr, rq->commit_ver, nullptr, {}};
+  if (rq->device) {
+    if (n && (!aligned16(rq->vk) || !aligned16(rq->sig) || (rq->k && !aligned16(rq->k)))) {
+      ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
+      return EDC_ERR_ARG;
+    }
+    CK(hipSetDevice(ctx->device));
+    if ((rc = valset_room(ctx, n, nc, hist))) return rc;
+    const uint32_t* k = reinterpret_cast<const uint32_t*>(rq->k);
+    if (n && !k) {
+      if ((rc = ensure_n(ctx, n))) return rc;
+      launch_challenge(ctx->st(), (uint32_t)n, rq->vk, rq->sig, rq->msg, rq->msg_off, ctx->kbuf);
+      CK(hipGetLastError());
+      k = ctx->kbuf;
+    }
+    all = ItemList{rq->vk, rq->sig, k, nullptr, n};
+    jn.d_vk = rq->vk;
+    jn.d_flag = rq->flag;
+  } else {
+    if (n && (rc = check_key_idx(ctx, rq->key_idx ? n : 0, rq->key_idx))) return rc;
+    if (n && (rc = commits_check_msg_or_k(ctx, n, rq->msg, rq->msg_off, rq->k))) return rc;
+    CK(hipSetDevice(ctx->device));
+    if ((rc = valset_room(ctx, n, nc, hist))) return rc;
+    hipStream_t st = ctx->st();
+    if (rq->k) {
+      if ((rc = ensure_n(ctx, n))) return rc;
+      if (n) CK(hipMemcpyAsync(ctx->kbuf, rq->k, n * 32, hipMemcpyHostToDevice, st));
+    } else if ((rc = upload_msgs(ctx, n, rq->msg, n ? rq->msg_off : nullptr))) {
+      return rc;
+    }
+    if (n) {
+      CK(hipMemcpyAsync(ctx->vs_flag, rq->flag, n, hipMemcpyHostToDevice, st));
+      if ((rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->vs_kidx, ctx->vk, ctx->sig))) return rc;
+      if (!rq->k) {
+        launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
+        CK(hipGetLastError());
+      }
+    }
+    all = ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n};
+    jn.d_vk = rq->key_idx ? nullptr : ctx->vk.get();
+    jn.d_kidx = ctx->vs_kidx;
+    jn.d_flag = ctx->vs_flag;
+    jn.host_k = n ? rq->k : nullptr;
+  }
+  *hashed = rq->k ? 0 : n;
+  if (rq->cached)
+    return cached_quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->q_power, ctx->q_flag, rq->z_seed,
+                             out, *hashed, &jn);
+  return valset_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, jn.d_vk, jn.d_kidx, jn.d_flag, jn.host_k,
+                    rq->z_seed, out, rq->commit_ver);
+}
+
+extern "C" {
+
+int edc_vq_verify(edc_ctx* ctx, const edc_vq_request* rq, edc_vq_result* rs) {
+  size_t m = 0, miss = 0;
+  QuorumOut out{nullptr, nullptr, nullptr, nullptr, &m, nullptr, nullptr};
+  if (rq && rs && rq->size == sizeof(edc_vq_request) && rs->size == sizeof(edc_vq_result))
+    out = QuorumOut{rs->commit_verdicts, rs->item_verdicts, rs->tally, rs->n_bad_commits,
+                    rs->n_checked ? rs->n_checked : &m, rq->cached ? (rs->n_miss ? rs->n_miss : &miss) : nullptr,
+                    rs->check8};
+  int rc;
+  if (vq_entry_done(ctx, rq, rs, out, &rc)) return rc;
+  size_t hashed = 0;
+  rc = rq->ts ? vq_run_tmpl(ctx, rq, out) : vq_run_plain(ctx, rq, out, &hashed);
+  if (rc < 0) return rc;
+  // the debug record, from the records of the stages that ran
+  const uint64_t n = rq->commit_off[rq->nc];
+  uint64_t* L = ctx->vq_last;
+  L[0] = n;
+  L[1] = *out.n_checked;
+  L[2] = rq->cached ? ctx->cq_last[2] : 0;
+  L[3] = rq->cached ? ctx->cq_last[3] : 0;
+  L[4] = rq->ts ? ctx->tq_last[2] : hashed;
+  L[5] = rq->cached ? ctx->cq_last[5] : 0;
+  L[6] = 0;     // reserved
+  L[7] = rq->ts ? ctx->tq_last[3] : 0;
+  ctx->vq_have = true;
+  return rc;
+}
+
+int edc_debug_vq_last(const edc_ctx* ctx, uint64_t out[8]) {
+  if (!ctx || !out || !ctx->vq_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->vq_last, sizeof(ctx->vq_last));
+  return EDC_OK;
 }
 
 }  // extern "C"

@@ -1320,8 +1320,8 @@ int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]);
  * edc_debug_valset_select  measurement hook: on host arrays checked as edc_valset_resolve, the join
  *   kernel and the double-vote scan (with the clearing of its workspace) alone, each run `reps`
  *   times between HIP events; ms (nullable) = {the join's mean time, the scan's}.
- * Not built: templated, cached, asynchronous submit / wait, incremental-verifier and multi-GPU
- *   forms of these entries.
+ * Not built: asynchronous submit / wait, incremental-verifier and multi-GPU forms. The templated and
+ *   cached forms are built as requests (edc_vq_verify, below), not as further forms of these entries.
  */
 #define EDC_DOUBLE_VOTE 4            /* two checked votes of one commit from the same member */
 int edc_valset_set_powers(edc_ctx* ctx, size_t m, const uint64_t* power);
@@ -1401,8 +1401,8 @@ int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
  *   EDC_DOUBLE_VOTE verdicts included, equals what edc_valset_quorum_verify[_device] gives after
  *   edc_valset_set_powers(base_power).
  * edc_debug_vhist_select  edc_debug_valset_select with the history's join kernel in ms[0].
- * Not built: templated, cached, asynchronous submit / wait, incremental-verifier and multi-GPU
- *   forms of these entries.
+ * Not built: asynchronous submit / wait, incremental-verifier and multi-GPU forms. The templated and
+ *   cached forms are built as requests (edc_vq_verify, below), not as further forms of these entries.
  */
 #define EDC_VHIST_NOT_MEMBER 0xFFFFFFFFFFFFFFFFull
 int edc_vhist_set(edc_ctx* ctx, size_t m, const uint64_t* base_power, size_t nv, const uint32_t* upd_off,
@@ -1427,6 +1427,116 @@ int edc_vhist_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
 int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
                            const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
                            int mode, int reps, float ms[2]);
+
+/*
+ * Validator-set requests: the validator-set and history entries above, the templated forms and the
+ * verified-signature table behind ONE entry that takes a request structure. The matrix
+ * {one set, history} x {messages, k, templates} x {plain, cached} x {host, device} is closed here;
+ * no flat entry is added for it. The reference crate's APIs keep their meaning: every vote that is
+ * verified is one batch::Item (src/batch.rs:76-94) in ONE batch::Verifier (src/batch.rs:127-137,
+ * :149-217), and its code is Item::verify_single's (src/batch.rs:104-107).
+ *
+ * Both structures begin with `size`, the caller's sizeof of the structure, so that fields can be
+ * appended later; any other value is EDC_ERR_ARG. Reserved fields must be 0.
+ *
+ * edc_vq_request
+ *   device      0: the per-item arrays (vk / key_idx, sig, flag, msg, msg_off, k, item_alt, var,
+ *               var_off) are host memory. 1: they are in this GPU's memory under the rules of the
+ *               *_device entries (vk / sig / k 16-byte aligned, var_off 4-byte aligned, msg_off
+ *               8-byte aligned; item_alt and var need no alignment). commit_off, commit_ver,
+ *               threshold, commit_tpl and the template set are host memory in both forms.
+ *   nc, commit_off, threshold, mode, z_seed   as edc_quorum_verify.
+ *   commit_ver  NULL: every commit is judged by the one set of edc_valset_set_powers. Non-NULL
+ *               (nc entries): by the history of edc_vhist_set, as edc_vhist_quorum_verify.
+ *   vk, key_idx exactly one; key_idx (positions in the registered list) in the host form only.
+ *   sig, flag   n x 64 bytes; one flag byte per vote, as edc_valset_quorum_verify.
+ *   messages    exactly one of: msg_off (n + 1 offsets into msg, which may be NULL when every
+ *               message is empty); k (n x 32, prehashed); ts (a template set) with commit_tpl,
+ *               alt_span, item_alt, var, var_off and, in the device form, var_bytes, which mean
+ *               exactly what they mean for edc_tmpl_quorum_verify[_device] (the host form takes
+ *               var_off[n] for var_bytes). Fields of a group that is not used must be NULL / 0.
+ *   cached      non-zero: the call runs through the context's verified-signature table.
+ * edc_vq_result  commit_verdicts (nc), item_verdicts (n), tally (nc), n_bad_commits, n_checked,
+ *   n_miss, check8 (32 bytes): all nullable, with the meaning they have for the entries above.
+ *   n_miss is written only when `cached`.
+ *
+ * Contract, every clause an equality against an entry above.
+ *   Join, selection, double votes: the checked bytes, planned[], dv[], pos, power and flag_out are
+ *     edc_valset_resolve's (edc_vhist_resolve's with commit_ver) for the same inputs, whatever the
+ *     message form and whatever the table holds: a hit still counts towards light mode's running
+ *     sum and still is a checked vote for the double-vote rule, whose scan runs on the selection's
+ *     skip bytes before any lookup.
+ *   No templates, not cached: every output equals edc_valset_quorum_verify[_device] /
+ *     edc_vhist_quorum_verify[_device] on the same inputs.
+ *   Templated: every output equals the same request with (msg, msg_off) holding the materialised
+ *     messages head[t] || hole || tail[t]. Select first, as edc_tmpl_quorum_*: only the checked
+ *     votes are gathered, assembled and hashed, and the arena is sized from n_checked. The all-n
+ *     checks of item_alt and the hole offsets apply to members and non-members alike; a
+ *     non-member's key, signature and hole bytes are never interpreted. No stream synchronization
+ *     is added to edc_tmpl_quorum_verify_device's; dv travels in the selection's one read-back.
+ *   Cached: hit, miss list, inserts, statistics and errors are those of "Cached quorum commit
+ *     sets", applied to the joined power / flag_out. Apart from the verdicts of double-vote
+ *     commits, *n_bad_commits and the return value, every output equals
+ *     edc_cached_quorum_verify[_device] (with templates edc_cached_tmpl_quorum_verify[_device])
+ *     handed those joined arrays. A commit with dv[c] = 1 is EDC_DOUBLE_VOTE whatever else holds;
+ *     its checked misses are still verified, and inserted if valid. The plain cached form adds no
+ *     synchronization; the templated one keeps the existing second read-back and nothing more.
+ *   Return value: EDC_OK iff every commit is EDC_OK; else 1 over 4 over 3, as edc_valset_*.
+ * Keys by position. With key_idx the join resolves by position, with no hash lookup, and 4 bytes per
+ *   key cross PCIe; the n keys are then expanded on the device from the registered list, as in every
+ *   other host form. Gathers that take only the kept votes' keys by position were built and measured
+ *   level with this, so the simpler path stands ("Validator-set requests").
+ * Errors: the union of what the composed entries check, on the host for host forms and on the
+ *   device for device forms (flags above 2, a commit's counted power, item_alt, hole offsets).
+ *   Further: a wrong `size`, a non-zero reserved field, both or neither of a one-of group, key_idx
+ *   with device = 1, `cached` without a table, commit_ver without a history, no commit_ver without
+ *   powers. A violation returns EDC_ERR_ARG with no verdict, nothing inserted, no counter changed
+ *   and no index formed outside the declared arrays; the context stays usable. nc = 0 returns
+ *   EDC_OK with no array read (after the checks that read no array). Synchronous on slot 0, refused
+ *   while a batch is pending there.
+ * edc_debug_vq_last  test hook, a host copy (no device work): out = {n, n_checked, hits, n_miss,
+ *   items SHA-512 ran over, records inserted, 0 (reserved), arena bytes} of the last request that
+ *   returned a verdict; EDC_ERR_ARG before any.
+ */
+typedef struct edc_vq_request {
+  uint32_t size;               /* sizeof(edc_vq_request) */
+  uint32_t device;
+  int32_t mode;                /* EDC_QUORUM_FULL / EDC_QUORUM_LIGHT */
+  uint32_t cached;
+  uint32_t alt_span;
+  uint32_t reserved;
+  size_t nc;
+  const uint32_t* commit_off;
+  const uint32_t* commit_ver;
+  const uint64_t* threshold;
+  const uint8_t* z_seed;
+  const uint8_t* vk;
+  const uint32_t* key_idx;
+  const uint8_t* sig;
+  const uint8_t* flag;
+  const uint8_t* msg;
+  const uint64_t* msg_off;
+  const uint8_t* k;
+  const edc_templates* ts;
+  const uint16_t* commit_tpl;
+  const uint8_t* item_alt;
+  const uint8_t* var;
+  const uint32_t* var_off;
+  size_t var_bytes;
+} edc_vq_request;
+typedef struct edc_vq_result {
+  uint32_t size;               /* sizeof(edc_vq_result) */
+  uint32_t reserved;
+  uint8_t* commit_verdicts;
+  uint8_t* item_verdicts;
+  uint64_t* tally;
+  int* n_bad_commits;
+  size_t* n_checked;
+  size_t* n_miss;
+  uint8_t* check8;
+} edc_vq_result;
+int edc_vq_verify(edc_ctx* ctx, const edc_vq_request* rq, edc_vq_result* rs);
+int edc_debug_vq_last(const edc_ctx* ctx, uint64_t out[8]);
 
 /*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
