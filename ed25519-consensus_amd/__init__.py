@@ -45,6 +45,7 @@ EDC_DOUBLE_VOTE = 4
 NO_POS = 0xFFFFFFFF
 # validator-set history (edc_vhist_*): the power of a position that is not a member
 VHIST_NOT_MEMBER = 0xFFFFFFFFFFFFFFFF
+NO_TRUST = 0xFFFFFFFF              # EDC_VQ_NO_TRUST: a commit of a trusting pair judged by its own set only
 
 # every symbol include/edc.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -88,6 +89,7 @@ ABI_SYMBOLS = [
     "edc_vhist_set", "edc_vhist_versions", "edc_vhist_totals", "edc_vhist_resolve", "edc_vhist_quorum_verify_device",
     "edc_vhist_quorum_verify", "edc_debug_vhist_select",
     "edc_vq_verify", "edc_debug_vq_last",
+    "edc_vq_trust_resolve", "edc_debug_vq_trust_last", "edc_debug_vq_trust_select",
 ]
 
 
@@ -108,14 +110,16 @@ class EdcVqRequest(ctypes.Structure):
                 ("key_idx", ctypes.c_void_p), ("sig", ctypes.c_void_p), ("flag", ctypes.c_void_p),
                 ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p), ("k", ctypes.c_void_p),
                 ("ts", ctypes.c_void_p), ("commit_tpl", ctypes.c_void_p), ("item_alt", ctypes.c_void_p),
-                ("var", ctypes.c_void_p), ("var_off", ctypes.c_void_p), ("var_bytes", ctypes.c_size_t)]
+                ("var", ctypes.c_void_p), ("var_off", ctypes.c_void_p), ("var_bytes", ctypes.c_size_t),
+                ("trust_ver", ctypes.c_void_p), ("trust_threshold", ctypes.c_void_p)]
 
 
 class EdcVqResult(ctypes.Structure):
     """struct edc_vq_result (include/edc.h): where a validator-set request writes; all nullable."""
     _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("commit_verdicts", ctypes.c_void_p),
                 ("item_verdicts", ctypes.c_void_p), ("tally", ctypes.c_void_p), ("n_bad_commits", ctypes.c_void_p),
-                ("n_checked", ctypes.c_void_p), ("n_miss", ctypes.c_void_p), ("check8", ctypes.c_void_p)]
+                ("n_checked", ctypes.c_void_p), ("n_miss", ctypes.c_void_p), ("check8", ctypes.c_void_p),
+                ("trust_verdicts", ctypes.c_void_p), ("trust_tally", ctypes.c_void_p), ("n_bad_trust", ctypes.c_void_p)]
 
 
 class EdcPlanInfo(ctypes.Structure):
@@ -440,6 +444,12 @@ def load_library(path=None):
         if hasattr(lib, "edc_vq_verify"):                    # absent from older A/B builds (tools/)
             lib.edc_vq_verify.argtypes = [c_vp, ctypes.POINTER(EdcVqRequest), ctypes.POINTER(EdcVqResult)]
             lib.edc_debug_vq_last.argtypes = [c_vp, c_u64p]
+        if hasattr(lib, "edc_vq_trust_resolve"):             # absent from older A/B builds (tools/)
+            lib.edc_vq_trust_resolve.argtypes = [c_vp, c_sz, c_u32p, c_u32p, c_u32p, c_u8p, c_u32p, c_u8p, c_u64p, c_u64p,
+                                                 ctypes.c_int] + [c_vp] * 13 + [c_szp]
+            lib.edc_debug_vq_trust_last.argtypes = [c_vp, c_u64p]
+            lib.edc_debug_vq_trust_select.argtypes = [c_vp, c_sz, c_u32p, c_u32p, c_u32p, c_u8p, c_u32p, c_u8p, c_u64p,
+                                                      c_u64p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         if path is None:
             _lib = lib
         return lib
@@ -1176,7 +1186,8 @@ class Engine:
     # the verified-signature table behind one request ----
     def vq_verify(self, commit_off, flags, thresholds, z_seed, light=True, versions=None, cached=False, device=False,
                   vks=None, key_idx=None, sigs=None, msgs=None, ks=None, msg_off=None, templates=None, commit_tpl=None,
-                  alt_span=1, item_alt=None, holes=None, var_off=None, var_bytes=None, raw=None):
+                  alt_span=1, item_alt=None, holes=None, var_off=None, var_bytes=None, raw=None, trust_versions=None,
+                  trust_thresholds=None):
         """edc_vq_verify. device=False: vks / sigs / msgs / ks / holes are sequences of bytes, key_idx /
         flags / item_alt sequences of ints, as the sibling host methods take them. device=True: vks,
         sigs, flags, msgs (the arena, with msg_off), ks, item_alt, holes (the hole bytes) and var_off
@@ -1184,13 +1195,19 @@ class Engine:
         one set of valset_set_powers), thresholds, commit_tpl and templates are host values in both.
         Exactly one of vks and key_idx; exactly one of msgs, ks and templates. Returns the dict
         quorum_verify returns, with n_miss when cached. raw: a dict of request field -> value that
-        overrides what was built (tests of the refusals)."""
+        overrides what was built (tests of the refusals).
+        trust_versions / trust_thresholds (one per commit, host; NO_TRUST: that commit has no trusting
+        side) make the request a trusting pair: every commit is also judged by the set of its trust
+        version against its trust threshold, the union of the votes either side selects is verified
+        once, and the dict gains trust_verdicts, trust_tally and n_bad_trust."""
         nc, off = self._commit_offsets(commit_off)
         n = off[nc] if nc else 0
         th = self._quorum_thresholds(nc, thresholds)
         ver = None if versions is None else self._vhist_versions_arg(nc, versions)
+        tver = None if trust_versions is None else self._vhist_versions_arg(nc, trust_versions)
+        tth = None if trust_thresholds is None else self._quorum_thresholds(nc, trust_thresholds)
         seed = bytes(z_seed)
-        keep = [off, th, ver, seed]
+        keep = [off, th, ver, seed, tver, tth]
         rq = EdcVqRequest(size=ctypes.sizeof(EdcVqRequest), device=int(bool(device)), mode=int(bool(light)),
                           cached=int(bool(cached)), nc=nc)
 
@@ -1205,6 +1222,8 @@ class Engine:
         rq.commit_off, rq.threshold, rq.z_seed = ctypes.addressof(off), ctypes.addressof(th), \
             ctypes.cast(seed, ctypes.c_void_p).value
         rq.commit_ver = None if ver is None else ctypes.addressof(ver)
+        rq.trust_ver = None if tver is None else ctypes.addressof(tver)
+        rq.trust_threshold = None if tth is None else ctypes.addressof(tth)
         if device:
             rq.vk, rq.sig, rq.flag, rq.msg, rq.msg_off, rq.k = (addr(x) for x in (vks, sigs, flags, msgs, msg_off, ks))
             if templates is not None:
@@ -1234,13 +1253,17 @@ class Engine:
         out = (ctypes.create_string_buffer(max(nc, 1)), ctypes.create_string_buffer(max(n, 1)),
                (ctypes.c_uint64 * max(nc, 1))(), ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0),
                ctypes.create_string_buffer(32))
-        rs = EdcVqResult(ctypes.sizeof(EdcVqResult), 0, *(ctypes.addressof(x) for x in out))
+        tout = (ctypes.create_string_buffer(max(nc, 1)), (ctypes.c_uint64 * max(nc, 1))(), ctypes.c_int(0))
+        rs = EdcVqResult(ctypes.sizeof(EdcVqResult), 0, *(ctypes.addressof(x) for x in out + tout))
         if raw and "result_size" in raw:
             rs.size = raw["result_size"]
         with self._lock:
             rc = self.lib.edc_vq_verify(self.ctx, ctypes.byref(rq), ctypes.byref(rs))
         self._check(rc)
-        return self._quorum_result(rc, nc, n, out, bool(cached))
+        res = self._quorum_result(rc, nc, n, out, bool(cached))
+        if rq.trust_ver:
+            res.update(trust_verdicts=list(tout[0].raw[:nc]), trust_tally=list(tout[1][:nc]), n_bad_trust=tout[2].value)
+        return res
 
     def vq_last(self):
         """edc_debug_vq_last: (n, n_checked, hits, n_miss, items SHA-512 ran over, records inserted, 0
@@ -1250,6 +1273,57 @@ class Engine:
             rc = self.lib.edc_debug_vq_last(self.ctx, out)
         self._check(rc)
         return tuple(out)
+
+    def vq_trust_last(self):
+        """edc_debug_vq_trust_last: (checked by A, checked by B, checked by both, union) of the last
+        trusting pair that returned a verdict on this engine."""
+        out = (ctypes.c_uint64 * 4)()
+        with self._lock:
+            rc = self.lib.edc_debug_vq_trust_last(self.ctx, out)
+        self._check(rc)
+        return tuple(out)
+
+    def _vq_trust_args(self, commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, vks, key_idx):
+        nc, off = self._commit_offsets(commit_off)
+        n = off[nc] if nc else 0
+        vkb, idx = _tmpl_keys(n, vks, key_idx)
+        return nc, n, (off, self._vhist_versions_arg(nc, versions), self._vhist_versions_arg(nc, trust_versions), vkb, idx,
+                       self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds),
+                       self._quorum_thresholds(nc, trust_thresholds))
+
+    def vq_trust_resolve(self, commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, light=True,
+                         vks=None, key_idx=None):
+        """edc_vq_trust_resolve: the paired join, both selections, the union and both double-vote scans
+        alone -> a dict: "a" and "b", each the dict vhist_resolve returns for that side (without
+        n_checked), "side" (bit 0 checked by A, bit 1 checked by B) and "n_checked" (the union's)."""
+        nc, n, args = self._vq_trust_args(commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, vks,
+                                          key_idx)
+        def side_out():
+            return ((ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))(), ctypes.create_string_buffer(max(n, 1)),
+                    ctypes.create_string_buffer(max(n, 1)), (ctypes.c_uint64 * max(nc, 1))(),
+                    ctypes.create_string_buffer(max(nc, 1)))
+        a, b = side_out(), side_out()
+        side, cnt = ctypes.create_string_buffer(max(n, 1)), ctypes.c_size_t(0)
+        with self._lock:
+            rc = self.lib.edc_vq_trust_resolve(self.ctx, nc, *args, int(bool(light)),
+                                               *(ctypes.addressof(x) for x in a + b + (side,)), ctypes.byref(cnt))
+        self._check(rc)
+        def side_dict(o):
+            return {"pos": list(o[0][:n]), "power": list(o[1][:n]), "flag": list(o[2].raw[:n]),
+                    "checked": list(o[3].raw[:n]), "planned": list(o[4][:nc]), "dv": list(o[5].raw[:nc])}
+        return {"a": side_dict(a), "b": side_dict(b), "side": list(side.raw[:n]), "n_checked": cnt.value}
+
+    def vq_trust_select_ms(self, commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, light=True,
+                           vks=None, key_idx=None, reps=20):
+        """edc_debug_vq_trust_select: mean milliseconds of the paired join, of both selections with the
+        union and its scan, and of both double-vote scans."""
+        nc, n, args = self._vq_trust_args(commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, vks,
+                                          key_idx)
+        ms = (ctypes.c_float * 3)()
+        with self._lock:
+            rc = self.lib.edc_debug_vq_trust_select(self.ctx, nc, *args, int(bool(light)), reps, ms)
+        self._check(rc)
+        return ms[0], ms[1], ms[2]
 
     def quorum_select_ms(self, commit_off, powers, flags, thresholds, light=True, reps=20):
         """edc_debug_quorum_select: mean time of the selection kernels alone, in milliseconds."""
@@ -2025,7 +2099,7 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
 
     @staticmethod
     def verify_quorum(verifiers, powers, flags, thresholds, light=True, z_seed=None, engine=None, cached=False,
-                      versions=None):
+                      versions=None, trust_versions=None, trust_thresholds=None):
         """Quorum check of many commits in ONE launch (a quorum commit set, edc_quorum_verify; not an
         API of the reference). verifiers: one batch.Verifier per commit, holding an item for EVERY
         validator of its set (any bytes for an absent one); powers / flags: one list per verifier, one
@@ -2042,8 +2116,18 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         (Engine.valset_set_powers; edc_valset_quorum_verify): a vote whose key is no member of it
         counts as absent, and a commit with two checked votes of one member gets EDC_DOUBLE_VOTE.
         versions (one per verifier, with powers=None only) judges every commit by that version of the
-        engine's validator-set history (Engine.vhist_set; edc_vhist_quorum_verify) instead."""
+        engine's validator-set history (Engine.vhist_set; edc_vhist_quorum_verify) instead.
+        trust_versions / trust_thresholds (one per verifier, with versions only; NO_TRUST for a commit
+        without a trusting side) judge every commit by a second set as well and verify each vote
+        once (a trusting pair, edc_vq_verify): the return value is then (commit verdicts, tallies, item
+        codes per verifier, trust verdicts, trust tallies)."""
         verifiers = list(verifiers)
+        if (trust_versions is None) != (trust_thresholds is None) or (trust_versions is not None and versions is None):
+            raise ValueError("verify_quorum: trust_versions and trust_thresholds go together, and with versions")
+        if trust_versions is not None:
+            trust_versions, trust_thresholds = [int(v) for v in trust_versions], list(trust_thresholds)
+            if len(trust_versions) != len(verifiers) or len(trust_thresholds) != len(verifiers):
+                raise ValueError("verify_quorum: one trust version and trust threshold per verifier")
         if versions is not None:
             if powers is not None or cached:
                 raise ValueError("verify_quorum: versions go with powers=None and have no cached form")
@@ -2075,7 +2159,7 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         if off[-1] >= 1 << 28:
             raise ValueError("verify_quorum: fewer than 2^28 items in one call")
         if not verifiers:
-            return [], [], []
+            return ([], [], [], [], []) if trust_versions is not None else ([], [], [])
         eng = engine or next((v._engine for v in verifiers if v._engine is not None), None) or default_engine()
         vks = [x for v in verifiers for x in v._vks]
         sigs = [x for v in verifiers for x in v._sigs]
@@ -2083,6 +2167,9 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         pw, fl = [x for p in powers for x in p], [x for f in flags for x in f]
         if from_set:
             def run(off, sigs, pw, fl, thresholds, z_seed, **kw):
+                if trust_versions is not None:
+                    return eng.vq_verify(off, fl, thresholds, z_seed, versions=versions, sigs=sigs,
+                                         trust_versions=trust_versions, trust_thresholds=trust_thresholds, **kw)
                 if versions is not None:
                     return eng.quorum_verify_vhist(off, versions, sigs, fl, thresholds, z_seed, **kw)
                 return eng.quorum_verify_valset(off, sigs, fl, thresholds, z_seed, **kw)
@@ -2099,6 +2186,8 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
                     ks[i] = k
             res = run(off, sigs, pw, fl, thresholds, z_seed, light=light, vks=vks, ks=ks)
         codes = [res["item_verdicts"][off[c]:off[c + 1]] for c in range(len(verifiers))]
+        if trust_versions is not None:
+            return res["commit_verdicts"], res["tally"], codes, res["trust_verdicts"], res["trust_tally"]
         return res["commit_verdicts"], res["tally"], codes
 
     class StreamVerifier:

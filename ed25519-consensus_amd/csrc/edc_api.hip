@@ -310,6 +310,19 @@ struct edc_ctx {
   // validator-set requests (edc_vq_verify): the host copy edc_debug_vq_last returns
   uint64_t vq_last[8] = {};
   bool vq_have = false;
+  // trusting pairs (trust_ver of a request): side B's copies of what side A keeps in q_* / vs_*
+  // (power, flag, who, pair set per item; threshold, planned, tally, cor, version and double-vote
+  // bytes per commit), each side's own skip bytes, the side byte per item, the device totals
+  // {A, B, both} with the pinned words they come back in, and the host copy
+  // edc_debug_vq_trust_last returns
+  size_t tr_cap_n = 0, tr_cap_c = 0;
+  DevBuf<uint64_t> tr_power, tr_set, tr_thr, tr_planned, tr_tally;
+  DevBuf<uint32_t> tr_who, tr_cor, tr_ver, tr_cnt;
+  DevBuf<uint8_t> tr_flag, tr_skip_a, tr_skip_b, tr_side, tr_dv;
+  PinnedBuf<uint8_t> tr_hdv;
+  PinnedBuf<uint32_t> tr_hcnt;
+  uint64_t vqt_last[4] = {};
+  bool vqt_have = false;
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -3659,12 +3672,40 @@ struct QuorumOut {
   uint8_t* check8;
 };
 
+// The trusting side (side B) of a paired request: the commits' trust versions (VQ_NO_TRUST: side A
+// only) and thresholds, and where side B's verdicts go (all nullable). Host memory. Side B's
+// device arrays are the context's tr_* ones, which ensure_trust has sized.
+struct QuorumTrust {
+  const uint32_t* ver;
+  const uint64_t* threshold;
+  uint8_t* verdicts;
+  uint64_t* tally;
+  int* n_bad;
+};
+
 // nc == 0: nothing to verify
-static int quorum_none(const QuorumOut& out) {
+static int quorum_none(const QuorumOut& out, const QuorumTrust* tr = nullptr) {
   if (out.n_bad_commits) *out.n_bad_commits = 0;
   if (out.n_checked) *out.n_checked = 0;
   if (out.n_miss) *out.n_miss = 0;
+  if (tr && tr->n_bad) *tr->n_bad = 0;
   return EDC_OK;
+}
+
+static int ensure_trust(edc_ctx* ctx, size_t n, size_t nc) {
+  hipStream_t st = ctx->st();
+  CK(grow_group(ctx->tr_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
+    return alloc_all(sized(ctx->tr_power, cap), sized(ctx->tr_flag, cap), sized(ctx->tr_who, cap), sized(ctx->tr_set, 2 * cap),
+                     sized(ctx->tr_skip_a, cap), sized(ctx->tr_skip_b, cap), sized(ctx->tr_side, cap));
+  }));
+  CK(grow_group(ctx->tr_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
+    hipError_t e = alloc_all(sized(ctx->tr_thr, cap), sized(ctx->tr_planned, cap), sized(ctx->tr_tally, cap),
+                             sized(ctx->tr_cor, cap), sized(ctx->tr_ver, cap), sized(ctx->tr_dv, cap));
+    return e != hipSuccess ? e : ctx->tr_hdv.alloc(cap);
+  }));
+  if (!ctx->tr_cnt) CK(ctx->tr_cnt.alloc(3 * QR_UNION_SLOTS));
+  if (!ctx->tr_hcnt) CK(ctx->tr_hcnt.alloc(3 * QR_UNION_SLOTS));
+  return 0;
 }
 
 // What every verify entry does first. True: *rc is the entry's result (a null argument, a cached
@@ -3761,20 +3802,41 @@ static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
 // Workspace, the staged offsets and thresholds, then the selection and the scan of its workgroup
 // counts on device-resident power / flag, all enqueued. A form with work of its own behind the
 // selection (n > 0 only) enqueues it between this and quorum_select_read.
+// tr (a trusting pair; ensure_trust has run and the paired join has written tr_power / tr_flag):
+// side A's selection writes tr_skip_a, side B's runs behind it on tr_power / tr_flag against
+// tr->threshold into tr_skip_b and tr_planned, reading the commit indices and reusing the tile
+// words of side A's (one stream: side A is done with them), and both raise the one error flag; the
+// union kernel then writes the skip bytes and tile counts every back-end reads, so that the scan,
+// the gathers and the lookup see ONE selection, the union's. Its totals {A, B, both} travel to
+// tr_hcnt with the read-back.
 static int quorum_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
-                                 int mode, const uint64_t* d_power, const uint8_t* d_flag) {
+                                 int mode, const uint64_t* d_power, const uint8_t* d_flag, const QuorumTrust* tr = nullptr) {
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
   hipStream_t st = ctx->st();
   if ((rc = sc_order_after_inserts(ctx, st))) return rc;
   CK(hipMemsetAsync(ctx->q_planned, 0, nc * sizeof(uint64_t), st));
+  if (tr) {
+    CK(hipMemsetAsync(ctx->tr_planned, 0, nc * sizeof(uint64_t), st));
+    memset(ctx->tr_hcnt.get(), 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t));
+  }
   if (!n) return 0;
   const uint32_t N = (uint32_t)n, nwg = (uint32_t)quorum_tiles(n);
   CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(ctx->q_thr, threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   CK(hipMemsetAsync(ctx->q_err, 0, sizeof(int), st));
   launch_quorum_select(st, N, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, d_power, d_flag, ctx->q_cidx,
-                       ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->sc_hit, ctx->sc_wg, ctx->q_planned, ctx->q_err);
+                       ctx->q_aggv, ctx->q_aggf, ctx->q_carry, tr ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), ctx->sc_wg,
+                       ctx->q_planned, ctx->q_err);
+  if (tr) {
+    CK(hipMemcpyAsync(ctx->tr_thr, tr->threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    CK(hipMemsetAsync(ctx->tr_cnt, 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t), st));
+    launch_quorum_select(st, N, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->tr_thr, ctx->tr_power, ctx->tr_flag,
+                         ctx->q_cidx, ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->tr_skip_b, ctx->sc_wg, ctx->tr_planned,
+                         ctx->q_err, true);
+    launch_quorum_union(st, N, ctx->tr_skip_a, ctx->tr_skip_b, ctx->sc_hit, ctx->tr_side, ctx->sc_wg, ctx->tr_cnt);
+    CK(hipMemcpyAsync(ctx->tr_hcnt.get(), ctx->tr_cnt, 3 * QR_UNION_SLOTS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  }
   launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
   CK(hipGetLastError());
   ctx->q_h[0] = ctx->q_h[1] = ctx->q_h[2] = 0;
@@ -3819,7 +3881,9 @@ static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* 
 // selection's read-back. d_vk: the n keys on the device, or null with d_kidx their positions;
 // d_flag: the caller's flags; cver (host): the commits' versions, null for the one set;
 // host_k: a host form's prehashed k, canonical for the checked votes (quorum_join_check_k).
-// valset_room has run.
+// trust: the trusting side of a paired request (needs cver), one more optional input of the same
+// stages: the paired join writes both sides, the selection and the double-vote scan run per side,
+// and the skip bytes are the union's. valset_room has run.
 struct QuorumJoin {
   const uint8_t* d_vk;
   const uint32_t* d_kidx;
@@ -3827,11 +3891,12 @@ struct QuorumJoin {
   const uint32_t* cver;
   const uint8_t* host_k;
   std::vector<uint8_t> skip;    // host_k: the skip bytes, read back with the selection
+  const QuorumTrust* trust = nullptr;
 };
 
 static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                                  int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
-                                 uint8_t* h_skip, const uint32_t* cver);
+                                 uint8_t* h_skip, const uint32_t* cver, const QuorumTrust* tr = nullptr);
 
 // quorum_select_enqueue, with the join in front and the double-vote scan behind it when jn is given
 // (d_power / d_flag are then q_power / q_flag, which the join writes)
@@ -3840,7 +3905,7 @@ static int quorum_front_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_
   if (!jn) return quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag);
   jn->skip.assign(jn->host_k ? n : 0, 0);
   return valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, jn->d_vk, jn->d_kidx, jn->d_flag,
-                               jn->skip.empty() ? nullptr : jn->skip.data(), jn->cver);
+                               jn->skip.empty() ? nullptr : jn->skip.data(), jn->cver, jn->trust);
 }
 
 static const char kJoinFlagMsg[] = "votes: a flag above 2 or a commit whose counted power passes 2^63 - 1";
@@ -3908,9 +3973,13 @@ struct QuorumCached {
 // synchronization, and a failed union's codes go back over the lookup's base codes, through the
 // list's positions in the looked-up list and that list's positions in the queue.
 // dv (a validator-set form, host, nc bytes): the commits that hold a double vote (valset_reduce).
+// tr (a trusting pair): the list is the union of both sides' checked votes. A passing union makes
+// each side's tally its planned[]; a failed one runs the tally kernel for both sides at once, each
+// masked by its bit of the side bytes. Side B is reduced with its own double-vote bytes (tr_hdv),
+// and the return value is taken over both sides.
 static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, const ItemList& list,
                          const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
-                         const QuorumCached* cq = nullptr, const uint8_t* dv = nullptr) {
+                         const QuorumCached* cq = nullptr, const uint8_t* dv = nullptr, const QuorumTrust* tr = nullptr) {
   hipStream_t st = ctx->st();
   const size_t m = list.count;
   std::vector<uint8_t> mv(m ? m : 1);
@@ -3925,11 +3994,12 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
     CK(hipGetLastError());
     CK(hipMemcpyAsync(ctx->sc_hctr, ctx->sc_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   }
-  std::vector<uint64_t> tal(nc);
-  std::vector<uint32_t> cor32;
-  std::vector<uint8_t> cor;
+  std::vector<uint64_t> tal(nc), tal_b(tr ? nc : 0);
+  std::vector<uint32_t> cor32, cor32_b;
+  std::vector<uint8_t> cor, cor_b;
   if (code == EDC_OK) {                 // every checked item verified: the tally is the plan
     CK(hipMemcpyAsync(tal.data(), ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (tr) CK(hipMemcpyAsync(tal_b.data(), ctx->tr_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (out.item_verdicts && n) CK(hipMemcpyAsync(out.item_verdicts, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     if (out.item_verdicts)
@@ -3956,20 +4026,51 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
     }
     CK(hipMemsetAsync(ctx->q_tally, 0, nc * sizeof(uint64_t), st));
     CK(hipMemsetAsync(ctx->q_cor, 0, nc * sizeof(uint32_t), st));
-    launch_quorum_tally(st, (uint32_t)n, ctx->q_cidx, d_power, d_flag, d_codes, ctx->q_tally, ctx->q_cor);
+    if (tr) {
+      CK(hipMemsetAsync(ctx->tr_tally, 0, nc * sizeof(uint64_t), st));
+      CK(hipMemsetAsync(ctx->tr_cor, 0, nc * sizeof(uint32_t), st));
+      launch_quorum_tally2(st, (uint32_t)n, ctx->q_cidx, ctx->tr_side, d_power, d_flag, ctx->tr_power, ctx->tr_flag, d_codes,
+                           ctx->q_tally, ctx->q_cor, ctx->tr_tally, ctx->tr_cor);
+    } else {
+      launch_quorum_tally(st, (uint32_t)n, ctx->q_cidx, d_power, d_flag, d_codes, ctx->q_tally, ctx->q_cor);
+    }
     CK(hipGetLastError());
     cor32.resize(nc);
     CK(hipMemcpyAsync(tal.data(), ctx->q_tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     CK(hipMemcpyAsync(cor32.data(), ctx->q_cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (tr) {
+      cor32_b.resize(nc);
+      CK(hipMemcpyAsync(tal_b.data(), ctx->tr_tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      CK(hipMemcpyAsync(cor32_b.data(), ctx->tr_cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
     if (out.item_verdicts) CK(hipMemcpyAsync(out.item_verdicts, d_codes, n, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     cor.resize(nc);
     for (size_t c = 0; c < nc; ++c) cor[c] = cor32[c] ? 1 : 0;
+    cor_b.resize(cor32_b.size());
+    for (size_t c = 0; c < cor_b.size(); ++c) cor_b[c] = cor32_b[c] ? 1 : 0;
   }
   size_t bad = 0;
   const uint8_t* corp = cor.empty() ? nullptr : cor.data();
-  const int res = dv ? valset_reduce(nc, corp, tal.data(), threshold, dv, out.commit_verdicts, &bad)
-                     : quorum_reduce(nc, corp, tal.data(), threshold, out.commit_verdicts, &bad);
+  int res = dv ? valset_reduce(nc, corp, tal.data(), threshold, dv, out.commit_verdicts, &bad)
+               : quorum_reduce(nc, corp, tal.data(), threshold, out.commit_verdicts, &bad);
+  if (tr) {
+    size_t bad_b = 0;
+    const int res_b = vq_trust_reduce(nc, tr->ver, cor_b.empty() ? nullptr : cor_b.data(), tal_b.data(), tr->threshold,
+                                      ctx->tr_hdv, tr->verdicts, &bad_b);
+    res = vq_trust_code(res, res_b);
+    if (tr->tally) memcpy(tr->tally, tal_b.data(), nc * sizeof(uint64_t));
+    if (tr->n_bad) *tr->n_bad = (int)bad_b;
+    uint64_t a = 0, b = 0, ab = 0;        // the union kernel's totals, spread over its slots
+    for (uint32_t j = 0; j < QR_UNION_SLOTS; ++j) {
+      a += ctx->tr_hcnt[3 * j];
+      b += ctx->tr_hcnt[3 * j + 1];
+      ab += ctx->tr_hcnt[3 * j + 2];
+    }
+    const uint64_t last[4] = {a, b, ab, a + b - ab};
+    memcpy(ctx->vqt_last, last, sizeof(last));
+    ctx->vqt_have = true;
+  }
   if (out.tally) memcpy(out.tally, tal.data(), nc * sizeof(uint64_t));
   if (out.n_bad_commits) *out.n_bad_commits = (int)bad;
   if (out.n_checked) *out.n_checked = cq ? cq->n_checked : m;
@@ -4387,14 +4488,15 @@ static int cached_quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
     return rc;
   if ((rc = quorum_gather(ctx, all, c, ctx->cq_leave, ctx->cq_wg, sc_area(ctx), &miss))) return rc;
   const QuorumCached cq{m, ctx->cq_code, all};
-  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, jn ? ctx->vs_hdv.get() : nullptr);
+  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, jn ? ctx->vs_hdv.get() : nullptr,
+                       jn ? jn->trust : nullptr);
 }
 
 // tmpl_quorum_list's list (the m checked votes, their k in kbuf) through the table and the batch:
 // the lookup, the second read-back, the counts, the misses gathered, quorum_finish.
 static int cached_tmpl_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, const ItemList& list,
                               const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
-                              const QuorumOut& out, const uint8_t* dv = nullptr) {
+                              const QuorumOut& out, const uint8_t* dv = nullptr, const QuorumTrust* tr = nullptr) {
   hipStream_t st = ctx->st();
   const size_t m = list.count;
   int rc;
@@ -4417,7 +4519,7 @@ static int cached_tmpl_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold
   if ((rc = quorum_gather(ctx, list, c, ctx->cq_leave, ctx->cq_wg, GatherArea{ctx->cq_g, ctx->cq_cap_g, ctx->cq_idx}, &miss)))
     return rc;
   const QuorumCached cq{m, ctx->cq_code, list};
-  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, dv);
+  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, dv, tr);
 }
 
 static int cached_tmpl_quorum_run(edc_ctx* ctx, const edc_templates* ts, const TmplShape& sh, size_t nc,
@@ -4550,9 +4652,10 @@ static int vhist_ready(edc_ctx* ctx, size_t nc, const uint32_t* cver) {
 
 // Workspace for n items in nc commits on slot 0; everything the selection allocates is allocated
 // here, so that nothing the resolve kernel has written moves afterwards.
-static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false) {
+static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false, bool pair = false) {
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
+  if (pair && (rc = ensure_trust(ctx, n, nc))) return rc;
   if (hist) CK(grow_group(ctx->vh_cap_c, nc, off_cap, sync_of(ctx->st()), [&](size_t cap) { return ctx->vh_cver.alloc(cap); }));
   return ensure_valset(ctx, n, nc);
 }
@@ -4561,27 +4664,46 @@ static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false) {
 // d_vk null) and flags are on the device, enqueued with the copies quorum_select_read's one
 // read-back then brings: the commits' double-vote bytes in vs_hdv and, if h_skip is given, the n
 // skip bytes. valset_room has run.
+// tr (a trusting pair, with cver): the paired join writes side B's arrays beside side A's, the
+// selection runs per side and leaves the union's skip bytes (quorum_select_enqueue), and the
+// double-vote scan runs once per side on that side's skip bytes, members and set; side B's bytes
+// travel to tr_hdv in the same read-back.
 static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                                  int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
-                                 uint8_t* h_skip, const uint32_t* cver) {
+                                 uint8_t* h_skip, const uint32_t* cver, const QuorumTrust* tr) {
   hipStream_t st = ctx->st();
   if (cver && n) {      // the history's join reads the offsets, which the selection stages (again) only behind it
     CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(ctx->vh_cver, cver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    launch_vhist_resolve(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, d_vk, d_kidx,
-                         ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
+    if (tr) {
+      CK(hipMemcpyAsync(ctx->tr_ver, tr->ver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      launch_vhist_resolve2(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, ctx->tr_ver, d_vk,
+                            d_kidx, ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who, ctx->tr_power, ctx->tr_flag,
+                            ctx->tr_who);
+    } else {
+      launch_vhist_resolve(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, d_vk, d_kidx,
+                           ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
+    }
   } else {
     launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, d_kidx, ctx->kc_reg, d_flag, ctx->q_power,
                           ctx->q_flag, ctx->vs_who);
   }
   CK(hipGetLastError());
-  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag);
+  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, tr);
   if (rc) return rc;
   memset(ctx->vs_hdv, 0, nc);
+  if (tr) memset(ctx->tr_hdv, 0, nc);
   if (n) {
     CK(hipMemsetAsync(ctx->vs_dv, 0, nc, st));
     CK(hipMemsetAsync(ctx->vs_set, 0, 2 * n * sizeof(uint64_t), st));
-    launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, ctx->sc_hit, ctx->vs_who, ctx->vs_set, ctx->vs_dv);
+    launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, tr ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), ctx->vs_who,
+                        ctx->vs_set, ctx->vs_dv);
+    if (tr) {
+      CK(hipMemsetAsync(ctx->tr_dv, 0, nc, st));
+      CK(hipMemsetAsync(ctx->tr_set, 0, 2 * n * sizeof(uint64_t), st));
+      launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, ctx->tr_skip_b, ctx->tr_who, ctx->tr_set, ctx->tr_dv);
+      CK(hipMemcpyAsync(ctx->tr_hdv, ctx->tr_dv, nc, hipMemcpyDeviceToHost, st));
+    }
     CK(hipGetLastError());
     CK(hipMemcpyAsync(ctx->vs_hdv, ctx->vs_dv, nc, hipMemcpyDeviceToHost, st));
     if (h_skip) CK(hipMemcpyAsync(h_skip, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
@@ -4592,8 +4714,8 @@ static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32
 // valset_select_enqueue and its read-back: *n_checked
 static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                          int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag, uint8_t* h_skip,
-                         size_t* n_checked, const uint32_t* cver = nullptr) {
-  int rc = valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, h_skip, cver);
+                         size_t* n_checked, const uint32_t* cver = nullptr, const QuorumTrust* tr = nullptr) {
+  int rc = valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, h_skip, cver, tr);
   return rc ? rc : quorum_select_read(ctx, n, n_checked, kJoinFlagMsg);
 }
 
@@ -4629,13 +4751,14 @@ static int valset_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
 // which must be canonical for the checked votes (the skip bytes come back with the read-back).
 static int valset_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
                       const ItemList& all, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
-                      const uint8_t* host_k, const uint8_t* z_seed, const QuorumOut& out, const uint32_t* cver) {
+                      const uint8_t* host_k, const uint8_t* z_seed, const QuorumOut& out, const uint32_t* cver,
+                      const QuorumTrust* tr = nullptr) {
   const size_t n = all.count;
   size_t m = 0;
   ItemList list;
   std::vector<uint8_t> skip(host_k ? n : 0);
   int rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, host_k && n ? skip.data() : nullptr, &m,
-                         cver);
+                         cver, tr);
   if (rc) return rc;
   for (size_t i = 0; i < skip.size(); ++i) {      // Scalar::from_hash never yields k >= l
     uint32_t w[8];
@@ -4646,7 +4769,7 @@ static int valset_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
     }
   }
   if ((rc = quorum_gather(ctx, all, m, ctx->sc_hit, ctx->sc_wg, sc_area(ctx), &list))) return rc;
-  return quorum_finish(ctx, nc, threshold, n, list, ctx->q_power, ctx->q_flag, z_seed, out, nullptr, ctx->vs_hdv);
+  return quorum_finish(ctx, nc, threshold, n, list, ctx->q_power, ctx->q_flag, z_seed, out, nullptr, ctx->vs_hdv, tr);
 }
 
 extern "C" {
@@ -5003,14 +5126,28 @@ struct VqForm {
   size_t n;
 };
 
-// the checks that read no array, then nc == 0; true: *rc is the entry's result
-static bool vq_entry_done(edc_ctx* ctx, const edc_vq_request* rq, const edc_vq_result* rs, const QuorumOut& out, int* rc) {
+// The sizes a structure may name: the one before the trusting pair's fields were appended, and
+// today's. With the earlier one the appended fields read as NULL.
+constexpr uint32_t VQ_REQUEST_SIZE_0 = offsetof(edc_vq_request, trust_ver);
+constexpr uint32_t VQ_RESULT_SIZE_0 = offsetof(edc_vq_result, trust_verdicts);
+
+static bool vq_sizes_ok(const edc_vq_request* rq, const edc_vq_result* rs) {
+  return rq && rs && (rq->size == sizeof(edc_vq_request) || rq->size == VQ_REQUEST_SIZE_0) &&
+         (rs->size == sizeof(edc_vq_result) || rs->size == VQ_RESULT_SIZE_0);
+}
+
+// the checks that read no array, then nc == 0; true: *rc is the entry's result. rq / rs: the
+// caller's structures copied into today's layout (vq_sizes_ok has passed unless ctx->err is set here).
+static bool vq_entry_done(edc_ctx* ctx, bool sizes_ok, const edc_vq_request* rq, const edc_vq_result* rs,
+                          const QuorumOut& out, const QuorumTrust* tr, int* rc) {
   *rc = EDC_ERR_ARG;
   if (!ctx || !rq || !rs) return true;
-  if (rq->size != sizeof(edc_vq_request) || rs->size != sizeof(edc_vq_result)) {
+  if (!sizes_ok) {
     ctx->err = "edc_vq_verify: size is the caller's sizeof of the structure";
     return true;
   }
+  if (!rq->trust_ver != !rq->trust_threshold) { ctx->err = "trust_ver and trust_threshold are given together"; return true; }
+  if (rq->trust_ver && !rq->commit_ver) { ctx->err = "trust_ver needs commit_ver: a trusting pair needs the history"; return true; }
   if (rq->reserved || rs->reserved || rq->device > 1) { ctx->err = "edc_vq_verify: reserved fields are 0, device is 0 or 1"; return true; }
   if (!rq->z_seed) { ctx->err = "null z_seed"; return true; }
   if (!rq->vk == !rq->key_idx) { ctx->err = "exactly one of vk and key_idx"; return true; }
@@ -5024,12 +5161,21 @@ static bool vq_entry_done(edc_ctx* ctx, const edc_vq_request* rq, const edc_vq_r
     return true;
   }
   if (rq->cached && (*rc = cq_ready(ctx))) return true;
-  if (!rq->nc) { *rc = quorum_none(out); return true; }
+  if (!rq->nc) { *rc = quorum_none(out, tr); return true; }
   return false;
 }
 
+// vhist_ready for the trusting side: every trust version is one of the history's or the sentinel
+static int vq_trust_ready(edc_ctx* ctx, size_t nc, const QuorumTrust* tr) {
+  if (tr && !vq_trust_check_versions(nc, tr->ver, ctx->vh.nv)) {
+    ctx->err = "trust_ver: a version past the history's last that is not EDC_VQ_NO_TRUST";
+    return EDC_ERR_ARG;
+  }
+  return 0;
+}
+
 // the templated forms: checks, staging, tmpl_quorum_list with the join, the finish
-static int vq_run_tmpl(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out) {
+static int vq_run_tmpl(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out, const QuorumTrust* tr) {
   const size_t nc = rq->nc;
   TmplShape sh;
   size_t n;
@@ -5041,14 +5187,14 @@ static int vq_run_tmpl(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& 
     rc = commits_check_tmpl(ctx, rq->ts, nc, rq->commit_off, rq->commit_tpl, true, rq->alt_span, rq->item_alt, rq->vk,
                             rq->key_idx, rq->sig, rq->var, rq->var_off, &sh, &n);
   if (rc || (rc = quorum_check(ctx, nc, rq->commit_off, rq->threshold, rq->mode, &n)) ||
-      (rc = rq->commit_ver ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx)))
+      (rc = rq->commit_ver ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx)) || (rc = vq_trust_ready(ctx, nc, tr)))
     return rc;
   if (n && !rq->flag) { ctx->err = "null input"; return EDC_ERR_ARG; }
   CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc, rq->commit_ver != nullptr))) return rc;
+  if ((rc = valset_room(ctx, n, nc, rq->commit_ver != nullptr, tr != nullptr))) return rc;
   hipStream_t st = ctx->st();
   TmplQuorumItems it{rq->vk, rq->sig, rq->item_alt, rq->var, rq->var_off, rq->var_bytes, ctx->q_power, ctx->q_flag};
-  QuorumJoin jn{rq->vk, nullptr, rq->flag, rq->commit_ver, nullptr, {}};
+  QuorumJoin jn{rq->vk, nullptr, rq->flag, rq->commit_ver, nullptr, {}, tr};
   if (!rq->device) {
     if ((rc = ensure_n(ctx, n))) return rc;
     it = TmplQuorumItems{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->q_power, ctx->q_flag};
@@ -5067,29 +5213,31 @@ static int vq_run_tmpl(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& 
                              rq->mode, &list, &jn)))
     return rc;
   return tmpl_quorum_done(ctx, rq->cached ? cached_tmpl_finish(ctx, nc, rq->threshold, n, list, it.power, it.flag,
-                                                               rq->z_seed, out, ctx->vs_hdv)
+                                                               rq->z_seed, out, ctx->vs_hdv, tr)
                                           : quorum_finish(ctx, nc, rq->threshold, n, list, it.power, it.flag, rq->z_seed,
-                                                          out, nullptr, ctx->vs_hdv));
+                                                          out, nullptr, ctx->vs_hdv, tr));
 }
 
 // the forms on messages or k: the checks and staging of valset_verify_*_entry, then valset_run or
 // cached_quorum_run with the join; *hashed: the items SHA-512 runs over
-static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out, size_t* hashed) {
+static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out, const QuorumTrust* tr,
+                        size_t* hashed) {
   const size_t nc = rq->nc;
   const bool hist = rq->commit_ver != nullptr;
   size_t n;
   int rc = quorum_check(ctx, nc, rq->commit_off, rq->threshold, rq->mode, &n);
-  if (rc || (rc = hist ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx))) return rc;
+  if (rc || (rc = hist ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx)) || (rc = vq_trust_ready(ctx, nc, tr)))
+    return rc;
   if (n && (!rq->sig || !rq->flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
   ItemList all;
-  QuorumJoin jn{nullptr, nullptr, nullptr, rq->commit_ver, nullptr, {}};
+  QuorumJoin jn{nullptr, nullptr, nullptr, rq->commit_ver, nullptr, {}, tr};
   if (rq->device) {
     if (n && (!aligned16(rq->vk) || !aligned16(rq->sig) || (rq->k && !aligned16(rq->k)))) {
       ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
       return EDC_ERR_ARG;
     }
     CK(hipSetDevice(ctx->device));
-    if ((rc = valset_room(ctx, n, nc, hist))) return rc;
+    if ((rc = valset_room(ctx, n, nc, hist, tr != nullptr))) return rc;
     const uint32_t* k = reinterpret_cast<const uint32_t*>(rq->k);
     if (n && !k) {
       if ((rc = ensure_n(ctx, n))) return rc;
@@ -5104,7 +5252,7 @@ static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut&
     if (n && (rc = check_key_idx(ctx, rq->key_idx ? n : 0, rq->key_idx))) return rc;
     if (n && (rc = commits_check_msg_or_k(ctx, n, rq->msg, rq->msg_off, rq->k))) return rc;
     CK(hipSetDevice(ctx->device));
-    if ((rc = valset_room(ctx, n, nc, hist))) return rc;
+    if ((rc = valset_room(ctx, n, nc, hist, tr != nullptr))) return rc;
     hipStream_t st = ctx->st();
     if (rq->k) {
       if ((rc = ensure_n(ctx, n))) return rc;
@@ -5131,22 +5279,36 @@ static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut&
     return cached_quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->q_power, ctx->q_flag, rq->z_seed,
                              out, *hashed, &jn);
   return valset_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, jn.d_vk, jn.d_kidx, jn.d_flag, jn.host_k,
-                    rq->z_seed, out, rq->commit_ver);
+                    rq->z_seed, out, rq->commit_ver, tr);
 }
 
 extern "C" {
 
-int edc_vq_verify(edc_ctx* ctx, const edc_vq_request* rq, edc_vq_result* rs) {
+int edc_vq_verify(edc_ctx* ctx, const edc_vq_request* rq_in, edc_vq_result* rs_in) {
   size_t m = 0, miss = 0;
   QuorumOut out{nullptr, nullptr, nullptr, nullptr, &m, nullptr, nullptr};
-  if (rq && rs && rq->size == sizeof(edc_vq_request) && rs->size == sizeof(edc_vq_result))
+  // the caller's structures in today's layout: fields past an earlier sizeof read as NULL
+  edc_vq_request q;
+  edc_vq_result r;
+  memset(&q, 0, sizeof(q));
+  memset(&r, 0, sizeof(r));
+  const bool sizes_ok = vq_sizes_ok(rq_in, rs_in);
+  if (sizes_ok) {
+    memcpy(&q, rq_in, rq_in->size);
+    memcpy(&r, rs_in, rs_in->size);
+  }
+  const edc_vq_request* rq = rq_in ? &q : nullptr;
+  const edc_vq_result* rs = rs_in ? &r : nullptr;
+  const QuorumTrust trust{q.trust_ver, q.trust_threshold, r.trust_verdicts, r.trust_tally, r.n_bad_trust};
+  const QuorumTrust* tr = q.trust_ver ? &trust : nullptr;
+  if (sizes_ok)
     out = QuorumOut{rs->commit_verdicts, rs->item_verdicts, rs->tally, rs->n_bad_commits,
                     rs->n_checked ? rs->n_checked : &m, rq->cached ? (rs->n_miss ? rs->n_miss : &miss) : nullptr,
                     rs->check8};
   int rc;
-  if (vq_entry_done(ctx, rq, rs, out, &rc)) return rc;
+  if (vq_entry_done(ctx, sizes_ok, rq, rs, out, tr, &rc)) return rc;
   size_t hashed = 0;
-  rc = rq->ts ? vq_run_tmpl(ctx, rq, out) : vq_run_plain(ctx, rq, out, &hashed);
+  rc = rq->ts ? vq_run_tmpl(ctx, rq, out, tr) : vq_run_plain(ctx, rq, out, tr, &hashed);
   if (rc < 0) return rc;
   // the debug record, from the records of the stages that ran
   const uint64_t n = rq->commit_off[rq->nc];
@@ -5166,6 +5328,118 @@ int edc_vq_verify(edc_ctx* ctx, const edc_vq_request* rq, edc_vq_result* rs) {
 int edc_debug_vq_last(const edc_ctx* ctx, uint64_t out[8]) {
   if (!ctx || !out || !ctx->vq_have) return EDC_ERR_ARG;
   memcpy(out, ctx->vq_last, sizeof(ctx->vq_last));
+  return EDC_OK;
+}
+
+int edc_debug_vq_trust_last(const edc_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out || !ctx->vqt_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->vqt_last, sizeof(ctx->vqt_last));
+  return EDC_OK;
+}
+
+// edc_vhist_resolve's body with the trusting side: the paired join, both selections, the union and
+// both double-vote scans, as the request runs them, and each side's arrays read back.
+int edc_vq_trust_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                         const uint32_t* trust_ver, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
+                         const uint64_t* threshold, const uint64_t* trust_threshold, int mode, uint32_t* pos, uint64_t* power,
+                         uint8_t* flag_out, uint8_t* checked, uint64_t* planned, uint8_t* dv, uint32_t* trust_pos,
+                         uint64_t* trust_power, uint8_t* trust_flag_out, uint8_t* trust_checked, uint64_t* trust_planned,
+                         uint8_t* trust_dv, uint8_t* side, size_t* n_checked) {
+  if (!ctx) return EDC_ERR_ARG;
+  if (!nc) {
+    if (n_checked) *n_checked = 0;
+    return EDC_OK;
+  }
+  if (vhist_ver_missing(ctx, true, commit_ver)) return EDC_ERR_ARG;
+  if (!trust_ver || !trust_threshold) { ctx->err = "null trust_ver / trust_threshold"; return EDC_ERR_ARG; }
+  const QuorumTrust tr{trust_ver, trust_threshold, nullptr, nullptr, nullptr};
+  size_t n, m = 0;
+  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, commit_ver);
+  if (rc || (rc = vq_trust_ready(ctx, nc, &tr))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = valset_room(ctx, n, nc, true, true)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
+  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx,
+                          ctx->vs_flag, nullptr, &m, commit_ver, &tr)))
+    return rc;
+  hipStream_t st = ctx->st();
+  std::vector<uint32_t> who(pos ? n : 0), who_b(trust_pos ? n : 0);
+  auto back = [&](void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  CK(back(who.data(), ctx->vs_who, who.size() * sizeof(uint32_t)));
+  CK(back(who_b.data(), ctx->tr_who, who_b.size() * sizeof(uint32_t)));
+  CK(back(power, ctx->q_power, n * sizeof(uint64_t)));
+  CK(back(trust_power, ctx->tr_power, n * sizeof(uint64_t)));
+  CK(back(flag_out, ctx->q_flag, n));
+  CK(back(trust_flag_out, ctx->tr_flag, n));
+  CK(back(planned, ctx->q_planned, nc * sizeof(uint64_t)));
+  CK(back(trust_planned, ctx->tr_planned, nc * sizeof(uint64_t)));
+  CK(back(checked, ctx->tr_skip_a, n));
+  CK(back(trust_checked, ctx->tr_skip_b, n));
+  CK(back(side, ctx->tr_side, n));
+  CK(hipStreamSynchronize(st));
+  for (size_t i = 0; i < who.size(); ++i) pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : ctx->vh_posh[who[i]];
+  for (size_t i = 0; i < who_b.size(); ++i) trust_pos[i] = who_b[i] == KC_EMPTY ? VALSET_NO_POS : ctx->vh_posh[who_b[i]];
+  for (size_t i = 0; i < n; ++i) {      // the kernels write skip bytes
+    if (checked) checked[i] = checked[i] ? 0 : 1;
+    if (trust_checked) trust_checked[i] = trust_checked[i] ? 0 : 1;
+  }
+  if (dv) memcpy(dv, ctx->vs_hdv, nc);
+  if (trust_dv) memcpy(trust_dv, ctx->tr_hdv, nc);
+  if (n_checked) *n_checked = m;
+  return EDC_OK;
+}
+
+// Mean times of the paired stages over reps runs on host keys and flags, as edc_debug_vhist_select
+// times one side's: ms[0] the paired join, ms[1] both selections, the union and the scan of its tile
+// counts, ms[2] both double-vote scans with the clearing of their sets.
+int edc_debug_vq_trust_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                              const uint32_t* trust_ver, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
+                              const uint64_t* threshold, const uint64_t* trust_threshold, int mode, int reps, float ms[3]) {
+  if (!ctx || reps < 1) return EDC_ERR_ARG;
+  if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+  size_t n = 0;
+  int rc = edc_vq_trust_resolve(ctx, nc, commit_off, commit_ver, trust_ver, vk, key_idx, flag, threshold, trust_threshold, mode,
+                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, nullptr, nullptr, nullptr);
+  if (rc || !nc || !(n = commit_off[nc])) return rc;
+  hipStream_t st = ctx->st();
+  const uint8_t* d_vk = key_idx ? nullptr : ctx->vk.get();
+  const uint32_t N = (uint32_t)n, NC = (uint32_t)nc, nwg = (uint32_t)quorum_tiles(n);
+  Event e[4];
+  for (Event& x : e) CK(x.create());
+  CK(hipEventRecord(e[0], st));
+  for (int r = 0; r < reps; ++r)        // every stage rewrites the values the resolve call left
+    launch_vhist_resolve2(st, N, NC, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, ctx->tr_ver, d_vk, ctx->vs_kidx,
+                          ctx->kc_reg, ctx->vs_flag, ctx->q_power, ctx->q_flag, ctx->vs_who, ctx->tr_power, ctx->tr_flag,
+                          ctx->tr_who);
+  CK(hipEventRecord(e[1], st));
+  for (int r = 0; r < reps; ++r) {
+    launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, ctx->q_power, ctx->q_flag, ctx->q_cidx,
+                         ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->tr_skip_a, ctx->sc_wg, ctx->q_planned, ctx->q_err);
+    CK(hipMemsetAsync(ctx->tr_cnt, 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t), st));
+    launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->tr_thr, ctx->tr_power, ctx->tr_flag, ctx->q_cidx,
+                         ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->tr_skip_b, ctx->sc_wg, ctx->tr_planned, ctx->q_err, true);
+    launch_quorum_union(st, N, ctx->tr_skip_a, ctx->tr_skip_b, ctx->sc_hit, ctx->tr_side, ctx->sc_wg, ctx->tr_cnt);
+    launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
+  }
+  CK(hipEventRecord(e[2], st));
+  for (int r = 0; r < reps; ++r) {
+    CK(hipMemsetAsync(ctx->vs_dv, 0, nc, st));
+    CK(hipMemsetAsync(ctx->vs_set, 0, 2 * n * sizeof(uint64_t), st));
+    launch_valset_pairs(st, N, ctx->q_coff, ctx->q_cidx, ctx->tr_skip_a, ctx->vs_who, ctx->vs_set, ctx->vs_dv);
+    CK(hipMemsetAsync(ctx->tr_dv, 0, nc, st));
+    CK(hipMemsetAsync(ctx->tr_set, 0, 2 * n * sizeof(uint64_t), st));
+    launch_valset_pairs(st, N, ctx->q_coff, ctx->q_cidx, ctx->tr_skip_b, ctx->tr_who, ctx->tr_set, ctx->tr_dv);
+  }
+  CK(hipGetLastError());
+  CK(hipEventRecord(e[3], st));
+  CK(hipEventSynchronize(e[3]));
+  for (int j = 0; j < 3 && ms; ++j) {
+    float t = 0.f;
+    CK(hipEventElapsedTime(&t, e[j], e[j + 1]));
+    ms[j] = t / (float)reps;
+  }
   return EDC_OK;
 }
 

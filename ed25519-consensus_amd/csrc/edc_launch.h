@@ -119,7 +119,20 @@ size_t quorum_tiles(size_t n);
 void launch_quorum_select(hipStream_t st, uint32_t n, uint32_t nc, int light, const uint32_t* commit_off,
                           const uint64_t* threshold, const uint64_t* power, const uint8_t* flag, uint32_t* cidx,
                           uint64_t* agg_v, uint32_t* agg_f, uint64_t* carry, uint8_t* skip, uint32_t* wg_checked,
-                          uint64_t* planned, int* err);
+                          uint64_t* planned, int* err, bool have_cidx = false);
+// trusting pairs (edc_vq_verify with trust_ver): launch_quorum_select runs once per side, the second
+// time with have_cidx (cidx is read, not searched for again), each into its own skip bytes and
+// planned[]. launch_quorum_union then writes what the back-ends read of ONE selection: skip[i] = 1
+// iff neither side checks item i, wg_checked[t] = tile t's union count (for launch_sc_scan),
+// side[i] = bit 0 checked by A | bit 1 checked by B, and adds the totals {A, B, both} to one of
+// QR_UNION_SLOTS triples of counts (3 * QR_UNION_SLOTS words, zeroed by the caller, who sums them). launch_quorum_tally2 is launch_quorum_tally for both sides in one pass:
+// side s counts item i iff bit s of side[i] is set, with its own power and flag.
+constexpr uint32_t QR_UNION_SLOTS = 64;
+void launch_quorum_union(hipStream_t st, uint32_t n, const uint8_t* skip_a, const uint8_t* skip_b, uint8_t* skip,
+                         uint8_t* side, uint32_t* wg_checked, uint32_t* counts);
+void launch_quorum_tally2(hipStream_t st, uint32_t n, const uint32_t* cidx, const uint8_t* side, const uint64_t* power_a,
+                          const uint8_t* flag_a, const uint64_t* power_b, const uint8_t* flag_b, const uint8_t* code,
+                          uint64_t* tally_a, uint32_t* cor_a, uint64_t* tally_b, uint32_t* cor_b);
 // after a failed union: code[i] = item i's code, 255 where it was not checked. tally[c] += power of
 // the checked flag-1 items with code 0, cor[c] |= the checked items' codes (both zeroed by the caller)
 void launch_quorum_tally(hipStream_t st, uint32_t n, const uint32_t* cidx, const uint64_t* power, const uint8_t* flag,
@@ -176,6 +189,14 @@ void launch_vhist_resolve(hipStream_t st, uint32_t n, uint32_t nc, const KeyCach
                           const uint32_t* commit_off, const uint32_t* commit_ver, const uint8_t* vk,
                           const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag, uint64_t* power,
                           uint8_t* flag_out, uint32_t* who);
+// launch_vhist_resolve for a trusting pair: item i judged at commit_ver[c] (side A) and at
+// trust_ver[c] (side B; VQ_NO_TRUST: no member on that side), with one signer lookup, one commit
+// search and one read of the list bounds for both.
+void launch_vhist_resolve2(hipStream_t st, uint32_t n, uint32_t nc, const KeyCacheView& kc, const VhistView& vh,
+                           const uint32_t* commit_off, const uint32_t* commit_ver, const uint32_t* trust_ver,
+                           const uint8_t* vk, const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag,
+                           uint64_t* power_a, uint8_t* flag_a, uint32_t* who_a, uint64_t* power_b, uint8_t* flag_b,
+                           uint32_t* who_b);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

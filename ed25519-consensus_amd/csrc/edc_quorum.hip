@@ -103,6 +103,9 @@ __device__ __forceinline__ void item_element(const uint32_t* __restrict__ commit
   x = flag[i] == QUORUM_COMMIT ? power[i] : 0;
 }
 
+// HAVE_CIDX: a second selection over the same commits (the trusting side of a paired request)
+// reads the commit indices the first one wrote instead of searching for them again
+template <bool HAVE_CIDX>
 __global__ void __launch_bounds__(QR_TILE) k_q_tile(uint32_t n, uint32_t nc, const uint32_t* __restrict__ commit_off,
                                                     const uint64_t* __restrict__ power,
                                                     const uint8_t* __restrict__ flag, uint32_t* __restrict__ cidx,
@@ -112,14 +115,18 @@ __global__ void __launch_bounds__(QR_TILE) k_q_tile(uint32_t n, uint32_t nc, con
   __shared__ uint32_t wf[QR_WAVES];
   // the workgroup's items [g0, g1]: their commits bound every lane's search
   const uint32_t g0 = blockIdx.x * QR_TILE;
-  const uint32_t g1 = (n - g0 < QR_TILE ? n : g0 + QR_TILE) - 1;
-  const uint32_t clo = commit_of(commit_off, 0, nc - 1, g0), chi = commit_of(commit_off, clo, nc - 1, g1);
+  uint32_t clo = 0, chi = 0;
+  if (!HAVE_CIDX) {
+    const uint32_t g1 = (n - g0 < QR_TILE ? n : g0 + QR_TILE) - 1;
+    clo = commit_of(commit_off, 0, nc - 1, g0);
+    chi = commit_of(commit_off, clo, nc - 1, g1);
+  }
   const uint32_t i = g0 + threadIdx.x;
   uint32_t f = 0;
   uint64_t v = 0;
   if (i < n) {
-    const uint32_t c = commit_of(commit_off, clo, chi, i);
-    cidx[i] = c;
+    const uint32_t c = HAVE_CIDX ? cidx[i] : commit_of(commit_off, clo, chi, i);
+    if (!HAVE_CIDX) cidx[i] = c;
     item_element(commit_off, power, flag, i, c, f, v);
     if (flag[i] > QUORUM_NIL || power[i] > QUORUM_MAX_POWER) *err = 1;
   }
@@ -216,6 +223,75 @@ __global__ void __launch_bounds__(QR_TILE) k_q_tally(uint32_t n, const uint32_t*
   const uint32_t c = cidx[i];
   if (v) atomicOr(&cor[c], (uint32_t)v);
   else if (flag[i] == QUORUM_COMMIT && power[i]) atomicAdd(&tally[c], (unsigned long long)power[i]);
+}
+
+// Trusting pairs (edc_vq_verify with trust_ver): one commit set judged by two sets at once. Each
+// side runs the selection above on its own power / flag and leaves its own skip bytes and planned[].
+//   k_q_union    per tile, behind both: skip[i] = 1 iff neither side checks item i, side[i] = bit 0
+//                checked by A | bit 1 checked by B, the tile's count of union items where
+//                k_sc_scan / k_sc_compact read the count of a single selection, and the totals
+//                {A, B, both} by one integer atomic add per tile and total (order-independent),
+//                spread over QR_UNION_SLOTS triples of words that the host sums, because
+//                thousands of tiles adding to the same three words serialize on them
+//   k_q_tally2   k_q_tally for both sides in one pass over the union's codes: side s counts item i
+//                iff bit s of side[i] is set, with its own power and flag, into its own tally / cor
+__global__ void __launch_bounds__(QR_TILE) k_q_union(uint32_t n, const uint8_t* __restrict__ skip_a,
+                                                     const uint8_t* __restrict__ skip_b, uint8_t* __restrict__ skip,
+                                                     uint8_t* __restrict__ side, uint32_t* __restrict__ wg_checked,
+                                                     uint32_t* __restrict__ counts) {
+  __shared__ uint32_t wa[QR_WAVES], wb[QR_WAVES], wab[QR_WAVES];
+  const uint32_t i = blockIdx.x * QR_TILE + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool a = i < n && skip_a[i] == 0, b = i < n && skip_b[i] == 0;
+  if (i < n) {
+    skip[i] = (a || b) ? 0 : 1;
+    side[i] = (uint8_t)((a ? 1 : 0) | (b ? 2 : 0));
+  }
+  const uint64_t ba = __ballot(a), bb = __ballot(b);
+  if (lane == 0) {
+    wa[wave] = (uint32_t)__popcll(ba);
+    wb[wave] = (uint32_t)__popcll(bb);
+    wab[wave] = (uint32_t)__popcll(ba & bb);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t sa = 0, sb = 0, sab = 0;
+    for (uint32_t w = 0; w < QR_WAVES; ++w) {
+      sa += wa[w];
+      sb += wb[w];
+      sab += wab[w];
+    }
+    wg_checked[blockIdx.x] = sa + sb - sab;
+    uint32_t* slot = counts + 3 * (blockIdx.x % QR_UNION_SLOTS);
+    if (sa) atomicAdd(&slot[0], sa);
+    if (sb) atomicAdd(&slot[1], sb);
+    if (sab) atomicAdd(&slot[2], sab);
+  }
+}
+
+__global__ void __launch_bounds__(QR_TILE) k_q_tally2(uint32_t n, const uint32_t* __restrict__ cidx,
+                                                      const uint8_t* __restrict__ side,
+                                                      const uint64_t* __restrict__ power_a,
+                                                      const uint8_t* __restrict__ flag_a,
+                                                      const uint64_t* __restrict__ power_b,
+                                                      const uint8_t* __restrict__ flag_b,
+                                                      const uint8_t* __restrict__ code,
+                                                      unsigned long long* __restrict__ tally_a, uint32_t* __restrict__ cor_a,
+                                                      unsigned long long* __restrict__ tally_b, uint32_t* __restrict__ cor_b) {
+  const uint32_t i = blockIdx.x * QR_TILE + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t v = code[i];
+  if (v == QUORUM_NOT_CHECKED) return;
+  const uint32_t c = cidx[i];
+  const uint8_t sd = side[i];
+  if (sd & 1) {
+    if (v) atomicOr(&cor_a[c], (uint32_t)v);
+    else if (flag_a[i] == QUORUM_COMMIT && power_a[i]) atomicAdd(&tally_a[c], (unsigned long long)power_a[i]);
+  }
+  if (sd & 2) {
+    if (v) atomicOr(&cor_b[c], (uint32_t)v);
+    else if (flag_b[i] == QUORUM_COMMIT && power_b[i]) atomicAdd(&tally_b[c], (unsigned long long)power_b[i]);
+  }
 }
 
 // Templated quorum commit sets (edc_tmpl_quorum_*): the selection runs first, and only the checked
@@ -358,6 +434,10 @@ __global__ void __launch_bounds__(QR_TILE) k_tq_gather(uint32_t n, uint32_t m, c
 // Of two lanes with the same pair exactly one wins the empty slot and the other then finds it there
 // (nothing is ever removed and both walk the same slots), so dv[c] = 1 iff some pair occurs twice,
 // whatever the order of the lanes; the stores to dv[c] all write 1.
+// A trusting pair runs the scan once per side, each with that side's skip bytes, its who[] and a set
+// and dv[] of its own: every launch sees one set in which commit c owns [2 off[c], 2 off[c+1]) and
+// inserts at most one pair per item of c, so the argument holds per side as it stands: a probe never
+// leaves the commit's span and never meets a full span.
 // the cache index of item i's signer: by its key bytes (KC_EMPTY for a key the cache does not hold)
 // or, with vk null, by its position in the registered list
 __device__ __forceinline__ uint32_t signer_index(const KeyCacheView& kc, const uint8_t* __restrict__ vk,
@@ -387,6 +467,19 @@ __global__ void __launch_bounds__(QR_TILE) k_vs_resolve(uint32_t n, KeyCacheView
   who[i] = member ? c : KC_EMPTY;
 }
 
+// the power of the change list [lo, end) at version v: its last entry with ver <= v (ver[lo] = 0 <= v,
+// so a list of one entry is not searched); VHIST_NOT_MEMBER for an empty list
+__device__ __forceinline__ uint64_t vh_power_at(const VhistView& vh, uint32_t lo, uint32_t end, uint32_t v) {
+  if (lo >= end) return VHIST_NOT_MEMBER;
+  uint32_t hi = end - 1;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+    if (vh.ver[mid] <= v) lo = mid;
+    else hi = mid - 1;
+  }
+  return vh.pow[lo];
+}
+
 // Validator-set history (vhist.h; edc_vhist_*): the join of k_vs_resolve with every commit judged
 // by the set of its own version. One lane per item, in front of the selection: the signer's cache
 // index as above; the item's commit by the search k_q_tile makes, bounded by the commits of the
@@ -413,24 +506,52 @@ __global__ void __launch_bounds__(QR_TILE) k_vh_resolve(uint32_t n, uint32_t nc,
   const uint32_t s = signer_index(kc, vk, key_idx, reg, i);
   const uint32_t v = commit_ver[commit_of(commit_off, clo, chi, i)];
   uint64_t pw = VHIST_NOT_MEMBER;
-  if (s < vh.count) {
-    uint32_t lo = vh.off[s];
-    const uint32_t end = vh.off[s + 1];
-    if (lo < end) {
-      uint32_t hi = end - 1;              // ver[lo] = 0 <= v
-      while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo + 1) >> 1);
-        if (vh.ver[mid] <= v) lo = mid;
-        else hi = mid - 1;
-      }
-      pw = vh.pow[lo];
-    }
-  }
+  if (s < vh.count) pw = vh_power_at(vh, vh.off[s], vh.off[s + 1], v);
   const bool member = pw != VHIST_NOT_MEMBER;
   const uint8_t fl = flag[i];
   power[i] = member ? pw : 0;
   flag_out[i] = (member || fl > QUORUM_NIL) ? fl : QUORUM_ABSENT;
   who[i] = member ? s : KC_EMPTY;
+}
+
+// Trusting pairs: k_vh_resolve for two versions of one commit. One signer lookup and one commit
+// search per vote, one read of the signer's list bounds, then two searches of that same list, for
+// commit_ver[c] (side A) and trust_ver[c] (side B); VQ_NO_TRUST makes the signer no member on side
+// B without a search. Each side gets the three arrays k_vh_resolve writes. A flag above 2 is passed
+// through on both sides, so the selection's check raises it on whichever runs.
+__global__ void __launch_bounds__(QR_TILE) k_vh_resolve2(uint32_t n, uint32_t nc, KeyCacheView kc, VhistView vh,
+                                                         const uint32_t* __restrict__ commit_off,
+                                                         const uint32_t* __restrict__ commit_ver,
+                                                         const uint32_t* __restrict__ trust_ver,
+                                                         const uint8_t* __restrict__ vk,
+                                                         const uint32_t* __restrict__ key_idx,
+                                                         const uint32_t* __restrict__ reg,
+                                                         const uint8_t* __restrict__ flag, uint64_t* __restrict__ power_a,
+                                                         uint8_t* __restrict__ flag_a, uint32_t* __restrict__ who_a,
+                                                         uint64_t* __restrict__ power_b, uint8_t* __restrict__ flag_b,
+                                                         uint32_t* __restrict__ who_b) {
+  const uint32_t g0 = blockIdx.x * QR_TILE;
+  const uint32_t g1 = (n - g0 < QR_TILE ? n : g0 + QR_TILE) - 1;
+  const uint32_t clo = commit_of(commit_off, 0, nc - 1, g0), chi = commit_of(commit_off, clo, nc - 1, g1);
+  const uint32_t i = g0 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = signer_index(kc, vk, key_idx, reg, i);
+  const uint32_t c = commit_of(commit_off, clo, chi, i);
+  const uint32_t va = commit_ver[c], vb = trust_ver[c];
+  uint64_t pa = VHIST_NOT_MEMBER, pb = VHIST_NOT_MEMBER;
+  if (s < vh.count) {
+    const uint32_t lo = vh.off[s], end = vh.off[s + 1];
+    pa = vh_power_at(vh, lo, end, va);
+    if (vb != VQ_NO_TRUST) pb = vh_power_at(vh, lo, end, vb);
+  }
+  const bool ma = pa != VHIST_NOT_MEMBER, mb = pb != VHIST_NOT_MEMBER;
+  const uint8_t fl = flag[i];
+  power_a[i] = ma ? pa : 0;
+  flag_a[i] = (ma || fl > QUORUM_NIL) ? fl : QUORUM_ABSENT;
+  who_a[i] = ma ? s : KC_EMPTY;
+  power_b[i] = mb ? pb : 0;
+  flag_b[i] = (mb || fl > QUORUM_NIL) ? fl : QUORUM_ABSENT;
+  who_b[i] = mb ? s : KC_EMPTY;
 }
 
 __global__ void __launch_bounds__(QR_TILE) k_vs_pairs(uint32_t n, const uint32_t* __restrict__ commit_off,
@@ -482,10 +603,15 @@ void launch_tmpl_quorum_gather(hipStream_t st, uint32_t n, uint32_t m, const uin
 void launch_quorum_select(hipStream_t st, uint32_t n, uint32_t nc, int light, const uint32_t* commit_off,
                           const uint64_t* threshold, const uint64_t* power, const uint8_t* flag, uint32_t* cidx,
                           uint64_t* agg_v, uint32_t* agg_f, uint64_t* carry, uint8_t* skip, uint32_t* wg_checked,
-                          uint64_t* planned, int* err) {
+                          uint64_t* planned, int* err, bool have_cidx) {
   if (!n || !nc) return;
   const uint32_t nt = (uint32_t)quorum_tiles(n);
-  hipLaunchKernelGGL(k_q_tile, dim3(nt), dim3(QR_TILE), 0, st, n, nc, commit_off, power, flag, cidx, agg_v, agg_f, err);
+  if (have_cidx)
+    hipLaunchKernelGGL(k_q_tile<true>, dim3(nt), dim3(QR_TILE), 0, st, n, nc, commit_off, power, flag, cidx, agg_v, agg_f,
+                       err);
+  else
+    hipLaunchKernelGGL(k_q_tile<false>, dim3(nt), dim3(QR_TILE), 0, st, n, nc, commit_off, power, flag, cidx, agg_v, agg_f,
+                       err);
   hipLaunchKernelGGL(k_q_carry, dim3(1), dim3(QR_CARRY_TILE), 0, st, nt, agg_v, agg_f, carry);
   hipLaunchKernelGGL(k_q_select, dim3(nt), dim3(QR_TILE), 0, st, n, light, commit_off, threshold, power, flag, cidx,
                      carry, skip, wg_checked, reinterpret_cast<unsigned long long*>(planned), err);
@@ -496,6 +622,32 @@ void launch_quorum_tally(hipStream_t st, uint32_t n, const uint32_t* cidx, const
   if (!n) return;
   hipLaunchKernelGGL(k_q_tally, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, cidx, power, flag, code,
                      reinterpret_cast<unsigned long long*>(tally), cor);
+}
+
+void launch_quorum_union(hipStream_t st, uint32_t n, const uint8_t* skip_a, const uint8_t* skip_b, uint8_t* skip,
+                         uint8_t* side, uint32_t* wg_checked, uint32_t* counts) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_q_union, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, skip_a, skip_b, skip, side,
+                     wg_checked, counts);
+}
+
+void launch_quorum_tally2(hipStream_t st, uint32_t n, const uint32_t* cidx, const uint8_t* side, const uint64_t* power_a,
+                          const uint8_t* flag_a, const uint64_t* power_b, const uint8_t* flag_b, const uint8_t* code,
+                          uint64_t* tally_a, uint32_t* cor_a, uint64_t* tally_b, uint32_t* cor_b) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_q_tally2, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, cidx, side, power_a, flag_a,
+                     power_b, flag_b, code, reinterpret_cast<unsigned long long*>(tally_a), cor_a,
+                     reinterpret_cast<unsigned long long*>(tally_b), cor_b);
+}
+
+void launch_vhist_resolve2(hipStream_t st, uint32_t n, uint32_t nc, const KeyCacheView& kc, const VhistView& vh,
+                           const uint32_t* commit_off, const uint32_t* commit_ver, const uint32_t* trust_ver,
+                           const uint8_t* vk, const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag,
+                           uint64_t* power_a, uint8_t* flag_a, uint32_t* who_a, uint64_t* power_b, uint8_t* flag_b,
+                           uint32_t* who_b) {
+  if (!n || !nc) return;
+  hipLaunchKernelGGL(k_vh_resolve2, dim3((uint32_t)quorum_tiles(n)), dim3(QR_TILE), 0, st, n, nc, kc, vh, commit_off,
+                     commit_ver, trust_ver, vk, key_idx, reg, flag, power_a, flag_a, who_a, power_b, flag_b, who_b);
 }
 
 void launch_valset_resolve(hipStream_t st, uint32_t n, const KeyCacheView& kc, const ValsetView& vs, const uint8_t* vk,

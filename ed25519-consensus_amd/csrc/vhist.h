@@ -116,4 +116,87 @@ inline uint64_t vhist_power_at(const VHist& h, uint32_t p, uint32_t v) {
   return h.pow[lo];
 }
 
+// Trusting pairs (edc_vq_verify with trust_ver, include/edc.h): one commit set judged by two sets at
+// once, side A at commit_ver[c] and side B at trust_ver[c]. VQ_NO_TRUST as trust_ver[c] gives commit
+// c side A only.
+constexpr uint32_t VQ_NO_TRUST = 0xFFFFFFFFu;        // EDC_VQ_NO_TRUST
+
+// every trust version is one of the history's or the sentinel
+inline bool vq_trust_check_versions(size_t nc, const uint32_t* trust_ver, uint32_t nv) {
+  for (size_t c = 0; c < nc; ++c)
+    if (trust_ver[c] > nv && trust_ver[c] != VQ_NO_TRUST) return false;
+  return true;
+}
+
+// The reference union of two selections over the same n items (checked_a / checked_b: what
+// quorum_select gives each side). side[i] (nullable) = bit 0 checked by A | bit 1 checked by B; a
+// vote is verified iff side[i] != 0. counts (nullable) = {A, B, both, union}. Returns the union's size.
+inline size_t vq_trust_union(size_t n, const uint8_t* checked_a, const uint8_t* checked_b, uint8_t* side,
+                             uint64_t counts[4]) {
+  uint64_t a = 0, b = 0, ab = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const bool ca = checked_a[i] != 0, cb = checked_b[i] != 0;
+    if (side) side[i] = (uint8_t)((ca ? 1 : 0) | (cb ? 2 : 0));
+    a += ca;
+    b += cb;
+    ab += ca && cb;
+  }
+  if (counts) {
+    counts[0] = a;
+    counts[1] = b;
+    counts[2] = ab;
+    counts[3] = a + b - ab;
+  }
+  return (size_t)(a + b - ab);
+}
+
+// quorum_tally for one side of a pair: the codes are the union's, and the side counts item i iff
+// bit `bit` (0: A, 1: B) of side[i] is set, with its own power and flag.
+inline void vq_trust_tally(size_t nc, const uint32_t* commit_off, const uint8_t* side, int bit, const uint64_t* power,
+                           const uint8_t* flag, const uint8_t* codes, uint64_t* tally, uint8_t* cor) {
+  for (size_t c = 0; c < nc; ++c) {
+    uint64_t t = 0;
+    uint8_t o = 0;
+    for (size_t i = commit_off[c]; i < commit_off[c + 1]; ++i) {
+      if (codes[i] == QUORUM_NOT_CHECKED || !((side[i] >> bit) & 1)) continue;
+      o |= codes[i];
+      if (flag[i] == QUORUM_COMMIT && codes[i] == 0) t += power[i];
+    }
+    tally[c] = t;
+    cor[c] = o;
+  }
+}
+
+// Side B's verdicts: per commit what quorum_reduce gives, EDC_DOUBLE_VOTE (4) where dv[c] != 0 (dv
+// null: none), and for a commit whose trust_ver[c] is VQ_NO_TRUST the verdict EDC_OK with tally[c]
+// set to 0, whatever the threshold. tally is in / out for that reason. commit_verdicts may be
+// null. *n_bad = commits that are not EDC_OK. Returns the side's code: 0, else 1 over 4 over 3.
+inline int vq_trust_reduce(size_t nc, const uint32_t* trust_ver, const uint8_t* cor, uint64_t* tally,
+                           const uint64_t* threshold, const uint8_t* dv, uint8_t* commit_verdicts, size_t* n_bad) {
+  size_t bad = 0, invalid = 0, twice = 0;
+  for (size_t c = 0; c < nc; ++c) {
+    uint8_t v;
+    if (trust_ver[c] == VQ_NO_TRUST) {
+      tally[c] = 0;
+      v = 0;
+    } else {
+      v = (cor && cor[c]) ? 1 : tally[c] <= threshold[c] ? QUORUM_SHORT : 0;
+      if (dv && dv[c]) v = 4;
+    }
+    bad += v != 0;
+    invalid += v == 1;
+    twice += v == 4;
+    if (commit_verdicts) commit_verdicts[c] = v;
+  }
+  if (n_bad) *n_bad = bad;
+  return invalid ? 1 : twice ? 4 : bad ? (int)QUORUM_SHORT : 0;
+}
+
+// the code of a pair from its sides' codes (each 0, 1, 3 or 4): 0 iff both are, else 1 over 4 over 3
+inline int vq_trust_code(int a, int b) {
+  if (a == 1 || b == 1) return 1;
+  if (a == 4 || b == 4) return 4;
+  return (a || b) ? (int)QUORUM_SHORT : 0;
+}
+
 }  // namespace edc

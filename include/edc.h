@@ -1437,7 +1437,9 @@ int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, 
  * :149-217), and its code is Item::verify_single's (src/batch.rs:104-107).
  *
  * Both structures begin with `size`, the caller's sizeof of the structure, so that fields can be
- * appended later; any other value is EDC_ERR_ARG. Reserved fields must be 0.
+ * appended later; a value that is neither today's sizeof nor the sizeof before the trusting pair's
+ * fields were appended (the structure up to and without trust_ver / trust_verdicts) is EDC_ERR_ARG.
+ * With the earlier sizeof the appended fields read as NULL. Reserved fields must be 0.
  *
  * edc_vq_request
  *   device      0: the per-item arrays (vk / key_idx, sig, flag, msg, msg_off, k, item_alt, var,
@@ -1496,8 +1498,62 @@ int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, 
  *   while a batch is pending there.
  * edc_debug_vq_last  test hook, a host copy (no device work): out = {n, n_checked, hits, n_miss,
  *   items SHA-512 ran over, records inserted, 0 (reserved), arena bytes} of the last request that
- *   returned a verdict; EDC_ERR_ARG before any.
+ *   returned a verdict; EDC_ERR_ARG before any. For a trusting pair n_checked is the union's.
+ *
+ * Trusting pairs: one commit judged by two sets at once. A light client that skips from a trusted
+ * height H to a later height H' asks two questions of the commit of H' (CometBFT's non-adjacent
+ * verification, named from memory): do the signers that the trusted set of H knows carry more than
+ * 1/3 of that set's power, and do the signers carry more than 2/3 of the commit's own set. A
+ * request answers both in one call and verifies every vote once.
+ *   trust_ver        (uint32_t, nc entries, host) NULL: no trusting side, the request runs exactly as
+ *                    described above. Needs commit_ver. Entry c is a version <= nv of the history, or
+ *                    EDC_VQ_NO_TRUST, which gives commit c side A only (an adjacent hop).
+ *   trust_threshold  (uint64_t, nc entries, host) given iff trust_ver is.
+ *   trust_verdicts (nc), trust_tally (nc), n_bad_trust  side B's commit_verdicts, tally and
+ *                    *n_bad_commits; nullable, not written when trust_ver is NULL.
+ * Let A be the same request without the trust fields and B the same request with
+ * commit_ver := trust_ver and threshold := trust_threshold; `mode` is shared.
+ *   Selection: side A's pos, power, flag_out, checked bytes, planned and dv are edc_vhist_resolve's
+ *     for A, side B's are edc_vhist_resolve's for B. A vote is verified iff either side checks it,
+ *     and *n_checked is the size of that union (in full mode: every signed vote of a member of
+ *     either set).
+ *   Verdicts: commit_verdicts, tally and *n_bad_commits equal request A's; trust_verdicts,
+ *     trust_tally and *n_bad_trust equal request B's. Each side's OR of codes, tally and
+ *     double-vote rule run over that side's checked votes and that side's members only, also when
+ *     the union batch fails: item codes are Item::verify_single's and depend on nothing else.
+ *   item_verdicts[i] is the code of vote i if either side checks it, else EDC_NOT_CHECKED; it equals
+ *     A's where A checks the vote and B's where B does.
+ *   check8, the verdict path and the z indices are bit-identical to
+ *     edc_batch_verify_prehashed_device on the union list in queue order with z_base = 0.
+ *   A commit whose trust_ver[c] is EDC_VQ_NO_TRUST: B checks none of its votes,
+ *     trust_verdicts[c] = EDC_OK, trust_tally[c] = 0, and it raises no B-side double vote.
+ *   Return value: EDC_OK iff every verdict of both arrays is EDC_OK; else 1 over 4 over 3, taken
+ *     over both arrays.
+ *   Templated: only the union is gathered, assembled and hashed, the arena is sized from the union
+ *     count, and every output equals the paired request on the materialised messages.
+ *   Cached: the lookup runs on the union, and a hit counts as verified for both sides. n_miss is the
+ *     number of union votes that are no live record; valid misses are inserted; commit-level outputs
+ *     equal the uncached paired request's. The selection and both double-vote scans never look at
+ *     the table.
+ *   No stream synchronization is added: both sides' double-vote bytes and the union's totals ride in
+ *     the selection's one read-back, both planned arrays in the copy that brings side A's, and the
+ *     cached templated form keeps its existing second read-back and nothing more.
+ *   Errors (EDC_ERR_ARG): trust_ver without commit_ver; trust_ver without trust_threshold or the
+ *     reverse; trust_ver[c] > nv other than the sentinel. The device checks of flags and of a
+ *     commit's counted power apply to each side (duplicates can push either past 2^63 - 1). On any
+ *     violation nothing is gathered, written, inserted or counted, and the context stays usable.
+ * edc_vq_trust_resolve  edc_vhist_resolve with trust_ver and trust_threshold: the paired join, both
+ *   selections, the union and both double-vote scans as the request runs them, on host keys and
+ *   flags without signatures. pos .. dv are side A's, trust_pos .. trust_dv side B's, side[i] =
+ *   bit 0 checked by A | bit 1 checked by B, *n_checked the union's size. All outputs nullable.
+ * edc_debug_vq_trust_last  test hook, a host copy: out = {checked by A, checked by B, checked by
+ *   both, union} of the last paired request that returned a verdict; EDC_ERR_ARG before any. Every
+ *   paired request pays for these totals: the union kernel adds them per tile (three integer
+ *   atomics spread over 64 slots), and 768 bytes come back in the selection's read-back.
+ * edc_debug_vq_trust_select  mean milliseconds over reps runs: ms[0] the paired join, ms[1] both
+ *   selections with the union and the scan of its tile counts, ms[2] both double-vote scans.
  */
+#define EDC_VQ_NO_TRUST 0xFFFFFFFFu
 typedef struct edc_vq_request {
   uint32_t size;               /* sizeof(edc_vq_request) */
   uint32_t device;
@@ -1523,6 +1579,8 @@ typedef struct edc_vq_request {
   const uint8_t* var;
   const uint32_t* var_off;
   size_t var_bytes;
+  const uint32_t* trust_ver;
+  const uint64_t* trust_threshold;
 } edc_vq_request;
 typedef struct edc_vq_result {
   uint32_t size;               /* sizeof(edc_vq_result) */
@@ -1534,9 +1592,22 @@ typedef struct edc_vq_result {
   size_t* n_checked;
   size_t* n_miss;
   uint8_t* check8;
+  uint8_t* trust_verdicts;
+  uint64_t* trust_tally;
+  int* n_bad_trust;
 } edc_vq_result;
 int edc_vq_verify(edc_ctx* ctx, const edc_vq_request* rq, edc_vq_result* rs);
 int edc_debug_vq_last(const edc_ctx* ctx, uint64_t out[8]);
+int edc_vq_trust_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                         const uint32_t* trust_ver, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
+                         const uint64_t* threshold, const uint64_t* trust_threshold, int mode, uint32_t* pos, uint64_t* power,
+                         uint8_t* flag_out, uint8_t* checked, uint64_t* planned, uint8_t* dv, uint32_t* trust_pos,
+                         uint64_t* trust_power, uint8_t* trust_flag_out, uint8_t* trust_checked, uint64_t* trust_planned,
+                         uint8_t* trust_dv, uint8_t* side, size_t* n_checked);
+int edc_debug_vq_trust_last(const edc_ctx* ctx, uint64_t out[4]);
+int edc_debug_vq_trust_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
+                              const uint32_t* trust_ver, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
+                              const uint64_t* threshold, const uint64_t* trust_threshold, int mode, int reps, float ms[3]);
 
 /*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
