@@ -1044,24 +1044,40 @@ class Engine:
         (NO_POS for a signer that is no member), power, flag, checked, planned, n_checked, dv."""
         return self._valset_resolve(self.lib.edc_valset_resolve, commit_off, None, flags, thresholds, light, vks, key_idx)
 
-    def _valset_resolve(self, fn, commit_off, versions, flags, thresholds, light, vks, key_idx):
-        """fn: edc_valset_resolve (versions None) or edc_vhist_resolve, which takes them behind the offsets"""
+    def _valset_args(self, commit_off, versions, flags, thresholds, vks, key_idx, trust_versions=None,
+                     trust_thresholds=None):
+        """(nc, n, the arguments the resolve entries and the timing hooks take between nc and mode):
+        the offsets, the commits' versions (None: the one set; a pair's trust versions behind them),
+        the keys, the flags and the thresholds (a pair's trust thresholds behind them)."""
         nc, off = self._commit_offsets(commit_off)
         n = off[nc] if nc else 0
-        ver = () if versions is None else (self._vhist_versions_arg(nc, versions),)
+        ver = [self._vhist_versions_arg(nc, v) for v in (versions, trust_versions) if v is not None]
         vkb, idx = _tmpl_keys(n, vks, key_idx)
-        fl, th = self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds)
-        pos, power = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))()
-        flag_out, checked = ctypes.create_string_buffer(max(n, 1)), ctypes.create_string_buffer(max(n, 1))
-        planned, dv = (ctypes.c_uint64 * max(nc, 1))(), ctypes.create_string_buffer(max(nc, 1))
+        fl = self._valset_flags(n, flags)
+        th = [self._quorum_thresholds(nc, t) for t in (thresholds, trust_thresholds) if t is not None]
+        return nc, n, (off, *ver, vkb, idx, fl, *th)
+
+    @staticmethod
+    def _valset_side(nc, n):
+        """One side's outputs of a resolve entry (pos, power, flag_out, checked, planned, dv) and the
+        function that turns them into that side's dict after the call."""
+        o = ((ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))(), ctypes.create_string_buffer(max(n, 1)),
+             ctypes.create_string_buffer(max(n, 1)), (ctypes.c_uint64 * max(nc, 1))(), ctypes.create_string_buffer(max(nc, 1)))
+
+        def result():
+            return {"pos": list(o[0][:n]), "power": list(o[1][:n]), "flag": list(o[2].raw[:n]),
+                    "checked": list(o[3].raw[:n]), "planned": list(o[4][:nc]), "dv": list(o[5].raw[:nc])}
+        return o, result
+
+    def _valset_resolve(self, fn, commit_off, versions, flags, thresholds, light, vks, key_idx):
+        """fn: edc_valset_resolve (versions None) or edc_vhist_resolve, which takes them behind the offsets"""
+        nc, n, args = self._valset_args(commit_off, versions, flags, thresholds, vks, key_idx)
+        o, result = self._valset_side(nc, n)
         cnt = ctypes.c_size_t(0)
         with self._lock:
-            rc = fn(self.ctx, nc, off, *ver, vkb, idx, fl, th, int(bool(light)), pos, power, flag_out, checked, planned,
-                    ctypes.byref(cnt), dv)
+            rc = fn(self.ctx, nc, *args, int(bool(light)), *o[:5], ctypes.byref(cnt), o[5])
         self._check(rc)
-        return {"pos": list(pos[:n]), "power": list(power[:n]), "flag": list(flag_out.raw[:n]),
-                "checked": list(checked.raw[:n]), "planned": list(planned[:nc]), "n_checked": cnt.value,
-                "dv": list(dv.raw[:nc])}
+        return dict(result(), n_checked=cnt.value)
 
     def quorum_verify_valset(self, commit_off, sigs, flags, thresholds, z_seed, light=True, vks=None, key_idx=None,
                              msgs=None, ks=None):
@@ -1081,13 +1097,10 @@ class Engine:
 
     def valset_select_ms(self, commit_off, flags, thresholds, light=True, vks=None, key_idx=None, reps=20):
         """edc_debug_valset_select: mean times of the join kernel and of the double-vote scan, in milliseconds."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        fl, th = self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds)
+        nc, _, args = self._valset_args(commit_off, None, flags, thresholds, vks, key_idx)
         ms = (ctypes.c_float * 2)()
         with self._lock:
-            rc = self.lib.edc_debug_valset_select(self.ctx, nc, off, vkb, idx, fl, th, int(bool(light)), reps, ms)
+            rc = self.lib.edc_debug_valset_select(self.ctx, nc, *args, int(bool(light)), reps, ms)
         self._check(rc)
         return ms[0], ms[1]
 
@@ -1171,14 +1184,10 @@ class Engine:
     def vhist_select_ms(self, commit_off, versions, flags, thresholds, light=True, vks=None, key_idx=None, reps=20):
         """edc_debug_vhist_select: mean times of the history's join kernel and of the double-vote scan,
         in milliseconds."""
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        ver = self._vhist_versions_arg(nc, versions)
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        fl, th = self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds)
+        nc, _, args = self._valset_args(commit_off, versions, flags, thresholds, vks, key_idx)
         ms = (ctypes.c_float * 2)()
         with self._lock:
-            rc = self.lib.edc_debug_vhist_select(self.ctx, nc, off, ver, vkb, idx, fl, th, int(bool(light)), reps, ms)
+            rc = self.lib.edc_debug_vhist_select(self.ctx, nc, *args, int(bool(light)), reps, ms)
         self._check(rc)
         return ms[0], ms[1]
 
@@ -1283,42 +1292,27 @@ class Engine:
         self._check(rc)
         return tuple(out)
 
-    def _vq_trust_args(self, commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, vks, key_idx):
-        nc, off = self._commit_offsets(commit_off)
-        n = off[nc] if nc else 0
-        vkb, idx = _tmpl_keys(n, vks, key_idx)
-        return nc, n, (off, self._vhist_versions_arg(nc, versions), self._vhist_versions_arg(nc, trust_versions), vkb, idx,
-                       self._valset_flags(n, flags), self._quorum_thresholds(nc, thresholds),
-                       self._quorum_thresholds(nc, trust_thresholds))
-
     def vq_trust_resolve(self, commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, light=True,
                          vks=None, key_idx=None):
         """edc_vq_trust_resolve: the paired join, both selections, the union and both double-vote scans
         alone -> a dict: "a" and "b", each the dict vhist_resolve returns for that side (without
         n_checked), "side" (bit 0 checked by A, bit 1 checked by B) and "n_checked" (the union's)."""
-        nc, n, args = self._vq_trust_args(commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, vks,
-                                          key_idx)
-        def side_out():
-            return ((ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))(), ctypes.create_string_buffer(max(n, 1)),
-                    ctypes.create_string_buffer(max(n, 1)), (ctypes.c_uint64 * max(nc, 1))(),
-                    ctypes.create_string_buffer(max(nc, 1)))
-        a, b = side_out(), side_out()
+        nc, n, args = self._valset_args(commit_off, versions, flags, thresholds, vks, key_idx, trust_versions,
+                                        trust_thresholds)
+        (a, result_a), (b, result_b) = self._valset_side(nc, n), self._valset_side(nc, n)
         side, cnt = ctypes.create_string_buffer(max(n, 1)), ctypes.c_size_t(0)
         with self._lock:
             rc = self.lib.edc_vq_trust_resolve(self.ctx, nc, *args, int(bool(light)),
                                                *(ctypes.addressof(x) for x in a + b + (side,)), ctypes.byref(cnt))
         self._check(rc)
-        def side_dict(o):
-            return {"pos": list(o[0][:n]), "power": list(o[1][:n]), "flag": list(o[2].raw[:n]),
-                    "checked": list(o[3].raw[:n]), "planned": list(o[4][:nc]), "dv": list(o[5].raw[:nc])}
-        return {"a": side_dict(a), "b": side_dict(b), "side": list(side.raw[:n]), "n_checked": cnt.value}
+        return {"a": result_a(), "b": result_b(), "side": list(side.raw[:n]), "n_checked": cnt.value}
 
     def vq_trust_select_ms(self, commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, light=True,
                            vks=None, key_idx=None, reps=20):
         """edc_debug_vq_trust_select: mean milliseconds of the paired join, of both selections with the
         union and its scan, and of both double-vote scans."""
-        nc, n, args = self._vq_trust_args(commit_off, versions, trust_versions, flags, thresholds, trust_thresholds, vks,
-                                          key_idx)
+        nc, _, args = self._valset_args(commit_off, versions, flags, thresholds, vks, key_idx, trust_versions,
+                                        trust_thresholds)
         ms = (ctypes.c_float * 3)()
         with self._lock:
             rc = self.lib.edc_debug_vq_trust_select(self.ctx, nc, *args, int(bool(light)), reps, ms)

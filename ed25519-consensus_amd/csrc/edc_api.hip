@@ -3799,6 +3799,27 @@ static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   return 0;
 }
 
+// One side's selection, as quorum_select_enqueue and the timing hook both launch it. Side A's writes
+// the skip bytes every back-end reads, or tr_skip_a when a side B follows (pair). Side B's (side_b:
+// d_power / d_flag are tr_power / tr_flag) clears the union's counts, selects against tr_thr into
+// tr_skip_b / tr_planned with side A's commit indices, and runs the union kernel.
+static hipError_t quorum_side_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, int mode, const uint64_t* d_power,
+                                     const uint8_t* d_flag, bool pair, bool side_b) {
+  const uint32_t N = (uint32_t)n, NC = (uint32_t)nc;
+  if (!side_b) {
+    launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, d_power, d_flag, ctx->q_cidx, ctx->q_aggv,
+                         ctx->q_aggf, ctx->q_carry, pair ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), ctx->sc_wg, ctx->q_planned,
+                         ctx->q_err);
+    return hipSuccess;
+  }
+  hipError_t e = hipMemsetAsync(ctx->tr_cnt, 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t), st);
+  if (e != hipSuccess) return e;
+  launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->tr_thr, d_power, d_flag, ctx->q_cidx, ctx->q_aggv,
+                       ctx->q_aggf, ctx->q_carry, ctx->tr_skip_b, ctx->sc_wg, ctx->tr_planned, ctx->q_err, true);
+  launch_quorum_union(st, N, ctx->tr_skip_a, ctx->tr_skip_b, ctx->sc_hit, ctx->tr_side, ctx->sc_wg, ctx->tr_cnt);
+  return hipSuccess;
+}
+
 // Workspace, the staged offsets and thresholds, then the selection and the scan of its workgroup
 // counts on device-resident power / flag, all enqueued. A form with work of its own behind the
 // selection (n > 0 only) enqueues it between this and quorum_select_read.
@@ -3821,20 +3842,14 @@ static int quorum_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32
     memset(ctx->tr_hcnt.get(), 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t));
   }
   if (!n) return 0;
-  const uint32_t N = (uint32_t)n, nwg = (uint32_t)quorum_tiles(n);
+  const uint32_t nwg = (uint32_t)quorum_tiles(n);
   CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(ctx->q_thr, threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   CK(hipMemsetAsync(ctx->q_err, 0, sizeof(int), st));
-  launch_quorum_select(st, N, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, d_power, d_flag, ctx->q_cidx,
-                       ctx->q_aggv, ctx->q_aggf, ctx->q_carry, tr ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), ctx->sc_wg,
-                       ctx->q_planned, ctx->q_err);
+  CK(quorum_side_launch(ctx, st, n, nc, mode, d_power, d_flag, tr != nullptr, false));
   if (tr) {
     CK(hipMemcpyAsync(ctx->tr_thr, tr->threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    CK(hipMemsetAsync(ctx->tr_cnt, 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t), st));
-    launch_quorum_select(st, N, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->tr_thr, ctx->tr_power, ctx->tr_flag,
-                         ctx->q_cidx, ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->tr_skip_b, ctx->sc_wg, ctx->tr_planned,
-                         ctx->q_err, true);
-    launch_quorum_union(st, N, ctx->tr_skip_a, ctx->tr_skip_b, ctx->sc_hit, ctx->tr_side, ctx->sc_wg, ctx->tr_cnt);
+    CK(quorum_side_launch(ctx, st, n, nc, mode, ctx->tr_power, ctx->tr_flag, true, true));
     CK(hipMemcpyAsync(ctx->tr_hcnt.get(), ctx->tr_cnt, 3 * QR_UNION_SLOTS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   }
   launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
@@ -3894,28 +3909,140 @@ struct QuorumJoin {
   const QuorumTrust* trust = nullptr;
 };
 
+static const char kJoinFlagMsg[] = "votes: a flag above 2 or a commit whose counted power passes 2^63 - 1";
+
+// The join's and the double-vote scan's workspace (edc_valset_* / edc_vhist_* / edc_vq_*, below).
+static int ensure_valset(edc_ctx* ctx, size_t n, size_t nc) {
+  hipStream_t st = ctx->st();
+  CK(grow_group(ctx->vs_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
+    return alloc_all(sized(ctx->vs_who, cap), sized(ctx->vs_kidx, cap), sized(ctx->vs_flag, cap), sized(ctx->vs_set, 2 * cap));
+  }));
+  CK(grow_group(ctx->vs_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
+    hipError_t e = ctx->vs_dv.alloc(cap);
+    return e != hipSuccess ? e : ctx->vs_hdv.alloc(cap);
+  }));
+  return 0;
+}
+
+static int valset_ready(edc_ctx* ctx) {
+  if (!ctx->vs_m) { ctx->err = "no voting powers on the registered list (edc_valset_set_powers)"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+// a history is set and every commit names one of its versions
+static int vhist_ready(edc_ctx* ctx, size_t nc, const uint32_t* cver) {
+  if (!ctx->vh.m) { ctx->err = "no validator-set history on the registered list (edc_vhist_set)"; return EDC_ERR_ARG; }
+  for (size_t c = 0; c < nc; ++c)
+    if (cver[c] > ctx->vh.nv) { ctx->err = "commit_ver: a version past the history's last"; return EDC_ERR_ARG; }
+  return 0;
+}
+
+// Workspace for n items in nc commits on slot 0; everything the selection allocates is allocated
+// here, so that nothing the resolve kernel has written moves afterwards.
+static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false, bool pair = false) {
+  int rc = init_slot(ctx, ctx->slot[0]);
+  if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
+  if (pair && (rc = ensure_trust(ctx, n, nc))) return rc;
+  if (hist) CK(grow_group(ctx->vh_cap_c, nc, off_cap, sync_of(ctx->st()), [&](size_t cap) { return ctx->vh_cver.alloc(cap); }));
+  return ensure_valset(ctx, n, nc);
+}
+
+// The join kernel of jn, as valset_select_enqueue and the timing hooks both launch it: the one
+// set's, the history's (cver) or the paired one (cver and trust), which writes side B's arrays too.
+// The history's read q_coff / vh_cver / tr_ver, which the caller has staged.
+static void valset_join_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, const QuorumJoin& jn) {
+  const uint32_t N = (uint32_t)n, NC = (uint32_t)nc;
+  if (jn.cver && jn.trust)
+    launch_vhist_resolve2(st, N, NC, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, ctx->tr_ver, jn.d_vk, jn.d_kidx,
+                          ctx->kc_reg, jn.d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who, ctx->tr_power, ctx->tr_flag,
+                          ctx->tr_who);
+  else if (jn.cver)
+    launch_vhist_resolve(st, N, NC, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, jn.d_vk, jn.d_kidx, ctx->kc_reg,
+                         jn.d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
+  else
+    launch_valset_resolve(st, N, ctx->kc(), ctx->vs(), jn.d_vk, jn.d_kidx, ctx->kc_reg, jn.d_flag, ctx->q_power, ctx->q_flag,
+                          ctx->vs_who);
+}
+
+// One side's double-vote scan of n > 0 votes with the clearing of its set and bytes, as every call
+// and the timing hooks run it: side A on its skip bytes (tr_skip_a in a pair) and vs_who, side B on
+// tr_skip_b and tr_who.
+static hipError_t valset_pairs_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, bool pair, bool side_b) {
+  uint8_t* dv = side_b ? ctx->tr_dv.get() : ctx->vs_dv.get();
+  uint64_t* set = side_b ? ctx->tr_set.get() : ctx->vs_set.get();
+  const uint8_t* skip = side_b ? ctx->tr_skip_b.get() : pair ? ctx->tr_skip_a.get() : ctx->sc_hit.get();
+  hipError_t e = hipMemsetAsync(dv, 0, nc, st);
+  if (e != hipSuccess || (e = hipMemsetAsync(set, 0, 2 * n * sizeof(uint64_t), st)) != hipSuccess) return e;
+  launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, skip, side_b ? ctx->tr_who.get() : ctx->vs_who.get(), set, dv);
+  return hipSuccess;
+}
+
+// The join, the selection and the double-vote scan of n votes whose keys (jn->d_vk, or jn->d_kidx
+// with d_vk null) and flags are on the device, enqueued with the copies quorum_select_read's one
+// read-back then brings: the commits' double-vote bytes in vs_hdv and, for a host form's prehashed
+// k, the n skip bytes in jn->skip. valset_room has run.
+// jn->trust (a trusting pair, with cver): the paired join writes side B's arrays beside side A's,
+// the selection runs per side and leaves the union's skip bytes (quorum_select_enqueue), and the
+// double-vote scan runs once per side on that side's skip bytes, members and set; side B's bytes
+// travel to tr_hdv in the same read-back.
 static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
-                                 int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
-                                 uint8_t* h_skip, const uint32_t* cver, const QuorumTrust* tr = nullptr);
+                                 int mode, QuorumJoin* jn) {
+  hipStream_t st = ctx->st();
+  const QuorumTrust* tr = jn->trust;
+  jn->skip.assign(jn->host_k ? n : 0, 0);
+  if (jn->cver && n) {  // the history's join reads the offsets, which the selection stages (again) only behind it
+    CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(ctx->vh_cver, jn->cver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (tr) CK(hipMemcpyAsync(ctx->tr_ver, tr->ver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  valset_join_launch(ctx, st, n, nc, *jn);
+  CK(hipGetLastError());
+  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, tr);
+  if (rc) return rc;
+  memset(ctx->vs_hdv, 0, nc);
+  if (tr) memset(ctx->tr_hdv, 0, nc);
+  if (n) {
+    CK(valset_pairs_launch(ctx, st, n, nc, tr != nullptr, false));
+    if (tr) {
+      CK(valset_pairs_launch(ctx, st, n, nc, true, true));
+      CK(hipMemcpyAsync(ctx->tr_hdv, ctx->tr_dv, nc, hipMemcpyDeviceToHost, st));
+    }
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(ctx->vs_hdv, ctx->vs_dv, nc, hipMemcpyDeviceToHost, st));
+    if (!jn->skip.empty()) CK(hipMemcpyAsync(jn->skip.data(), ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
+  }
+  return 0;
+}
+
+// valset_select_enqueue and its read-back: *n_checked
+static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
+                         int mode, QuorumJoin* jn, size_t* n_checked) {
+  int rc = valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, jn);
+  return rc ? rc : quorum_select_read(ctx, n, n_checked, kJoinFlagMsg);
+}
 
 // quorum_select_enqueue, with the join in front and the double-vote scan behind it when jn is given
 // (d_power / d_flag are then q_power / q_flag, which the join writes)
 static int quorum_front_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                                 int mode, const uint64_t* d_power, const uint8_t* d_flag, QuorumJoin* jn) {
-  if (!jn) return quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag);
-  jn->skip.assign(jn->host_k ? n : 0, 0);
-  return valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, jn->d_vk, jn->d_kidx, jn->d_flag,
-                               jn->skip.empty() ? nullptr : jn->skip.data(), jn->cver, jn->trust);
+  if (jn) return valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, jn);
+  return quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag);
 }
-
-static const char kJoinFlagMsg[] = "votes: a flag above 2 or a commit whose counted power passes 2^63 - 1";
 
 // behind the read-back: Scalar::from_hash never yields k >= l, so a checked vote's k must be canonical
 static int quorum_join_check_k(edc_ctx* ctx, const QuorumJoin* jn) {
-  for (size_t i = 0; jn && i < jn->skip.size(); ++i) {
-    uint32_t w[8];
-    memcpy(w, jn->host_k + 32 * i, 32);
-    if (!jn->skip[i] && w[7] >= 0x10000000u && !sc_is_canonical(w)) {
+  if (!jn) return 0;
+  // One test per vote on its top word and skip byte, without a branch on the skip byte alone: in light
+  // mode the skip bytes change every few dozen votes, and a loop that branched on them took a
+  // millisecond longer over 2^20 votes (profiles/valset_refactor_bench.log, the probe section and the
+  // earlier sessions; DESIGN.md, "Validator-set requests").
+  const uint8_t *skip = jn->skip.data(), *k = jn->host_k;
+  for (size_t i = 0, n = jn->skip.size(); i < n; ++i) {
+    uint32_t w7, w[8];
+    memcpy(&w7, k + 32 * i + 28, 4);
+    if (!((w7 >= 0x10000000u) & !skip[i])) continue;
+    memcpy(w, k + 32 * i, 32);
+    if (!sc_is_canonical(w)) {
       ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
       return EDC_ERR_ARG;
     }
@@ -4082,15 +4209,20 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
   return res;
 }
 
-// A checked quorum commit set whose items (all: vk, sig, k of the n votes; power, flag) are on the device.
+// A checked quorum commit set whose items (all: vk, sig, k of the n votes; power, flag) are on the
+// device. jn (a validator-set form): power and flag are q_power / q_flag, which the join writes.
 static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
                       const ItemList& all, const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
-                      const QuorumOut& out) {
+                      const QuorumOut& out, QuorumJoin* jn = nullptr) {
+  const size_t n = all.count;
   size_t m = 0;
   ItemList list;
-  int rc = quorum_select_run(ctx, all.count, nc, commit_off, threshold, mode, d_power, d_flag, &m);
-  if (rc || (rc = quorum_gather(ctx, all, m, ctx->sc_hit, ctx->sc_wg, sc_area(ctx), &list))) return rc;
-  return quorum_finish(ctx, nc, threshold, all.count, list, d_power, d_flag, z_seed, out);
+  int rc = quorum_front_enqueue(ctx, n, nc, commit_off, threshold, mode, d_power, d_flag, jn);
+  if (rc || (rc = quorum_select_read(ctx, n, &m, jn ? kJoinFlagMsg : nullptr)) || (rc = quorum_join_check_k(ctx, jn)) ||
+      (rc = quorum_gather(ctx, all, m, ctx->sc_hit, ctx->sc_wg, sc_area(ctx), &list)))
+    return rc;
+  return quorum_finish(ctx, nc, threshold, n, list, d_power, d_flag, z_seed, out, nullptr, jn ? ctx->vs_hdv.get() : nullptr,
+                       jn ? jn->trust : nullptr);
 }
 
 extern "C" {
@@ -4622,103 +4754,15 @@ int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
 // per-commit bytes come back with the selection's one read-back. Everything after that is the
 // quorum entries' own: quorum_gather, then quorum_finish with the double-vote bytes.
 // edc_vhist_*: the same entries with every commit judged by the set of its own version (cver, the
-// commits' versions on the host; null in this section: the one set of edc_valset_set_powers). Only
-// the join differs: the offsets and versions go to the device in front of it, and k_vh_resolve
-// stands where k_vs_resolve does.
-static int ensure_valset(edc_ctx* ctx, size_t n, size_t nc) {
-  hipStream_t st = ctx->st();
-  CK(grow_group(ctx->vs_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
-    return alloc_all(sized(ctx->vs_who, cap), sized(ctx->vs_kidx, cap), sized(ctx->vs_flag, cap), sized(ctx->vs_set, 2 * cap));
-  }));
-  CK(grow_group(ctx->vs_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
-    hipError_t e = ctx->vs_dv.alloc(cap);
-    return e != hipSuccess ? e : ctx->vs_hdv.alloc(cap);
-  }));
-  return 0;
-}
-
-static int valset_ready(edc_ctx* ctx) {
-  if (!ctx->vs_m) { ctx->err = "no voting powers on the registered list (edc_valset_set_powers)"; return EDC_ERR_ARG; }
-  return 0;
-}
-
-// a history is set and every commit names one of its versions
-static int vhist_ready(edc_ctx* ctx, size_t nc, const uint32_t* cver) {
-  if (!ctx->vh.m) { ctx->err = "no validator-set history on the registered list (edc_vhist_set)"; return EDC_ERR_ARG; }
-  for (size_t c = 0; c < nc; ++c)
-    if (cver[c] > ctx->vh.nv) { ctx->err = "commit_ver: a version past the history's last"; return EDC_ERR_ARG; }
-  return 0;
-}
-
-// Workspace for n items in nc commits on slot 0; everything the selection allocates is allocated
-// here, so that nothing the resolve kernel has written moves afterwards.
-static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false, bool pair = false) {
-  int rc = init_slot(ctx, ctx->slot[0]);
-  if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
-  if (pair && (rc = ensure_trust(ctx, n, nc))) return rc;
-  if (hist) CK(grow_group(ctx->vh_cap_c, nc, off_cap, sync_of(ctx->st()), [&](size_t cap) { return ctx->vh_cver.alloc(cap); }));
-  return ensure_valset(ctx, n, nc);
-}
-
-// The join, the selection and the double-vote scan of n votes whose keys (d_vk, or d_kidx with
-// d_vk null) and flags are on the device, enqueued with the copies quorum_select_read's one
-// read-back then brings: the commits' double-vote bytes in vs_hdv and, if h_skip is given, the n
-// skip bytes. valset_room has run.
-// tr (a trusting pair, with cver): the paired join writes side B's arrays beside side A's, the
-// selection runs per side and leaves the union's skip bytes (quorum_select_enqueue), and the
-// double-vote scan runs once per side on that side's skip bytes, members and set; side B's bytes
-// travel to tr_hdv in the same read-back.
-static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
-                                 int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
-                                 uint8_t* h_skip, const uint32_t* cver, const QuorumTrust* tr) {
-  hipStream_t st = ctx->st();
-  if (cver && n) {      // the history's join reads the offsets, which the selection stages (again) only behind it
-    CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(ctx->vh_cver, cver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (tr) {
-      CK(hipMemcpyAsync(ctx->tr_ver, tr->ver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      launch_vhist_resolve2(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, ctx->tr_ver, d_vk,
-                            d_kidx, ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who, ctx->tr_power, ctx->tr_flag,
-                            ctx->tr_who);
-    } else {
-      launch_vhist_resolve(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, d_vk, d_kidx,
-                           ctx->kc_reg, d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
-    }
-  } else {
-    launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, d_kidx, ctx->kc_reg, d_flag, ctx->q_power,
-                          ctx->q_flag, ctx->vs_who);
-  }
-  CK(hipGetLastError());
-  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, tr);
-  if (rc) return rc;
-  memset(ctx->vs_hdv, 0, nc);
-  if (tr) memset(ctx->tr_hdv, 0, nc);
-  if (n) {
-    CK(hipMemsetAsync(ctx->vs_dv, 0, nc, st));
-    CK(hipMemsetAsync(ctx->vs_set, 0, 2 * n * sizeof(uint64_t), st));
-    launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, tr ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), ctx->vs_who,
-                        ctx->vs_set, ctx->vs_dv);
-    if (tr) {
-      CK(hipMemsetAsync(ctx->tr_dv, 0, nc, st));
-      CK(hipMemsetAsync(ctx->tr_set, 0, 2 * n * sizeof(uint64_t), st));
-      launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, ctx->tr_skip_b, ctx->tr_who, ctx->tr_set, ctx->tr_dv);
-      CK(hipMemcpyAsync(ctx->tr_hdv, ctx->tr_dv, nc, hipMemcpyDeviceToHost, st));
-    }
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(ctx->vs_hdv, ctx->vs_dv, nc, hipMemcpyDeviceToHost, st));
-    if (h_skip) CK(hipMemcpyAsync(h_skip, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
-  }
-  return 0;
-}
-
-// valset_select_enqueue and its read-back: *n_checked
-static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
-                         int mode, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag, uint8_t* h_skip,
-                         size_t* n_checked, const uint32_t* cver = nullptr, const QuorumTrust* tr = nullptr) {
-  int rc = valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, h_skip, cver, tr);
-  return rc ? rc : quorum_select_read(ctx, n, n_checked, kJoinFlagMsg);
-}
-
+// commits' versions on the host; null: the one set of edc_valset_set_powers). Only the join
+// differs: the offsets and versions go to the device in front of it, and k_vh_resolve stands where
+// k_vs_resolve does.
+// The workspace, the launches and the select pair stand with QuorumJoin in the quorum section
+// (ensure_valset ... valset_select), where quorum_run and its siblings take the join as an optional
+// stage. Here: one body per kind of entry, for these two families and for the requests below.
+//   verify   vq_run_plain (messages or k) and, for requests only, vq_run_tmpl
+//   resolve  valset_resolve_body, one side or a trusting pair
+//   timing   valset_debug_select_body, which launches what valset_select_enqueue launches
 // keys (bytes into ctx->vk, or positions into vs_kidx) and flags (vs_flag) of n > 0 host votes
 static int valset_stage_votes(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag) {
   hipStream_t st = ctx->st();
@@ -4744,32 +4788,6 @@ static int valset_check_host(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
     if (!flag) { ctx->err = "null input"; return EDC_ERR_ARG; }
   }
   return 0;
-}
-
-// A checked validator-set commit set whose items (all: vk, sig, k) are on the device and whose keys
-// or positions and flags are where valset_select reads them. host_k: a host form's prehashed k,
-// which must be canonical for the checked votes (the skip bytes come back with the read-back).
-static int valset_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
-                      const ItemList& all, const uint8_t* d_vk, const uint32_t* d_kidx, const uint8_t* d_flag,
-                      const uint8_t* host_k, const uint8_t* z_seed, const QuorumOut& out, const uint32_t* cver,
-                      const QuorumTrust* tr = nullptr) {
-  const size_t n = all.count;
-  size_t m = 0;
-  ItemList list;
-  std::vector<uint8_t> skip(host_k ? n : 0);
-  int rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, d_kidx, d_flag, host_k && n ? skip.data() : nullptr, &m,
-                         cver, tr);
-  if (rc) return rc;
-  for (size_t i = 0; i < skip.size(); ++i) {      // Scalar::from_hash never yields k >= l
-    uint32_t w[8];
-    memcpy(w, host_k + 32 * i, 32);
-    if (!skip[i] && w[7] >= 0x10000000u && !sc_is_canonical(w)) {
-      ctx->err = "prehashed k is not a canonical scalar (must be < l, as Scalar::from_hash returns)";
-      return EDC_ERR_ARG;
-    }
-  }
-  if ((rc = quorum_gather(ctx, all, m, ctx->sc_hit, ctx->sc_wg, sc_area(ctx), &list))) return rc;
-  return quorum_finish(ctx, nc, threshold, n, list, ctx->q_power, ctx->q_flag, z_seed, out, nullptr, ctx->vs_hdv, tr);
 }
 
 extern "C" {
@@ -4822,156 +4840,238 @@ int edc_valset_size(const edc_ctx* ctx) { return ctx ? (int)ctx->vs_m : 0; }
 
 }  // extern "C"
 
-// The bodies of the entries, for both sections. hist: an edc_vhist_* entry, which needs cver.
+// hist: an edc_vhist_* entry, which needs cver
 static bool vhist_ver_missing(edc_ctx* ctx, bool hist, const uint32_t* cver) {
   if (hist && !cver) ctx->err = "null commit_ver";
   return hist && !cver;
 }
 
-static int valset_resolve_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
-                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
-                                int mode, uint32_t* pos, uint64_t* power, uint8_t* flag_out, uint8_t* checked,
-                                uint64_t* planned, size_t* n_checked, uint8_t* dv) {
-  if (!ctx) return EDC_ERR_ARG;
-  if (!nc) {
-    if (n_checked) *n_checked = 0;
-    return EDC_OK;
+// vhist_ready for the trusting side: every trust version is one of the history's or the sentinel
+static int vq_trust_ready(edc_ctx* ctx, size_t nc, const QuorumTrust* tr) {
+  if (tr && !vq_trust_check_versions(nc, tr->ver, ctx->vh.nv)) {
+    ctx->err = "trust_ver: a version past the history's last that is not EDC_VQ_NO_TRUST";
+    return EDC_ERR_ARG;
   }
-  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
-  size_t n, m = 0;
-  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, cver);
-  if (rc) return rc;
-  CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc, hist)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
-  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx,
-                          ctx->vs_flag, nullptr, &m, cver)))
+  return 0;
+}
+
+// Every verify entry on messages or k, below the checks of the request's shape that its caller has
+// made (edc_vq_verify: vq_entry_done; the edc_valset_* / edc_vhist_* entries: valset_verify_entry):
+// the checks of the arrays (n > 0 only), the staging, then quorum_run or cached_quorum_run with the
+// join. *hashed: the items SHA-512 runs over.
+static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out, const QuorumTrust* tr,
+                        size_t* hashed) {
+  const size_t nc = rq->nc;
+  const bool hist = rq->commit_ver != nullptr;
+  size_t n;
+  int rc = quorum_check(ctx, nc, rq->commit_off, rq->threshold, rq->mode, &n);
+  if (rc || (rc = hist ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx)) || (rc = vq_trust_ready(ctx, nc, tr)))
     return rc;
+  if (n && (!rq->sig || !rq->flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  ItemList all;
+  QuorumJoin jn{nullptr, nullptr, nullptr, rq->commit_ver, nullptr, {}, tr};
+  if (rq->device) {
+    if (n && (!rq->vk || (!rq->k && !rq->msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+    if (n && (!aligned16(rq->vk) || !aligned16(rq->sig) || (rq->k && !aligned16(rq->k)))) {
+      ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
+      return EDC_ERR_ARG;
+    }
+    CK(hipSetDevice(ctx->device));
+    if ((rc = valset_room(ctx, n, nc, hist, tr != nullptr))) return rc;
+    const uint32_t* k = reinterpret_cast<const uint32_t*>(rq->k);
+    if (n && !k) {
+      if ((rc = ensure_n(ctx, n))) return rc;
+      launch_challenge(ctx->st(), (uint32_t)n, rq->vk, rq->sig, rq->msg, rq->msg_off, ctx->kbuf);
+      CK(hipGetLastError());
+      k = ctx->kbuf;
+    }
+    all = ItemList{rq->vk, rq->sig, k, nullptr, n};
+    jn.d_vk = rq->vk;
+    jn.d_flag = rq->flag;
+  } else {
+    if (n && ((rc = commits_check_keys(ctx, n, rq->vk, rq->key_idx)) ||
+              (rc = commits_check_msg_or_k(ctx, n, rq->msg, rq->msg_off, rq->k))))
+      return rc;
+    CK(hipSetDevice(ctx->device));
+    if ((rc = valset_room(ctx, n, nc, hist, tr != nullptr))) return rc;
+    hipStream_t st = ctx->st();
+    if (rq->k) {
+      if ((rc = ensure_n(ctx, n))) return rc;
+      if (n) CK(hipMemcpyAsync(ctx->kbuf, rq->k, n * 32, hipMemcpyHostToDevice, st));
+    } else if ((rc = upload_msgs(ctx, n, rq->msg, n ? rq->msg_off : nullptr))) {
+      return rc;
+    }
+    if (n) {                  // 4 + 64 + 1 bytes per vote in the key_idx form: the keys are expanded on the device
+      CK(hipMemcpyAsync(ctx->vs_flag, rq->flag, n, hipMemcpyHostToDevice, st));
+      if ((rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->vs_kidx, ctx->vk, ctx->sig))) return rc;
+      if (!rq->k) {
+        launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
+        CK(hipGetLastError());
+      }
+    }
+    all = ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n};
+    jn.d_vk = rq->key_idx ? nullptr : ctx->vk.get();
+    jn.d_kidx = ctx->vs_kidx;
+    jn.d_flag = ctx->vs_flag;
+    jn.host_k = n ? rq->k : nullptr;
+  }
+  *hashed = rq->k ? 0 : n;
+  if (rq->cached)
+    return cached_quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->q_power, ctx->q_flag, rq->z_seed,
+                             out, *hashed, &jn);
+  return quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->q_power, ctx->q_flag, rq->z_seed, out, &jn);
+}
+
+// The edc_valset_* / edc_vhist_* verify entries: what they accept and refuse before the arrays are
+// looked at is their own, not the request's (a set of empty commits needs no array at all, where
+// the request always names its keys), and they leave the request's debug record alone. Then the
+// request's plain body on a request with no template set, no table and no trusting side.
+static int valset_verify_entry(edc_ctx* ctx, bool hist, bool device, size_t nc, const uint32_t* commit_off,
+                               const uint32_t* cver, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                               const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k, const uint8_t* flag,
+                               const uint64_t* threshold, int mode, const uint8_t* z_seed, const QuorumOut& out) {
+  int rc;
+  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
+  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
+  edc_vq_request rq;
+  memset(&rq, 0, sizeof(rq));
+  rq.size = sizeof(rq);
+  rq.device = device;
+  rq.mode = mode;
+  rq.nc = nc;
+  rq.commit_off = commit_off;
+  rq.commit_ver = cver;
+  rq.threshold = threshold;
+  rq.z_seed = z_seed;
+  rq.vk = vk;
+  rq.key_idx = key_idx;
+  rq.sig = sig;
+  rq.flag = flag;
+  rq.msg = msg;
+  rq.msg_off = msg_off;
+  rq.k = k;
+  size_t hashed;
+  return vq_run_plain(ctx, &rq, out, nullptr, &hashed);
+}
+
+// One side's outputs of a resolve entry, host memory, all nullable.
+struct ResolveSide {
+  uint32_t* pos;
+  uint64_t* power;
+  uint8_t *flag, *checked;
+  uint64_t* planned;
+  uint8_t* dv;
+};
+
+// What the resolve entries and the timing hooks do first, on host keys and flags: the checks, the
+// workspace, the staging, then valset_select with its read-back. *n: the votes; *m: the checked
+// ones (the union's in a pair). tr (edc_vq_trust_*; with hist): the trusting side's versions and
+// thresholds, both needed. nc == 0: EDC_OK with nothing done.
+static int valset_resolve_select(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
+                                 const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
+                                 int mode, const QuorumTrust* tr, size_t* n, size_t* m) {
+  *n = *m = 0;
+  if (!ctx) return EDC_ERR_ARG;
+  if (!nc) return EDC_OK;
+  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
+  if (tr && (!tr->ver || !tr->threshold)) { ctx->err = "null trust_ver / trust_threshold"; return EDC_ERR_ARG; }
+  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, n, cver);
+  if (rc || (rc = vq_trust_ready(ctx, nc, tr))) return rc;
+  CK(hipSetDevice(ctx->device));
+  if ((rc = valset_room(ctx, *n, nc, hist, tr != nullptr)) || (*n && (rc = valset_stage_votes(ctx, *n, vk, key_idx, flag))))
+    return rc;
+  QuorumJoin jn{key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, cver, nullptr, {}, tr};
+  return valset_select(ctx, *n, nc, commit_off, threshold, mode, &jn, m);
+}
+
+// edc_valset_resolve, edc_vhist_resolve (hist) and edc_vq_trust_resolve (tr, with b and side): the
+// join, the selection and the double-vote scan as the verify entries run them, and each side's
+// arrays read back. One side's skip bytes are the selection's (sc_hit); a pair's are tr_skip_a /
+// tr_skip_b, sc_hit then holding the union's.
+static int valset_resolve_body(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
+                               const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
+                               int mode, const ResolveSide& a, size_t* n_checked, const QuorumTrust* tr = nullptr,
+                               const ResolveSide& b = ResolveSide{}, uint8_t* side = nullptr) {
+  size_t n, m;
+  const int rc = valset_resolve_select(ctx, hist, nc, commit_off, cver, vk, key_idx, flag, threshold, mode, tr, &n, &m);
+  if (rc || !nc) {
+    if (!rc && n_checked) *n_checked = 0;
+    return rc;
+  }
   const std::vector<uint32_t>& posh = hist ? ctx->vh_posh : ctx->vs_posh;
   hipStream_t st = ctx->st();
-  std::vector<uint32_t> who(pos ? n : 0);
-  if (pos && n) CK(hipMemcpyAsync(who.data(), ctx->vs_who, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  if (power && n) CK(hipMemcpyAsync(power, ctx->q_power, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  if (flag_out && n) CK(hipMemcpyAsync(flag_out, ctx->q_flag, n, hipMemcpyDeviceToHost, st));
-  if (planned) CK(hipMemcpyAsync(planned, ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  if (checked && n) CK(hipMemcpyAsync(checked, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
+  std::vector<uint32_t> who(a.pos ? n : 0), who_b(b.pos ? n : 0);
+  auto back = [&](void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  CK(back(who.data(), ctx->vs_who, who.size() * sizeof(uint32_t)));
+  CK(back(who_b.data(), ctx->tr_who, who_b.size() * sizeof(uint32_t)));
+  CK(back(a.power, ctx->q_power, n * sizeof(uint64_t)));
+  CK(back(b.power, ctx->tr_power, n * sizeof(uint64_t)));
+  CK(back(a.flag, ctx->q_flag, n));
+  CK(back(b.flag, ctx->tr_flag, n));
+  CK(back(a.planned, ctx->q_planned, nc * sizeof(uint64_t)));
+  CK(back(b.planned, ctx->tr_planned, nc * sizeof(uint64_t)));
+  CK(back(a.checked, tr ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), n));
+  CK(back(b.checked, ctx->tr_skip_b, n));
+  CK(back(side, ctx->tr_side, n));
   CK(hipStreamSynchronize(st));
-  for (size_t i = 0; i < who.size(); ++i) pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : posh[who[i]];
-  if (checked)
-    for (size_t i = 0; i < n; ++i) checked[i] = checked[i] ? 0 : 1;      // the kernel writes the skip byte
-  if (dv) memcpy(dv, ctx->vs_hdv, nc);
+  for (size_t i = 0; i < who.size(); ++i) a.pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : posh[who[i]];
+  for (size_t i = 0; i < who_b.size(); ++i) b.pos[i] = who_b[i] == KC_EMPTY ? VALSET_NO_POS : posh[who_b[i]];
+  for (size_t i = 0; i < n; ++i) {      // the kernels write skip bytes
+    if (a.checked) a.checked[i] = a.checked[i] ? 0 : 1;
+    if (b.checked) b.checked[i] = b.checked[i] ? 0 : 1;
+  }
+  if (a.dv) memcpy(a.dv, ctx->vs_hdv, nc);
+  if (b.dv) memcpy(b.dv, ctx->tr_hdv, nc);
   if (n_checked) *n_checked = m;
   return EDC_OK;
 }
 
-static int valset_verify_device_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
-                                      const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
-                                      const uint64_t* d_msg_off, const uint8_t* d_k, const uint8_t* d_flag,
-                                      const uint64_t* threshold, int mode, const uint8_t z_seed[32], const QuorumOut& out) {
-  int rc;
-  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
-  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
-  size_t n;
-  if ((rc = quorum_check(ctx, nc, commit_off, threshold, mode, &n)) ||
-      (rc = hist ? vhist_ready(ctx, nc, cver) : valset_ready(ctx)))
-    return rc;
-  if (n && (!d_vk || !d_sig || (!d_k && !d_msg_off) || !d_flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)))) {
-    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
-    return EDC_ERR_ARG;
-  }
-  CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc, hist))) return rc;
-  const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
-  if (n && !k) {
-    if ((rc = ensure_n(ctx, n))) return rc;
-    launch_challenge(ctx->st(), (uint32_t)n, d_vk, d_sig, d_msg, d_msg_off, ctx->kbuf);
-    CK(hipGetLastError());
-    k = ctx->kbuf;
-  }
-  return valset_run(ctx, nc, commit_off, threshold, mode, ItemList{d_vk, d_sig, k, nullptr, n}, d_vk, nullptr, d_flag,
-                    nullptr, z_seed, out, cver);
-}
-
-static int valset_verify_host_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
-                                    const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
-                                    const uint64_t* msg_off, const uint8_t* k, const uint8_t* flag,
-                                    const uint64_t* threshold, int mode, const uint8_t z_seed[32], const QuorumOut& out) {
-  int rc;
-  if (quorum_entry_done(ctx, z_seed, false, nc, out, &rc)) return rc;
-  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
-  size_t n;
-  if ((rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, cver))) return rc;
-  if (n) {
-    if (!sig) { ctx->err = "null input"; return EDC_ERR_ARG; }
-    if ((rc = commits_check_msg_or_k(ctx, n, msg, msg_off, k))) return rc;
-  }
-  CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc, hist))) return rc;
-  hipStream_t st = ctx->st();
-  if (k) {
-    if ((rc = ensure_n(ctx, n))) return rc;
-    if (n) CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
-  } else if ((rc = upload_msgs(ctx, n, msg, n ? msg_off : nullptr))) {
-    return rc;
-  }
-  if (n) {                  // 4 + 64 + 1 bytes per vote in the key_idx form: the keys are expanded on the device
-    CK(hipMemcpyAsync(ctx->vs_flag, flag, n, hipMemcpyHostToDevice, st));
-    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->vs_kidx, ctx->vk, ctx->sig))) return rc;
-    if (!k) {
-      launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
-      CK(hipGetLastError());
-    }
-  }
-  return valset_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n},
-                    key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, n ? k : nullptr, z_seed, out, cver);
-}
-
-static int valset_debug_select_entry(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
-                                     const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
-                                     const uint64_t* threshold, int mode, int reps, float ms[2]) {
+// Mean times over reps runs of the stages valset_select_enqueue launches, through the helpers it
+// launches them with, on host keys and flags: ms[0] the join; with three intervals (the pair's
+// hook) ms[1] the selection per side, the union and the scan of its tile counts; the last the
+// double-vote scan per side with the clearing of its set and bytes. Every stage rewrites the values
+// the selection in front left (planned is a maximum).
+static int valset_debug_select_body(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
+                                    const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
+                                    const uint64_t* threshold, int mode, int reps, int intervals, float* ms,
+                                    const QuorumTrust* tr = nullptr) {
   if (!ctx || reps < 1) return EDC_ERR_ARG;
-  if (ms) ms[0] = ms[1] = 0.f;
-  if (!nc) return EDC_OK;
-  if (vhist_ver_missing(ctx, hist, cver)) return EDC_ERR_ARG;
-  size_t n, m = 0;
-  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, cver);
-  if (rc) return rc;
-  CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc, hist)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
-  const uint8_t* d_vk = key_idx ? nullptr : ctx->vk.get();
-  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, d_vk, ctx->vs_kidx, ctx->vs_flag, nullptr, &m, cver)))
-    return rc;
-  if (!n) return EDC_OK;
+  for (int j = 0; j < intervals && ms; ++j) ms[j] = 0.f;
+  size_t n, m;
+  const int rc = valset_resolve_select(ctx, hist, nc, commit_off, cver, vk, key_idx, flag, threshold, mode, tr, &n, &m);
+  if (rc || !n) return rc;
   hipStream_t st = ctx->st();
-  Event e0, e1, e2;
-  CK(e0.create());
-  CK(e1.create());
-  CK(e2.create());
-  CK(hipEventRecord(e0, st));
-  for (int r = 0; r < reps; ++r) {      // the resolve kernel rewrites the same values
-    if (hist)                           // the offsets and versions are where valset_select left them
-      launch_vhist_resolve(st, (uint32_t)n, (uint32_t)nc, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, d_vk, ctx->vs_kidx,
-                           ctx->kc_reg, ctx->vs_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
-    else
-      launch_valset_resolve(st, (uint32_t)n, ctx->kc(), ctx->vs(), d_vk, ctx->vs_kidx, ctx->kc_reg, ctx->vs_flag,
-                            ctx->q_power, ctx->q_flag, ctx->vs_who);
+  const QuorumJoin jn{key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, cver, nullptr, {}, tr};
+  const uint32_t nwg = (uint32_t)quorum_tiles(n);
+  Event e[4];
+  for (int j = 0; j <= intervals; ++j) CK(e[j].create());
+  int at = 0;
+  CK(hipEventRecord(e[at++], st));
+  for (int r = 0; r < reps; ++r) valset_join_launch(ctx, st, n, nc, jn);        // the offsets and versions are staged
+  CK(hipGetLastError());
+  CK(hipEventRecord(e[at++], st));
+  if (intervals == 3) {
+    for (int r = 0; r < reps; ++r) {
+      CK(quorum_side_launch(ctx, st, n, nc, mode, ctx->q_power, ctx->q_flag, tr != nullptr, false));
+      if (tr) CK(quorum_side_launch(ctx, st, n, nc, mode, ctx->tr_power, ctx->tr_flag, true, true));
+      launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
+    }
+    CK(hipGetLastError());
+    CK(hipEventRecord(e[at++], st));
+  }
+  for (int r = 0; r < reps; ++r) {
+    CK(valset_pairs_launch(ctx, st, n, nc, tr != nullptr, false));
+    if (tr) CK(valset_pairs_launch(ctx, st, n, nc, true, true));
   }
   CK(hipGetLastError());
-  CK(hipEventRecord(e1, st));
-  for (int r = 0; r < reps; ++r) {      // the scan with the clearing of its set and bytes, as every call runs it
-    CK(hipMemsetAsync(ctx->vs_dv, 0, nc, st));
-    CK(hipMemsetAsync(ctx->vs_set, 0, 2 * n * sizeof(uint64_t), st));
-    launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, ctx->sc_hit, ctx->vs_who, ctx->vs_set, ctx->vs_dv);
-  }
-  CK(hipGetLastError());
-  CK(hipEventRecord(e2, st));
-  CK(hipEventSynchronize(e2));
-  float t0 = 0.f, t1 = 0.f;
-  CK(hipEventElapsedTime(&t0, e0, e1));
-  CK(hipEventElapsedTime(&t1, e1, e2));
-  if (ms) {
-    ms[0] = t0 / (float)reps;
-    ms[1] = t1 / (float)reps;
+  CK(hipEventRecord(e[at], st));
+  CK(hipEventSynchronize(e[at]));
+  for (int j = 0; j < intervals && ms; ++j) {
+    float t = 0.f;
+    CK(hipEventElapsedTime(&t, e[j], e[j + 1]));
+    ms[j] = t / (float)reps;
   }
   return EDC_OK;
 }
@@ -4981,8 +5081,8 @@ extern "C" {
 int edc_valset_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk, const uint32_t* key_idx,
                        const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos, uint64_t* power,
                        uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked, uint8_t* dv) {
-  return valset_resolve_entry(ctx, false, nc, commit_off, nullptr, vk, key_idx, flag, threshold, mode, pos, power, flag_out,
-                              checked, planned, n_checked, dv);
+  return valset_resolve_body(ctx, false, nc, commit_off, nullptr, vk, key_idx, flag, threshold, mode,
+                             ResolveSide{pos, power, flag_out, checked, planned, dv}, n_checked);
 }
 
 int edc_valset_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* d_vk,
@@ -4991,8 +5091,8 @@ int edc_valset_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* com
                                     const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
                                     uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
   const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
-  return valset_verify_device_entry(ctx, false, nc, commit_off, nullptr, d_vk, d_sig, d_msg, d_msg_off, d_k, d_flag,
-                                    threshold, mode, z_seed, out);
+  return valset_verify_entry(ctx, false, true, nc, commit_off, nullptr, d_vk, nullptr, d_sig, d_msg, d_msg_off, d_k, d_flag,
+                             threshold, mode, z_seed, out);
 }
 
 int edc_valset_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
@@ -5001,14 +5101,14 @@ int edc_valset_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
                              const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts, uint64_t* tally,
                              int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
   const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
-  return valset_verify_host_entry(ctx, false, nc, commit_off, nullptr, vk, key_idx, sig, msg, msg_off, k, flag, threshold,
-                                  mode, z_seed, out);
+  return valset_verify_entry(ctx, false, false, nc, commit_off, nullptr, vk, key_idx, sig, msg, msg_off, k, flag, threshold,
+                             mode, z_seed, out);
 }
 
 int edc_debug_valset_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint8_t* vk,
                             const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, int reps,
                             float ms[2]) {
-  return valset_debug_select_entry(ctx, false, nc, commit_off, nullptr, vk, key_idx, flag, threshold, mode, reps, ms);
+  return valset_debug_select_body(ctx, false, nc, commit_off, nullptr, vk, key_idx, flag, threshold, mode, reps, 2, ms);
 }
 
 // ---------------------------------------------------------------- validator-set history
@@ -5076,8 +5176,8 @@ int edc_vhist_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
                       const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold, int mode, uint32_t* pos,
                       uint64_t* power, uint8_t* flag_out, uint8_t* checked, uint64_t* planned, size_t* n_checked,
                       uint8_t* dv) {
-  return valset_resolve_entry(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, pos, power,
-                              flag_out, checked, planned, n_checked, dv);
+  return valset_resolve_body(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode,
+                             ResolveSide{pos, power, flag_out, checked, planned, dv}, n_checked);
 }
 
 int edc_vhist_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
@@ -5087,8 +5187,8 @@ int edc_vhist_quorum_verify_device(edc_ctx* ctx, size_t nc, const uint32_t* comm
                                    uint8_t* item_verdicts, uint64_t* tally, int* n_bad_commits, size_t* n_checked,
                                    uint8_t check8[32]) {
   const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
-  return valset_verify_device_entry(ctx, true, nc, commit_off, commit_ver, d_vk, d_sig, d_msg, d_msg_off, d_k, d_flag,
-                                    threshold, mode, z_seed, out);
+  return valset_verify_entry(ctx, true, true, nc, commit_off, commit_ver, d_vk, nullptr, d_sig, d_msg, d_msg_off, d_k, d_flag,
+                             threshold, mode, z_seed, out);
 }
 
 int edc_vhist_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
@@ -5097,14 +5197,14 @@ int edc_vhist_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
                             int mode, const uint8_t z_seed[32], uint8_t* commit_verdicts, uint8_t* item_verdicts,
                             uint64_t* tally, int* n_bad_commits, size_t* n_checked, uint8_t check8[32]) {
   const QuorumOut out{commit_verdicts, item_verdicts, tally, n_bad_commits, n_checked, nullptr, check8};
-  return valset_verify_host_entry(ctx, true, nc, commit_off, commit_ver, vk, key_idx, sig, msg, msg_off, k, flag, threshold,
-                                  mode, z_seed, out);
+  return valset_verify_entry(ctx, true, false, nc, commit_off, commit_ver, vk, key_idx, sig, msg, msg_off, k, flag,
+                             threshold, mode, z_seed, out);
 }
 
 int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
                            const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
                            int mode, int reps, float ms[2]) {
-  return valset_debug_select_entry(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, reps, ms);
+  return valset_debug_select_body(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, reps, 2, ms);
 }
 
 }  // extern "C"
@@ -5113,18 +5213,18 @@ int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, 
 // edc_vq_verify: the stages above composed behind one request. Every form is the request's checks
 // and staging, then the join (QuorumJoin) in front of the selection the form's pipeline already
 // enqueues and the double-vote scan behind it:
-//   plain            valset_run: join, selection, scan, one read-back, gather, quorum_finish
+//   plain            quorum_run with the join: join, selection, scan, one read-back, gather, quorum_finish
 //   plain cached     cached_quorum_run with the join: ... scan, masked lookup, one read-back, ...
 //   templated        tmpl_quorum_list with the join, then quorum_finish
 //   templated cached tmpl_quorum_list with the join, then cached_tmpl_finish
+// The plain forms' body, vq_run_plain, stands with the validator-set entries above, which are that
+// body on a request of their own making; the templated forms' is vq_run_tmpl here. What is the
+// request's alone is in front of the bodies (the structures' sizes, vq_entry_done) and behind them
+// (the debug record).
 // A host request by key position (key_idx) stages 4 bytes per key and expands the keys on the
 // device (stage_keys_sigs), as every host form does; the join still resolves by position. Gathers
 // that take the kept keys by position instead were measured level with this (DESIGN.md,
 // "Validator-set requests") and are not kept.
-struct VqForm {
-  bool hist, tmpl, dev;
-  size_t n;
-};
 
 // The sizes a structure may name: the one before the trusting pair's fields were appended, and
 // today's. With the earlier one the appended fields read as NULL.
@@ -5163,15 +5263,6 @@ static bool vq_entry_done(edc_ctx* ctx, bool sizes_ok, const edc_vq_request* rq,
   if (rq->cached && (*rc = cq_ready(ctx))) return true;
   if (!rq->nc) { *rc = quorum_none(out, tr); return true; }
   return false;
-}
-
-// vhist_ready for the trusting side: every trust version is one of the history's or the sentinel
-static int vq_trust_ready(edc_ctx* ctx, size_t nc, const QuorumTrust* tr) {
-  if (tr && !vq_trust_check_versions(nc, tr->ver, ctx->vh.nv)) {
-    ctx->err = "trust_ver: a version past the history's last that is not EDC_VQ_NO_TRUST";
-    return EDC_ERR_ARG;
-  }
-  return 0;
 }
 
 // the templated forms: checks, staging, tmpl_quorum_list with the join, the finish
@@ -5216,70 +5307,6 @@ static int vq_run_tmpl(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& 
                                                                rq->z_seed, out, ctx->vs_hdv, tr)
                                           : quorum_finish(ctx, nc, rq->threshold, n, list, it.power, it.flag, rq->z_seed,
                                                           out, nullptr, ctx->vs_hdv, tr));
-}
-
-// the forms on messages or k: the checks and staging of valset_verify_*_entry, then valset_run or
-// cached_quorum_run with the join; *hashed: the items SHA-512 runs over
-static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& out, const QuorumTrust* tr,
-                        size_t* hashed) {
-  const size_t nc = rq->nc;
-  const bool hist = rq->commit_ver != nullptr;
-  size_t n;
-  int rc = quorum_check(ctx, nc, rq->commit_off, rq->threshold, rq->mode, &n);
-  if (rc || (rc = hist ? vhist_ready(ctx, nc, rq->commit_ver) : valset_ready(ctx)) || (rc = vq_trust_ready(ctx, nc, tr)))
-    return rc;
-  if (n && (!rq->sig || !rq->flag)) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  ItemList all;
-  QuorumJoin jn{nullptr, nullptr, nullptr, rq->commit_ver, nullptr, {}, tr};
-  if (rq->device) {
-    if (n && (!aligned16(rq->vk) || !aligned16(rq->sig) || (rq->k && !aligned16(rq->k)))) {
-      ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
-      return EDC_ERR_ARG;
-    }
-    CK(hipSetDevice(ctx->device));
-    if ((rc = valset_room(ctx, n, nc, hist, tr != nullptr))) return rc;
-    const uint32_t* k = reinterpret_cast<const uint32_t*>(rq->k);
-    if (n && !k) {
-      if ((rc = ensure_n(ctx, n))) return rc;
-      launch_challenge(ctx->st(), (uint32_t)n, rq->vk, rq->sig, rq->msg, rq->msg_off, ctx->kbuf);
-      CK(hipGetLastError());
-      k = ctx->kbuf;
-    }
-    all = ItemList{rq->vk, rq->sig, k, nullptr, n};
-    jn.d_vk = rq->vk;
-    jn.d_flag = rq->flag;
-  } else {
-    if (n && (rc = check_key_idx(ctx, rq->key_idx ? n : 0, rq->key_idx))) return rc;
-    if (n && (rc = commits_check_msg_or_k(ctx, n, rq->msg, rq->msg_off, rq->k))) return rc;
-    CK(hipSetDevice(ctx->device));
-    if ((rc = valset_room(ctx, n, nc, hist, tr != nullptr))) return rc;
-    hipStream_t st = ctx->st();
-    if (rq->k) {
-      if ((rc = ensure_n(ctx, n))) return rc;
-      if (n) CK(hipMemcpyAsync(ctx->kbuf, rq->k, n * 32, hipMemcpyHostToDevice, st));
-    } else if ((rc = upload_msgs(ctx, n, rq->msg, n ? rq->msg_off : nullptr))) {
-      return rc;
-    }
-    if (n) {
-      CK(hipMemcpyAsync(ctx->vs_flag, rq->flag, n, hipMemcpyHostToDevice, st));
-      if ((rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->vs_kidx, ctx->vk, ctx->sig))) return rc;
-      if (!rq->k) {
-        launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
-        CK(hipGetLastError());
-      }
-    }
-    all = ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n};
-    jn.d_vk = rq->key_idx ? nullptr : ctx->vk.get();
-    jn.d_kidx = ctx->vs_kidx;
-    jn.d_flag = ctx->vs_flag;
-    jn.host_k = n ? rq->k : nullptr;
-  }
-  *hashed = rq->k ? 0 : n;
-  if (rq->cached)
-    return cached_quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->q_power, ctx->q_flag, rq->z_seed,
-                             out, *hashed, &jn);
-  return valset_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, jn.d_vk, jn.d_kidx, jn.d_flag, jn.host_k,
-                    rq->z_seed, out, rq->commit_ver, tr);
 }
 
 extern "C" {
@@ -5337,110 +5364,28 @@ int edc_debug_vq_trust_last(const edc_ctx* ctx, uint64_t out[4]) {
   return EDC_OK;
 }
 
-// edc_vhist_resolve's body with the trusting side: the paired join, both selections, the union and
-// both double-vote scans, as the request runs them, and each side's arrays read back.
+// edc_vhist_resolve with the trusting side: the paired join, both selections, the union and both
+// double-vote scans, as the request runs them.
 int edc_vq_trust_resolve(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
                          const uint32_t* trust_ver, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
                          const uint64_t* threshold, const uint64_t* trust_threshold, int mode, uint32_t* pos, uint64_t* power,
                          uint8_t* flag_out, uint8_t* checked, uint64_t* planned, uint8_t* dv, uint32_t* trust_pos,
                          uint64_t* trust_power, uint8_t* trust_flag_out, uint8_t* trust_checked, uint64_t* trust_planned,
                          uint8_t* trust_dv, uint8_t* side, size_t* n_checked) {
-  if (!ctx) return EDC_ERR_ARG;
-  if (!nc) {
-    if (n_checked) *n_checked = 0;
-    return EDC_OK;
-  }
-  if (vhist_ver_missing(ctx, true, commit_ver)) return EDC_ERR_ARG;
-  if (!trust_ver || !trust_threshold) { ctx->err = "null trust_ver / trust_threshold"; return EDC_ERR_ARG; }
   const QuorumTrust tr{trust_ver, trust_threshold, nullptr, nullptr, nullptr};
-  size_t n, m = 0;
-  int rc = valset_check_host(ctx, nc, commit_off, vk, key_idx, flag, threshold, mode, &n, commit_ver);
-  if (rc || (rc = vq_trust_ready(ctx, nc, &tr))) return rc;
-  CK(hipSetDevice(ctx->device));
-  if ((rc = valset_room(ctx, n, nc, true, true)) || (n && (rc = valset_stage_votes(ctx, n, vk, key_idx, flag)))) return rc;
-  if ((rc = valset_select(ctx, n, nc, commit_off, threshold, mode, key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx,
-                          ctx->vs_flag, nullptr, &m, commit_ver, &tr)))
-    return rc;
-  hipStream_t st = ctx->st();
-  std::vector<uint32_t> who(pos ? n : 0), who_b(trust_pos ? n : 0);
-  auto back = [&](void* dst, const void* src, size_t bytes) {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  CK(back(who.data(), ctx->vs_who, who.size() * sizeof(uint32_t)));
-  CK(back(who_b.data(), ctx->tr_who, who_b.size() * sizeof(uint32_t)));
-  CK(back(power, ctx->q_power, n * sizeof(uint64_t)));
-  CK(back(trust_power, ctx->tr_power, n * sizeof(uint64_t)));
-  CK(back(flag_out, ctx->q_flag, n));
-  CK(back(trust_flag_out, ctx->tr_flag, n));
-  CK(back(planned, ctx->q_planned, nc * sizeof(uint64_t)));
-  CK(back(trust_planned, ctx->tr_planned, nc * sizeof(uint64_t)));
-  CK(back(checked, ctx->tr_skip_a, n));
-  CK(back(trust_checked, ctx->tr_skip_b, n));
-  CK(back(side, ctx->tr_side, n));
-  CK(hipStreamSynchronize(st));
-  for (size_t i = 0; i < who.size(); ++i) pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : ctx->vh_posh[who[i]];
-  for (size_t i = 0; i < who_b.size(); ++i) trust_pos[i] = who_b[i] == KC_EMPTY ? VALSET_NO_POS : ctx->vh_posh[who_b[i]];
-  for (size_t i = 0; i < n; ++i) {      // the kernels write skip bytes
-    if (checked) checked[i] = checked[i] ? 0 : 1;
-    if (trust_checked) trust_checked[i] = trust_checked[i] ? 0 : 1;
-  }
-  if (dv) memcpy(dv, ctx->vs_hdv, nc);
-  if (trust_dv) memcpy(trust_dv, ctx->tr_hdv, nc);
-  if (n_checked) *n_checked = m;
-  return EDC_OK;
+  return valset_resolve_body(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode,
+                             ResolveSide{pos, power, flag_out, checked, planned, dv}, n_checked, &tr,
+                             ResolveSide{trust_pos, trust_power, trust_flag_out, trust_checked, trust_planned, trust_dv}, side);
 }
 
-// Mean times of the paired stages over reps runs on host keys and flags, as edc_debug_vhist_select
-// times one side's: ms[0] the paired join, ms[1] both selections, the union and the scan of its tile
-// counts, ms[2] both double-vote scans with the clearing of their sets.
+// edc_debug_vhist_select for a pair, with the selections between the join and the scans: ms[0] the
+// paired join, ms[1] both selections, the union and the scan of its tile counts, ms[2] both
+// double-vote scans with the clearing of their sets.
 int edc_debug_vq_trust_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint32_t* commit_ver,
                               const uint32_t* trust_ver, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag,
                               const uint64_t* threshold, const uint64_t* trust_threshold, int mode, int reps, float ms[3]) {
-  if (!ctx || reps < 1) return EDC_ERR_ARG;
-  if (ms) ms[0] = ms[1] = ms[2] = 0.f;
-  size_t n = 0;
-  int rc = edc_vq_trust_resolve(ctx, nc, commit_off, commit_ver, trust_ver, vk, key_idx, flag, threshold, trust_threshold, mode,
-                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                nullptr, nullptr, nullptr, nullptr);
-  if (rc || !nc || !(n = commit_off[nc])) return rc;
-  hipStream_t st = ctx->st();
-  const uint8_t* d_vk = key_idx ? nullptr : ctx->vk.get();
-  const uint32_t N = (uint32_t)n, NC = (uint32_t)nc, nwg = (uint32_t)quorum_tiles(n);
-  Event e[4];
-  for (Event& x : e) CK(x.create());
-  CK(hipEventRecord(e[0], st));
-  for (int r = 0; r < reps; ++r)        // every stage rewrites the values the resolve call left
-    launch_vhist_resolve2(st, N, NC, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, ctx->tr_ver, d_vk, ctx->vs_kidx,
-                          ctx->kc_reg, ctx->vs_flag, ctx->q_power, ctx->q_flag, ctx->vs_who, ctx->tr_power, ctx->tr_flag,
-                          ctx->tr_who);
-  CK(hipEventRecord(e[1], st));
-  for (int r = 0; r < reps; ++r) {
-    launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, ctx->q_power, ctx->q_flag, ctx->q_cidx,
-                         ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->tr_skip_a, ctx->sc_wg, ctx->q_planned, ctx->q_err);
-    CK(hipMemsetAsync(ctx->tr_cnt, 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t), st));
-    launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->tr_thr, ctx->tr_power, ctx->tr_flag, ctx->q_cidx,
-                         ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->tr_skip_b, ctx->sc_wg, ctx->tr_planned, ctx->q_err, true);
-    launch_quorum_union(st, N, ctx->tr_skip_a, ctx->tr_skip_b, ctx->sc_hit, ctx->tr_side, ctx->sc_wg, ctx->tr_cnt);
-    launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
-  }
-  CK(hipEventRecord(e[2], st));
-  for (int r = 0; r < reps; ++r) {
-    CK(hipMemsetAsync(ctx->vs_dv, 0, nc, st));
-    CK(hipMemsetAsync(ctx->vs_set, 0, 2 * n * sizeof(uint64_t), st));
-    launch_valset_pairs(st, N, ctx->q_coff, ctx->q_cidx, ctx->tr_skip_a, ctx->vs_who, ctx->vs_set, ctx->vs_dv);
-    CK(hipMemsetAsync(ctx->tr_dv, 0, nc, st));
-    CK(hipMemsetAsync(ctx->tr_set, 0, 2 * n * sizeof(uint64_t), st));
-    launch_valset_pairs(st, N, ctx->q_coff, ctx->q_cidx, ctx->tr_skip_b, ctx->tr_who, ctx->tr_set, ctx->tr_dv);
-  }
-  CK(hipGetLastError());
-  CK(hipEventRecord(e[3], st));
-  CK(hipEventSynchronize(e[3]));
-  for (int j = 0; j < 3 && ms; ++j) {
-    float t = 0.f;
-    CK(hipEventElapsedTime(&t, e[j], e[j + 1]));
-    ms[j] = t / (float)reps;
-  }
-  return EDC_OK;
+  const QuorumTrust tr{trust_ver, trust_threshold, nullptr, nullptr, nullptr};
+  return valset_debug_select_body(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, reps, 3, ms, &tr);
 }
 
 }  // extern "C"
