@@ -479,6 +479,12 @@ def _arena(msgs):
     return b"".join(bytes(m) for m in msgs) or b"\0", offs
 
 
+def _joined(*lists):
+    """Each list of byte strings as one buffer; an empty list as one zero byte, so that the C side
+    gets a pointer it never reads, not null."""
+    return tuple(b"".join(x) or b"\0" for x in lists)
+
+
 def _tmpl_items(tpl, holes, var_off=None):
     """(uint16 tpl[n], var bytes, uint32 var_off[n+1]) of a templated call: the holes packed back to
     back. var_off overrides the offsets computed from the holes (tests of the refusals)."""
@@ -542,54 +548,49 @@ class Engine:
     def batch_verify(self, vks, sigs, msgs, z_seed=None, z=None, want_check8=False):
         n = len(vks)
         arena, offs = _arena(msgs)
+        vkb, sigb = _joined(vks, sigs)
         check8 = ctypes.create_string_buffer(32) if want_check8 else None
         with self._lock:
             if z is not None:
-                rc = self.lib.edc_batch_verify_z(self.ctx, n, b"".join(vks) or b"\0", b"".join(sigs) or b"\0", arena,
-                                                 offs, bytes(z) or b"\0", check8)
+                rc = self.lib.edc_batch_verify_z(self.ctx, n, vkb, sigb, arena, offs, bytes(z) or b"\0", check8)
             else:
-                rc = self.lib.edc_batch_verify(self.ctx, n, b"".join(vks) or b"\0", b"".join(sigs) or b"\0", arena,
-                                               offs, bytes(z_seed), check8)
+                rc = self.lib.edc_batch_verify(self.ctx, n, vkb, sigb, arena, offs, bytes(z_seed), check8)
         self._check(rc)
         return rc, (check8.raw if check8 is not None else None)
 
     def batch_verify_prehashed(self, vks, sigs, ks, z_seed=None, z=None, want_check8=False):
         """Batch of prehashed items {vk_bytes, sig, k} (edc_batch_verify_prehashed): the reference's
         Verifier::verify over Items whose k was computed at Item::from (src/batch.rs:76-94)."""
-        n = len(vks)
         check8 = ctypes.create_string_buffer(32) if want_check8 else None
         with self._lock:
             rc = self.lib.edc_batch_verify_prehashed(
-                self.ctx, n, b"".join(vks) or b"\0", b"".join(sigs) or b"\0", b"".join(ks) or b"\0",
+                self.ctx, len(vks), *_joined(vks, sigs, ks),
                 bytes(z_seed) if z is None else None, (bytes(z) or b"\0") if z is not None else None, check8)
         self._check(rc)
         return rc, (check8.raw if check8 is not None else None)
 
-    def batch_submit_prehashed(self, vks, sigs, ks, z_seed, z_base=0, want_check8=False):
-        """Asynchronous prehashed batch from host buffers (edc_batch_submit_prehashed)."""
-        n = len(vks)
-        bufs = (b"".join(vks) or b"\0", b"".join(sigs) or b"\0", b"".join(ks) or b"\0", bytes(z_seed))
+    def _batch_submit(self, fn, n, bufs, z_base, want_check8):
+        """One host submission: fn(ctx, n, *bufs, z_base, want_check8) -> ticket; bufs, the staged host
+        buffers with the z seed last, are kept alive here until batch_wait(ticket)."""
         with self._lock:
-            t = self.lib.edc_batch_submit_prehashed(self.ctx, n, bufs[0], bufs[1], bufs[2], bufs[3], z_base,
-                                                    1 if want_check8 else 0)
+            t = fn(self.ctx, n, *bufs, z_base, 1 if want_check8 else 0)
             if t < 0:
                 self._check(t)
             self._host_inflight[t] = bufs
         return t
+
+    def batch_submit_prehashed(self, vks, sigs, ks, z_seed, z_base=0, want_check8=False):
+        """Asynchronous prehashed batch from host buffers (edc_batch_submit_prehashed)."""
+        return self._batch_submit(self.lib.edc_batch_submit_prehashed, len(vks), (*_joined(vks, sigs, ks), bytes(z_seed)),
+                                  z_base, want_check8)
 
     def batch_submit_prehashed_indexed(self, key_idx, sigs, ks, z_seed, z_base=0, want_check8=False):
         """edc_batch_submit_prehashed with keys given as positions in the last keycache_load list
         (100 bytes per item over PCIe)."""
         n = len(sigs)
         idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
-        bufs = (idx, b"".join(sigs) or b"\0", b"".join(ks) or b"\0", bytes(z_seed))
-        with self._lock:
-            t = self.lib.edc_batch_submit_prehashed_indexed(self.ctx, n, bufs[0], bufs[1], bufs[2], bufs[3], z_base,
-                                                            1 if want_check8 else 0)
-            if t < 0:
-                self._check(t)
-            self._host_inflight[t] = bufs
-        return t
+        return self._batch_submit(self.lib.edc_batch_submit_prehashed_indexed, n, (idx, *_joined(sigs, ks), bytes(z_seed)),
+                                  z_base, want_check8)
 
     def batch_verify_prehashed_fallback(self, vks, sigs, ks, z_seed):
         """(code, per-item Item::verify_single codes, number invalid, check8) of a prehashed batch."""
@@ -598,39 +599,23 @@ class Engine:
         v = ctypes.create_string_buffer(max(n, 1))
         cnt = ctypes.c_int(0)
         with self._lock:
-            rc = self.lib.edc_batch_verify_prehashed_fallback(self.ctx, n, b"".join(vks) or b"\0",
-                                                              b"".join(sigs) or b"\0", b"".join(ks) or b"\0",
-                                                              bytes(z_seed), v, ctypes.byref(cnt), check8)
+            rc = self.lib.edc_batch_verify_prehashed_fallback(self.ctx, n, *_joined(vks, sigs, ks), bytes(z_seed), v,
+                                                              ctypes.byref(cnt), check8)
         self._check(rc)
         return rc, list(v.raw[:n]), cnt.value, check8.raw
 
     def batch_submit(self, vks, sigs, msgs, z_seed, z_base=0, want_check8=False):
         """Asynchronous host-buffer batch (edc_batch_submit): returns a ticket; the staged host
         buffers are kept alive here until batch_wait(ticket)."""
-        n = len(vks)
-        arena, offs = _arena(msgs)
-        bufs = (b"".join(vks) or b"\0", b"".join(sigs) or b"\0", arena, offs, bytes(z_seed))
-        with self._lock:
-            t = self.lib.edc_batch_submit(self.ctx, n, bufs[0], bufs[1], bufs[2], bufs[3], bufs[4], z_base,
-                                          1 if want_check8 else 0)
-            if t < 0:
-                self._check(t)
-            self._host_inflight[t] = bufs
-        return t
+        return self._batch_submit(self.lib.edc_batch_submit, len(vks), (*_joined(vks, sigs), *_arena(msgs), bytes(z_seed)),
+                                  z_base, want_check8)
 
     def batch_submit_indexed(self, key_idx, sigs, msgs, z_seed, z_base=0, want_check8=False):
         """edc_batch_submit with keys given as positions in the last keycache_load list."""
         n = len(sigs)
-        arena, offs = _arena(msgs)
         idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
-        bufs = (idx, b"".join(sigs) or b"\0", arena, offs, bytes(z_seed))
-        with self._lock:
-            t = self.lib.edc_batch_submit_indexed(self.ctx, n, bufs[0], bufs[1], bufs[2], bufs[3], bufs[4], z_base,
-                                                  1 if want_check8 else 0)
-            if t < 0:
-                self._check(t)
-            self._host_inflight[t] = bufs
-        return t
+        return self._batch_submit(self.lib.edc_batch_submit_indexed, n, (idx, *_joined(sigs), *_arena(msgs), bytes(z_seed)),
+                                  z_base, want_check8)
 
     # ---- templated messages (edc_tmpl_*): msg_i = head[tpl[i]] || hole_i || tail[tpl[i]] ----
     def tmpl_expand_device(self, templates, n, d_tpl, d_var, d_var_off, var_bytes, d_msg_out, msg_cap, d_msg_off_out):
@@ -1377,16 +1362,14 @@ class Engine:
         arena, offs = _arena(msgs)
         out = ctypes.create_string_buffer(max(n, 1))
         with self._lock:
-            self._check(self.lib.edc_verify_each(self.ctx, n, b"".join(vks) or b"\0", b"".join(sigs) or b"\0",
-                                                 arena, offs, out))
+            self._check(self.lib.edc_verify_each(self.ctx, n, *_joined(vks, sigs), arena, offs, out))
         return list(out.raw[:n])
 
     def verify_prehashed_each(self, vks, sigs, ks):
         n = len(vks)
         out = ctypes.create_string_buffer(max(n, 1))
         with self._lock:
-            self._check(self.lib.edc_verify_prehashed_each(self.ctx, n, b"".join(vks) or b"\0",
-                                                           b"".join(sigs) or b"\0", b"".join(ks) or b"\0", out))
+            self._check(self.lib.edc_verify_prehashed_each(self.ctx, n, *_joined(vks, sigs, ks), out))
         return list(out.raw[:n])
 
     def challenge(self, vks, sigs, msgs):
@@ -1394,8 +1377,7 @@ class Engine:
         arena, offs = _arena(msgs)
         out = ctypes.create_string_buffer(max(32 * n, 1))
         with self._lock:
-            self._check(self.lib.edc_challenge(self.ctx, n, b"".join(vks) or b"\0", b"".join(sigs) or b"\0",
-                                               arena, offs, out))
+            self._check(self.lib.edc_challenge(self.ctx, n, *_joined(vks, sigs), arena, offs, out))
         return [out.raw[32 * i:32 * i + 32] for i in range(n)]
 
     def decompress(self, encs):
@@ -1522,7 +1504,7 @@ class Engine:
         if len(msgs if ks is None else ks) != n:
             raise ValueError("lists of different lengths")
         if ks is not None:
-            return None, None, b"".join(ks) or b"\0"
+            return None, None, _joined(ks)[0]
         arena, offs = _arena(msgs)
         return arena, offs, None
 
@@ -1537,8 +1519,8 @@ class Engine:
         check8 = ctypes.create_string_buffer(32)
         miss = ctypes.c_size_t(0)
         with self._lock:
-            rc = self.lib.edc_sigcache_batch_verify(self.ctx, n, b"".join(vks) or b"\0", b"".join(sigs) or b"\0",
-                                                    arena, offs, kb, seed, check8, ctypes.byref(miss))
+            rc = self.lib.edc_sigcache_batch_verify(self.ctx, n, *_joined(vks, sigs), arena, offs, kb, seed, check8,
+                                                    ctypes.byref(miss))
         self._check(rc)
         return rc, check8.raw, miss.value
 
@@ -1565,8 +1547,7 @@ class Engine:
         out = ctypes.create_string_buffer(max(n, 1))
         miss = ctypes.c_size_t(0)
         with self._lock:
-            self._check(self.lib.edc_sigcache_verify_each(self.ctx, n, b"".join(vks) or b"\0",
-                                                          b"".join(sigs) or b"\0", arena, offs, kb, out,
+            self._check(self.lib.edc_sigcache_verify_each(self.ctx, n, *_joined(vks, sigs), arena, offs, kb, out,
                                                           ctypes.byref(miss)))
         return list(out.raw[:n]), miss.value
 

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -672,6 +673,15 @@ static void seed_words(const uint8_t* seed, uint32_t w[8]) {
                 : 0u;
 }
 
+// The message offsets as the kernels read them (0-based): the caller's own when they start at 0,
+// else rebased into `keep`, which must outlive the copy that reads it.
+static const uint64_t* rebased_offsets(size_t n, const uint64_t* msg_off, std::vector<uint64_t>& keep) {
+  if (msg_off[0] == 0) return msg_off;
+  keep.resize(n + 1);
+  for (size_t i = 0; i <= n; ++i) keep[i] = msg_off[i] - msg_off[0];
+  return keep.data();
+}
+
 // Stage the message arena + offsets (0-based) into the context's device buffers (slot 0 stream).
 static int upload_msgs(edc_ctx* ctx, size_t n, const uint8_t* msg, const uint64_t* msg_off) {
   if (n && !msg_off) { ctx->err = "null msg_off"; return EDC_ERR_ARG; }
@@ -686,25 +696,25 @@ static int upload_msgs(edc_ctx* ctx, size_t n, const uint8_t* msg, const uint64_
   if (!n) return 0;
   hipStream_t st = ctx->st();
   if (mbytes) CK(hipMemcpyAsync(ctx->msg, msg + msg_off[0], mbytes, hipMemcpyHostToDevice, st));
-  if (msg_off[0] == 0) {
-    CK(hipMemcpyAsync(ctx->off, msg_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  } else {
-    std::vector<uint64_t> o(n + 1);
-    for (size_t i = 0; i <= n; ++i) o[i] = msg_off[i] - msg_off[0];
-    CK(hipMemcpyAsync(ctx->off, o.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    CK(hipStreamSynchronize(st));
-  }
+  std::vector<uint64_t> tmp;
+  const uint64_t* off = rebased_offsets(n, msg_off, tmp);
+  CK(hipMemcpyAsync(ctx->off, off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  if (off != msg_off) CK(hipStreamSynchronize(st));   // tmp does not outlive this call
   return 0;
 }
 
-// Stage the host inputs (keys, signatures, messages) into the context's device buffers.
-static int upload(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
-                  const uint64_t* msg_off) {
+// Stage host items into the context's device buffers on slot 0's stream: keys, signatures and
+// either the messages (k null: upload_msgs, which also makes the room) or the 32-byte challenges
+// into k_dst, the slot's k array or ctx->kbuf, for which the caller has made the room (its own
+// ensure_* calls). No synchronization beyond upload_msgs' own.
+static int stage_host(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
+                      const uint64_t* msg_off, const uint8_t* k = nullptr, uint32_t* k_dst = nullptr) {
   if (n && (!vk || !sig)) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  int rc = upload_msgs(ctx, n, msg, msg_off);
+  int rc = k ? 0 : upload_msgs(ctx, n, msg, msg_off);
   if (rc || !n) return rc;
   CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, ctx->st()));
   CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, ctx->st()));
+  if (k) CK(hipMemcpyAsync(k_dst, k, n * 32, hipMemcpyHostToDevice, ctx->st()));
   return 0;
 }
 
@@ -736,46 +746,72 @@ static int stage_keys_sigs(edc_ctx* ctx, hipStream_t st, size_t n, const uint8_t
   return 0;
 }
 
-static int upload_slot(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
-                       const uint64_t* msg_off, const uint32_t* key_idx = nullptr) {
-  if (n && ((!vk && !key_idx) || !sig || !msg_off)) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  const size_t mbytes = n ? (size_t)(msg_off[n] - msg_off[0]) : 0;
+// One batch's inputs as enqueue_batch, run_batch_sync, batch_with_fallback and fallback_ranges
+// read them, all on the device: the items (keys, signatures and either the message arena with its
+// 0-based offsets or, k given, the prehashed challenges: then the messages are not read and may be
+// null), where z comes from (d_z, else drawn from z_seed at z_base + i), and whether the result
+// block carries the compressed check8 (a submission's want_check8; the synchronous helpers set it
+// themselves from the check8 they are given).
+struct BatchIn {
+  const uint8_t *vk, *sig, *msg;
+  const uint64_t* off;
+  const uint32_t* k;
+  const uint8_t* z_seed;
+  uint64_t z_base;
+  const uint8_t* d_z;
+  bool compress;
+};
+
+// Messages (k null) or, for prehashed items (reference Item = {vk_bytes, sig, k},
+// src/batch.rs:76-80), the 32-byte challenges straight into the slot's k array: 128 B per item
+// over PCIe, 100 B with key_idx, and no message bytes. `in` is pointed at the staged items.
+static int upload_slot(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                       const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k, BatchIn& in) {
+  if (n && ((!vk && !key_idx) || !sig || (!k && !msg_off))) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  const size_t mbytes = n && !k ? (size_t)(msg_off[n] - msg_off[0]) : 0;
   if (mbytes && !msg) { ctx->err = "null msg"; return EDC_ERR_ARG; }
   int rc = ensure_slot_inputs(ctx, s, n, mbytes);
+  if (!rc && k) rc = ensure_slot(ctx, s, n);
   if (rc) return rc;
+  in.vk = s.in_vk;
+  in.sig = s.in_sig;
+  in.msg = k ? nullptr : s.in_msg.get();
+  in.off = k ? nullptr : s.in_off.get();
+  in.k = k ? s.k.get() : nullptr;
   if (!n) return 0;
   hipStream_t st = s.st;
-  const uint64_t* off = msg_off;
-  if (msg_off[0] != 0) {
-    s.in_rebased.resize(n + 1);
-    for (size_t i = 0; i <= n; ++i) s.in_rebased[i] = msg_off[i] - msg_off[0];
-    off = s.in_rebased.data();
+  if (k) {
+    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, s.in_idx, s.in_vk, s.in_sig))) return rc;
+    CK(hipMemcpyAsync(s.k, k, n * 32, hipMemcpyHostToDevice, st));
+    return 0;
   }
-  CK(hipMemcpyAsync(s.in_off, off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  // rebased offsets stay alive in the slot until it is reused
+  CK(hipMemcpyAsync(s.in_off, rebased_offsets(n, msg_off, s.in_rebased), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   if (mbytes) CK(hipMemcpyAsync(s.in_msg, msg + msg_off[0], mbytes, hipMemcpyHostToDevice, st));
   return stage_keys_sigs(ctx, st, n, vk, key_idx, sig, s.in_idx, s.in_vk, s.in_sig);
 }
 
-// Prehashed host submissions (reference Item = {vk_bytes, sig, k}, src/batch.rs:76-80): keys and
-// signatures into the slot's input buffers, the 32-byte challenges straight into the slot's k
-// array (128 B per item over PCIe, no message bytes).
-static int upload_slot_prehashed(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* vk, const uint8_t* sig,
-                                 const uint8_t* k, const uint32_t* key_idx = nullptr) {
-  if (n && ((!vk && !key_idx) || !sig || !k)) { ctx->err = "null input"; return EDC_ERR_ARG; }
-  int rc = ensure_slot_inputs(ctx, s, n, 0);
-  if (rc) return rc;
-  rc = ensure_slot(ctx, s, n);
-  if (rc || !n) return rc;
-  // with key_idx, 100 B per item
-  if ((rc = stage_keys_sigs(ctx, s.st, n, vk, key_idx, sig, s.in_idx, s.in_vk, s.in_sig))) return rc;
-  CK(hipMemcpyAsync(s.k, k, n * 32, hipMemcpyHostToDevice, s.st));
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// caller-supplied device arrays are read with 16-byte loads: every pointer given (null: not given,
+// passes) must be aligned; `what` names them in the refusal
+static int check_aligned16(edc_ctx* ctx, const char* what, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (!aligned16(p)) { ctx->err = std::string(what) + " must be 16-byte aligned"; return EDC_ERR_ARG; }
   return 0;
 }
-
-// caller-supplied device k arrays are read with 16-byte loads
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // sub-arrays of one staged piece start at 16-byte boundaries
 static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// Scalar::from_hash never yields k >= l: the per-item entries refuse such a caller k here, on the
+// host; the batch entries refuse it at the wait (FLAG_KARG)
+static int k_all_canonical(edc_ctx* ctx, size_t n, const uint8_t* k) {
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t w[8];
+    memcpy(w, k + 32 * i, 32);
+    if (!sc_is_canonical(w)) { ctx->err = "prehashed k is not a canonical scalar"; return EDC_ERR_ARG; }
+  }
+  return 0;
+}
 
 static uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -810,16 +846,14 @@ static uint32_t key_lanes(const edc_ctx* ctx, size_t n, bool per_sig) {
 // z and coefficients, ZIP215 decode of R_i and the keys. No host synchronization. With d_k (the
 // prehashed entries: the caller's queue-time k, src/batch.rs:76-94) SHA-512 is skipped and the
 // messages are not read (d_msg / d_off may be null).
-static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
-                          const uint8_t* d_msg, const uint64_t* d_off, const uint8_t* z_seed, uint64_t z_base,
-                          const uint8_t* d_z, bool with_bin, const MsmPlan* P, bool force_per_sig = false,
-                          bool split = false, const uint32_t* d_k = nullptr) {
+static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const BatchIn& in, const MsmPlan* P,
+                          bool force_per_sig = false, bool split = false) {
+  const uint8_t *d_vk = in.vk, *d_sig = in.sig, *d_z = in.d_z;
+  const uint32_t* d_k = in.k;
+  const bool with_bin = P != nullptr;
   if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
-  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_z && !aligned16(d_z)) || (d_k && !aligned16(d_k)))) {
-    ctx->err = "device vk / sig / z / k arrays must be 16-byte aligned";
-    return EDC_ERR_ARG;
-  }
-  int rc = ensure_slot(ctx, s, n);
+  int rc = n ? check_aligned16(ctx, "device vk / sig / z / k arrays", {d_vk, d_sig, d_z, d_k}) : 0;
+  if (!rc) rc = ensure_slot(ctx, s, n);
   if (rc) return rc;
   s.kin = d_k ? d_k : s.k;
   s.nmulti = 0;
@@ -827,7 +861,7 @@ static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, 
   const uint32_t T = (uint32_t)next_pow2(2 * (n < 128 ? 128 : n));
   if (T > s.cap_T) { ctx->err = "hash table capacity"; return EDC_ERR_ARG; }
   uint32_t seed[8];
-  seed_words(z_seed, seed);
+  seed_words(in.z_seed, seed);
   hipStream_t st = s.st;
   s.timed = ctx->timing;
   auto mark = [&](int ph) {
@@ -861,7 +895,7 @@ static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, 
   // sort chain queued behind SHA-512 ran after the decode instead of beside it.
   const bool dual = EDC_DUAL_STREAM && s.st2 && !s.timed;
   mark(PH_CHALLENGE);
-  if (!d_k && EDC_RUN(2)) launch_challenge(st, N, d_vk, d_sig, d_msg, d_off, s.k);
+  if (!d_k && EDC_RUN(2)) launch_challenge(st, N, d_vk, d_sig, in.msg, in.off, s.k);
   if (dual) {
     CK(hipEventRecord(s.ev_keys, st));
     CK(hipStreamWaitEvent(s.st2, s.ev_keys, 0));
@@ -871,7 +905,7 @@ static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, 
     CK(hipEventRecord(s.ev_dec, s.st2));
   }
   mark(PH_COEF);
-  if (EDC_RUN(4)) launch_coef(st, N, d_sig, s.kin, d_z, seed, z_base, s.key_index, s.scal, s.key_acc, s.u_acc, s.itembad, s.flags,
+  if (EDC_RUN(4)) launch_coef(st, N, d_sig, s.kin, d_z, seed, in.z_base, s.key_index, s.scal, s.key_acc, s.u_acc, s.itembad, s.flags,
               per_sig, s.coef_part, split);
   mark(PH_MSM_BIN);
   if (with_bin && EDC_RUN(8))
@@ -893,10 +927,7 @@ static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, 
 }
 
 // Enqueue the whole batch pipeline on slot s (device-resident inputs); no host synchronization.
-static int enqueue_batch(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
-                         const uint8_t* d_msg, const uint64_t* d_off, const uint8_t* z_seed, uint64_t z_base,
-                         const uint8_t* d_z, int want_compress, const uint32_t* d_k = nullptr,
-                         bool latency = false) {
+static int enqueue_batch(edc_ctx* ctx, Slot& s, size_t n, const BatchIn& in, bool latency = false) {
   if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
   int rc = ensure_slot(ctx, s, n);
   if (rc) return rc;
@@ -904,7 +935,7 @@ static int enqueue_batch(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, c
   const MsmPlan P = batch_plan(ctx, n, per_sig, split);
   rc = ensure_msm(ctx, s, P, split ? msm_entry_capacity(P, 2 + 3 * n, 0) : msm_entry_capacity(P, n, n + 1));
   if (rc) return rc;
-  rc = enqueue_prefix(ctx, s, n, d_vk, d_sig, d_msg, d_off, z_seed, z_base, d_z, true, &P, per_sig, split, d_k);
+  rc = enqueue_prefix(ctx, s, n, in, &P, per_sig, split);
   if (rc) return rc;
   hipStream_t st = s.st;
   if (s.timed) (void)hipEventRecord(s.ev[PH_MSM_BUCKET], st);
@@ -914,7 +945,7 @@ static int enqueue_batch(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, c
   s.acc_nbin = P.nbin();
   if (s.timed) (void)hipEventRecord(s.ev[PH_MSM_TAIL], st);
   // the final kernel stores the result block to d_out and straight into the pinned h_out
-  if (EDC_RUN(128)) launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, want_compress, s.d_out, s.h_out);
+  if (EDC_RUN(128)) launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, in.compress, s.d_out, s.h_out);
   if (s.timed) {
     (void)hipEventRecord(s.ev[PH_N], st);
     // the accumulation's entry count (the last bin's offset + count), read at the wait without
@@ -947,10 +978,7 @@ static int multi_args(edc_ctx* ctx, uint32_t nb, size_t n_per, const uint8_t* d_
     return EDC_ERR_ARG;
   }
   if ((size_t)nb * n_per >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
-  if (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k))) {
-    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
-    return EDC_ERR_ARG;
-  }
+  if (check_aligned16(ctx, "device vk / sig / k arrays", {d_vk, d_sig, d_k})) return EDC_ERR_ARG;
   if (!d_k && (!d_msg || !d_off)) { ctx->err = "null msg"; return EDC_ERR_ARG; }
   return 0;
 }
@@ -1188,16 +1216,23 @@ static int finish_batch(edc_ctx* ctx, Slot& s, uint8_t check8[32], uint8_t parti
 }
 
 // Synchronous batch on slot 0.
-static int run_batch_sync(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
-                          const uint64_t* d_off, const uint8_t* z_seed, uint64_t z_base, const uint8_t* d_z,
-                          uint8_t check8[32], uint8_t partial[128], int* bad, const uint32_t* d_k = nullptr) {
+static int run_batch_sync(edc_ctx* ctx, size_t n, BatchIn in, uint8_t check8[32], uint8_t partial[128], int* bad) {
   Slot* s = claim_slot0(ctx);
   if (!s) return EDC_ERR_ARG;
+  in.compress = check8 != nullptr;
   // a synchronous call is one batch on an otherwise idle GPU: latency-shaped kernels (see
   // launch_msm_bucket); pipelined submissions keep the work-minimal ones
-  int rc = enqueue_batch(ctx, *s, n, d_vk, d_sig, d_msg, d_off, z_seed, z_base, d_z, check8 != nullptr, d_k, true);
+  int rc = enqueue_batch(ctx, *s, n, in, true);
   if (rc) return rc;
   return finish_batch(ctx, *s, check8, partial, bad);
+}
+
+// One submission on the claimed slot (null: refused, ctx->err says why), its items on the device:
+// the work-minimal pipeline, and the ticket once that is enqueued.
+static int64_t submit_batch(edc_ctx* ctx, Slot* s, size_t n, const BatchIn& in) {
+  if (!s) return EDC_ERR_ARG;
+  const int rc = enqueue_batch(ctx, *s, n, in);
+  return rc ? rc : take_ticket(ctx, *s);
 }
 
 // ---- synchronous host-buffer calls, copy overlapped with compute ----
@@ -1447,19 +1482,12 @@ static int run_host_sync(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_
   if (!host_chunked_ok(ctx, n)) {
     int rc = init_slot(ctx, s);
     if (rc) return rc;
-    if (k) {
-      if ((rc = ensure_n(ctx, n)) || (rc = ensure_slot(ctx, s, n))) return rc;
-      if (n) {
-        CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, ctx->st()));
-        CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, ctx->st()));
-        CK(hipMemcpyAsync(s.k, k, n * 32, hipMemcpyHostToDevice, ctx->st()));
-      }
-    } else if ((rc = upload(ctx, n, vk, sig, msg, msg_off))) {
-      return rc;
-    }
+    if (k && ((rc = ensure_n(ctx, n)) || (rc = ensure_slot(ctx, s, n)))) return rc;
+    if ((rc = stage_host(ctx, n, vk, sig, msg, msg_off, k, s.k))) return rc;
     if (z && n) CK(hipMemcpyAsync(ctx->zexp, z, n * 16, hipMemcpyHostToDevice, ctx->st()));
-    return run_batch_sync(ctx, n, ctx->vk, ctx->sig, k ? nullptr : ctx->msg, k ? nullptr : ctx->off,
-                          z ? nullptr : z_seed, 0, z ? ctx->zexp : nullptr, check8, nullptr, nullptr, k ? s.k : nullptr);
+    const BatchIn in{ctx->vk, ctx->sig, k ? nullptr : ctx->msg.get(), k ? nullptr : ctx->off.get(), k ? s.k.get() : nullptr,
+                     z ? nullptr : z_seed, 0, z ? ctx->zexp.get() : nullptr, false};
+    return run_batch_sync(ctx, n, in, check8, nullptr, nullptr);
   }
   std::vector<uint64_t> rebased;
   const int rc = enqueue_host_chunked(ctx, n, vk, sig, msg, msg_off, k, z, z_seed, check8 != nullptr, rebased);
@@ -1707,7 +1735,8 @@ int edc_batch_verify_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const u
                             uint64_t z_base, const uint8_t* d_z, uint8_t check8[32]) {
   if (!ctx || (!z_seed && !d_z)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  return run_batch_sync(ctx, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, z_base, d_z, check8, nullptr, nullptr);
+  return run_batch_sync(ctx, n, BatchIn{d_vk, d_sig, d_msg, d_msg_off, nullptr, z_seed, z_base, d_z, false},
+                        check8, nullptr, nullptr);
 }
 
 int64_t edc_batch_submit_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
@@ -1715,29 +1744,29 @@ int64_t edc_batch_submit_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, con
                                 uint64_t z_base, const uint8_t* d_z, int want_check8) {
   if (!ctx || (!z_seed && !d_z)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  Slot* sp = claim_next_slot(ctx);
-  if (!sp) return EDC_ERR_ARG;
-  Slot& s = *sp;
+  Slot* s = claim_next_slot(ctx);
 #ifdef EDC_BATCH_STAMPS
-  s.t_submit_us = host_us();
+  if (s) s->t_submit_us = host_us();
 #endif
-  int rc = enqueue_batch(ctx, s, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, z_base, d_z, want_check8 != 0);
-  if (rc) return rc;
-  return take_ticket(ctx, s);
+  return submit_batch(ctx, s, n, BatchIn{d_vk, d_sig, d_msg, d_msg_off, nullptr, z_seed, z_base, d_z, want_check8 != 0});
+}
+
+// the host submissions: the items are staged by upload_slot, z is drawn from the seed
+static int64_t submit_host(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig,
+                           const uint8_t* msg, const uint64_t* msg_off, const uint8_t* k, const uint8_t* z_seed,
+                           uint64_t z_base, int want_check8) {
+  Slot* s = claim_next_slot(ctx);
+  if (!s) return EDC_ERR_ARG;
+  BatchIn in{nullptr, nullptr, nullptr, nullptr, nullptr, z_seed, z_base, nullptr, want_check8 != 0};
+  const int rc = upload_slot(ctx, *s, n, vk, key_idx, sig, msg, msg_off, k, in);
+  return rc ? rc : submit_batch(ctx, s, n, in);
 }
 
 int64_t edc_batch_submit(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                          const uint64_t* msg_off, const uint8_t z_seed[32], uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  Slot* sp = claim_next_slot(ctx);
-  if (!sp) return EDC_ERR_ARG;
-  Slot& s = *sp;
-  int rc = upload_slot(ctx, s, n, vk, sig, msg, msg_off);
-  if (rc) return rc;
-  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.in_msg, s.in_off, z_seed, z_base, nullptr, want_check8 != 0);
-  if (rc) return rc;
-  return take_ticket(ctx, s);
+  return submit_host(ctx, n, vk, nullptr, sig, msg, msg_off, nullptr, z_seed, z_base, want_check8);
 }
 
 int64_t edc_batch_submit_indexed(edc_ctx* ctx, size_t n, const uint32_t* key_idx, const uint8_t* sig,
@@ -1745,15 +1774,8 @@ int64_t edc_batch_submit_indexed(edc_ctx* ctx, size_t n, const uint32_t* key_idx
                                  uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed || (n && !key_idx)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  if (check_key_idx(ctx, n, key_idx)) return EDC_ERR_ARG;
-  Slot* sp = claim_next_slot(ctx);
-  if (!sp) return EDC_ERR_ARG;
-  Slot& s = *sp;
-  int rc = upload_slot(ctx, s, n, nullptr, sig, msg, msg_off, key_idx);
-  if (rc) return rc;
-  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, s.in_msg, s.in_off, z_seed, z_base, nullptr, want_check8 != 0);
-  if (rc) return rc;
-  return take_ticket(ctx, s);
+  if (check_key_idx(ctx, n, key_idx)) return EDC_ERR_ARG;    // before the claim: a refused call takes no ticket
+  return submit_host(ctx, n, nullptr, key_idx, sig, msg, msg_off, nullptr, z_seed, z_base, want_check8);
 }
 
 int edc_batch_wait(edc_ctx* ctx, int64_t ticket, uint8_t check8[32], uint8_t partial[128], int* bad) {
@@ -1777,7 +1799,8 @@ int64_t edc_batch_submit_multi_device(edc_ctx* ctx, size_t nb, size_t n_per, con
   int rc;
   if (ctx->multi_union) {        // one batch over all items first (finish_multi)
     rc = multi_args(ctx, nbv, n_per, d_vk, d_sig, d_msg, d_msg_off, dk);
-    if (!rc) rc = enqueue_batch(ctx, s, (size_t)nbv * n_per, d_vk, d_sig, d_msg, d_msg_off, z_seed, z_base, nullptr, 0, dk);
+    if (!rc)
+      rc = enqueue_batch(ctx, s, (size_t)nbv * n_per, BatchIn{d_vk, d_sig, d_msg, d_msg_off, dk, z_seed, z_base, nullptr, false});
     if (rc) return rc;
     s.nmulti = nbv;
     s.mu_union = true;
@@ -1825,7 +1848,8 @@ int edc_batch_partial_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const 
                              uint64_t z_base, const uint8_t* d_z, uint8_t partial[128], int* bad) {
   if (!ctx || !partial || (!z_seed && !d_z)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  int rc = run_batch_sync(ctx, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, z_base, d_z, nullptr, partial, bad);
+  int rc = run_batch_sync(ctx, n, BatchIn{d_vk, d_sig, d_msg, d_msg_off, nullptr, z_seed, z_base, d_z, false}, nullptr,
+                          partial, bad);
   return rc < 0 ? rc : 0;
 }
 
@@ -1900,7 +1924,7 @@ int edc_challenge(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig,
                   const uint64_t* msg_off, uint8_t* k_out) {
   if (!ctx || (n && !k_out)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  int rc = upload(ctx, n, vk, sig, msg, msg_off);
+  int rc = stage_host(ctx, n, vk, sig, msg, msg_off);
   if (rc) return rc;
   if (!n) return 0;
   launch_challenge(ctx->st(), (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
@@ -1982,10 +2006,10 @@ static int64_t tmpl_batch_run(edc_ctx* ctx, bool sync, const edc_templates* ts, 
   if (!s) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
   if ((rc = tmpl_upload_slot(ctx, *s, n, vk, key_idx, sig, it, sh))) return rc;
-  rc = enqueue_batch(ctx, *s, n, s->in_vk, s->in_sig, s->tw.arena, s->tw.off, z_seed, z_base, nullptr, compress, nullptr,
-                     sync);
-  if (rc) return rc;
-  return sync ? finish_batch(ctx, *s, check8, nullptr, nullptr) : take_ticket(ctx, *s);
+  const BatchIn in{s->in_vk, s->in_sig, s->tw.arena, s->tw.off, nullptr, z_seed, z_base, nullptr, compress};
+  if (!sync) return submit_batch(ctx, s, n, in);
+  if ((rc = enqueue_batch(ctx, *s, n, in, true))) return rc;
+  return finish_batch(ctx, *s, check8, nullptr, nullptr);
 }
 
 int edc_tmpl_batch_verify(edc_ctx* ctx, const edc_templates* ts, size_t n, const uint8_t* vk, const uint32_t* key_idx,
@@ -2017,7 +2041,8 @@ int edc_tmpl_batch_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t n
     CK(hipMemcpyAsync(s.tw.h_flag, s.tw.flag, sizeof(int), hipMemcpyDeviceToHost, s.st));
     s.tw.check = true;
   }
-  rc = run_batch_sync(ctx, n, d_vk, d_sig, s.tw.arena, s.tw.off, z_seed, z_base, d_z, check8, nullptr, nullptr);
+  rc = run_batch_sync(ctx, n, BatchIn{d_vk, d_sig, s.tw.arena, s.tw.off, nullptr, z_seed, z_base, d_z, false},
+                      check8, nullptr, nullptr);
   s.tw.check = false;           // also when the batch never reached its wait
   return rc;
 }
@@ -2029,45 +2054,48 @@ int64_t edc_tmpl_batch_submit(edc_ctx* ctx, const edc_templates* ts, size_t n, c
   return tmpl_batch_run(ctx, false, ts, n, vk, key_idx, sig, tpl, var, var_off, z_seed, z_base, want_check8 != 0, nullptr);
 }
 
+// The per-item pass over n device items on stream st, the caller having made ensure_n's room:
+// Item::from's challenges into ctx->kbuf where the items come with messages (d_k null), then
+// Item::verify_single (src/batch.rs:104-107) with one quad of lanes per item (quad: the caller's
+// choice, for lists of at most kQuadVerifyMax items, whose pass is latency-bound) or one lane per
+// item, the codes into d_codes; h_codes given: copied there and waited for.
+static int verify_items(edc_ctx* ctx, hipStream_t st, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
+                        const uint8_t* d_msg, const uint64_t* d_off, const uint32_t* d_k, bool quad, uint8_t* d_codes,
+                        uint8_t* h_codes) {
+  if (!d_k) {
+    launch_challenge(st, (uint32_t)n, d_vk, d_sig, d_msg, d_off, ctx->kbuf);
+    d_k = ctx->kbuf;
+  }
+  if (quad)
+    launch_verify_quad(st, (uint32_t)n, d_vk, d_sig, d_k, ctx->btab, d_codes, ctx->kc(), ctx->bcomb);
+  else
+    launch_verify_single(st, (uint32_t)n, d_vk, d_sig, d_k, ctx->btab, ctx->vtab, d_codes, ctx->kc(), ctx->bcomb);
+  CK(hipGetLastError());
+  if (!h_codes) return 0;
+  CK(hipMemcpyAsync(h_codes, d_codes, n, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// The three entries below take one lane per item at every n.
 int edc_verify_prehashed_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* k,
                               uint8_t* verdicts) {
   if (!ctx || (n && (!vk || !sig || !k || !verdicts))) return EDC_ERR_ARG;
-  for (size_t i = 0; i < n; ++i) {        // Scalar::from_hash never yields k >= l (batch paths: FLAG_KARG)
-    uint32_t w[8];
-    memcpy(w, k + 32 * i, 32);
-    if (!sc_is_canonical(w)) { ctx->err = "prehashed k is not a canonical scalar"; return EDC_ERR_ARG; }
-  }
+  if (k_all_canonical(ctx, n, k)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
   int rc = ensure_n(ctx, n);
-  if (rc) return rc;
-  if (!n) return 0;
-  hipStream_t st = ctx->st();
-  CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
-  launch_verify_single(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->kbuf, ctx->btab, ctx->vtab, ctx->verdicts,
-                       ctx->kc(), ctx->bcomb);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(verdicts, ctx->verdicts, n, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  return 0;
+  if (rc || !n) return rc;
+  if ((rc = stage_host(ctx, n, vk, sig, nullptr, nullptr, k, ctx->kbuf))) return rc;
+  return verify_items(ctx, ctx->st(), n, ctx->vk, ctx->sig, nullptr, nullptr, ctx->kbuf, false, ctx->verdicts, verdicts);
 }
 
 int edc_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                     const uint64_t* msg_off, uint8_t* verdicts) {
   if (!ctx || (n && !verdicts)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  int rc = upload(ctx, n, vk, sig, msg, msg_off);
-  if (rc) return rc;
-  if (!n) return 0;
-  hipStream_t st = ctx->st();
-  launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
-  launch_verify_single(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->kbuf, ctx->btab, ctx->vtab, ctx->verdicts,
-                       ctx->kc(), ctx->bcomb);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(verdicts, ctx->verdicts, n, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  return 0;
+  int rc = stage_host(ctx, n, vk, sig, msg, msg_off);
+  if (rc || !n) return rc;
+  return verify_items(ctx, ctx->st(), n, ctx->vk, ctx->sig, ctx->msg, ctx->off, nullptr, false, ctx->verdicts, verdicts);
 }
 
 int edc_verify_each_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
@@ -2075,14 +2103,9 @@ int edc_verify_each_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const ui
   if (!ctx || (n && (!d_vk || !d_sig || !d_msg_off || !d_verdicts))) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
   int rc = ensure_n(ctx, n);
-  if (rc) return rc;
-  if (!n) return 0;
-  hipStream_t st = ctx->st();
-  launch_challenge(st, (uint32_t)n, d_vk, d_sig, d_msg, d_msg_off, ctx->kbuf);
-  launch_verify_single(st, (uint32_t)n, d_vk, d_sig, ctx->kbuf, ctx->btab, ctx->vtab, d_verdicts,
-                       ctx->kc(), ctx->bcomb);
-  CK(hipGetLastError());
-  CK(hipStreamSynchronize(st));
+  if (rc || !n) return rc;
+  if ((rc = verify_items(ctx, ctx->st(), n, d_vk, d_sig, d_msg, d_msg_off, nullptr, false, d_verdicts, nullptr))) return rc;
+  CK(hipStreamSynchronize(ctx->st()));
   return 0;
 }
 
@@ -2115,15 +2138,9 @@ static int verify_listed(edc_ctx* ctx, Slot& s, const std::vector<uint32_t>& idx
   hipStream_t st = s.st;
   CK(hipMemcpyAsync(ctx->fb_idx, idx.data(), c * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   launch_gather_items(st, (uint32_t)c, ctx->fb_idx, d_vk, d_sig, s.kin, g_vk, g_sig, g_k);
-  if (c <= kQuadVerifyMax)   // latency-bound: one quad of lanes per item
-    launch_verify_quad(st, (uint32_t)c, g_vk, g_sig, g_k, ctx->btab, ctx->verdicts, ctx->kc(), ctx->bcomb);
-  else
-    launch_verify_single(st, (uint32_t)c, g_vk, g_sig, g_k, ctx->btab, ctx->vtab, ctx->verdicts, ctx->kc(),
-                         ctx->bcomb);
-  CK(hipGetLastError());
   std::vector<uint8_t> v(c);
-  CK(hipMemcpyAsync(v.data(), ctx->verdicts, c, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
+  if ((rc = verify_items(ctx, st, c, g_vk, g_sig, nullptr, nullptr, g_k, c <= kQuadVerifyMax, ctx->verdicts, v.data())))
+    return rc;
   for (size_t j = 0; j < c; ++j) {
     verdicts[idx[j]] = v[j];
     *invalid += v[j] != 0;
@@ -2131,33 +2148,53 @@ static int verify_listed(edc_ctx* ctx, Slot& s, const std::vector<uint32_t>& idx
   return 0;
 }
 
-// After a failed batch on slot s (its k, decoded points, key grouping and per-item failure bits
-// still in place): the batch equation restricted to ~fb_ranges (default 32) contiguous ranges in
-// ONE MSM pass (range-tagged bins, fb_bits = 9-bit windows by default), [8]P_g == 0 per range; ranges whose check fails or that
-// hold an item with an undecodable R / key or a non-canonical s are verified item by item.
-// Items of passing ranges are valid (ZIP215: batch == single, with a fresh secret z: see
-// include/edc.h). verdicts (host, n bytes) receive Item::verify_single's code for every item.
-static int fallback_ranges(edc_ctx* ctx, Slot& s, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
-                           const uint8_t* d_msg, const uint64_t* d_off, const uint8_t* z_seed, uint64_t z_base,
-                           bool per_sig, uint32_t m, uint8_t* verdicts) {
-  memset(verdicts, 0, n);
-  if (!n) return 0;
-  // ~FB_RANGES ranges: each range-window bin then holds enough digits to amortize its fixed
-  // 256-bucket reduction, and a failing range costs no more than a small one in the per-item pass
-  // (that pass is latency-bound: one lane per item)
-  // the range count is capped so that the range-tagged plan fits MSM_MAX_BINS (G * bins per range)
+// How the grouped fallback cuts n items into ranges.
+struct FallbackGeometry {
+  size_t rsize;      // items per range, a multiple of COEF_CHUNK (k_coef's workgroups start on one)
+  uint32_t G, bpr;   // ranges (none of n = 0 items); MSM bins per range
+};
+
+// ~fb_ranges ranges: each range-window bin then holds enough digits to amortize its fixed
+// 256-bucket reduction, and a failing range costs no more than a small one in the per-item pass.
+// The range count is capped so that the range-tagged plan fits MSM_MAX_BINS (G * bins per range).
+static FallbackGeometry fallback_geometry(const edc_ctx* ctx, size_t n) {
   const uint32_t bpr = make_plan(ctx->fb_bits, ctx->fb_bits, 1).bins_per_range;
+  if (!n) return FallbackGeometry{0, 0, bpr};
   const uint32_t gmax = MSM_MAX_BINS / bpr;
   const uint32_t granges = ctx->fb_ranges < gmax ? ctx->fb_ranges : gmax;
   const size_t target = (n + granges - 1) / granges;
   const size_t rsize = (target + COEF_CHUNK - 1) / COEF_CHUNK * COEF_CHUNK;
-  const uint32_t G = (uint32_t)((n + rsize - 1) / rsize);
+  return FallbackGeometry{rsize, (uint32_t)((n + rsize - 1) / rsize), bpr};
+}
+
+// After a failed batch on slot s (its k, decoded points, key grouping and per-item failure bits
+// still in place): the batch equation restricted to ~fb_ranges (default 128) contiguous ranges in
+// ONE MSM pass (range-tagged bins, fb_bits = 9-bit windows by default), [8]P_g == 0 per range;
+// ranges whose check fails or that hold an item with an undecodable R / key or a non-canonical s
+// are verified item by item. Items of passing ranges are valid (ZIP215: batch == single, with a
+// fresh secret z: see include/edc.h). verdicts (host, n bytes) receive Item::verify_single's code
+// for every item. in: the failed batch's items and z seed / base (its k is s.kin; d_z is not read,
+// the fallback draws its z from the seed). redid (nullable): whether the prefix was redone on s,
+// which overwrites the grouped key state a caller may keep there.
+static int fallback_ranges(edc_ctx* ctx, Slot& s, size_t n, const BatchIn& in, bool per_sig, uint32_t m, uint8_t* verdicts,
+                           bool* redid = nullptr) {
+  const uint8_t *d_vk = in.vk, *d_sig = in.sig, *z_seed = in.z_seed;
+  const uint64_t z_base = in.z_base;
+  if (redid) *redid = false;
+  memset(verdicts, 0, n);
+  if (!n) return 0;
+  const FallbackGeometry geo = fallback_geometry(ctx, n);
+  const size_t rsize = geo.rsize;
+  const uint32_t G = geo.G;
   if (!per_sig && (size_t)G * m > s.cap_n) {
     // too many distinct keys for per-(range, key) sums: redo the prefix with one key term per
     // signature (the same group element)
     // (s.kin already holds this batch's k: computed by the first prefix or the caller's)
-    int rc = enqueue_prefix(ctx, s, n, d_vk, d_sig, d_msg, d_off, z_seed, z_base, nullptr, false, nullptr, true, false,
-                            s.kin);
+    if (redid) *redid = true;
+    BatchIn again = in;
+    again.k = s.kin;
+    again.d_z = nullptr;
+    int rc = enqueue_prefix(ctx, s, n, again, nullptr, true, false);
     if (rc) return rc;
     CK(hipStreamSynchronize(s.st));
     per_sig = true;
@@ -2217,24 +2254,24 @@ int edc_find_invalid_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const u
   if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
   if (!n) return 0;
-  int rc = enqueue_prefix(ctx, s, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, 0, nullptr, false, nullptr);
+  const BatchIn in{d_vk, d_sig, d_msg, d_msg_off, nullptr, z_seed, 0, nullptr, false};
+  int rc = enqueue_prefix(ctx, s, n, in, nullptr);
   if (rc) return rc;
   CK(hipStreamSynchronize(s.st));
   bool per_sig;
   uint32_t m;
   rc = slot_grouping(ctx, s, &per_sig, &m);
   if (rc) return rc;
-  return fallback_ranges(ctx, s, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, 0, per_sig, m, verdicts);
+  return fallback_ranges(ctx, s, n, in, per_sig, m, verdicts);
 }
 
 }  // extern "C"
 
-// batch on slot 0, then (on failure) the grouped fallback reusing its state; d_k: prehashed k
-static int batch_with_fallback(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig, const uint8_t* d_msg,
-                               const uint64_t* d_msg_off, const uint32_t* d_k, const uint8_t* z_seed,
-                               uint8_t* verdicts, int* n_invalid, uint8_t check8[32]) {
+// batch on slot 0, then (on failure) the grouped fallback reusing its state; z from in.z_seed at base 0
+static int batch_with_fallback(edc_ctx* ctx, size_t n, const BatchIn& in, uint8_t* verdicts, int* n_invalid,
+                               uint8_t check8[32]) {
   if (n_invalid) *n_invalid = 0;
-  int rc = run_batch_sync(ctx, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, 0, nullptr, check8, nullptr, nullptr, d_k);
+  int rc = run_batch_sync(ctx, n, in, check8, nullptr, nullptr);
   if (rc <= 0) {
     if (rc == 0 && n) memset(verdicts, 0, n);
     return rc;
@@ -2244,11 +2281,14 @@ static int batch_with_fallback(edc_ctx* ctx, size_t n, const uint8_t* d_vk, cons
   uint32_t m;
   int r2 = slot_grouping(ctx, s, &per_sig, &m);
   if (r2) return r2;
-  r2 = fallback_ranges(ctx, s, n, d_vk, d_sig, d_msg, d_msg_off, z_seed, 0, per_sig, m, verdicts);
+  r2 = fallback_ranges(ctx, s, n, in, per_sig, m, verdicts);
   if (r2 < 0) return r2;
   if (n_invalid) *n_invalid = r2;
   return EDC_INVALID_SIGNATURE;
 }
+
+// nothing of an empty prehashed batch is read, but its k must not be null (null is the message form)
+static const uint8_t kNoItems[1] = {0};
 
 extern "C" {
 
@@ -2257,7 +2297,8 @@ int edc_batch_verify_fallback_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk
                                      uint8_t* verdicts, int* n_invalid, uint8_t check8[32]) {
   if (!ctx || !z_seed || (n && (!d_vk || !d_sig || !d_msg_off || !verdicts))) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  return batch_with_fallback(ctx, n, d_vk, d_sig, d_msg, d_msg_off, nullptr, z_seed, verdicts, n_invalid, check8);
+  return batch_with_fallback(ctx, n, BatchIn{d_vk, d_sig, d_msg, d_msg_off, nullptr, z_seed, 0, nullptr, false},
+                             verdicts, n_invalid, check8);
 }
 
 // ---- prehashed items: the reference's batch::Item {vk_bytes, sig, k} (src/batch.rs:76-94) ----
@@ -2265,10 +2306,8 @@ int edc_batch_verify_prehashed(edc_ctx* ctx, size_t n, const uint8_t* vk, const 
                                const uint8_t z_seed[32], const uint8_t* z, uint8_t check8[32]) {
   if (!ctx || (!z_seed && !z) || (n && (!vk || !sig || !k || (!z_seed && !z)))) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  if (!n) {     // empty batch: Ok through the one-piece path (no input is read)
-    static const uint8_t none[1] = {0};
-    return run_host_sync(ctx, 0, none, none, nullptr, nullptr, none, nullptr, z ? nullptr : z_seed, check8);
-  }
+  if (!n)       // empty batch: Ok through the one-piece path (no input is read)
+    return run_host_sync(ctx, 0, kNoItems, kNoItems, nullptr, nullptr, kNoItems, nullptr, z ? nullptr : z_seed, check8);
   return run_host_sync(ctx, n, vk, sig, nullptr, nullptr, k, z, z_seed, check8);
 }
 
@@ -2276,10 +2315,10 @@ int edc_batch_verify_prehashed_device(edc_ctx* ctx, size_t n, const uint8_t* d_v
                                       const uint8_t* d_k, const uint8_t z_seed[32], uint64_t z_base,
                                       const uint8_t* d_z, uint8_t check8[32]) {
   if (!ctx || (!z_seed && !d_z) || (n && (!d_vk || !d_sig || !d_k))) return EDC_ERR_ARG;
-  if (!aligned16(d_k) || (d_z && !aligned16(d_z))) { ctx->err = "d_k / d_z must be 16-byte aligned"; return EDC_ERR_ARG; }
+  if (check_aligned16(ctx, "d_k / d_z", {d_k, d_z})) return EDC_ERR_ARG;     // before the device is touched
   CK(hipSetDevice(ctx->device));
-  return run_batch_sync(ctx, n, d_vk, d_sig, nullptr, nullptr, z_seed, z_base, d_z, check8, nullptr, nullptr,
-                        reinterpret_cast<const uint32_t*>(d_k));
+  const BatchIn in{d_vk, d_sig, nullptr, nullptr, reinterpret_cast<const uint32_t*>(d_k), z_seed, z_base, d_z, false};
+  return run_batch_sync(ctx, n, in, check8, nullptr, nullptr);
 }
 
 int64_t edc_batch_submit_prehashed_indexed(edc_ctx* ctx, size_t n, const uint32_t* key_idx, const uint8_t* sig,
@@ -2287,44 +2326,25 @@ int64_t edc_batch_submit_prehashed_indexed(edc_ctx* ctx, size_t n, const uint32_
                                            int want_check8) {
   if (!ctx || !z_seed || (n && !key_idx)) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  if (check_key_idx(ctx, n, key_idx)) return EDC_ERR_ARG;
-  Slot* sp = claim_next_slot(ctx);
-  if (!sp) return EDC_ERR_ARG;
-  Slot& s = *sp;
-  int rc = upload_slot_prehashed(ctx, s, n, nullptr, sig, k, key_idx);
-  if (rc) return rc;
-  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, nullptr, nullptr, z_seed, z_base, nullptr, want_check8 != 0, s.k);
-  if (rc) return rc;
-  return take_ticket(ctx, s);
+  if (check_key_idx(ctx, n, key_idx)) return EDC_ERR_ARG;    // before the claim: a refused call takes no ticket
+  return submit_host(ctx, n, nullptr, key_idx, sig, nullptr, nullptr, n ? k : kNoItems, z_seed, z_base, want_check8);
 }
 
 int64_t edc_batch_submit_prehashed(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* k,
                                    const uint8_t z_seed[32], uint64_t z_base, int want_check8) {
   if (!ctx || !z_seed) return EDC_ERR_ARG;
   CK(hipSetDevice(ctx->device));
-  Slot* sp = claim_next_slot(ctx);
-  if (!sp) return EDC_ERR_ARG;
-  Slot& s = *sp;
-  int rc = upload_slot_prehashed(ctx, s, n, vk, sig, k);
-  if (rc) return rc;
-  rc = enqueue_batch(ctx, s, n, s.in_vk, s.in_sig, nullptr, nullptr, z_seed, z_base, nullptr, want_check8 != 0, s.k);
-  if (rc) return rc;
-  return take_ticket(ctx, s);
+  return submit_host(ctx, n, vk, nullptr, sig, nullptr, nullptr, n ? k : kNoItems, z_seed, z_base, want_check8);
 }
 
 int64_t edc_batch_submit_prehashed_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
                                           const uint8_t* d_k, const uint8_t z_seed[32], uint64_t z_base,
                                           const uint8_t* d_z, int want_check8) {
   if (!ctx || (!z_seed && !d_z) || (n && (!d_vk || !d_sig || !d_k))) return EDC_ERR_ARG;
-  if (!aligned16(d_k) || (d_z && !aligned16(d_z))) { ctx->err = "d_k / d_z must be 16-byte aligned"; return EDC_ERR_ARG; }
+  if (check_aligned16(ctx, "d_k / d_z", {d_k, d_z})) return EDC_ERR_ARG;     // before the device is touched
   CK(hipSetDevice(ctx->device));
-  Slot* sp = claim_next_slot(ctx);
-  if (!sp) return EDC_ERR_ARG;
-  Slot& s = *sp;
-  int rc = enqueue_batch(ctx, s, n, d_vk, d_sig, nullptr, nullptr, z_seed, z_base, d_z, want_check8 != 0,
-                         reinterpret_cast<const uint32_t*>(d_k));
-  if (rc) return rc;
-  return take_ticket(ctx, s);
+  return submit_batch(ctx, claim_next_slot(ctx), n, BatchIn{d_vk, d_sig, nullptr, nullptr, reinterpret_cast<const uint32_t*>(d_k),
+                                                            z_seed, z_base, d_z, want_check8 != 0});
 }
 
 int edc_batch_verify_prehashed_fallback(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig,
@@ -2335,24 +2355,20 @@ int edc_batch_verify_prehashed_fallback(edc_ctx* ctx, size_t n, const uint8_t* v
   if (!claim_slot0(ctx)) return EDC_ERR_ARG;
   Slot& s = ctx->slot[0];
   int rc = ensure_n(ctx, n);
-  if (rc) return rc;
-  rc = ensure_slot(ctx, s, n);
-  if (rc) return rc;
-  if (n) {
-    CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, ctx->st()));
-    CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, ctx->st()));
-    CK(hipMemcpyAsync(s.k, k, n * 32, hipMemcpyHostToDevice, ctx->st()));
-  }
-  return batch_with_fallback(ctx, n, ctx->vk, ctx->sig, nullptr, nullptr, s.k, z_seed, verdicts, n_invalid, check8);
+  if (rc || (rc = ensure_slot(ctx, s, n)) || (rc = stage_host(ctx, n, vk, sig, nullptr, nullptr, n ? k : kNoItems, s.k)))
+    return rc;
+  return batch_with_fallback(ctx, n, BatchIn{ctx->vk, ctx->sig, nullptr, nullptr, s.k, z_seed, 0, nullptr, false},
+                             verdicts, n_invalid, check8);
 }
 
 int edc_batch_verify_prehashed_fallback_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* d_sig,
                                                const uint8_t* d_k, const uint8_t z_seed[32], uint8_t* verdicts,
                                                int* n_invalid, uint8_t check8[32]) {
   if (!ctx || !z_seed || (n && (!d_vk || !d_sig || !d_k || !verdicts))) return EDC_ERR_ARG;
-  if (!aligned16(d_k)) { ctx->err = "d_k must be 16-byte aligned"; return EDC_ERR_ARG; }
+  if (check_aligned16(ctx, "d_k", {d_k})) return EDC_ERR_ARG;                // before the device is touched
   CK(hipSetDevice(ctx->device));
-  return batch_with_fallback(ctx, n, d_vk, d_sig, nullptr, nullptr, reinterpret_cast<const uint32_t*>(d_k), z_seed,
+  return batch_with_fallback(ctx, n, BatchIn{d_vk, d_sig, nullptr, nullptr, reinterpret_cast<const uint32_t*>(d_k), z_seed, 0,
+                                             nullptr, false},
                              verdicts, n_invalid, check8);
 }
 
@@ -2497,7 +2513,7 @@ static int commits_check_tmpl_device(edc_ctx* ctx, const edc_templates* ts, size
 static int commits_enqueue(edc_ctx* ctx, Slot& s, size_t nc, const uint32_t* commit_off, size_t n, const uint8_t* d_vk,
                            const uint8_t* d_sig, const uint8_t* d_msg, const uint64_t* d_off, const uint32_t* d_k,
                            const uint8_t* z_seed, bool latency) {
-  int rc = enqueue_batch(ctx, s, n, d_vk, d_sig, d_msg, d_off, z_seed, 0, nullptr, 0, d_k, latency);
+  int rc = enqueue_batch(ctx, s, n, BatchIn{d_vk, d_sig, d_msg, d_off, d_k, z_seed, 0, nullptr, false}, latency);
   if (rc) return rc;
   s.commits = true;
   s.cm_nc = nc;
@@ -2514,13 +2530,11 @@ static int commits_enqueue_host(edc_ctx* ctx, Slot& s, size_t nc, const uint32_t
                                 const uint8_t* vk, const uint32_t* key_idx, const uint8_t* sig, const uint8_t* msg,
                                 const uint64_t* msg_off, const uint8_t* k, const uint8_t* z_seed, bool latency) {
   static const uint64_t no_off[1] = {0};
-  int rc;
-  if (k && n) {
-    if ((rc = upload_slot_prehashed(ctx, s, n, vk, sig, k, key_idx))) return rc;
-    return commits_enqueue(ctx, s, nc, commit_off, n, s.in_vk, s.in_sig, nullptr, nullptr, s.k, z_seed, latency);
-  }
-  if ((rc = upload_slot(ctx, s, n, vk, sig, msg, n ? msg_off : no_off, key_idx))) return rc;
-  return commits_enqueue(ctx, s, nc, commit_off, n, s.in_vk, s.in_sig, s.in_msg, s.in_off, nullptr, z_seed, latency);
+  BatchIn in{};
+  // an empty set takes the message form whatever it was given
+  const int rc = upload_slot(ctx, s, n, vk, key_idx, sig, msg, n ? msg_off : no_off, n ? k : nullptr, in);
+  if (rc) return rc;
+  return commits_enqueue(ctx, s, nc, commit_off, n, in.vk, in.sig, in.msg, in.off, in.k, z_seed, latency);
 }
 
 // A checked templated commit set into slot s (as tmpl_upload_slot): the per-item template array
@@ -2632,8 +2646,8 @@ static int commits_finish(edc_ctx* ctx, Slot& s, uint8_t* commit_verdicts, uint8
     own.resize(n);
     codes = own.data();
   }
-  rc = fallback_ranges(ctx, s, n, s.cm_vk, s.cm_sig, s.cm_msg, s.cm_moff, s.cm_seed, 0, per_sig, (uint32_t)f[FLAG_NKEYS],
-                       codes);
+  rc = fallback_ranges(ctx, s, n, BatchIn{s.cm_vk, s.cm_sig, s.cm_msg, s.cm_moff, nullptr, s.cm_seed, 0, nullptr, false}, per_sig,
+                       (uint32_t)f[FLAG_NKEYS], codes);
   if (rc < 0) return rc;
   const size_t bad = commits_reduce(nc, off, codes, commit_verdicts);
   if (n_bad) *n_bad = (int)bad;
@@ -3399,10 +3413,7 @@ static int sc_batch(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* 
   int rc = sc_ready(ctx);
   if (rc) return rc;
   if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
-  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || (d_k && !aligned16(d_k)))) {
-    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
-    return EDC_ERR_ARG;
-  }
+  if (n && check_aligned16(ctx, "device vk / sig / k arrays", {d_vk, d_sig, d_k})) return EDC_ERR_ARG;
   if (n_invalid) *n_invalid = 0;
   const uint32_t* k = reinterpret_cast<const uint32_t*>(d_k);
   if (n && !k) {            // Item::from for every item: the record, and so the lookup, needs k
@@ -3416,13 +3427,14 @@ static int sc_batch(edc_ctx* ctx, size_t n, const uint8_t* d_vk, const uint8_t* 
   if (n_miss) *n_miss = M.n;
   // an empty miss list still runs the n = 0 batch, whose k is never read
   const uint32_t* mk = M.n ? M.k : reinterpret_cast<const uint32_t*>(ctx->sc_hdr.get());
+  const BatchIn in{M.vk, M.sig, nullptr, nullptr, mk, z_seed, 0, nullptr, false};
   if (!verdicts) {
-    rc = run_batch_sync(ctx, M.n, M.vk, M.sig, nullptr, nullptr, z_seed, 0, nullptr, check8, nullptr, nullptr, mk);
+    rc = run_batch_sync(ctx, M.n, in, check8, nullptr, nullptr);
     if (rc != EDC_OK) return rc;     // a failed batch inserts nothing
     return (rc = sc_insert(ctx, M, nullptr)) ? rc : EDC_OK;
   }
   std::vector<uint8_t> mv(M.n ? M.n : 1);
-  const int code = batch_with_fallback(ctx, M.n, M.vk, M.sig, nullptr, nullptr, mk, z_seed, mv.data(), n_invalid, check8);
+  const int code = batch_with_fallback(ctx, M.n, in, mv.data(), n_invalid, check8);
   if (code < 0) return code;
   if (M.n) CK(hipMemcpyAsync(ctx->sc_mverd, mv.data(), M.n, hipMemcpyHostToDevice, ctx->st()));
   if ((rc = sc_verdicts_out(ctx, n, M, ctx->sc_mverd, verdicts))) return rc;
@@ -3514,10 +3526,7 @@ int edc_sigcache_lookup_device(edc_ctx* ctx, size_t n, const uint8_t* d_vk, cons
   int rc = sc_ready(ctx);
   if (rc) return rc;
   if (n >= (1ull << 28)) { ctx->err = "batch too large for one call (max 2^28 items)"; return EDC_ERR_ARG; }
-  if (n && (!aligned16(d_vk) || !aligned16(d_sig) || !aligned16(d_k))) {
-    ctx->err = "device vk / sig / k arrays must be 16-byte aligned";
-    return EDC_ERR_ARG;
-  }
+  if (n && check_aligned16(ctx, "device vk / sig / k arrays", {d_vk, d_sig, d_k})) return EDC_ERR_ARG;
   if ((rc = sc_order_after_inserts(ctx, ctx->st()))) return rc;
   launch_sc_lookup(ctx->st(), ctx->sc(), (uint32_t)n, d_vk, d_sig, reinterpret_cast<const uint32_t*>(d_k), d_hit,
                    nullptr);
@@ -3547,15 +3556,9 @@ int edc_sigcache_batch_verify_fallback_device(edc_ctx* ctx, size_t n, const uint
 // the message arena or the caller's k (into kbuf)
 static int sc_upload(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
                      const uint64_t* msg_off, const uint8_t* k) {
-  if (!k) return upload(ctx, n, vk, sig, msg, msg_off);
-  int rc = init_slot(ctx, ctx->slot[0]);
-  if (rc) return rc;
-  if ((rc = ensure_n(ctx, n)) || !n) return rc;
-  hipStream_t st = ctx->st();
-  CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(ctx->sig, sig, n * 64, hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(ctx->kbuf, k, n * 32, hipMemcpyHostToDevice, st));
-  return 0;
+  int rc = 0;
+  if (k && ((rc = init_slot(ctx, ctx->slot[0])) || (rc = ensure_n(ctx, n)))) return rc;
+  return stage_host(ctx, n, vk, sig, msg, msg_off, k, ctx->kbuf);
 }
 
 int edc_sigcache_batch_verify(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint8_t* sig, const uint8_t* msg,
@@ -3578,11 +3581,7 @@ int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const ui
   if (rc) return rc;
   // a hit is byte-identical to an inserted record, whose k was canonical: checking every k is
   // checking the misses' (Scalar::from_hash never yields k >= l)
-  for (size_t i = 0; k && i < n; ++i) {
-    uint32_t w[8];
-    memcpy(w, k + 32 * i, 32);
-    if (!sc_is_canonical(w)) { ctx->err = "prehashed k is not a canonical scalar"; return EDC_ERR_ARG; }
-  }
+  if (k && k_all_canonical(ctx, n, k)) return EDC_ERR_ARG;
   if ((rc = sc_upload(ctx, n, vk, sig, msg, msg_off, k))) return rc;
   hipStream_t st = ctx->st();
   if (n && !k) {
@@ -3592,12 +3591,8 @@ int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const ui
   ScMiss M;
   if ((rc = sc_partition(ctx, n, ctx->vk, ctx->sig, ctx->kbuf, &M))) return rc;
   if (n_miss) *n_miss = M.n;
-  if (M.n <= kQuadVerifyMax)
-    launch_verify_quad(st, (uint32_t)M.n, M.vk, M.sig, M.k, ctx->btab, ctx->verdicts, ctx->kc(), ctx->bcomb);
-  else
-    launch_verify_single(st, (uint32_t)M.n, M.vk, M.sig, M.k, ctx->btab, ctx->vtab, ctx->verdicts, ctx->kc(),
-                         ctx->bcomb);
-  CK(hipGetLastError());
+  if ((rc = verify_items(ctx, st, M.n, M.vk, M.sig, nullptr, nullptr, M.k, M.n <= kQuadVerifyMax, ctx->verdicts, nullptr)))
+    return rc;
   if ((rc = sc_verdicts_out(ctx, n, M, ctx->verdicts, verdicts))) return rc;
   if ((rc = sc_insert(ctx, M, ctx->verdicts))) return rc;
   CK(hipStreamSynchronize(st));
@@ -4110,8 +4105,8 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
   hipStream_t st = ctx->st();
   const size_t m = list.count;
   std::vector<uint8_t> mv(m ? m : 1);
-  const int code = batch_with_fallback(ctx, m, list.vk, list.sig, nullptr, nullptr, list.k, z_seed, mv.data(), nullptr,
-                                       out.check8);
+  const BatchIn in{list.vk, list.sig, nullptr, nullptr, list.k, z_seed, 0, nullptr, false};
+  const int code = batch_with_fallback(ctx, m, in, mv.data(), nullptr, out.check8);
   if (code < 0) return code;
   const unsigned long long ins0 = cq ? ctx->sc_hctr[0] : 0;
   if (cq && m) {
@@ -5703,11 +5698,7 @@ static int verifier_queue_host(edc_verifier* v, size_t m, const uint8_t* vk, con
   if (m && ((!vk && !key_idx) || !sig || (!k && !msg_off && !tm))) { ctx->err = "null input"; return EDC_ERR_ARG; }
   if (verifier_spent(v)) return EDC_ERR_ARG;
   if (!m) return 0;
-  if (key_idx) {
-    uint32_t mx = 0;
-    for (size_t i = 0; i < m; ++i) mx = key_idx[i] > mx ? key_idx[i] : mx;
-    if (mx >= ctx->kc_reg_m) { ctx->err = "key index outside the registered key list"; return EDC_ERR_ARG; }
-  }
+  if (key_idx && check_key_idx(ctx, m, key_idx)) return EDC_ERR_ARG;
   // templated items (tm, already checked): the arena is built on the device, sized by its bound
   const size_t mbytes = k ? 0 : tm ? tmpl_arena_bound(m, *tsh, tm->var_off[m]) : (size_t)(msg_off[m] - msg_off[0]);
   if (mbytes && !msg && !tm) { ctx->err = "null msg"; return EDC_ERR_ARG; }
@@ -6009,14 +6000,11 @@ static int verifier_fallback(edc_verifier* v, const uint8_t* z_seed, uint8_t* ve
   int r2 = slot_grouping(ctx, s, &per_sig, &m);
   if (r2) return r2;
   // with too many distinct keys for per-(range, key) sums the fallback redoes the prefix with one
-  // key term per signature on this slot (fallback_ranges), which overwrites the verifier's grouped
-  // key state: it is rebuilt below
-  const uint32_t bpr = make_plan(ctx->fb_bits, ctx->fb_bits, 1).bins_per_range;
-  const uint32_t gmax = MSM_MAX_BINS / bpr, granges = ctx->fb_ranges < gmax ? ctx->fb_ranges : gmax;
-  const size_t rsize = ((n + granges - 1) / granges + COEF_CHUNK - 1) / COEF_CHUNK * COEF_CHUNK;
-  const size_t G = (n + rsize - 1) / rsize;
-  const bool redo = !per_sig && G * m > s.cap_n;
-  r2 = fallback_ranges(ctx, s, n, v->vk, v->sig, nullptr, nullptr, z_seed, 0, per_sig, m, verdicts);
+  // key term per signature on this slot (fallback_ranges says so), which overwrites the verifier's
+  // grouped key state: it is rebuilt below
+  bool redo = false;
+  r2 = fallback_ranges(ctx, s, n, BatchIn{v->vk, v->sig, nullptr, nullptr, nullptr, z_seed, 0, nullptr, false}, per_sig, m,
+                       verdicts, &redo);
   s.kin = v->k;
   if (redo) {
     CK(hipStreamSynchronize(s.st));
@@ -6206,9 +6194,10 @@ static int shard_partial(edc_ctx* c, Shard& s, const uint8_t* vk, const uint8_t*
                          const uint64_t* msg_off, const uint8_t* z_seed) {
   if (hipSetDevice(c->device) != hipSuccess) return EDC_ERR_HIP;
   const size_t m = s.hi - s.lo;
-  int rc = upload(c, m, vk + 32 * s.lo, sig + 64 * s.lo, msg, msg_off + s.lo);
+  int rc = stage_host(c, m, vk + 32 * s.lo, sig + 64 * s.lo, msg, msg_off + s.lo);
   if (rc) return rc;
-  rc = run_batch_sync(c, m, c->vk, c->sig, c->msg, c->off, z_seed, s.lo, nullptr, nullptr, s.partial, &s.bad);
+  rc = run_batch_sync(c, m, BatchIn{c->vk, c->sig, c->msg, c->off, nullptr, z_seed, s.lo, nullptr, false}, nullptr, s.partial,
+                      &s.bad);
   return rc < 0 ? rc : 0;
 }
 
@@ -6512,7 +6501,8 @@ int edc_multi_batch_verify_fallback(edc_multi* M, size_t n, const uint8_t* vk, c
     uint32_t keys;
     int r = slot_grouping(c, sl, &per_sig, &keys);
     if (r) return r;
-    return fallback_ranges(c, sl, m, c->vk, c->sig, c->msg, c->off, z_seed, s.lo, per_sig, keys, verdicts + s.lo);
+    return fallback_ranges(c, sl, m, BatchIn{c->vk, c->sig, c->msg, c->off, nullptr, z_seed, s.lo, nullptr, false}, per_sig, keys,
+                           verdicts + s.lo);
   });
   int total = 0;
   for (size_t g = 0; g < sh.size(); ++g) {
