@@ -90,6 +90,7 @@ ABI_SYMBOLS = [
     "edc_vhist_quorum_verify", "edc_debug_vhist_select",
     "edc_vq_verify", "edc_debug_vq_last",
     "edc_vq_trust_resolve", "edc_debug_vq_trust_last", "edc_debug_vq_trust_select",
+    "edc_valhash_valset", "edc_valhash_vhist", "edc_valhash_vhist_match", "edc_debug_valhash_ms",
 ]
 
 
@@ -450,6 +451,11 @@ def load_library(path=None):
             lib.edc_debug_vq_trust_last.argtypes = [c_vp, c_u64p]
             lib.edc_debug_vq_trust_select.argtypes = [c_vp, c_sz, c_u32p, c_u32p, c_u32p, c_u8p, c_u32p, c_u8p, c_u64p,
                                                       c_u64p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+        if hasattr(lib, "edc_valhash_vhist"):                # absent from older A/B builds (tools/)
+            lib.edc_valhash_valset.argtypes = [c_vp, c_vp]
+            lib.edc_valhash_vhist.argtypes = [c_vp, ctypes.c_uint32, c_sz, c_vp]
+            lib.edc_valhash_vhist_match.argtypes = [c_vp, c_sz, c_u32p, c_vp, c_vp, c_szp]
+            lib.edc_debug_valhash_ms.argtypes = [c_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         if path is None:
             _lib = lib
         return lib
@@ -1131,6 +1137,46 @@ class Engine:
         total, members = (ctypes.c_uint64 * max(count, 1))(), (ctypes.c_uint32 * max(count, 1))()
         self._check(self.lib.edc_vhist_totals(self.ctx, v0, count, total, members))
         return list(total[:count]), list(members[:count])
+
+    # ---- validator-set hashes (edc_valhash_*): the Merkle root of a set, as include/edc.h states it ----
+    def valset_hash(self):
+        """edc_valhash_valset: the 32-byte root of the one set of valset_set_powers."""
+        out = ctypes.create_string_buffer(32)
+        with self._lock:
+            self._check(self.lib.edc_valhash_valset(self.ctx, out))
+        return out.raw
+
+    def vhist_hashes(self, v0=0, count=None):
+        """edc_valhash_vhist -> the roots of the versions v0 .. v0 + count - 1 of the history (count
+        None: up to the last), 32 bytes each."""
+        if count is None:
+            count = max(self.vhist_versions() - v0, 0)
+        out = ctypes.create_string_buffer(max(32 * count, 1))
+        with self._lock:
+            self._check(self.lib.edc_valhash_vhist(self.ctx, v0, count, out))
+        return [out.raw[32 * j:32 * j + 32] for j in range(count)]
+
+    def vhist_hash_match(self, commit_versions, expect):
+        """edc_valhash_vhist_match: expect[c] (32 bytes, the validators_hash of commit c's header) against
+        the root of version commit_versions[c], compared on the device -> (ok, n_mismatch): one
+        0 / 1 per commit and the number of zeros."""
+        expect = [bytes(e) for e in expect]
+        nc = len(expect)
+        if any(len(e) != 32 for e in expect):
+            raise InvalidSliceLength("expect: 32 bytes per commit")
+        ver = self._vhist_versions_arg(nc, commit_versions)
+        ok, bad = ctypes.create_string_buffer(max(nc, 1)), ctypes.c_size_t(0)
+        with self._lock:
+            self._check(self.lib.edc_valhash_vhist_match(self.ctx, nc, ver, b"".join(expect) or b"\0", ok, ctypes.byref(bad)))
+        return list(ok.raw[:nc]), int(bad.value)
+
+    def valhash_ms(self, reps=20):
+        """edc_debug_valhash_ms: mean times (ms) of the root kernel over every version of the history
+        and of the address kernel over the registered list."""
+        ms = (ctypes.c_float * 2)()
+        with self._lock:
+            self._check(self.lib.edc_debug_valhash_ms(self.ctx, reps, ms))
+        return {"roots": float(ms[0]), "addresses": float(ms[1])}
 
     @staticmethod
     def _vhist_versions_arg(nc, versions):
@@ -2164,6 +2210,32 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
         if trust_versions is not None:
             return res["commit_verdicts"], res["tally"], codes, res["trust_verdicts"], res["trust_tally"]
         return res["commit_verdicts"], res["tally"], codes
+
+    @staticmethod
+    def validator_set_hashes(versions=None, expect=None, engine=None):
+        """The Merkle root of the validator sets verify_quorum judges by (edc_valhash_*; not an API of
+        the reference): what a light client compares with the validators_hash of the header it
+        trusts before it judges a commit by a set it was handed. versions=None: the root of every
+        version of the engine's validator-set history (Engine.vhist_set), or, on an engine without a
+        history, [the root of its one set] (Engine.valset_set_powers). versions a list: the root of
+        each, in that order; a version is hashed once however often it occurs. With expect (32 bytes
+        per entry of versions) the compare runs on the device and the return value is
+        (ok, n_mismatch): ok[c] = 1 iff the root of versions[c] equals expect[c]."""
+        eng = engine or default_engine()
+        if expect is not None:
+            if versions is None:
+                raise ValueError("validator_set_hashes: expect goes with versions")
+            return eng.vhist_hash_match(list(versions), list(expect))
+        if versions is None:
+            return eng.vhist_hashes() if eng.vhist_versions() else [eng.valset_hash()]
+        versions = [int(v) for v in versions]
+        roots, run = {}, []
+        for v in sorted(set(versions)) + [None]:             # consecutive runs, one call each
+            if run and v != run[-1] + 1:
+                roots.update(zip(run, eng.vhist_hashes(run[0], len(run))))
+                run = []
+            run.append(v)
+        return [roots[v] for v in versions]
 
     class StreamVerifier:
         """reference src/batch.rs:110-217 with the reference's division of work: queue() does the

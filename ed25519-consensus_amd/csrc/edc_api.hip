@@ -25,6 +25,7 @@
 #include "quorum.h"
 #include "valset.h"
 #include "vhist.h"
+#include "valhash.h"
 #include "sigcache.h"
 #include "devbuf.h"
 
@@ -308,6 +309,14 @@ struct edc_ctx {
   uint32_t vh_count = 0;
   size_t vh_cap_c = 0;
   VhistView vhv() const { return VhistView{vh_off, vh_ver, vh_pow, vh_count}; }
+  // validator-set hashes (valhash.h; edc_valhash_valset, edc_valhash_vhist, edc_valhash_vhist_match): the
+  // address order of the registered list, ranked on the first call after a list is loaded (rank by
+  // position, by_rank the cache index of each rank; vx_ranked) and dropped with the history. Per
+  // call, on slot 0's stream: the roots, the staged versions | root indices | expected hashes, and
+  // the match bytes. No root is kept between calls.
+  DevBuf<uint32_t> vx_rank, vx_by_rank, vx_in;
+  bool vx_ranked = false;
+  DevBuf<uint8_t> vx_roots, vx_ok;
   // validator-set requests (edc_vq_verify): the host copy edc_debug_vq_last returns
   uint64_t vq_last[8] = {};
   bool vq_have = false;
@@ -1652,7 +1661,8 @@ edc_ctx* edc_create(int device) {
     ctx->sc_k1 = splitmix64(ctx->secret ^ 0x7369676361636831ull);
   }
   (void)hipGetLastError();   // launch checks below must not see an earlier, unrelated failure
-  bool ok = hipSetDevice(device) == hipSuccess && msm_init_device() == hipSuccess && init_slot(ctx, ctx->slot[0]) == 0 &&
+  bool ok = hipSetDevice(device) == hipSuccess && msm_init_device() == hipSuccess && valhash_init_device() == hipSuccess &&
+            init_slot(ctx, ctx->slot[0]) == 0 &&
             ctx->btab.alloc(BTAB_TOTAL * NIELS_WORDS) == hipSuccess;
   if (ok) {
     launch_init_btable(ctx->st(), ctx->btab);
@@ -1680,6 +1690,8 @@ static void free_vhist(edc_ctx* ctx) {
   ctx->vh_count = 0;
   ctx->vh = VHist();
   ctx->vh_posh.clear();
+  reset_all(ctx->vx_rank, ctx->vx_by_rank);     // the address order goes where the history goes
+  ctx->vx_ranked = false;
 }
 
 static void free_keycache(edc_ctx* ctx) {
@@ -5200,6 +5212,171 @@ int edc_debug_vhist_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, 
                            const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
                            int mode, int reps, float ms[2]) {
   return valset_debug_select_body(ctx, true, nc, commit_off, commit_ver, vk, key_idx, flag, threshold, mode, reps, 2, ms);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- validator-set hashes
+// edc_valhash_valset, edc_valhash_vhist, edc_valhash_vhist_match (valhash.h, edc_valhash.hip): what
+// they refuse (valhash_ready, then the entry's own arguments), the address order of the list
+// (valhash_ranks), then one workgroup per root on slot 0's stream and the read-back. hist: the
+// history's versions; else the one set of edc_valset_set_powers.
+static int valhash_ready(edc_ctx* ctx, bool hist) {
+  CK(hipSetDevice(ctx->device));
+  if (!ctx->kc_reg_m) { ctx->err = "no registered key list (edc_keycache_load)"; return EDC_ERR_ARG; }
+  const int rc = hist ? vhist_ready(ctx, 0, nullptr) : valset_ready(ctx);
+  if (rc) return rc;
+  return claim_slot0(ctx) ? 0 : EDC_ERR_ARG;
+}
+
+// The address order of the registered list, once per list; run behind every check of an entry, so
+// that a refused call has done no device work and changed nothing.
+static int valhash_ranks(edc_ctx* ctx) {
+  if (ctx->vx_ranked) return 0;
+  const uint32_t m = ctx->kc_reg_m;
+  hipStream_t st = ctx->st();
+  DevBuf<uint8_t> d_addr;
+  DevBuf<uint32_t> d_rank, d_by;          // committed to the context only on success
+  CK(alloc_all(sized(d_addr, (size_t)m * VALHASH_ADDR_BYTES), sized(d_rank, m), sized(d_by, m)));
+  launch_valhash_addr(st, m, ctx->kc_keys, ctx->kc_reg, d_addr);
+  CK(hipGetLastError());
+  std::vector<uint8_t> addr((size_t)m * VALHASH_ADDR_BYTES);
+  CK(hipMemcpyAsync(addr.data(), d_addr, addr.size(), hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  std::vector<uint32_t> rank(m), by(m);
+  valhash_rank(m, addr.data(), rank.data());
+  for (uint32_t p = 0; p < m; ++p) by[rank[p]] = ctx->kc_regh[p];
+  CK(hipMemcpy(d_rank, rank.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CK(hipMemcpy(d_by, by.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
+  ctx->vx_rank = std::move(d_rank);
+  ctx->vx_by_rank = std::move(d_by);
+  ctx->vx_ranked = true;
+  return 0;
+}
+
+static ValhashSrc valhash_src(const edc_ctx* ctx, bool hist) {
+  return ValhashSrc{ctx->kc_keys, ctx->kc_reg, ctx->kc_reg_m, hist, ctx->vhv(), ctx->vs(), ctx->vx_rank, ctx->vx_by_rank};
+}
+
+// the largest member count among the versions ver[0 .. n), checked against the cap
+static int valhash_max_members(edc_ctx* ctx, size_t n, const uint32_t* ver, uint32_t v0, uint32_t* max_members) {
+  uint32_t mx = 0;
+  for (size_t j = 0; j < n; ++j) mx = std::max(mx, ctx->vh.members[ver ? ver[j] : v0 + j]);
+  if (mx > VALHASH_MAX_MEMBERS) { ctx->err = "validator-set hash: a version above EDC_VALHASH_MAX_MEMBERS members"; return EDC_ERR_ARG; }
+  *max_members = mx;
+  return 0;
+}
+
+extern "C" {
+
+int edc_valhash_valset(edc_ctx* ctx, uint8_t out[32]) {
+  if (!ctx) return EDC_ERR_ARG;
+  int rc = valhash_ready(ctx, false);
+  if (rc) return rc;
+  if (!out) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  if (ctx->vs_m > VALHASH_MAX_MEMBERS) { ctx->err = "validator-set hash: a set above EDC_VALHASH_MAX_MEMBERS members"; return EDC_ERR_ARG; }
+  if ((rc = valhash_ranks(ctx))) return rc;
+  hipStream_t st = ctx->st();
+  CK(grow(ctx->vx_roots, 32, byte_cap, sync_of(st)));
+  CK(launch_valhash_roots(st, valhash_src(ctx, false), 1, nullptr, 0, ctx->vs_m, ctx->vx_roots));
+  CK(hipGetLastError());
+  uint8_t root[32];                     // out is written only by a call that succeeds
+  CK(hipMemcpyAsync(root, ctx->vx_roots, 32, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  memcpy(out, root, 32);
+  return EDC_OK;
+}
+
+int edc_valhash_vhist(edc_ctx* ctx, uint32_t v0, size_t count, uint8_t* out) {
+  if (!ctx) return EDC_ERR_ARG;
+  int rc = valhash_ready(ctx, true);
+  if (rc) return rc;
+  const size_t nver = (size_t)ctx->vh.nv + 1;
+  if (v0 > nver || count > nver - v0) { ctx->err = "validator-set hashes: a range past the history's last version"; return EDC_ERR_ARG; }
+  if (!count) return EDC_OK;
+  if (!out) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  uint32_t mx;
+  if ((rc = valhash_max_members(ctx, count, nullptr, v0, &mx)) || (rc = valhash_ranks(ctx))) return rc;
+  hipStream_t st = ctx->st();
+  CK(grow(ctx->vx_roots, count * 32, byte_cap, sync_of(st)));
+  CK(launch_valhash_roots(st, valhash_src(ctx, true), (uint32_t)count, nullptr, v0, mx, ctx->vx_roots));
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(st));         // a failed kernel must not leave part of out written
+  CK(hipMemcpy(out, ctx->vx_roots, count * 32, hipMemcpyDeviceToHost));
+  return EDC_OK;
+}
+
+int edc_valhash_vhist_match(edc_ctx* ctx, size_t nc, const uint32_t* commit_ver, const uint8_t* expect, uint8_t* ok,
+                         size_t* n_mismatch) {
+  if (!ctx) return EDC_ERR_ARG;
+  int rc = valhash_ready(ctx, true);
+  if (rc) return rc;
+  if (!nc) {
+    if (n_mismatch) *n_mismatch = 0;
+    return EDC_OK;
+  }
+  if (!commit_ver || !expect || !ok) { ctx->err = "null input"; return EDC_ERR_ARG; }
+  if (nc >= (1ull << 32)) { ctx->err = "validator-set hashes: fewer than 2^32 commits"; return EDC_ERR_ARG; }
+  if ((rc = vhist_ready(ctx, nc, commit_ver))) return rc;
+  // every distinct version is hashed once: the sorted distinct versions, and per commit its place
+  std::vector<uint32_t> vers(commit_ver, commit_ver + nc);
+  std::sort(vers.begin(), vers.end());
+  vers.erase(std::unique(vers.begin(), vers.end()), vers.end());
+  const size_t nd = vers.size();
+  uint32_t mx;
+  if ((rc = valhash_max_members(ctx, nd, vers.data(), 0, &mx)) || (rc = valhash_ranks(ctx))) return rc;
+  // staged in one piece: expect (8 nc words, 16-byte aligned) | the commits' root indices | the versions
+  std::vector<uint32_t> in(9 * nc + nd);
+  memcpy(in.data(), expect, nc * 32);
+  for (size_t c = 0; c < nc; ++c)
+    in[8 * nc + c] = (uint32_t)(std::lower_bound(vers.begin(), vers.end(), commit_ver[c]) - vers.begin());
+  std::copy(vers.begin(), vers.end(), in.begin() + 9 * nc);
+  hipStream_t st = ctx->st();
+  CK(grow(ctx->vx_roots, nd * 32, byte_cap, sync_of(st)));
+  CK(grow(ctx->vx_in, in.size(), item_cap, sync_of(st)));
+  CK(grow(ctx->vx_ok, nc, byte_cap, sync_of(st)));
+  CK(hipMemcpyAsync(ctx->vx_in, in.data(), in.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  CK(launch_valhash_roots(st, valhash_src(ctx, true), (uint32_t)nd, ctx->vx_in + 9 * nc, 0, mx, ctx->vx_roots));
+  launch_valhash_match(st, (uint32_t)nc, ctx->vx_roots, ctx->vx_in + 8 * nc, reinterpret_cast<const uint8_t*>(ctx->vx_in.get()),
+                       ctx->vx_ok);
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(st));         // a failed kernel must not leave part of ok written
+  CK(hipMemcpy(ok, ctx->vx_ok, nc, hipMemcpyDeviceToHost));
+  if (n_mismatch) *n_mismatch = (size_t)std::count(ok, ok + nc, (uint8_t)0);
+  return EDC_OK;
+}
+
+// Measurement hook: mean times over reps launches of the root kernel over every version of the
+// history (ms[0]) and of the address kernel over the registered list (ms[1]).
+int edc_debug_valhash_ms(edc_ctx* ctx, int reps, float ms[2]) {
+  if (!ctx || reps < 1 || !ms) return EDC_ERR_ARG;
+  ms[0] = ms[1] = 0.f;
+  int rc = valhash_ready(ctx, true);
+  if (rc) return rc;
+  const size_t nver = (size_t)ctx->vh.nv + 1;
+  uint32_t mx;
+  if ((rc = valhash_max_members(ctx, nver, nullptr, 0, &mx)) || (rc = valhash_ranks(ctx))) return rc;
+  hipStream_t st = ctx->st();
+  DevBuf<uint8_t> d_addr;
+  CK(d_addr.alloc((size_t)ctx->kc_reg_m * VALHASH_ADDR_BYTES));
+  CK(grow(ctx->vx_roots, nver * 32, byte_cap, sync_of(st)));
+  Event e[3];
+  for (Event& x : e) CK(x.create());
+  CK(hipEventRecord(e[0], st));
+  for (int r = 0; r < reps; ++r)
+    CK(launch_valhash_roots(st, valhash_src(ctx, true), (uint32_t)nver, nullptr, 0, mx, ctx->vx_roots));
+  CK(hipGetLastError());
+  CK(hipEventRecord(e[1], st));
+  for (int r = 0; r < reps; ++r) launch_valhash_addr(st, ctx->kc_reg_m, ctx->kc_keys, ctx->kc_reg, d_addr);
+  CK(hipGetLastError());
+  CK(hipEventRecord(e[2], st));
+  CK(hipEventSynchronize(e[2]));
+  for (int j = 0; j < 2; ++j) {
+    float t = 0.f;
+    CK(hipEventElapsedTime(&t, e[j], e[j + 1]));
+    ms[j] = t / (float)reps;
+  }
+  return EDC_OK;
 }
 
 }  // extern "C"

@@ -182,6 +182,22 @@ struct VhistView {
   const uint64_t* pow;
   uint32_t count;
 };
+#if defined(__HIPCC__)
+// the power of the change list [lo, end) at version v: its last entry with ver <= v (ver[lo] = 0 <= v,
+// so a list of one entry is not searched); VHIST_NOT_MEMBER (~0) for an empty list. The one search
+// of the history on the device: the join kernels (edc_quorum.hip) and the root kernel
+// (edc_valhash.hip) both resolve a power with it.
+__device__ __forceinline__ uint64_t vh_power_at(const VhistView& vh, uint32_t lo, uint32_t end, uint32_t v) {
+  if (lo >= end) return ~0ull;
+  uint32_t hi = end - 1;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+    if (vh.ver[mid] <= v) lo = mid;
+    else hi = mid - 1;
+  }
+  return vh.pow[lo];
+}
+#endif
 // launch_vhist_resolve stands where launch_valset_resolve does and writes the same three arrays,
 // with item i judged at commit_ver[c], c the commit of i by commit_off (nc + 1 offsets and nc
 // versions on the device, every version checked by the caller against the history).
@@ -197,6 +213,35 @@ void launch_vhist_resolve2(hipStream_t st, uint32_t n, uint32_t nc, const KeyCac
                            const uint8_t* vk, const uint32_t* key_idx, const uint32_t* reg, const uint8_t* flag,
                            uint64_t* power_a, uint8_t* flag_a, uint32_t* who_a, uint64_t* power_b, uint8_t* flag_b,
                            uint32_t* who_b);
+// edc_valhash.hip: validator-set hashes (valhash.h; edc_valhash_valset, edc_valhash_vhist,
+// edc_valhash_vhist_match). What the root kernel reads: the registered list (m positions, reg[p] the
+// cache index of position p, keys the cache's raw key words), the set (hist: the history's change
+// lists, else the one set's powers) and the address order (rank[p] of position p; by_rank[r] the
+// cache index of the position with rank r).
+struct ValhashSrc {
+  const uint32_t* keys;
+  const uint32_t* reg;
+  uint32_t m;
+  bool hist;
+  VhistView vh;
+  ValsetView vs;
+  const uint32_t* rank;
+  const uint32_t* by_rank;
+};
+// addr (m x 20 bytes, by position) = the first 20 bytes of SHA-256 of each position's key
+void launch_valhash_addr(hipStream_t st, uint32_t m, const uint32_t* keys, const uint32_t* reg, uint8_t* addr);
+// One workgroup per root: root j (32 bytes at roots + 32 j) is that of version vers[j], or of
+// v0 + j with vers null; a source without a history has one set and ignores the version.
+// max_members: no requested version holds more (at most VALHASH_MAX_MEMBERS; the caller checked).
+// It sizes the workgroup's LDS, up to the 112 KB valhash_init_device allows: per-device kernel
+// attributes (the root kernel's dynamic LDS beyond 64 KB); call on every device a context uses,
+// after hipSetDevice, as msm_init_device.
+hipError_t valhash_init_device();
+hipError_t launch_valhash_roots(hipStream_t st, const ValhashSrc& src, uint32_t nroots, const uint32_t* vers, uint32_t v0,
+                          uint32_t max_members, uint8_t* roots);
+// ok[c] = 1 iff the 32 bytes at expect + 32 c equal root idx[c]
+void launch_valhash_match(hipStream_t st, uint32_t nc, const uint8_t* roots, const uint32_t* idx, const uint8_t* expect,
+                          uint8_t* ok);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

@@ -467,19 +467,6 @@ __global__ void __launch_bounds__(QR_TILE) k_vs_resolve(uint32_t n, KeyCacheView
   who[i] = member ? c : KC_EMPTY;
 }
 
-// the power of the change list [lo, end) at version v: its last entry with ver <= v (ver[lo] = 0 <= v,
-// so a list of one entry is not searched); VHIST_NOT_MEMBER for an empty list
-__device__ __forceinline__ uint64_t vh_power_at(const VhistView& vh, uint32_t lo, uint32_t end, uint32_t v) {
-  if (lo >= end) return VHIST_NOT_MEMBER;
-  uint32_t hi = end - 1;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo + 1) >> 1);
-    if (vh.ver[mid] <= v) lo = mid;
-    else hi = mid - 1;
-  }
-  return vh.pow[lo];
-}
-
 // Validator-set history (vhist.h; edc_vhist_*): the join of k_vs_resolve with every commit judged
 // by the set of its own version. One lane per item, in front of the selection: the signer's cache
 // index as above; the item's commit by the search k_q_tile makes, bounded by the commits of the

@@ -1610,6 +1610,67 @@ int edc_debug_vq_trust_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
                               const uint64_t* threshold, const uint64_t* trust_threshold, int mode, int reps, float ms[3]);
 
 /*
+ * Validator-set hashes: the Merkle root of a validator set, of every version of the history on the
+ * GPU. The quorum entries above judge a commit BY a set; a light client gets that set from an
+ * untrusted provider, and before it may judge by it, it must check that the set hashes to the
+ * validators_hash of the header it trusts. These entries compute that hash where the sets already
+ * live, and only 32 bytes per version (or one byte per commit) cross PCIe. Not an API of the
+ * reference crate, whose APIs keep their meaning as stated there.
+ *
+ * The function. The library's contract is these bytes. Agreement with CometBFT's
+ * ValidatorSet.Hash() is the intent, but it is stated from memory, as the sections above are, and
+ * no chain data was at hand to check it against. For a set S of members (position p of the
+ * registered list, its 32-byte key key_p, its power w_p <= 2^63 - 1):
+ *   Address  addr_p = the first 20 bytes of SHA-256(key_p).
+ *   Order    The members are ordered by power descending, then addr ascending as byte strings. A tie
+ *            on both is broken by position ascending (the history and the one set reject a list
+ *            that holds a key twice, so this needs a 160-bit collision).
+ *   Leaf     leaf_p = 0A 22 0A 20 | key_p | (10 | uvarint(w_p) if w_p > 0, else nothing). The
+ *            uvarint is base-128, little-endian, 1 to 9 bytes. A leaf is 36 to 46 bytes, so with the
+ *            00 prefix it is always one SHA-256 block. A member of power 0 ("a member without
+ *            weight") omits the field, as proto3 does.
+ *   Root     RFC 6962's MTH with SHA-256 over the ordered leaves: the empty set -> SHA-256 of the
+ *            empty string; one leaf -> SHA-256(00 | leaf); n > 1 -> SHA-256(01 | MTH(first k) |
+ *            MTH(rest)), with k the largest power of two below n.
+ *   Members  The members of version v are the positions whose power at v is not
+ *            EDC_VHIST_NOT_MEMBER. The one-set form takes the members of edc_valset_set_powers
+ *            exactly as the edc_valset_* join defines them.
+ * Member cap. One workgroup sorts and hashes one set in LDS, so a set holds at most
+ *   EDC_VALHASH_MAX_MEMBERS = 4096 members (28 bytes of LDS per padded slot, 112 KB of the CU's
+ *   160 KB). A call that asks for a version above the cap is EDC_ERR_ARG, with nothing
+ *   written. Larger sets are not built.
+ *
+ * edc_valhash_valset  out = the root of the one set of edc_valset_set_powers.
+ * edc_valhash_vhist  out (count x 32 host bytes) = the roots of the versions v0 .. v0 + count - 1.
+ *   The range rules are edc_vhist_totals': v0 > nv + 1 or count > nv + 1 - v0 is EDC_ERR_ARG.
+ * edc_valhash_vhist_match  expect (nc x 32 host bytes) holds the validators_hash of each commit's
+ *   header: ok[c] = 1 iff the root of version commit_ver[c] equals the 32 bytes at expect + 32 c,
+ *   else 0; *n_mismatch (nullable) = the number of zeros. Versions may repeat and come in any
+ *   order; each distinct version is hashed once. The compare runs on the device and nc bytes come
+ *   back. commit_ver[c] > nv is EDC_ERR_ARG, checked on the host. The return value is EDC_OK
+ *   whether or not everything matches: a mismatch is data.
+ * Errors of all three: EDC_ERR_ARG with nothing written and the context usable when there is no
+ *   registered key list, no history (edc_valhash_valset: no powers), or a required output or input is
+ *   NULL. With those in place count = 0 and nc = 0 return EDC_OK, read no array and write only
+ *   *n_mismatch = 0. Synchronous on slot 0 and refused while a batch is pending there.
+ * What is kept. The address order does not depend on the version: the first call after a key list
+ *   is loaded hashes every key on the device and ranks the addresses once; edc_keycache_load,
+ *   edc_keycache_clear and clearing the history drop the ranks, edc_keycache_add keeps them (a key
+ *   it adds is a member of no version). No root is kept between calls: every call hashes what it is
+ *   asked for from the history as it stands.
+ * edc_debug_valhash_ms  measurement hook: mean times over reps launches of the root kernel over
+ *   every version of the history (ms[0]) and of the address kernel over the list (ms[1]).
+ * Not built: sets above the cap (a multi-workgroup sort), asynchronous, incremental and multi-GPU
+ *   forms, device-resident outputs.
+ */
+#define EDC_VALHASH_MAX_MEMBERS 4096
+int edc_valhash_valset(edc_ctx* ctx, uint8_t out[32]);
+int edc_valhash_vhist(edc_ctx* ctx, uint32_t v0, size_t count, uint8_t* out);
+int edc_valhash_vhist_match(edc_ctx* ctx, size_t nc, const uint32_t* commit_ver, const uint8_t* expect, uint8_t* ok,
+                         size_t* n_mismatch);
+int edc_debug_valhash_ms(edc_ctx* ctx, int reps, float ms[2]);
+
+/*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
  * one batch::Verifier::verify (reference src/batch.rs:149-217) split into contiguous shards, one
  * per listed device (a device may be listed more than once: several contexts on one GPU). Shard g
