@@ -98,16 +98,7 @@ struct Slot {
   DevBuf<unsigned long long> key_acc, u_acc;
   DevBuf<uint32_t> coef_part;        // k_coef's per-workgroup key slots (merged by k_coef_merge)
   DevBuf<uint8_t> itembad, keybad;   // per-item / per-key failure bits (fallback)
-  // MSM workspace, grown on demand to the plan's bins / entries
-  uint32_t cap_bins = 0, cap_ranges = 0;
-  size_t cap_entries = 0;
-  DevBuf<uint32_t> counts, offsets, cursor;
-  DevBuf<uint2> entries;
-  DevBuf<uint32_t> sorted;      // entries' point indices sorted by bucket within each bin
-  DevBuf<uint32_t> slice_W, slice_T, win;
-  DevBuf<uint32_t> buckets;     // bins x 256 bucket sums (extended)
-  DevBuf<uint32_t> heads;       // bins x 256 head partials of the segmented accumulation
-  DevBuf<uint32_t> bucket_end;  // bins x 256 bucket end positions of the sorted entries
+  MsmWs msm;                    // MSM workspace (edc_launch.h), grown on demand by ensure_msm
   DevBuf<int> flags;
   DevBuf<uint8_t> d_out;        // 256-byte result block (kMultiMax of them for a multi-batch launch)
   PinnedBuf<uint8_t> h_out;     // pinned mirror
@@ -476,10 +467,7 @@ static int ensure_slot(edc_ctx* ctx, Slot& s, size_t n) {
   CK(grow_group(s.cap_n, n, item_cap, sync_of(s.st), [&](size_t cap) {
     const size_t T = next_pow2(2 * cap);
     s.cap_T = 0;
-    s.cap_bins = s.cap_ranges = 0;   // the MSM workspace goes with the slot's arrays
-    s.cap_entries = 0;
-    reset_all(s.counts, s.offsets, s.cursor, s.slice_W, s.slice_T, s.win, s.buckets, s.heads, s.bucket_end, s.entries,
-              s.sorted);
+    s.msm = MsmWs();   // the MSM workspace goes with the slot's arrays
     hipError_t e = alloc_all(
         sized(s.k, cap * 8), sized(s.key_slot, cap), sized(s.key_index, cap), sized(s.key_rep, cap), sized(s.table, T),
         sized(s.slot_key, T),
@@ -501,22 +489,23 @@ static int ensure_slot(edc_ctx* ctx, Slot& s, size_t n) {
 static int ensure_msm(edc_ctx* ctx, Slot& s, const MsmPlan& P, size_t entries) {
   const uint32_t nbin = P.nbin();
   if (nbin > MSM_MAX_BINS || P.nwin > MSM_MAX_WIN) { ctx->err = "MSM plan too large"; return EDC_ERR_ARG; }
-  if (nbin > s.cap_bins || P.nranges > s.cap_ranges) {   // two capacities: each keeps its maximum
+  MsmWs& w = s.msm;
+  if (nbin > w.cap_bins || P.nranges > w.cap_ranges) {   // two capacities: each keeps its maximum
     CK(hipStreamSynchronize(s.st));
-    const uint32_t nb = nbin > s.cap_bins ? nbin : s.cap_bins;
-    const uint32_t nr = P.nranges > s.cap_ranges ? P.nranges : (s.cap_ranges ? s.cap_ranges : 1);
-    s.cap_bins = s.cap_ranges = 0;
-    CK(alloc_all(sized(s.counts, nb), sized(s.offsets, nb), sized(s.cursor, nb), sized(s.slice_W, (size_t)nb * EXT_WORDS),
-                 sized(s.slice_T, (size_t)nb * EXT_WORDS), sized(s.win, (size_t)nr * MSM_MAX_WIN * EXT_WORDS),
-                 sized(s.buckets, msm_bucket_words(nb)), sized(s.heads, msm_bucket_words(nb)),
-                 sized(s.bucket_end, (size_t)nb * NSLICE)));
-    s.cap_bins = nb;
-    s.cap_ranges = nr;
+    const uint32_t nb = nbin > w.cap_bins ? nbin : w.cap_bins;
+    const uint32_t nr = P.nranges > w.cap_ranges ? P.nranges : (w.cap_ranges ? w.cap_ranges : 1);
+    w.cap_bins = w.cap_ranges = 0;
+    CK(alloc_all(sized(w.counts, nb), sized(w.offsets, nb), sized(w.cursor, nb), sized(w.slice_W, (size_t)nb * EXT_WORDS),
+                 sized(w.slice_T, (size_t)nb * EXT_WORDS), sized(w.win, (size_t)nr * MSM_MAX_WIN * EXT_WORDS),
+                 sized(w.buckets, msm_bucket_words(nb)), sized(w.heads, msm_bucket_words(nb)),
+                 sized(w.bucket_end, (size_t)nb * NSLICE)));
+    w.cap_bins = nb;
+    w.cap_ranges = nr;
   }
-  if (entries > s.cap_entries)
-    CK(grow_group(s.cap_entries, entries, entry_cap, sync_of(s.st), [&](size_t cap) {
+  if (entries > w.cap_entries)
+    CK(grow_group(w.cap_entries, entries, entry_cap, sync_of(s.st), [&](size_t cap) {
       // + 256 per possible bin: each bin's lane-major region is padded to whole rounds (k_msm_sort)
-      return alloc_all(sized(s.entries, cap), sized(s.sorted, cap + 256 * (size_t)MSM_MAX_BINS));
+      return alloc_all(sized(w.entries, cap), sized(w.sorted, cap + 256 * (size_t)MSM_MAX_BINS));
     }));
   return 0;
 }
@@ -851,6 +840,57 @@ static uint32_t key_lanes(const edc_ctx* ctx, size_t n, bool per_sig) {
   return (uint32_t)(lanes < n ? lanes : n);
 }
 
+// ---- the front of a batch ----
+// the header of the batch about to be enqueued on slot s (kin: where its challenges are read)
+static void slot_begin(Slot& s, const uint32_t* kin, uint32_t nmulti, bool timed, bool per_sig, uint32_t n) {
+  s.kin = kin;
+  s.nmulti = nmulti;
+  s.timed = timed;
+  s.per_sig = per_sig;
+  s.n_batch = n;
+}
+// digit entries and terms of an n-item batch's MSM (wide or split coefficients, edc_common.h)
+static size_t batch_entry_room(const MsmPlan& P, size_t n, bool split) {
+  return split ? msm_entry_capacity(P, 2 + 3 * n, 0) : msm_entry_capacity(P, n, n + 1);
+}
+static uint32_t batch_term_count(uint32_t n, bool split) { return split ? 2 + 3 * n : 1 + 2 * n; }
+
+// The key table of one batch: T slots of the slot's hash table and, when it groups its keys, the salt
+struct KeyTable {
+  uint32_t T = 0, salt[2] = {0, 0};
+  bool per_sig = false, force_overflow = false;
+};
+// Host only: the table of an n-item batch on slot s (refused when the slot's arrays cannot hold
+// it). A grouping batch draws a fresh salt, one step of the context's batch counter.
+static int key_table(edc_ctx* ctx, const Slot& s, size_t n, bool per_sig, KeyTable& kt) {
+  kt.T = (uint32_t)next_pow2(2 * (n < 128 ? 128 : n));
+  kt.per_sig = per_sig;
+  kt.force_overflow = ctx->key_grouping == 3;
+  if (kt.T > s.cap_T) { ctx->err = "hash table capacity"; return EDC_ERR_ARG; }
+  if (!per_sig) {
+    const uint64_t h = splitmix64(ctx->secret ^ splitmix64(ctx->nbatches++));
+    kt.salt[0] = (uint32_t)h;
+    kt.salt[1] = (uint32_t)(h >> 32);
+  }
+  return 0;
+}
+
+// The per-batch resets (with the MSM bin counts[0..nbin), or null / 0) and, when grouping, the key
+// grouping of the n keys at vk (kstride: launch_keys' kcap). before_keys runs between the two
+// launches (the chunked path waits there for its keys to land); false from it ends the front.
+static bool no_wait() { return true; }
+template <typename F = bool (*)()>
+static bool launch_front(hipStream_t st, Slot& s, const KeyTable& kt, uint32_t n, const uint8_t* vk, uint32_t* counts,
+                         uint32_t nbin, uint32_t kstride = 0xFFFFFFFFu, F before_keys = no_wait) {
+  launch_init_batch(st, s.flags, kt.per_sig ? (int)n : -1, s.u_acc, s.d_out, kt.per_sig ? nullptr : s.table.get(),
+                    kt.per_sig ? 0u : kt.T, counts, nbin);
+  if (!before_keys()) return false;
+  if (!kt.per_sig)
+    launch_keys(st, n, vk, s.table, kt.T - 1, kt.salt, kt.force_overflow, s.slot_key, s.key_slot, s.key_rep, s.key_index,
+                s.key_acc, s.flags, kstride);
+  return true;
+}
+
 // Enqueue the per-signature prefix of the pipeline on slot s: key grouping, SHA-512 challenges,
 // z and coefficients, ZIP215 decode of R_i and the keys. No host synchronization. With d_k (the
 // prehashed entries: the caller's queue-time k, src/batch.rs:76-94) SHA-512 is skipped and the
@@ -864,30 +904,20 @@ static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const BatchIn& in, co
   int rc = n ? check_aligned16(ctx, "device vk / sig / z / k arrays", {d_vk, d_sig, d_z, d_k}) : 0;
   if (!rc) rc = ensure_slot(ctx, s, n);
   if (rc) return rc;
-  s.kin = d_k ? d_k : s.k;
-  s.nmulti = 0;
   const uint32_t N = (uint32_t)n;
-  const uint32_t T = (uint32_t)next_pow2(2 * (n < 128 ? 128 : n));
-  if (T > s.cap_T) { ctx->err = "hash table capacity"; return EDC_ERR_ARG; }
+  const bool per_sig = force_per_sig || choose_per_sig(ctx, n);
+  KeyTable kt;
+  if ((rc = key_table(ctx, s, n, per_sig, kt))) return rc;
+  slot_begin(s, d_k ? d_k : s.k.get(), 0, ctx->timing, per_sig, N);
   uint32_t seed[8];
   seed_words(in.z_seed, seed);
   hipStream_t st = s.st;
-  s.timed = ctx->timing;
   auto mark = [&](int ph) {
     if (s.timed) (void)hipEventRecord(s.ev[ph], st);
   };
-  const bool per_sig = force_per_sig || choose_per_sig(ctx, n);
-  s.per_sig = per_sig;
-  s.n_batch = N;
   mark(PH_KEYS);
-  launch_init_batch(st, s.flags, per_sig ? (int)N : -1, s.u_acc, s.d_out, per_sig ? nullptr : s.table, per_sig ? 0u : T,
-                    with_bin && EDC_RUN(8) ? s.counts : nullptr, with_bin && EDC_RUN(8) ? P->nbin() : 0u);
-  if (!per_sig) {
-    const uint64_t h = splitmix64(ctx->secret ^ splitmix64(ctx->nbatches++));
-    const uint32_t salt[2] = {(uint32_t)h, (uint32_t)(h >> 32)};
-    launch_keys(st, N, d_vk, s.table, T - 1, salt, ctx->key_grouping == 3, s.slot_key, s.key_slot, s.key_rep,
-                s.key_index, s.key_acc, s.flags);
-  }
+  const bool clear_counts = with_bin && EDC_RUN(8);
+  launch_front(st, s, kt, N, d_vk, clear_counts ? s.msm.counts.get() : nullptr, clear_counts ? P->nbin() : 0u);
   // dual-stream builds (untimed batches): the decode only needs the key grouping, so it runs on
   // the slot's second stream beside SHA-512 / coefficients / binning; its per-item R bits go to
   // their own array (itembad + cap_n), so no byte is written by both streams.
@@ -918,12 +948,10 @@ static int enqueue_prefix(edc_ctx* ctx, Slot& s, size_t n, const BatchIn& in, co
               per_sig, s.coef_part, split);
   mark(PH_MSM_BIN);
   if (with_bin && EDC_RUN(8))
-    launch_msm_bin(st, *P, batch_terms(*P, s, N, split), split ? 2 + 3 * N : 1 + 2 * N, s.counts, s.offsets, s.cursor,
-                   s.entries, s.flags, true);
+    launch_msm_bin(st, *P, batch_terms(*P, s, N, split), batch_term_count(N, split), s.msm, s.flags, true);
   // the per-bin bucket sort needs only the binning: before the decode join, so on the dual-stream
   // slot it runs beside the decode instead of after it
-  if (with_bin && EDC_RUN(256))
-    launch_msm_sort(st, *P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
+  if (with_bin && EDC_RUN(256)) launch_msm_sort(st, *P, s.msm);
   // the points are decoded last, right before the accumulation gathers them, so the freshly
   // written point table (134 MB at 2^20) is still in the Infinity Cache for the random row gathers
   mark(PH_DECOMP);
@@ -942,26 +970,25 @@ static int enqueue_batch(edc_ctx* ctx, Slot& s, size_t n, const BatchIn& in, boo
   if (rc) return rc;
   const bool per_sig = choose_per_sig(ctx, n), split = choose_split(ctx);
   const MsmPlan P = batch_plan(ctx, n, per_sig, split);
-  rc = ensure_msm(ctx, s, P, split ? msm_entry_capacity(P, 2 + 3 * n, 0) : msm_entry_capacity(P, n, n + 1));
+  rc = ensure_msm(ctx, s, P, batch_entry_room(P, n, split));
   if (rc) return rc;
   rc = enqueue_prefix(ctx, s, n, in, &P, per_sig, split);
   if (rc) return rc;
   hipStream_t st = s.st;
   if (s.timed) (void)hipEventRecord(s.ev[PH_MSM_BUCKET], st);
-  launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
-                    s.slice_T, s.probe_runs ? EDC_PROBE_SKIP : 0, s.timed ? s.ev_acc[0] : nullptr,
+  launch_msm_bucket(st, P, s.msm, s.pts, s.probe_runs ? EDC_PROBE_SKIP : 0, s.timed ? s.ev_acc[0] : nullptr,
                     s.timed ? s.ev_acc[1] : nullptr, latency, s.flags);
   s.acc_nbin = P.nbin();
   if (s.timed) (void)hipEventRecord(s.ev[PH_MSM_TAIL], st);
   // the final kernel stores the result block to d_out and straight into the pinned h_out
-  if (EDC_RUN(128)) launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, in.compress, s.d_out, s.h_out);
+  if (EDC_RUN(128)) launch_msm_tail(st, P, s.msm, s.flags, in.compress, s.d_out, s.h_out);
   if (s.timed) {
     (void)hipEventRecord(s.ev[PH_N], st);
     // the accumulation's entry count (the last bin's offset + count), read at the wait without
     // another sync; queued after the last phase event so that no phase time includes the copies
     if (s.acc_nbin) {
-      CK(hipMemcpyAsync(s.h_acc, s.offsets + s.acc_nbin - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      CK(hipMemcpyAsync(s.h_acc + 1, s.counts + s.acc_nbin - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      CK(hipMemcpyAsync(s.h_acc, s.msm.offsets + s.acc_nbin - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      CK(hipMemcpyAsync(s.h_acc + 1, s.msm.counts + s.acc_nbin - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
   }
   CK(hipGetLastError());
@@ -1022,24 +1049,13 @@ static int enqueue_multi(edc_ctx* ctx, Slot& s, uint32_t nb, size_t n_per, const
                  sized(s.mb_bad, kMultiMax)));
   }
   const uint32_t n = (uint32_t)N;
-  const uint32_t T = (uint32_t)next_pow2(2 * (N < 128 ? 128 : N));
-  if (T > s.cap_T) { ctx->err = "hash table capacity"; return EDC_ERR_ARG; }
+  KeyTable kt;
+  if ((rc = key_table(ctx, s, N, per_sig, kt))) return rc;
   uint32_t seed[8];
   seed_words(z_seed, seed);
   hipStream_t st = s.st;
-  s.timed = false;
-  s.kin = d_k ? d_k : s.k;
-  s.per_sig = per_sig;
-  s.n_batch = n;
-  s.nmulti = nb;
-  launch_init_batch(st, s.flags, per_sig ? (int)n : -1, s.u_acc, s.d_out, per_sig ? nullptr : s.table, per_sig ? 0u : T,
-                    s.counts, P.nbin());
-  if (!per_sig) {
-    const uint64_t h = splitmix64(ctx->secret ^ splitmix64(ctx->nbatches++));
-    const uint32_t salt[2] = {(uint32_t)h, (uint32_t)(h >> 32)};
-    launch_keys(st, n, d_vk, s.table, T - 1, salt, ctx->key_grouping == 3, s.slot_key, s.key_slot, s.key_rep,
-                s.key_index, s.key_acc, s.flags, kstride);
-  }
+  slot_begin(s, d_k ? d_k : s.k.get(), nb, false, per_sig, n);
+  launch_front(st, s, kt, n, d_vk, s.msm.counts, P.nbin(), kstride);
   const bool dual = EDC_DUAL_STREAM && s.st2;       // same contract (and order) as enqueue_prefix
   if (!d_k) launch_challenge(st, n, d_vk, d_sig, d_msg, d_off, s.k);
   if (dual) {
@@ -1052,8 +1068,8 @@ static int enqueue_multi(edc_ctx* ctx, Slot& s, uint32_t nb, size_t n_per, const
   launch_multi_coef(st, n, nb, kstride, per_sig, d_sig, s.kin, seed, z_base, s.key_index, s.scal, s.mb_acc, s.u_acc,
                     s.itembad, s.flags, s.mb_xpt, s.mb_xrg, s.mb_xscal);
   const MsmTerms terms{n, (uint32_t)n_per, 0u, nb, 1u, s.scal, s.mb_xpt, s.mb_xrg, s.mb_xscal, 0u, per_sig ? 3u : 1u};
-  launch_msm_bin(st, P, terms, (uint32_t)(N + full_max), s.counts, s.offsets, s.cursor, s.entries, s.flags, true);
-  launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
+  launch_msm_bin(st, P, terms, (uint32_t)(N + full_max), s.msm, s.flags, true);
+  launch_msm_sort(st, P, s.msm);
   if (dual) CK(hipStreamWaitEvent(st, s.ev_dec, 0));
   else
     launch_decompress(st, n, d_sig, d_vk, s.key_rep, per_sig, s.pts, s.itembad + s.cap_n, s.keybad, s.flags, ctx->kc(),
@@ -1061,9 +1077,8 @@ static int enqueue_multi(edc_ctx* ctx, Slot& s, uint32_t nb, size_t n_per, const
   CK(hipMemsetAsync(s.mb_bad, 0, nb, st));
   launch_range_prebad(st, n, (uint32_t)n_per, s.itembad, s.itembad + s.cap_n, s.keybad, s.key_index, per_sig, s.mb_bad,
                       s.flags);
-  launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
-                    s.slice_T);
-  launch_msm_multi_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, s.mb_bad, want_compress, s.d_out, s.h_out);
+  launch_msm_bucket(st, P, s.msm, s.pts);
+  launch_msm_multi_tail(st, P, s.msm, s.flags, s.mb_bad, want_compress, s.d_out, s.h_out);
   CK(hipGetLastError());
   s.pending = true;
   return 0;
@@ -1330,26 +1345,21 @@ static int enqueue_host_chunked(edc_ctx* ctx, size_t n, const uint8_t* vk, const
   }
   const bool per_sig = choose_per_sig(ctx, n), split = choose_split(ctx);
   const MsmPlan P = batch_plan(ctx, n, per_sig, split);
-  rc = ensure_msm(ctx, s, P, split ? msm_entry_capacity(P, 2 + 3 * n, 0) : msm_entry_capacity(P, n, n + 1));
+  rc = ensure_msm(ctx, s, P, batch_entry_room(P, n, split));
   if (rc) return rc;
   const uint32_t N = (uint32_t)n;
-  const uint32_t T = (uint32_t)next_pow2(2 * (n < 128 ? 128 : n));
-  if (T > s.cap_T) { ctx->err = "hash table capacity"; return EDC_ERR_ARG; }
+  KeyTable kt;   // drawn here, on the calling thread: the launcher thread only reads it
+  if ((rc = key_table(ctx, s, n, per_sig, kt))) return rc;
   uint32_t seed[8];
   seed_words(z_seed, seed);
   hipStream_t st = s.st, st2 = s.st2, cs = ctx->hcs;
-  s.kin = s.k;
-  s.nmulti = 0;
-  s.timed = false;
-  s.per_sig = per_sig;
-  s.n_batch = N;
+  slot_begin(s, s.k, 0, false, per_sig, N);
   const std::vector<size_t> cb = host_chunks(n);
   const int nchunks = (int)cb.size() - 1;
   if (!k && msg_off[0] != 0) {
     rebased.resize(n + 1);
     for (size_t i = 0; i <= n; ++i) rebased[i] = msg_off[i] - msg_off[0];
   }
-  const uint64_t salt64 = per_sig ? 0 : splitmix64(ctx->secret ^ splitmix64(ctx->nbatches++));
   const KeyCacheView kc = ctx->kc();
 
   // the launcher thread: every kernel, each piece's behind that piece's events. Two copying
@@ -1372,15 +1382,14 @@ static int enqueue_host_chunked(edc_ctx* ctx, size_t n, const uint8_t* vk, const
     if (e_ != hipSuccess) return fail(#expr, e_);  \
   } while (0)
     LK(hipSetDevice(ctx->device));
-    launch_init_batch(st, s.flags, per_sig ? (int)N : -1, s.u_acc, s.d_out, per_sig ? nullptr : s.table,
-                      per_sig ? 0u : T, s.counts, P.nbin());
-    if (!gate.wait(1)) return;
-    LK(hipStreamWaitEvent(st, ctx->hev[0], 0));
-    if (!per_sig) {
-      const uint32_t salt[2] = {(uint32_t)salt64, (uint32_t)(salt64 >> 32)};
-      launch_keys(st, N, ctx->vk, s.table, T - 1, salt, ctx->key_grouping == 3, s.slot_key, s.key_slot, s.key_rep,
-                  s.key_index, s.key_acc, s.flags);
-    }
+    // the resets run under the keys' copy; the grouping waits for it
+    const bool front = launch_front(st, s, kt, N, ctx->vk, s.msm.counts, P.nbin(), 0xFFFFFFFFu, [&] {
+      if (!gate.wait(1)) return false;
+      const hipError_t e = hipStreamWaitEvent(st, ctx->hev[0], 0);
+      if (e != hipSuccess) fail("hipStreamWaitEvent(st, ctx->hev[0], 0)", e);
+      return e == hipSuccess;
+    });
+    if (!front) return;
     LK(hipEventRecord(s.ev_keys, st));
     LK(hipStreamWaitEvent(st2, s.ev_keys, 0));
     launch_decompress_range(st2, N, 0, 0, key_lanes(ctx, n, per_sig), ctx->sig, ctx->vk, s.key_rep, per_sig, s.pts,
@@ -1405,13 +1414,11 @@ static int enqueue_host_chunked(edc_ctx* ctx, size_t n, const uint8_t* vk, const
     }
     LK(hipEventRecord(s.ev_dec, st2));
     launch_coef_finish(st, N, s.key_acc, s.u_acc, s.scal, s.flags, per_sig, s.coef_part, split);
-    launch_msm_bin(st, P, batch_terms(P, s, N, split), split ? 2 + 3 * N : 1 + 2 * N, s.counts, s.offsets, s.cursor,
-                   s.entries, s.flags, true);
-    launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
+    launch_msm_bin(st, P, batch_terms(P, s, N, split), batch_term_count(N, split), s.msm, s.flags, true);
+    launch_msm_sort(st, P, s.msm);
     LK(hipStreamWaitEvent(st, s.ev_dec, 0));
-    launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads,
-                      s.slice_W, s.slice_T, 0, nullptr, nullptr, true);
-    launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, want_compress, s.d_out, s.h_out);
+    launch_msm_bucket(st, P, s.msm, s.pts, 0, nullptr, nullptr, true);
+    launch_msm_tail(st, P, s.msm, s.flags, want_compress, s.d_out, s.h_out);
     LK(hipGetLastError());
 #undef LK
   });
@@ -2226,11 +2233,10 @@ static int fallback_ranges(edc_ctx* ctx, Slot& s, size_t n, const BatchIn& in, b
                     s.scal, s.key_acc, s.u_acc, s.flags, ctx->fb_xpt, ctx->fb_xrg, ctx->fb_xscal);
   const MsmTerms terms{(uint32_t)n, (uint32_t)rsize, npoint, (uint32_t)nx, 1, s.scal, ctx->fb_xpt, ctx->fb_xrg,
                        ctx->fb_xscal};
-  launch_msm_bin(st, P, terms, npoint + (uint32_t)nx, s.counts, s.offsets, s.cursor, s.entries, s.flags);
-  launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
-  launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
-                    s.slice_T);
-  launch_msm_range_tail(st, P, s.slice_W, s.slice_T, s.win, ctx->fb_rv);
+  launch_msm_bin(st, P, terms, npoint + (uint32_t)nx, s.msm, s.flags);
+  launch_msm_sort(st, P, s.msm);
+  launch_msm_bucket(st, P, s.msm, s.pts);
+  launch_msm_range_tail(st, P, s.msm, ctx->fb_rv);
   CK(hipMemsetAsync(ctx->fb_rv + G, 0, G, st));
   launch_range_prebad(st, (uint32_t)n, (uint32_t)rsize, s.itembad, s.itembad + s.cap_n, s.keybad, s.key_index, per_sig,
                       ctx->fb_rv + G);
@@ -5589,17 +5595,17 @@ static bool verifier_split(const edc_verifier* v) {
   return ctx->kc_m && ctx->bcomb && ctx->key_split == 0 && v->hi_ok && v->hi_gen == ctx->kc_gen;
 }
 
-static uint32_t verifier_table_size(size_t cap) { return (uint32_t)next_pow2(2 * (cap < 128 ? 128 : cap)); }
-
-// flags, key table and the R bits of a verifier with nothing queued
+// flags, key table (sized for the verifier's capacity, with a fresh salt) and the R bits of a
+// verifier with nothing queued
 static int verifier_clear(edc_verifier* v) {
   edc_ctx* ctx = v->ctx;
   Slot& s = v->s;
-  v->T = verifier_table_size(v->cap);
-  if (v->T > s.cap_T) { ctx->err = "hash table capacity"; return EDC_ERR_ARG; }
-  const uint64_t h = splitmix64(ctx->secret ^ splitmix64(ctx->nbatches++));
-  v->salt[0] = (uint32_t)h;
-  v->salt[1] = (uint32_t)(h >> 32);
+  KeyTable kt;
+  const int rc = key_table(ctx, s, v->cap, false, kt);
+  v->T = kt.T;
+  if (rc) return rc;
+  v->salt[0] = kt.salt[0];
+  v->salt[1] = kt.salt[1];
   launch_init_batch(s.st, s.flags, -1, s.u_acc, s.d_out, s.table, v->T, nullptr, 0);
   CK(hipGetLastError());
   return 0;
@@ -5723,12 +5729,11 @@ static int verifier_fold(edc_verifier* v) {
   launch_z_range(st, seed, (uint32_t)a, cnt, s.scal);
   // one range of cnt short terms, term t = R of item a + t (MsmTerms::skip)
   const MsmTerms terms{cnt, 0x80000000u, cnt, 0u, 1u, s.scal, nullptr, nullptr, nullptr, 0u, 0u, (uint32_t)a};
-  launch_msm_bin(st, P, terms, cnt, s.counts, s.offsets, s.cursor, s.entries, s.flags);
-  launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
-  launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
-                    s.slice_T, 0, nullptr, nullptr, true, s.flags);
+  launch_msm_bin(st, P, terms, cnt, s.msm, s.flags);
+  launch_msm_sort(st, P, s.msm);
+  launch_msm_bucket(st, P, s.msm, s.pts, 0, nullptr, nullptr, true, s.flags);
   uint8_t* blk = reinterpret_cast<uint8_t*>(v->run + 64);
-  launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, 0, blk);
+  launch_msm_tail(st, P, s.msm, s.flags, 0, blk);
   launch_point_accum(st, v->run, blk);
   CK(hipGetLastError());
   fold_done(v->fold, b);
@@ -5959,22 +5964,17 @@ static int verifier_enqueue_verify(edc_verifier* v, const uint8_t* z_seed, const
   seed_words(z_seed, seed);
   hipStream_t st = s.st;
   if (z) CK(hipMemcpyAsync(v->zexp, z, n * 16, hipMemcpyHostToDevice, st));
-  s.kin = v->k;
-  s.nmulti = 0;
-  s.timed = false;
-  s.per_sig = false;            // an overflow (FLAG_OVF) is resolved on the device
-  s.n_batch = N;
-  launch_verifier_begin(st, N, s.flags, s.key_acc, s.u_acc, s.d_out, s.counts, P.nbin());
+  slot_begin(s, v->k, 0, false, false, N);   // per_sig false: an overflow (FLAG_OVF) is resolved on the device
+  launch_verifier_begin(st, N, s.flags, s.key_acc, s.u_acc, s.d_out, s.msm.counts, P.nbin());
   launch_coef(st, N, v->sig, v->k, z ? v->zexp : nullptr, seed, 0, s.key_index, s.scal, s.key_acc, s.u_acc, s.itembad,
               s.flags, false, s.coef_part, split);
   launch_msm_bin(st, P, batch_terms(P, s, N, split, (uint32_t)skip), (uint32_t)(split ? 2 + nl + 2 * n : 1 + nl + n),
-                 s.counts, s.offsets, s.cursor, s.entries, s.flags, true);
-  launch_msm_sort(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.buckets);
+                 s.msm, s.flags, true);
+  launch_msm_sort(st, P, s.msm);
   launch_verifier_place_keys(st, N, v->vk, verifier_kpts(v), verifier_khi(v), s.pts, s.keybad, s.flags, ctx->kc(), split);
-  launch_msm_bucket(st, P, s.counts, s.offsets, s.entries, s.sorted, s.bucket_end, s.pts, s.buckets, s.heads, s.slice_W,
-                    s.slice_T, 0, nullptr, nullptr, true, s.flags);
+  launch_msm_bucket(st, P, s.msm, s.pts, 0, nullptr, nullptr, true, s.flags);
   s.acc_nbin = P.nbin();
-  launch_msm_tail(st, P, s.slice_W, s.slice_T, s.win, s.flags, want_compress, s.d_out, s.h_out, eager ? v->run : nullptr);
+  launch_msm_tail(st, P, s.msm, s.flags, want_compress, s.d_out, s.h_out, eager ? v->run : nullptr);
   CK(hipGetLastError());
   s.pending = true;
   return 0;

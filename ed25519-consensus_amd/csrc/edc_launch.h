@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "keycache.h"
 #include "edc_common.h"
+#include "devbuf.h"
 
 namespace edc {
 // edc_prep.hip
@@ -245,32 +246,40 @@ void launch_valhash_match(hipStream_t st, uint32_t nc, const uint8_t* roots, con
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();
-// edc_msm.hip (counts_zeroed: the caller already cleared counts, e.g. launch_init_batch)
-void launch_msm_bin(hipStream_t st, const MsmPlan& P, const MsmTerms& T, uint32_t max_terms, uint32_t* counts,
-                    uint32_t* offsets, uint32_t* cursor, uint2* entries, const int* flags, bool counts_zeroed = false);
+// The MSM workspace of one slot: every buffer the binning, sort, accumulation and tail kernels pass
+// between them. Grown by its owner before a batch is enqueued (edc_api.hip ensure_msm); the
+// launchers below take it whole, so a buffer added here reaches every call site.
+struct MsmWs {
+  uint32_t cap_bins = 0, cap_ranges = 0;   // bins of the per-bin arrays, ranges of win
+  size_t cap_entries = 0;                  // digits of entries / sorted
+  devbuf::DevBuf<uint32_t> counts, offsets, cursor;
+  devbuf::DevBuf<uint2> entries;
+  devbuf::DevBuf<uint32_t> sorted;         // entries' point indices sorted by bucket within each bin
+  devbuf::DevBuf<uint32_t> slice_W, slice_T, win;
+  devbuf::DevBuf<uint32_t> buckets;        // bins x 256 bucket sums (extended)
+  devbuf::DevBuf<uint32_t> heads;          // bins x 256 head partials of the segmented accumulation
+  devbuf::DevBuf<uint32_t> bucket_end;     // bins x 256 bucket end positions of the sorted entries
+};
+// edc_msm.hip (counts_zeroed: the caller already cleared ws.counts, e.g. launch_init_batch)
+void launch_msm_bin(hipStream_t st, const MsmPlan& P, const MsmTerms& T, uint32_t max_terms, MsmWs& ws, const int* flags,
+                    bool counts_zeroed = false);
 // per-bin counting sort of the binned entries by bucket (needs only the binning: enqueued right
 // after launch_msm_bin, so on a dual-stream slot it overlaps the decode)
-void launch_msm_sort(hipStream_t st, const MsmPlan& P, const uint32_t* counts, const uint32_t* offsets,
-                     const uint2* entries, uint32_t* sorted, uint32_t* bucket_end, uint32_t* buckets);
+void launch_msm_sort(hipStream_t st, const MsmPlan& P, MsmWs& ws);
 // accumulation (+ bin reduction) of the sorted entries; launch_msm_sort must have run
-void launch_msm_bucket(hipStream_t st, const MsmPlan& P, const uint32_t* counts, const uint32_t* offsets,
-                       const uint2* entries, uint32_t* sorted, uint32_t* bucket_end, const uint32_t* pts,
-                       uint32_t* buckets, uint32_t* heads, uint32_t* slice_W, uint32_t* slice_T, int probe_skip = 0,
+void launch_msm_bucket(hipStream_t st, const MsmPlan& P, MsmWs& ws, const uint32_t* pts, int probe_skip = 0,
                        hipEvent_t acc_begin = nullptr, hipEvent_t acc_end = nullptr, bool latency = false,
                        int* stamp_flags = nullptr);   // EDC_BATCH_STAMPS builds: the batch's flags
 size_t msm_bucket_words(uint32_t nbin);
-void launch_msm_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                     uint32_t* win, int* flags, int want_compress, uint8_t* out, uint8_t* hout = nullptr,
-                     const uint32_t* extra = nullptr);   // extra: an extended point added before the x8
+void launch_msm_tail(hipStream_t st, const MsmPlan& P, MsmWs& ws, int* flags, int want_compress, uint8_t* out,
+                     uint8_t* hout = nullptr, const uint32_t* extra = nullptr);   // extra: an extended point added before the x8
 // eager verifier: run (EXT_WORDS words) += the partial point of result block blk; blk = null: run = identity
 void launch_point_accum(hipStream_t st, uint32_t* run, const uint8_t* blk);
-void launch_msm_range_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                           uint32_t* win, uint8_t* rverdict);
+void launch_msm_range_tail(hipStream_t st, const MsmPlan& P, MsmWs& ws, uint8_t* rverdict);
 // several batches in one launch: per range the window combine, Horner, x8 and identity, one
 // 256-byte result block per range at out + 256 g (and hout + 256 g)
-void launch_msm_multi_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                           uint32_t* win, const int* flags, const uint8_t* rbad, int want_compress, uint8_t* out,
-                           uint8_t* hout);
+void launch_msm_multi_tail(hipStream_t st, const MsmPlan& P, MsmWs& ws, const int* flags, const uint8_t* rbad,
+                           int want_compress, uint8_t* out, uint8_t* hout);
 void launch_combine_records(hipStream_t st, uint32_t g, const uint8_t* recs, uint32_t stride, uint8_t* out);
 void launch_combine(hipStream_t st, uint32_t g, const uint8_t* partials, int bad, int want_compress,
                     uint8_t* out);

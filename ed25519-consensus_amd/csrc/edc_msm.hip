@@ -1072,10 +1072,10 @@ extern "C" int edc_debug_set_scatter_stage(uint32_t max_entries) {
   return 0;
 }
 
-void launch_msm_bin(hipStream_t st, const MsmPlan& P, const MsmTerms& T, uint32_t max_terms, uint32_t* counts,
-                    uint32_t* offsets, uint32_t* cursor, uint2* entries, const int* flags, bool counts_zeroed) {
+void launch_msm_bin(hipStream_t st, const MsmPlan& P, const MsmTerms& T, uint32_t max_terms, MsmWs& ws, const int* flags,
+                    bool counts_zeroed) {
   const uint32_t nbin = P.nbin();
-  if (!counts_zeroed) (void)hipMemsetAsync(counts, 0, nbin * sizeof(uint32_t), st);
+  if (!counts_zeroed) (void)hipMemsetAsync(ws.counts, 0, nbin * sizeof(uint32_t), st);
   // terms per workgroup: up to 4096 (long runs of entries per bin for the scatter's writes), but
   // at least ~256 workgroups so small batches still fill the GPU
   uint32_t per = max_terms / 256;
@@ -1114,14 +1114,14 @@ void launch_msm_bin(hipStream_t st, const MsmPlan& P, const MsmTerms& T, uint32_
   // more, 84 us at 4,097; profiles/r05/r05ar, r05as)
   const uint32_t cper = std::max(256u, per / EDC_COUNT_SPLIT);
   hipLaunchKernelGGL(k_msm_count, dim3(cdiv(max_terms ? max_terms : 1, cper)), dim3(256), nbin * sizeof(uint32_t), st, P, T,
-                     cper, counts, flags);
-  hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), 0, st, nbin, counts, offsets, cursor);
+                     cper, ws.counts.get(), flags);
+  hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), 0, st, nbin, ws.counts.get(), ws.offsets.get(), ws.cursor.get());
 #ifdef EDC_PROBE_EXTRA_SCANS   // measurement only: N more (idempotent) dependent launches per batch
   for (int r = 0; r < EDC_PROBE_EXTRA_SCANS; ++r)
-    hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), 0, st, nbin, counts, offsets, cursor);
+    hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), 0, st, nbin, ws.counts.get(), ws.offsets.get(), ws.cursor.get());
 #endif
   hipLaunchKernelGGL(k_msm_scatter, dim3(sgrid), dim3(SCATTER_THREADS), bins_bytes + (size_t)stage_cap * sizeof(uint2), st, P, T,
-                     SB, cursor, entries, flags, stage_cap);
+                     SB, ws.cursor.get(), ws.entries.get(), flags, stage_cap);
 }
 
 hipError_t msm_init_device() {
@@ -1131,21 +1131,20 @@ hipError_t msm_init_device() {
 
 static const size_t kReduceLds = (size_t)NSLICE * EXT_WORDS * sizeof(uint32_t);  // 256 points; scans reuse them
 
-void launch_msm_sort(hipStream_t st, const MsmPlan& P, const uint32_t* counts, const uint32_t* offsets,
-                     const uint2* entries, uint32_t* sorted, uint32_t* bucket_end, uint32_t* buckets) {
-  hipLaunchKernelGGL(k_msm_sort, dim3(P.nbin()), dim3(256), 0, st, counts, offsets, entries, sorted, bucket_end, buckets);
+void launch_msm_sort(hipStream_t st, const MsmPlan& P, MsmWs& ws) {
+  hipLaunchKernelGGL(k_msm_sort, dim3(P.nbin()), dim3(256), 0, st, ws.counts.get(), ws.offsets.get(), ws.entries.get(),
+                     ws.sorted.get(), ws.bucket_end.get(), ws.buckets.get());
 }
 
-void launch_msm_bucket(hipStream_t st, const MsmPlan& P, const uint32_t* counts, const uint32_t* offsets,
-                       const uint2* entries, uint32_t* sorted, uint32_t* bucket_end, const uint32_t* pts,
-                       uint32_t* buckets, uint32_t* heads, uint32_t* slice_W, uint32_t* slice_T, int probe_skip,
+void launch_msm_bucket(hipStream_t st, const MsmPlan& P, MsmWs& ws, const uint32_t* pts, int probe_skip,
                        hipEvent_t acc_begin, hipEvent_t acc_end, bool latency, int* stamp_flags) {
+  uint32_t *counts = ws.counts, *buckets = ws.buckets, *slice_W = ws.slice_W, *slice_T = ws.slice_T;
   // one workgroup per bin (accumulation of the entries k_msm_sort ordered), then the bin
   // reductions (probe_skip: timing-probe builds only, edc_api.hip EDC_PROBE_SKIP; 0 in the product)
   if (acc_begin) (void)hipEventRecord(acc_begin, st);      // timed batches: the accumulation alone
   if (!(probe_skip & 32))
-    hipLaunchKernelGGL(k_msm_accum_dma, dim3(P.nbin()), dim3(256), 0, st, counts, offsets, sorted, bucket_end, pts,
-                       buckets, heads, slice_W, slice_T, stamp_flags);
+    hipLaunchKernelGGL(k_msm_accum_dma, dim3(P.nbin()), dim3(256), 0, st, counts, ws.offsets.get(), ws.sorted.get(),
+                       ws.bucket_end.get(), pts, buckets, ws.heads.get(), slice_W, slice_T, stamp_flags);
   if (acc_end) (void)hipEventRecord(acc_end, st);
   if (probe_skip & 64) return;
   // latency: one synchronous batch on an idle GPU (edc_batch_verify*): the quad-cooperative weighted
@@ -1190,8 +1189,9 @@ static void launch_final(hipStream_t st, const MsmPlan& P, const uint32_t* slice
                        from, from_w, extra);
 }
 
-void launch_msm_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                     uint32_t* win, int* flags, int want_compress, uint8_t* out, uint8_t* hout, const uint32_t* extra) {
+void launch_msm_tail(hipStream_t st, const MsmPlan& P, MsmWs& ws, int* flags, int want_compress, uint8_t* out,
+                     uint8_t* hout, const uint32_t* extra) {
+  uint32_t *slice_W = ws.slice_W, *slice_T = ws.slice_T, *win = ws.win;
   const uint32_t r = top_run_start(P);
   if (plan_multi(P) && r < P.nwin && r > 0 && P.nwin < MSM_MAX_WIN) {
     // window combines beside the top-run Horner; hbuf = the unused last window record of range 0
@@ -1205,16 +1205,16 @@ void launch_msm_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, 
   launch_final(st, P, slice_W, win, flags, want_compress, out, hout, nullptr, 0u, extra);
 }
 
-void launch_msm_range_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                           uint32_t* win, uint8_t* rverdict) {
+void launch_msm_range_tail(hipStream_t st, const MsmPlan& P, MsmWs& ws, uint8_t* rverdict) {
+  uint32_t *slice_W = ws.slice_W, *slice_T = ws.slice_T, *win = ws.win;
   if (plan_multi(P))
     hipLaunchKernelGGL(k_msm_window, dim3(P.nwin * P.nranges), dim3(256), kReduceLds, st, P, slice_W, slice_T, win);
   hipLaunchKernelGGL(k_msm_range_final, dim3(P.nranges), dim3(64), 0, st, P, slice_W, win, rverdict);
 }
 
-void launch_msm_multi_tail(hipStream_t st, const MsmPlan& P, const uint32_t* slice_W, const uint32_t* slice_T,
-                           uint32_t* win, const int* flags, const uint8_t* rbad, int want_compress, uint8_t* out,
-                           uint8_t* hout) {
+void launch_msm_multi_tail(hipStream_t st, const MsmPlan& P, MsmWs& ws, const int* flags, const uint8_t* rbad,
+                           int want_compress, uint8_t* out, uint8_t* hout) {
+  uint32_t *slice_W = ws.slice_W, *slice_T = ws.slice_T, *win = ws.win;
   if (plan_multi(P))
     hipLaunchKernelGGL(k_msm_window, dim3(P.nwin * P.nranges), dim3(256), kReduceLds, st, P, slice_W, slice_T, win);
   hipLaunchKernelGGL(k_msm_multi_final, dim3(P.nranges), dim3(64), 0, st, P, slice_W, win, flags, rbad, want_compress,
