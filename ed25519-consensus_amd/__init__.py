@@ -91,7 +91,26 @@ ABI_SYMBOLS = [
     "edc_vq_verify", "edc_debug_vq_last",
     "edc_vq_trust_resolve", "edc_debug_vq_trust_last", "edc_debug_vq_trust_select",
     "edc_valhash_valset", "edc_valhash_vhist", "edc_valhash_vhist_match", "edc_debug_valhash_ms",
+    "edc_header_hashes", "edc_header_bind", "edc_debug_header_ms",
 ]
+# header hashes (include/edc.h, edc_header_*)
+HEADER_MAX_LEAVES = 64
+HEADER_NONE = 0xFFFFFFFF
+HEADER_BAD_HASH, HEADER_BAD_VALS, HEADER_BAD_NEXT, HEADER_BAD_LINK = 1, 2, 4, 8
+
+
+class EdcHeaderSet(ctypes.Structure):
+    """struct edc_header_set (include/edc.h): headers as their ordered leaves, host memory."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("nh", ctypes.c_size_t),
+                ("leaf_off", ctypes.c_void_p), ("byte_off", ctypes.c_void_p), ("bytes", ctypes.c_void_p)]
+
+
+class EdcHeaderRules(ctypes.Structure):
+    """struct edc_header_rules (include/edc.h): what each header is compared with; arrays nullable."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("expect", ctypes.c_void_p),
+                ("vals_ver", ctypes.c_void_p), ("vals_leaf", ctypes.c_uint32), ("vals_pos", ctypes.c_uint32),
+                ("next_ver", ctypes.c_void_p), ("next_leaf", ctypes.c_uint32), ("next_pos", ctypes.c_uint32),
+                ("link", ctypes.c_void_p), ("link_leaf", ctypes.c_uint32), ("link_pos", ctypes.c_uint32)]
 
 
 class EdcTemplates(ctypes.Structure):
@@ -456,6 +475,11 @@ def load_library(path=None):
             lib.edc_valhash_vhist.argtypes = [c_vp, ctypes.c_uint32, c_sz, c_vp]
             lib.edc_valhash_vhist_match.argtypes = [c_vp, c_sz, c_u32p, c_vp, c_vp, c_szp]
             lib.edc_debug_valhash_ms.argtypes = [c_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+        if hasattr(lib, "edc_header_bind"):                  # absent from older A/B builds (tools/)
+            c_hsp = ctypes.POINTER(EdcHeaderSet)
+            lib.edc_header_hashes.argtypes = [c_vp, c_hsp, c_vp]
+            lib.edc_header_bind.argtypes = [c_vp, c_hsp, ctypes.POINTER(EdcHeaderRules), c_vp, c_vp, c_szp]
+            lib.edc_debug_header_ms.argtypes = [c_vp, c_hsp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         if path is None:
             _lib = lib
         return lib
@@ -1177,6 +1201,77 @@ class Engine:
         with self._lock:
             self._check(self.lib.edc_debug_valhash_ms(self.ctx, reps, ms))
         return {"roots": float(ms[0]), "addresses": float(ms[1])}
+
+    # ---- header hashes (edc_header_*): the Merkle root of a header given as its ordered leaves ----
+    @staticmethod
+    def _header_set(headers):
+        """headers: a list of lists of bytes -> (EdcHeaderSet, the buffers it points into)"""
+        headers = [[bytes(x) for x in h] for h in headers]
+        leaf_off, byte_off = [0], [0]
+        for h in headers:
+            leaf_off.append(leaf_off[-1] + len(h))
+            for x in h:
+                byte_off.append(byte_off[-1] + len(x))
+        if leaf_off[-1] >= 1 << 32 or byte_off[-1] >= 1 << 32:
+            raise ValueError("leaf and byte offsets are uint32")
+        lo, bo = (ctypes.c_uint32 * len(leaf_off))(*leaf_off), (ctypes.c_uint32 * len(byte_off))(*byte_off)
+        data = ctypes.create_string_buffer(b"".join(x for h in headers for x in h), max(byte_off[-1], 1))
+        hs = EdcHeaderSet(ctypes.sizeof(EdcHeaderSet), 0, len(headers), ctypes.addressof(lo), ctypes.addressof(bo),
+                          ctypes.addressof(data) if byte_off[-1] else None)
+        return hs, (lo, bo, data)
+
+    def header_hashes(self, headers):
+        """edc_header_hashes: headers, a list of lists of bytes (each header's ordered leaves) -> the
+        32-byte Merkle root of each."""
+        hs, keep = self._header_set(headers)
+        nh = len(headers)
+        out = ctypes.create_string_buffer(max(32 * nh, 1))
+        with self._lock:
+            self._check(self.lib.edc_header_hashes(self.ctx, ctypes.byref(hs), out))
+        return [out.raw[32 * h:32 * h + 32] for h in range(nh)]
+
+    def header_bind(self, headers, expect=None, vals=None, nexts=None, link=None, vals_at=(7, 2), next_at=(8, 2),
+                    link_at=(4, 2)):
+        """edc_header_bind: hashes every header and holds it to the rules given. expect: 32 bytes per
+        header; vals / nexts: per header the history version whose validator-set root the header
+        names at (leaf, position) vals_at / next_at; link: per header the index of the header of this
+        list whose root it names at link_at. None in place of a list: no such rule; None (or
+        HEADER_NONE) as an entry: that header is skipped. -> (bad, n_bad, roots): per header the
+        HEADER_BAD_* bits, the number of non-zero ones, the 32-byte roots."""
+        hs, keep = self._header_set(headers)
+        nh = len(headers)
+
+        def u32s(name, xs):
+            if xs is None:
+                return None
+            xs = [HEADER_NONE if x is None else int(x) for x in xs]
+            if len(xs) != nh:
+                raise ValueError("%s: one entry per header" % name)
+            if any(x < 0 or x >= 1 << 32 for x in xs):
+                raise ValueError("%s: entries are uint32" % name)
+            return (ctypes.c_uint32 * max(nh, 1))(*xs)
+        exp = None
+        if expect is not None:
+            expect = [bytes(e) for e in expect]
+            if len(expect) != nh or any(len(e) != 32 for e in expect):
+                raise InvalidSliceLength("expect: 32 bytes per header")
+            exp = ctypes.create_string_buffer(b"".join(expect), max(32 * nh, 1))
+        arrs = [u32s("vals", vals), u32s("nexts", nexts), u32s("link", link)]
+        addr = lambda a: ctypes.addressof(a) if a is not None else None
+        r = EdcHeaderRules(ctypes.sizeof(EdcHeaderRules), 0, addr(exp), addr(arrs[0]), vals_at[0], vals_at[1],
+                           addr(arrs[1]), next_at[0], next_at[1], addr(arrs[2]), link_at[0], link_at[1])
+        bad, out, n_bad = ctypes.create_string_buffer(max(nh, 1)), ctypes.create_string_buffer(max(32 * nh, 1)), ctypes.c_size_t(0)
+        with self._lock:
+            self._check(self.lib.edc_header_bind(self.ctx, ctypes.byref(hs), ctypes.byref(r), bad, out, ctypes.byref(n_bad)))
+        return list(bad.raw[:nh]), int(n_bad.value), [out.raw[32 * h:32 * h + 32] for h in range(nh)]
+
+    def header_ms(self, headers, reps=20):
+        """edc_debug_header_ms: mean times (ms) of the root kernel and of the bind kernel over headers."""
+        hs, keep = self._header_set(headers)
+        ms = (ctypes.c_float * 2)()
+        with self._lock:
+            self._check(self.lib.edc_debug_header_ms(self.ctx, ctypes.byref(hs), reps, ms))
+        return {"roots": float(ms[0]), "bind": float(ms[1])}
 
     @staticmethod
     def _vhist_versions_arg(nc, versions):
@@ -2236,6 +2331,79 @@ class batch:  # namespace mirroring `ed25519_consensus::batch`
                 run = []
             run.append(v)
         return [roots[v] for v in versions]
+
+    @staticmethod
+    def _header_engine(name, engine):
+        eng = engine if engine is not None else default_engine()
+        if not isinstance(eng, Engine):
+            raise ValueError("%s: engine is no Engine" % name)
+        return eng
+
+    @staticmethod
+    def header_hashes(headers, engine=None):
+        """The hash of block headers (edc_header_hashes; not an API of the reference): headers is a
+        list of headers, each the list of its ordered leaves as bytes (cometbft_header_leaves builds
+        the 14 of a CometBFT header) -> the 32-byte RFC 6962 Merkle root of each."""
+        return batch._header_engine("header_hashes", engine).header_hashes(headers)
+
+    @staticmethod
+    def verify_headers(headers, expect=None, vals=None, nexts=None, link=None, vals_at=(7, 2), next_at=(8, 2),
+                       link_at=(4, 2), engine=None):
+        """Hashes every header and binds it (edc_header_bind; not an API of the reference): to the hash
+        it must have (expect, what the votes of its commit sign), to the validator-set roots of the
+        engine's history (vals, nexts: per header a version of Engine.vhist_set, compared with the 32
+        bytes at (leaf, position) vals_at / next_at) and to another header of the list (link: per
+        header the index of the header whose hash it carries at link_at, as a header carries its
+        predecessor's in last_block_id). None for a list: no such rule; None as an entry: that header
+        is skipped. -> (bad, n_bad, roots): per header 0 or the HEADER_BAD_* bits of the rules that do
+        not hold, the number of non-zero entries, the hashes."""
+        return batch._header_engine("verify_headers", engine).header_bind(headers, expect, vals, nexts, link, vals_at, next_at,
+                                                                          link_at)
+
+    @staticmethod
+    def cometbft_header_leaves(version_block=0, version_app=0, chain_id="", height=0, time_seconds=0, time_nanos=0,
+                               last_block_hash=b"", last_parts_total=0, last_parts_hash=b"", last_commit_hash=b"",
+                               data_hash=b"", validators_hash=b"", next_validators_hash=b"", consensus_hash=b"",
+                               app_hash=b"", last_results_hash=b"", evidence_hash=b"", proposer_address=b""):
+        """The 14 leaves of a CometBFT header, in the order Header.Hash() hashes them, from the field
+        values: pure Python, no device work. The proto3 encodings are stated from memory, as
+        include/edc.h states the hash; the contract is the bytes written here. uvarint is base-128,
+        little-endian; a negative int64 is its 64-bit two's complement (10 bytes). Zero and empty
+        fields are omitted everywhere, so a leaf may be empty; only the part-set header inside the
+        block id is always emitted.
+           0  version               (08 uvarint(block) if block != 0) | (10 uvarint(app) if app != 0)
+           1  chain_id              0A uvarint(len) utf-8 bytes, or nothing for ""
+           2  height                08 uvarint(height), or nothing for 0
+           3  time                  (08 uvarint(seconds) if seconds != 0) | (10 uvarint(nanos) if nanos != 0)
+           4  last_block_id         (0A uvarint(len) hash if hash) | 12 uvarint(len(P)) P, with the part-set
+                                    header P = (08 uvarint(total) if total != 0) | (12 uvarint(len) hash if
+                                    hash); 12 00 for an empty one. With two 32-byte hashes and total < 128
+                                    this is 72 bytes and the block hash starts at position 2.
+           5..12 last_commit_hash, data_hash, validators_hash, next_validators_hash, consensus_hash,
+                 app_hash, last_results_hash, evidence_hash: 0A uvarint(len) bytes, or nothing when empty;
+                 a 32-byte hash starts at position 2, behind 0A 20
+          13  proposer_address      the same"""
+        def uv(x):
+            x = int(x) & 0xFFFFFFFFFFFFFFFF
+            out = bytearray()
+            while x >= 0x80:
+                out.append((x & 0x7F) | 0x80)
+                x >>= 7
+            out.append(x)
+            return bytes(out)
+        num = lambda tag, x: bytes([tag]) + uv(x) if int(x) != 0 else b""
+        blob = lambda tag, b: bytes([tag]) + uv(len(b)) + bytes(b) if len(b) else b""
+        parts = num(0x08, last_parts_total) + blob(0x12, last_parts_hash)
+        return [
+            num(0x08, version_block) + num(0x10, version_app),
+            blob(0x0A, chain_id.encode() if isinstance(chain_id, str) else bytes(chain_id)),
+            num(0x08, height),
+            num(0x08, time_seconds) + num(0x10, time_nanos),
+            blob(0x0A, last_block_hash) + b"\x12" + uv(len(parts)) + parts,
+            blob(0x0A, last_commit_hash), blob(0x0A, data_hash), blob(0x0A, validators_hash),
+            blob(0x0A, next_validators_hash), blob(0x0A, consensus_hash), blob(0x0A, app_hash),
+            blob(0x0A, last_results_hash), blob(0x0A, evidence_hash), blob(0x0A, proposer_address),
+        ]
 
     class StreamVerifier:
         """reference src/batch.rs:110-217 with the reference's division of work: queue() does the

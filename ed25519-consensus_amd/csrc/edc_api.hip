@@ -26,6 +26,7 @@
 #include "valset.h"
 #include "vhist.h"
 #include "valhash.h"
+#include "hdrhash.h"
 #include "sigcache.h"
 #include "devbuf.h"
 
@@ -308,6 +309,14 @@ struct edc_ctx {
   DevBuf<uint32_t> vx_rank, vx_by_rank, vx_in;
   bool vx_ranked = false;
   DevBuf<uint8_t> vx_roots, vx_ok;
+  // header hashes (hdrhash.h; edc_header_hashes, edc_header_bind): per call, on slot 0's stream, the
+  // staged set (leaf offsets, byte offsets, the bytes as whole words), the staged rules (expect;
+  // vals index | next index | link | the distinct versions), what comes back in one piece
+  // (roots | count, 16 bytes | bad) and its pinned host copy. The set roots of the named versions
+  // go through vx_roots. Nothing is kept between calls.
+  DevBuf<uint32_t> hd_leaf, hd_byte, hd_words, hd_expect, hd_meta;
+  DevBuf<uint8_t> hd_out;
+  PinnedBuf<uint8_t> hd_host;
   // validator-set requests (edc_vq_verify): the host copy edc_debug_vq_last returns
   uint64_t vq_last[8] = {};
   bool vq_have = false;
@@ -5374,6 +5383,241 @@ int edc_debug_valhash_ms(edc_ctx* ctx, int reps, float ms[2]) {
   CK(hipGetLastError());
   CK(hipEventRecord(e[1], st));
   for (int r = 0; r < reps; ++r) launch_valhash_addr(st, ctx->kc_reg_m, ctx->kc_keys, ctx->kc_reg, d_addr);
+  CK(hipGetLastError());
+  CK(hipEventRecord(e[2], st));
+  CK(hipEventSynchronize(e[2]));
+  for (int j = 0; j < 2; ++j) {
+    float t = 0.f;
+    CK(hipEventElapsedTime(&t, e[j], e[j + 1]));
+    ms[j] = t / (float)reps;
+  }
+  return EDC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- header hashes
+// edc_header_hashes, edc_header_bind (hdrhash.h, edc_header.hip): what they refuse (header_check
+// for the set, the entry's own arguments, header_rules_check for the rules; all of it before any
+// device work, so that a refused call has changed nothing), the staging of the set (header_stage),
+// then on slot 0's stream the set roots of the named versions (the root kernel of the set hashes),
+// the header roots, the rules, one read-back into pinned memory and one synchronization.
+struct HeaderCall {
+  uint32_t nh = 0, nl = 0, nbytes = 0, max_leaves = 0;
+  size_t roots_at() const { return 0; }
+  size_t count_at() const { return (size_t)32 * nh; }
+  size_t bad_at() const { return (size_t)32 * nh + 16; }
+  size_t out_bytes() const { return (size_t)33 * nh + 16; }
+};
+
+static int header_check(edc_ctx* ctx, const edc_header_set* hs, HeaderCall* hc) {
+  if (!hs || hs->size != sizeof(edc_header_set) || hs->reserved) { ctx->err = "header set: NULL, a wrong size or a non-zero reserved"; return EDC_ERR_ARG; }
+  *hc = HeaderCall{};
+  if (!hs->nh) return 0;
+  if (hs->nh >= (1ull << 32)) { ctx->err = "header set: fewer than 2^32 headers"; return EDC_ERR_ARG; }
+  if (!hs->leaf_off || !hs->byte_off) { ctx->err = "header set: null offsets"; return EDC_ERR_ARG; }
+  if (hs->leaf_off[0]) { ctx->err = "header set: leaf_off starts at 0"; return EDC_ERR_ARG; }
+  uint32_t mx = 0;
+  for (size_t h = 0; h < hs->nh; ++h) {
+    if (hs->leaf_off[h + 1] < hs->leaf_off[h]) { ctx->err = "header set: leaf_off is not monotone"; return EDC_ERR_ARG; }
+    mx = std::max(mx, hs->leaf_off[h + 1] - hs->leaf_off[h]);
+  }
+  if (mx > HEADER_MAX_LEAVES) { ctx->err = "header set: a header above EDC_HEADER_MAX_LEAVES leaves"; return EDC_ERR_ARG; }
+  const uint32_t nl = hs->leaf_off[hs->nh];
+  if (hs->byte_off[0]) { ctx->err = "header set: byte_off starts at 0"; return EDC_ERR_ARG; }
+  for (size_t j = 0; j < nl; ++j)
+    if (hs->byte_off[j + 1] < hs->byte_off[j]) { ctx->err = "header set: byte_off is not monotone"; return EDC_ERR_ARG; }
+  const uint32_t nbytes = hs->byte_off[nl];
+  if (nbytes && !hs->bytes) { ctx->err = "header set: null bytes"; return EDC_ERR_ARG; }
+  if (nbytes >= 0xFFFFFFFFu - 1023) { ctx->err = "header set: fewer than 2^32 - 1024 bytes"; return EDC_ERR_ARG; }
+  hc->nh = (uint32_t)hs->nh;
+  hc->nl = nl;
+  hc->nbytes = nbytes;
+  hc->max_leaves = mx;
+  return 0;
+}
+
+// The set on the device and room for what comes back. The byte array is staged as whole words,
+// the last one zeroed first, so that the kernels may read the word of any byte.
+static int header_stage(edc_ctx* ctx, const edc_header_set* hs, const HeaderCall& hc, HeaderSrc* src) {
+  int rc = init_slot(ctx, ctx->slot[0]);
+  if (rc) return rc;
+  hipStream_t st = ctx->st();
+  const size_t nw = ((size_t)hc.nbytes + 3) / 4;
+  CK(grow(ctx->hd_leaf, (size_t)hc.nh + 1, off_cap, sync_of(st)));
+  CK(grow(ctx->hd_byte, (size_t)hc.nl + 1, off_cap, sync_of(st)));
+  CK(grow(ctx->hd_words, nw, item_cap, sync_of(st)));
+  CK(grow(ctx->hd_out, hc.out_bytes(), byte_cap, sync_of(st)));
+  CK(grow(ctx->hd_host, hc.out_bytes(), byte_cap, sync_of(st)));
+  CK(hipMemcpyAsync(ctx->hd_leaf, hs->leaf_off, ((size_t)hc.nh + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->hd_byte, hs->byte_off, ((size_t)hc.nl + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (nw) {
+    CK(hipMemsetAsync(ctx->hd_words + (nw - 1), 0, sizeof(uint32_t), st));
+    CK(hipMemcpyAsync(ctx->hd_words, hs->bytes, hc.nbytes, hipMemcpyHostToDevice, st));
+  }
+  *src = HeaderSrc{hc.nh, ctx->hd_leaf, ctx->hd_byte, ctx->hd_words};
+  return 0;
+}
+
+// the entries' common front: the context's device, the set, slot 0
+static int header_ready(edc_ctx* ctx, const edc_header_set* hs, HeaderCall* hc) {
+  CK(hipSetDevice(ctx->device));
+  const int rc = header_check(ctx, hs, hc);
+  if (rc) return rc;
+  return claim_slot0(ctx) ? 0 : EDC_ERR_ARG;
+}
+
+extern "C" {
+
+int edc_header_hashes(edc_ctx* ctx, const edc_header_set* hs, uint8_t* out) {
+  if (!ctx) return EDC_ERR_ARG;
+  HeaderCall hc;
+  int rc = header_ready(ctx, hs, &hc);
+  if (rc) return rc;
+  if (!hc.nh) return EDC_OK;
+  if (!out) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  HeaderSrc src;
+  if ((rc = header_stage(ctx, hs, hc, &src))) return rc;
+  hipStream_t st = ctx->st();
+  launch_header_roots(st, src, hc.max_leaves, ctx->hd_out);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(ctx->hd_host, ctx->hd_out, (size_t)32 * hc.nh, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));         // out is written only by a call that succeeds
+  memcpy(out, ctx->hd_host, (size_t)32 * hc.nh);
+  return EDC_OK;
+}
+
+int edc_header_bind(edc_ctx* ctx, const edc_header_set* hs, const edc_header_rules* r, uint8_t* bad, uint8_t* out,
+                    size_t* n_bad) {
+  if (!ctx) return EDC_ERR_ARG;
+  HeaderCall hc;
+  int rc = header_ready(ctx, hs, &hc);
+  if (rc) return rc;
+  if (!r || r->size != sizeof(edc_header_rules) || r->reserved) { ctx->err = "header rules: NULL, a wrong size or a non-zero reserved"; return EDC_ERR_ARG; }
+  if (!hc.nh) {
+    if (n_bad) *n_bad = 0;
+    return EDC_OK;
+  }
+  if (!bad) { ctx->err = "null output"; return EDC_ERR_ARG; }
+  const size_t nh = hc.nh;
+  // every distinct version either array names is hashed once: the sorted distinct versions, and
+  // per header its place among them
+  const bool by_ver = r->vals_ver || r->next_ver;
+  std::vector<uint32_t> vers;
+  uint32_t mx = 0;
+  if (by_ver) {
+    if (!ctx->kc_reg_m) { ctx->err = "no registered key list (edc_keycache_load)"; return EDC_ERR_ARG; }
+    if ((rc = vhist_ready(ctx, 0, nullptr))) return rc;
+    for (const uint32_t* ver : {r->vals_ver, r->next_ver}) {
+      if (!ver) continue;
+      for (size_t h = 0; h < nh; ++h) {
+        if (ver[h] == EDC_HEADER_NONE) continue;
+        if (ver[h] > ctx->vh.nv) { ctx->err = "header rules: a version past the history's last"; return EDC_ERR_ARG; }
+        vers.push_back(ver[h]);
+      }
+    }
+    std::sort(vers.begin(), vers.end());
+    vers.erase(std::unique(vers.begin(), vers.end()), vers.end());
+    if ((rc = valhash_max_members(ctx, vers.size(), vers.data(), 0, &mx))) return rc;
+  }
+  if (r->link)
+    for (size_t h = 0; h < nh; ++h)
+      if (r->link[h] != EDC_HEADER_NONE && r->link[h] >= nh) { ctx->err = "header rules: a link past the set's last header"; return EDC_ERR_ARG; }
+  const size_t nd = vers.size();
+  if ((rc = init_slot(ctx, ctx->slot[0])) || (nd && (rc = valhash_ranks(ctx)))) return rc;
+  // staged in one piece: vals index | next index | link | the versions, each part only when asked for
+  std::vector<uint32_t> meta;
+  size_t at_vals = 0, at_next = 0, at_link = 0, at_vers = 0;
+  auto place = [&](const uint32_t* ver, size_t* at) {
+    if (!ver) return;
+    *at = meta.size();
+    for (size_t h = 0; h < nh; ++h)
+      meta.push_back(ver[h] == EDC_HEADER_NONE ? EDC_HEADER_NONE
+                                               : (uint32_t)(std::lower_bound(vers.begin(), vers.end(), ver[h]) - vers.begin()));
+  };
+  place(r->vals_ver, &at_vals);
+  place(r->next_ver, &at_next);
+  if (r->link) {
+    at_link = meta.size();
+    meta.insert(meta.end(), r->link, r->link + nh);
+  }
+  at_vers = meta.size();
+  meta.insert(meta.end(), vers.begin(), vers.end());
+
+  HeaderSrc src;
+  if ((rc = header_stage(ctx, hs, hc, &src))) return rc;
+  hipStream_t st = ctx->st();
+  if (r->expect) {
+    CK(grow(ctx->hd_expect, nh * 8, item_cap, sync_of(st)));
+    CK(hipMemcpyAsync(ctx->hd_expect, r->expect, nh * 32, hipMemcpyHostToDevice, st));
+  }
+  if (!meta.empty()) {
+    CK(grow(ctx->hd_meta, meta.size(), item_cap, sync_of(st)));
+    CK(hipMemcpyAsync(ctx->hd_meta, meta.data(), meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  if (nd) {
+    CK(grow(ctx->vx_roots, nd * 32, byte_cap, sync_of(st)));
+    CK(launch_valhash_roots(st, valhash_src(ctx, true), (uint32_t)nd, ctx->hd_meta + at_vers, 0, mx, ctx->vx_roots));
+  }
+  uint8_t* const d_out = ctx->hd_out;
+  uint32_t* const d_cnt = reinterpret_cast<uint32_t*>(d_out + hc.count_at());
+  CK(hipMemsetAsync(d_cnt, 0, 16, st));
+  launch_header_roots(st, src, hc.max_leaves, d_out + hc.roots_at());
+  HeaderBind hb{};
+  hb.expect = r->expect ? ctx->hd_expect.get() : nullptr;
+  hb.vals_idx = r->vals_ver ? ctx->hd_meta + at_vals : nullptr;
+  hb.next_idx = r->next_ver ? ctx->hd_meta + at_next : nullptr;
+  hb.link = r->link ? ctx->hd_meta + at_link : nullptr;
+  hb.set_roots = nd ? reinterpret_cast<const uint32_t*>(ctx->vx_roots.get()) : nullptr;
+  hb.vals_leaf = r->vals_leaf; hb.vals_pos = r->vals_pos;
+  hb.next_leaf = r->next_leaf; hb.next_pos = r->next_pos;
+  hb.link_leaf = r->link_leaf; hb.link_pos = r->link_pos;
+  launch_header_bind(st, src, hb, d_out + hc.roots_at(), d_out + hc.bad_at(), d_cnt);
+  CK(hipGetLastError());
+  // the bad bytes, the count and, when asked for, the roots: one copy, one synchronization
+  const size_t from = out ? hc.roots_at() : hc.count_at();
+  uint8_t* const host = ctx->hd_host;
+  CK(hipMemcpyAsync(host + from, d_out + from, hc.out_bytes() - from, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));         // a failed kernel must not leave part of an output written
+  memcpy(bad, host + hc.bad_at(), nh);
+  if (out) memcpy(out, host + hc.roots_at(), nh * 32);
+  if (n_bad) {
+    uint32_t c;
+    memcpy(&c, host + hc.count_at(), sizeof(c));
+    *n_bad = c;
+  }
+  return EDC_OK;
+}
+
+// Measurement hook: mean times over reps launches of the root kernel over hs (ms[0]) and of the
+// bind kernel with all four compares per header, each against the header's own root (expect, and
+// the leaves 7, 8 and 4 at position 2), which needs no history (ms[1]).
+int edc_debug_header_ms(edc_ctx* ctx, const edc_header_set* hs, int reps, float ms[2]) {
+  if (!ctx || reps < 1 || !ms) return EDC_ERR_ARG;
+  HeaderCall hc;
+  int rc = header_ready(ctx, hs, &hc);
+  if (rc) return rc;
+  ms[0] = ms[1] = 0.f;
+  if (!hc.nh) return EDC_OK;
+  HeaderSrc src;
+  if ((rc = header_stage(ctx, hs, hc, &src))) return rc;
+  hipStream_t st = ctx->st();
+  std::vector<uint32_t> own(hc.nh);
+  for (uint32_t h = 0; h < hc.nh; ++h) own[h] = h;
+  CK(grow(ctx->hd_meta, own.size(), item_cap, sync_of(st)));
+  CK(hipMemcpyAsync(ctx->hd_meta, own.data(), own.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  uint8_t* const d_out = ctx->hd_out;
+  const uint32_t* const d_roots = reinterpret_cast<const uint32_t*>(d_out + hc.roots_at());
+  uint32_t* const d_cnt = reinterpret_cast<uint32_t*>(d_out + hc.count_at());
+  CK(hipMemsetAsync(d_cnt, 0, 16, st));
+  const HeaderBind hb{d_roots, ctx->hd_meta, ctx->hd_meta, ctx->hd_meta, d_roots, 7, 2, 8, 2, 4, 2};
+  Event e[3];
+  for (Event& x : e) CK(x.create());
+  CK(hipEventRecord(e[0], st));
+  for (int i = 0; i < reps; ++i) launch_header_roots(st, src, hc.max_leaves, d_out + hc.roots_at());
+  CK(hipGetLastError());
+  CK(hipEventRecord(e[1], st));
+  for (int i = 0; i < reps; ++i) launch_header_bind(st, src, hb, d_out + hc.roots_at(), d_out + hc.bad_at(), d_cnt);
   CK(hipGetLastError());
   CK(hipEventRecord(e[2], st));
   CK(hipEventSynchronize(e[2]));

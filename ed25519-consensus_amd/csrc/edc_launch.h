@@ -243,6 +243,35 @@ hipError_t launch_valhash_roots(hipStream_t st, const ValhashSrc& src, uint32_t 
 // ok[c] = 1 iff the 32 bytes at expect + 32 c equal root idx[c]
 void launch_valhash_match(hipStream_t st, uint32_t nc, const uint8_t* roots, const uint32_t* idx, const uint8_t* expect,
                           uint8_t* ok);
+// edc_header.hip: header hashes (hdrhash.h; edc_header_hashes, edc_header_bind). A header set on
+// the device: header h owns the leaves [leaf_off[h], leaf_off[h + 1]) (at most HEADER_MAX_LEAVES),
+// leaf j the bytes [byte_off[j], byte_off[j + 1]) of the byte array, which is held as aligned words:
+// a whole number of them, zero behind the last byte, so that the word of any byte can be read whole.
+struct HeaderSrc {
+  uint32_t nh;
+  const uint32_t* leaf_off;
+  const uint32_t* byte_off;
+  const uint32_t* words;
+};
+// What the rules compare with, all on the device and each array nullable (no rule): expect, nh x 8
+// words; vals_idx / next_idx, per header the index into set_roots (8 words each, as
+// launch_valhash_roots wrote them) or HEADER_NONE; link, per header the index of another header
+// of the set or HEADER_NONE.
+struct HeaderBind {
+  const uint32_t* expect;
+  const uint32_t* vals_idx;
+  const uint32_t* next_idx;
+  const uint32_t* link;
+  const uint32_t* set_roots;
+  uint32_t vals_leaf, vals_pos, next_leaf, next_pos, link_leaf, link_pos;
+};
+// roots (nh x 32 bytes, 16-byte aligned) = the Merkle root of every header; max_leaves: no header
+// holds more (the caller checked it against HEADER_MAX_LEAVES). It sizes the lane group of a header.
+void launch_header_roots(hipStream_t st, const HeaderSrc& src, uint32_t max_leaves, uint8_t* roots);
+// bad[h] = the EDC_HEADER_BAD_* bits of header h under the rules, with roots as written above;
+// *n_bad (zeroed by the caller) += the number of non-zero bytes
+void launch_header_bind(hipStream_t st, const HeaderSrc& src, const HeaderBind& rules, const uint8_t* roots, uint8_t* bad,
+                        uint32_t* n_bad);
 // edc_msm.hip: per-device kernel attributes (the scatter's dynamic LDS beyond 64 KB); call on
 // every device a context uses, after hipSetDevice
 hipError_t msm_init_device();

@@ -129,4 +129,63 @@ EDC_HD void sha256_node(const uint32_t l[8], const uint32_t r[8], uint32_t out[8
   for (int j = 0; j < 8; ++j) out[j] = h[j];
 }
 
+// The four message bytes be (big-endian, the first byte on top) that start rel bytes into a message
+// whose data ends after len bytes: whole inside it as they are, past its end cut, the padding's 80
+// behind the last byte, nothing after that. rel and len are small enough for rel + 4 not to wrap.
+EDC_HD uint32_t sha256_tail(uint32_t be, uint32_t rel, uint32_t len) {
+  if (rel + 4 <= len) return be;
+  if (rel > len) return 0;
+  const uint32_t nb = len - rel;        // 0..3 bytes of data in this word
+  return (be & ~(0xFFFFFFFFu >> (8 * nb))) | (0x80000000u >> (8 * nb));
+}
+
+// The leaf hash of a Merkle tree over arbitrary byte strings (edc_header.hip):
+// SHA-256(00 | bytes[a .. b)) for any length, 0 included, one block or many. words is the byte
+// array as aligned little-endian words (the array starts on a word boundary and its allocation is
+// a whole number of words: the word that holds byte b - 1 is read whole). The leaf may start at
+// any byte. With the 00 in front, message word W >= 1 is the four bytes from a + 4 W - 1, so every
+// word of the message has the same shift against the aligned words: each aligned word is read once,
+// joined with the one before it, and byte-swapped. A word without a byte of the leaf is not read,
+// and what lies behind the leaf's end in a word that is read is masked away (sha256_tail). The
+// padding is the 80 behind the last byte, zeros, and the 64-bit bit length 8 (1 + b - a) in the last
+// two words of the last block; 1 + b - a + 9 bytes rounded up to 64 give the block count.
+// b < 2^32 - 1024 (the caller checks it), so no sum here wraps.
+EDC_HD void sha256_leaf_stream(const uint32_t* words, uint32_t a, uint32_t b, uint32_t out[8]) {
+  const uint32_t len = b - a;
+  const uint32_t nblk = (len >> 6) + (((len & 63) + 73) >> 6);
+  const uint32_t lim = (b + 3) >> 2;    // words with a byte below b
+  auto ld = [&](uint32_t j) -> uint32_t { return j < lim ? words[j] : 0u; };
+  // the word of a + 4 W - 1 and the shift, for W >= 1: W = 1 is a + 3
+  const uint32_t j1 = (a + 3) >> 2, sh = ((a + 3) & 3) * 8;
+  uint32_t cur = ld(j1), j = j1;        // cur = words[j], the low part of the next message word
+  uint32_t h[8];
+  sha256_init(h);
+  for (uint32_t k = 0; k < nblk; ++k) {
+    uint32_t w[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      if (k == 0 && t == 0) {
+        // 00, then the first three bytes: the four bytes from a, one to the right
+        const uint32_t i0 = a >> 2, s0 = (a & 3) * 8;
+        const uint32_t lo = ld(i0), hi = ld(i0 + 1);
+        const uint32_t v = s0 ? (lo >> s0) | (hi << (32 - s0)) : lo;
+        w[0] = sha256_tail(sha256_bswap(v), 0, len) >> 8;
+      } else {
+        const uint32_t nxt = ld(j + 1);
+        const uint32_t v = sh ? (cur >> sh) | (nxt << (32 - sh)) : cur;
+        w[t] = sha256_tail(sha256_bswap(v), 64 * k + 4 * t - 1, len);
+        cur = nxt;
+        ++j;
+      }
+    }
+    if (k + 1 == nblk) {
+      w[14] |= (len + 1) >> 29;
+      w[15] |= (len + 1) << 3;
+    }
+    sha256_compress(h, w);
+  }
+#pragma unroll
+  for (int t = 0; t < 8; ++t) out[t] = h[t];
+}
+
 }  // namespace edc

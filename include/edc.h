@@ -1671,6 +1671,99 @@ int edc_valhash_vhist_match(edc_ctx* ctx, size_t nc, const uint32_t* commit_ver,
 int edc_debug_valhash_ms(edc_ctx* ctx, int reps, float ms[2]);
 
 /*
+ * Header hashes: the Merkle root of many block headers at once, bound to validator-set roots and
+ * to each other. The set hashes above give the root a light client compares with the
+ * validators_hash of the header it trusts; these entries hash the header itself, so that nothing
+ * between a vote and the set it is judged by is taken on faith: the expected bytes of
+ * edc_valhash_vhist_match come out of a header whose own hash is checked, the block id the votes
+ * sign is that hash, and the walk backwards from a trusted header to older ones (header h carries
+ * the hash of header h - 1 in its last_block_id) is a chain of such hashes. Not an API of the
+ * reference crate, whose APIs keep their meaning as stated there.
+ *
+ * The function. The library's contract is these bytes. Agreement with CometBFT's Header.Hash() is
+ * the intent, but it is stated from memory, as the sections above are, and no chain data was at hand
+ * to check it against. The library parses no protobuf: a header is given as its ordered LEAVES,
+ * opaque byte strings of any length, 0 included (for CometBFT the 14 encoded fields). The hash of a
+ * header of n leaves is RFC 6962's MTH with SHA-256 over them: no leaf -> SHA-256 of the empty
+ * string; one leaf -> SHA-256(00 | leaf); n > 1 -> SHA-256(01 | MTH(first k) | MTH(rest)), with k
+ * the largest power of two below n. A leaf hash takes one SHA-256 block up to 54 bytes, two up to
+ * 118, three up to 182, and so on. A header holds at most EDC_HEADER_MAX_LEAVES = 64 leaves (one
+ * lane per leaf, one header inside one wave).
+ *
+ * edc_header_set  nh headers in host memory: header h owns the leaves leaf_off[h] .. leaf_off[h + 1]
+ *   - 1, leaf j is bytes[byte_off[j] .. byte_off[j + 1]). Both offset arrays start at 0 and are
+ *   monotone; leaves are packed in any way the offsets allow (back to back, at any byte alignment).
+ *   bytes may be NULL when byte_off[last] = 0. byte_off[last] < 2^32 - 1024.
+ * edc_header_hashes  out (nh x 32 host bytes) = the hash of every header. Needs no key list and no
+ *   history.
+ * edc_header_bind  hashes every header and answers up to four questions per header; bad[h] is the
+ *   OR of the bits of the questions whose answer is no, 0 for a header every rule accepts;
+ *   *n_bad (nullable) = the number of non-zero bytes; out (nullable) = the hashes, as
+ *   edc_header_hashes gives them.
+ *     expect     EDC_HEADER_BAD_HASH iff the header's hash differs from the 32 bytes at expect + 32 h.
+ *     byte rule  (leaf L, position P, source root S): holds iff L < n, leaf L has at least P + 32
+ *                bytes, and the 32 bytes from position P equal S. Otherwise the rule's bit is set.
+ *     vals_ver   S = the root of history version vals_ver[h], exactly as edc_valhash_vhist returns
+ *                it, at (vals_leaf, vals_pos): EDC_HEADER_BAD_VALS.
+ *     next_ver   the same at (next_leaf, next_pos): EDC_HEADER_BAD_NEXT.
+ *     link       S = this call's own hash of header link[h] of THIS SET, at (link_leaf, link_pos):
+ *                EDC_HEADER_BAD_LINK. Links may point forwards or backwards in the array, may
+ *                repeat, and may name the header itself.
+ *   A rule whose array is NULL sets no bit, and an entry EDC_HEADER_NONE skips its header. For
+ *   CometBFT the caller passes leaves 7 (validators_hash) and 8 (next_validators_hash) at position
+ *   2, behind the bytes 0A 20, and for the link leaf 4 (last_block_id) at position 2. Each distinct
+ *   version named by vals_ver or next_ver is hashed once, by the root kernel of the set hashes. The
+ *   return value is EDC_OK whether or not every rule holds: a mismatch is data.
+ * Errors: EDC_ERR_ARG with nothing written and the context usable for a wrong size or a non-zero
+ *   reserved in either structure; a NULL ctx, hs or r, or a NULL required output (out of
+ *   edc_header_hashes, bad); a NULL offset array, offsets that do not start at 0 or are not
+ *   monotone, NULL bytes with byte_off[last] > 0, byte_off[last] >= 2^32 - 1024 or nh >= 2^32; a header
+ *   above EDC_HEADER_MAX_LEAVES leaves; a version above the history's last other than the
+ *   sentinel; a non-NULL vals_ver or next_ver without a registered key list and a history
+ *   (edc_keycache_load, edc_vhist_set), even when every entry is the sentinel; a named version above
+ *   EDC_VALHASH_MAX_MEMBERS members; a link[h] >= nh other than the sentinel. nh = 0 returns EDC_OK,
+ *   reads no array and writes only *n_bad = 0. Synchronous on slot 0 and refused while a batch is
+ *   pending there.
+ * edc_debug_header_ms  measurement hook: mean times over reps launches of the root kernel over hs
+ *   (ms[0]) and of the bind kernel (ms[1]) with all four compares per header, each against the
+ *   header's own hash (expect, and leaves 7, 8 and 4 at position 2), so it needs no history.
+ * Not built: device-resident inputs or outputs; asynchronous and multi-GPU forms; headers above 64
+ *   leaves; parsing protobuf in the library; reading the block id out of a template head (the
+ *   caller builds the heads from the same commit it passes as expect).
+ */
+#define EDC_HEADER_MAX_LEAVES 64
+#define EDC_HEADER_NONE 0xFFFFFFFFu
+#define EDC_HEADER_BAD_HASH 1   /* root != expect                                   */
+#define EDC_HEADER_BAD_VALS 2   /* 32 bytes at (vals_leaf, vals_pos) != set root     */
+#define EDC_HEADER_BAD_NEXT 4   /* 32 bytes at (next_leaf, next_pos) != next root    */
+#define EDC_HEADER_BAD_LINK 8   /* 32 bytes at (link_leaf, link_pos) != linked root  */
+
+typedef struct edc_header_set {
+  uint32_t size;             /* sizeof(edc_header_set); anything else: EDC_ERR_ARG */
+  uint32_t reserved;         /* 0 */
+  size_t nh;                 /* headers */
+  const uint32_t* leaf_off;  /* nh + 1, from 0, monotone: header h owns leaves [leaf_off[h], leaf_off[h+1]) */
+  const uint32_t* byte_off;  /* leaf_off[nh] + 1, from 0, monotone: leaf j = bytes[byte_off[j] .. byte_off[j+1]) */
+  const uint8_t* bytes;      /* may be NULL when byte_off[last] == 0 */
+} edc_header_set;
+
+typedef struct edc_header_rules {
+  uint32_t size, reserved;
+  const uint8_t* expect;       /* nh x 32 or NULL: the hash each header must have */
+  const uint32_t* vals_ver;    /* nh or NULL: history version whose root the header names; EDC_HEADER_NONE skips a header */
+  uint32_t vals_leaf, vals_pos;
+  const uint32_t* next_ver;    /* the same, for next_validators_hash */
+  uint32_t next_leaf, next_pos;
+  const uint32_t* link;        /* nh or NULL: index of another header OF THIS SET whose root the header names; EDC_HEADER_NONE skips */
+  uint32_t link_leaf, link_pos;
+} edc_header_rules;
+
+int edc_header_hashes(edc_ctx* ctx, const edc_header_set* hs, uint8_t* out /* nh x 32 */);
+int edc_header_bind(edc_ctx* ctx, const edc_header_set* hs, const edc_header_rules* r,
+                    uint8_t* bad /* nh bytes */, uint8_t* out /* nh x 32, nullable */, size_t* n_bad /* nullable */);
+int edc_debug_header_ms(edc_ctx* ctx, const edc_header_set* hs, int reps, float ms[2]);
+
+/*
  * Several GPUs in one process (a node verifying each block's votes across all of its MI355X):
  * one batch::Verifier::verify (reference src/batch.rs:149-217) split into contiguous shards, one
  * per listed device (a device may be listed more than once: several contexts on one GPU). Shard g
