@@ -147,6 +147,75 @@ struct Slot {
   uint64_t t_submit_us = 0;     // host time of the submission (EDC_BATCH_STAMPS builds only)
 };
 
+// Quorum workspace ("Quorum workspace"). What ONE side of a quorum call owns on the
+// device and in pinned memory. Every call has side A; a trusting pair (trust_ver of a request) has
+// side B too, the same arrays again. Three tiers of allocation: votes (every quorum call), join (the
+// validator-set forms), and what only a history (ver) or a pair (skip; all of side B) needs.
+struct QuorumSide {
+  // votes tier (side_votes_room): the power and flag the selection reads, staged by a host form or
+  // written by the join (cap_n votes); the staged thresholds, the selection's plan, the tally
+  // kernel's sums and its correction words (cap_c commits)
+  size_t cap_n = 0, cap_c = 0;
+  DevBuf<uint64_t> power, thr, planned, tally;
+  DevBuf<uint8_t> flag;
+  DevBuf<uint32_t> cor;
+  // join tier (side_join_room): the members' cache indices and the pair set of the double-vote scan,
+  // 2 words per vote (join_n votes); the commits' double-vote bytes and the pinned bytes they come
+  // back in (join_c commits)
+  size_t join_n = 0, join_c = 0;
+  DevBuf<uint32_t> who;
+  DevBuf<uint64_t> set;
+  DevBuf<uint8_t> dv;
+  PinnedBuf<uint8_t> hdv;
+  DevBuf<uint32_t> ver;         // the commits' versions: a history form's, side B's trust versions
+  DevBuf<uint8_t> skip;         // this side's own skip bytes in a pair (side_skip); alone, side A writes sc_hit
+};
+
+// The per-call state of the quorum family (quorum.h, valset.h, vhist.h; edc_quorum_*, edc_tmpl_quorum_*,
+// edc_cached_*, edc_valset_*, edc_vhist_*, edc_vq_*), all on slot 0's stream. The gathers use the
+// sc_* staging.
+struct QuorumWs {
+  QuorumSide side[2];
+  QuorumSide &a = side[0], &b = side[1];
+  // both sides read these. With side A's votes tier: the staged offsets (cap_c + 1), the votes'
+  // commit indices and the scan's tile words (cap_n votes); the error flag; the pinned words the
+  // flag, the checked count, the checked hole bytes (templated forms) and the checked misses and
+  // hits (cached forms) come back in
+  size_t cap_n = 0, cap_c = 0;
+  DevBuf<uint32_t> coff, cidx, aggf;
+  DevBuf<uint64_t> aggv, carry;
+  DevBuf<int> err;
+  PinnedBuf<uint32_t> h;
+  // with side A's join tier: the staged key positions and flags of the host forms (join_n votes)
+  size_t join_n = 0;
+  DevBuf<uint32_t> kidx;
+  DevBuf<uint8_t> vflag;
+  // pair tier: the union's side byte per vote, its device totals {A, B, both} and the pinned words
+  // they come back in
+  DevBuf<uint8_t> sideb;
+  DevBuf<uint32_t> cnt;
+  PinnedBuf<uint32_t> hcnt;
+  // templated forms (edc_tmpl_quorum_*): the all-n template array and the staged commit_tpl, the
+  // tiles' hole bytes (+ their total, which comes back in h[2]), the gathered template indices /
+  // hole offsets / holes of the checked votes, the host form's staged var_off | item_alt | var, the
+  // pinned word the arena's size comes back in
+  DevBuf<uint16_t> tq_tpl, tq_ctpl, tq_gtpl;
+  DevBuf<uint32_t> tq_wgh, tq_gvoff;
+  DevBuf<uint8_t> tq_gvar, tq_in;
+  PinnedBuf<uint64_t> tq_harena;
+  // cached forms (edc_cached_*): the masked lookup's leave-out bytes and base codes, its workgroup
+  // counts (misses + total, then hits + total), and for the templated forms, whose first staging
+  // area holds the gathered checked list, the second one (miss positions in that list, the misses'
+  // vk | sig | k)
+  size_t cq_cap_n = 0, cq_cap_g = 0;
+  DevBuf<uint8_t> cq_leave, cq_code, cq_g;
+  DevBuf<uint32_t> cq_wg, cq_idx;
+  // the host copies edc_debug_tmpl_quorum_last, edc_debug_cached_quorum_last, edc_debug_vq_last and
+  // edc_debug_vq_trust_last return
+  uint64_t tq_last[4] = {}, cq_last[6] = {}, vq_last[8] = {}, vqt_last[4] = {};
+  bool tq_have = false, cq_have = false, vq_have = false, vqt_have = false;
+};
+
 struct edc_ctx {
   int device = 0;
   std::string err;
@@ -241,65 +310,26 @@ struct edc_ctx {
   SigCacheView sc() const {
     return SigCacheView{sc_hdr, sc_rec, (uint32_t)(sc_cap - 1), sc_gen, sc_keep, sc_k0, sc_k1};
   }
-  // quorum commit sets (quorum.h; edc_quorum_*), on slot 0's stream: the staged offsets and
-  // thresholds and the per-commit results (q_cap_c commits); the items' commit indices, the staged
-  // power / flag of the host forms and the scan's tile words (q_cap_n items); the error flag; the
-  // pinned words the flag and the checked count come back in. The gather uses the sc_* staging.
-  size_t q_cap_c = 0, q_cap_n = 0;
-  DevBuf<uint32_t> q_coff, q_cor, q_cidx, q_aggf;
-  DevBuf<uint64_t> q_thr, q_planned, q_tally, q_power, q_aggv, q_carry;
-  DevBuf<uint8_t> q_flag;
-  DevBuf<int> q_err;
-  PinnedBuf<uint32_t> q_h;
-  // templated quorum commit sets (edc_tmpl_quorum_*): the all-n template array and the staged
-  // commit_tpl, the tiles' hole bytes (+ their total, which comes back in q_h[2]), the gathered
-  // template indices / hole offsets / holes of the checked votes, the host form's staged
-  // var_off | item_alt | var, the pinned word the arena's size comes back in, and the host copy
-  // edc_debug_tmpl_quorum_last returns
-  DevBuf<uint16_t> tq_tpl, tq_ctpl, tq_gtpl;
-  DevBuf<uint32_t> tq_wgh, tq_gvoff;
-  DevBuf<uint8_t> tq_gvar, tq_in;
-  PinnedBuf<uint64_t> tq_harena;
-  uint64_t tq_last[4] = {};
-  bool tq_have = false;
-  // cached quorum commit sets (edc_cached_*): the masked lookup's leave-out bytes and base codes,
-  // its workgroup counts (misses + total, then hits + total), and for the templated forms, whose
-  // first staging area holds the gathered checked list, the second one (miss positions in that
-  // list, the misses' vk | sig | k); the host copy edc_debug_cached_quorum_last returns
-  size_t cq_cap_n = 0, cq_cap_g = 0;
-  DevBuf<uint8_t> cq_leave, cq_code, cq_g;
-  DevBuf<uint32_t> cq_wg, cq_idx;
-  uint64_t cq_last[6] = {};
-  bool cq_have = false;
+  QuorumWs qw;                  // quorum commit sets and everything built on them, per call (above)
   // validator-set quorum commit sets (valset.h; edc_valset_*). The powers of the registered list
   // (edc_valset_set_powers), by cache index: power, member byte and position on the device for the
   // vs_count keys the cache held then, the positions on the host too (vs_posh) beside the host copy
-  // of kc_reg; vs_m members. Per call, on slot 0's stream: the staged flags and key positions of
-  // the host forms and the members' cache indices (vs_cap_n items), the pair set of the double-vote
-  // scan (2 words per item), the commits' double-vote bytes and the pinned bytes they come back in
-  // (vs_cap_c commits)
+  // of kc_reg; vs_m members. The per-call workspace is QuorumWs's join tier.
   std::vector<uint32_t> kc_regh, vs_posh;
   DevBuf<uint64_t> vs_power;
   DevBuf<uint8_t> vs_member;
   DevBuf<uint32_t> vs_pos;
   uint32_t vs_count = 0, vs_m = 0;
-  size_t vs_cap_n = 0, vs_cap_c = 0;
-  DevBuf<uint32_t> vs_who, vs_kidx;
-  DevBuf<uint64_t> vs_set;
-  DevBuf<uint8_t> vs_flag, vs_dv;
-  PinnedBuf<uint8_t> vs_hdv;
   ValsetView vs() const { return ValsetView{vs_power, vs_member, vs_pos, vs_count}; }
   // validator-set history (vhist.h; edc_vhist_*), independent of the powers above: the change
   // lists by cache index on the device (vh_count keys the cache held at edc_vhist_set), the
   // history by position (totals, the reference lists) and each cache index's position on the host;
-  // vh.m = 0: none. Per call the commits' versions (vh_cap_c commits); the rest of the per-call
-  // workspace is the vs_* one.
+  // vh.m = 0: none. The commits' versions of a call are a QuorumSide's.
   VHist vh;
   std::vector<uint32_t> vh_posh;
-  DevBuf<uint32_t> vh_off, vh_ver, vh_cver;
+  DevBuf<uint32_t> vh_off, vh_ver;
   DevBuf<uint64_t> vh_pow;
   uint32_t vh_count = 0;
-  size_t vh_cap_c = 0;
   VhistView vhv() const { return VhistView{vh_off, vh_ver, vh_pow, vh_count}; }
   // validator-set hashes (valhash.h; edc_valhash_valset, edc_valhash_vhist, edc_valhash_vhist_match): the
   // address order of the registered list, ranked on the first call after a list is loaded (rank by
@@ -317,22 +347,6 @@ struct edc_ctx {
   DevBuf<uint32_t> hd_leaf, hd_byte, hd_words, hd_expect, hd_meta;
   DevBuf<uint8_t> hd_out;
   PinnedBuf<uint8_t> hd_host;
-  // validator-set requests (edc_vq_verify): the host copy edc_debug_vq_last returns
-  uint64_t vq_last[8] = {};
-  bool vq_have = false;
-  // trusting pairs (trust_ver of a request): side B's copies of what side A keeps in q_* / vs_*
-  // (power, flag, who, pair set per item; threshold, planned, tally, cor, version and double-vote
-  // bytes per commit), each side's own skip bytes, the side byte per item, the device totals
-  // {A, B, both} with the pinned words they come back in, and the host copy
-  // edc_debug_vq_trust_last returns
-  size_t tr_cap_n = 0, tr_cap_c = 0;
-  DevBuf<uint64_t> tr_power, tr_set, tr_thr, tr_planned, tr_tally;
-  DevBuf<uint32_t> tr_who, tr_cor, tr_ver, tr_cnt;
-  DevBuf<uint8_t> tr_flag, tr_skip_a, tr_skip_b, tr_side, tr_dv;
-  PinnedBuf<uint8_t> tr_hdv;
-  PinnedBuf<uint32_t> tr_hcnt;
-  uint64_t vqt_last[4] = {};
-  bool vqt_have = false;
   uint64_t mu_hits = 0, mu_reruns = 0;  // union-first launches that passed / were rerun per batch
   // incremental verifiers bound to this context (edc_verifier_create): their streams are drained
   // with the slots' whenever the key cache they read is rebuilt
@@ -3639,20 +3653,50 @@ int edc_sigcache_verify_each(edc_ctx* ctx, size_t n, const uint8_t* vk, const ui
 // runs the tally kernel. All on slot 0.
 // Every form is its checks and staging (*_inputs), then quorum_select_enqueue, what the form adds
 // behind the selection, quorum_select_read, quorum_gather and quorum_finish.
+// The sync() of one tier's growth: its groups of one dimension (votes, commits) grow together, and
+// the stream is drained once in front of the first of them.
+struct GrowSync {
+  hipStream_t st;
+  bool did[2] = {false, false};
+  auto once(int d) { return [this, d] { return std::exchange(did[d], true) ? hipSuccess : hipStreamSynchronize(st); }; }
+  auto n() { return once(0); }
+  auto c() { return once(1); }
+};
+
+static int side_votes_room(edc_ctx* ctx, QuorumSide& s, size_t n, size_t nc, GrowSync& g) {
+  CK(grow_group(s.cap_c, nc, off_cap, g.c(), [&](size_t cap) {
+    return alloc_all(sized(s.thr, cap), sized(s.planned, cap), sized(s.tally, cap), sized(s.cor, cap));
+  }));
+  CK(grow_group(s.cap_n, n ? n : 1, item_cap, g.n(), [&](size_t cap) { return alloc_all(sized(s.power, cap), sized(s.flag, cap)); }));
+  return 0;
+}
+
+static int side_join_room(edc_ctx* ctx, QuorumSide& s, size_t n, size_t nc, GrowSync& g) {
+  CK(grow_group(s.join_n, n ? n : 1, item_cap, g.n(), [&](size_t cap) { return alloc_all(sized(s.who, cap), sized(s.set, 2 * cap)); }));
+  CK(grow_group(s.join_c, nc, off_cap, g.c(), [&](size_t cap) {
+    const hipError_t e = s.dv.alloc(cap);
+    return e != hipSuccess ? e : s.hdv.alloc(cap);
+  }));
+  return 0;
+}
+
+// Where a side's selection writes its skip bytes: its own array in a pair; alone, side A writes the
+// bytes the gathers and the lookup read.
+static uint8_t* side_skip(edc_ctx* ctx, const QuorumSide& s, bool pair) { return pair ? s.skip.get() : ctx->sc_hit.get(); }
+
+// votes tier: side A's, and what both sides read
 static int ensure_quorum(edc_ctx* ctx, size_t n, size_t nc) {
-  hipStream_t st = ctx->st();
-  CK(grow_group(ctx->q_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
-    return alloc_all(sized(ctx->q_coff, cap + 1), sized(ctx->q_thr, cap), sized(ctx->q_planned, cap), sized(ctx->q_tally, cap),
-                     sized(ctx->q_cor, cap));
-  }));
-  CK(grow_group(ctx->q_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
+  QuorumWs& q = ctx->qw;
+  GrowSync g{ctx->st()};
+  const int rc = side_votes_room(ctx, q.a, n, nc, g);
+  if (rc) return rc;
+  CK(grow_group(q.cap_c, nc, off_cap, g.c(), [&](size_t cap) { return q.coff.alloc(cap + 1); }));
+  CK(grow_group(q.cap_n, n ? n : 1, item_cap, g.n(), [&](size_t cap) {
     const size_t tiles = quorum_tiles(cap);
-    return alloc_all(sized(ctx->q_cidx, cap), sized(ctx->q_power, cap), sized(ctx->q_flag, cap), sized(ctx->q_aggv, tiles),
-                     sized(ctx->q_aggf, tiles), sized(ctx->q_carry, tiles));
+    return alloc_all(sized(q.cidx, cap), sized(q.aggv, tiles), sized(q.aggf, tiles), sized(q.carry, tiles));
   }));
-  if (!ctx->q_err) CK(ctx->q_err.alloc(1));
-  // flag, checked count, checked hole bytes (templated form), checked misses and hits (cached forms)
-  if (!ctx->q_h) CK(ctx->q_h.alloc(6));
+  if (!q.err) CK(q.err.alloc(1));
+  if (!q.h) CK(q.h.alloc(6));
   return 0;
 }
 
@@ -3714,19 +3758,17 @@ static int quorum_none(const QuorumOut& out, const QuorumTrust* tr = nullptr) {
   return EDC_OK;
 }
 
+// pair tier: side B's votes and join tiers and its versions, each side's own skip bytes, the union's
 static int ensure_trust(edc_ctx* ctx, size_t n, size_t nc) {
-  hipStream_t st = ctx->st();
-  CK(grow_group(ctx->tr_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
-    return alloc_all(sized(ctx->tr_power, cap), sized(ctx->tr_flag, cap), sized(ctx->tr_who, cap), sized(ctx->tr_set, 2 * cap),
-                     sized(ctx->tr_skip_a, cap), sized(ctx->tr_skip_b, cap), sized(ctx->tr_side, cap));
-  }));
-  CK(grow_group(ctx->tr_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
-    hipError_t e = alloc_all(sized(ctx->tr_thr, cap), sized(ctx->tr_planned, cap), sized(ctx->tr_tally, cap),
-                             sized(ctx->tr_cor, cap), sized(ctx->tr_ver, cap), sized(ctx->tr_dv, cap));
-    return e != hipSuccess ? e : ctx->tr_hdv.alloc(cap);
-  }));
-  if (!ctx->tr_cnt) CK(ctx->tr_cnt.alloc(3 * QR_UNION_SLOTS));
-  if (!ctx->tr_hcnt) CK(ctx->tr_hcnt.alloc(3 * QR_UNION_SLOTS));
+  QuorumWs& q = ctx->qw;
+  QuorumSide& b = q.b;
+  GrowSync g{ctx->st()};
+  int rc = side_votes_room(ctx, b, n, nc, g);
+  if (rc || (rc = side_join_room(ctx, b, n, nc, g))) return rc;
+  CK(grow(b.ver, nc, off_cap, g.c()));
+  for (DevBuf<uint8_t>* skip : {&q.a.skip, &b.skip, &q.sideb}) CK(grow(*skip, n ? n : 1, item_cap, g.n()));
+  if (!q.cnt) CK(q.cnt.alloc(3 * QR_UNION_SLOTS));
+  if (!q.hcnt) CK(q.hcnt.alloc(3 * QR_UNION_SLOTS));
   return 0;
 }
 
@@ -3743,8 +3785,8 @@ static bool quorum_entry_done(edc_ctx* ctx, const uint8_t* z_seed, bool cached, 
 static int quorum_stage_votes(edc_ctx* ctx, size_t n, size_t nc, const uint64_t* power, const uint8_t* flag) {
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || !n) return rc;
-  CK(hipMemcpyAsync(ctx->q_power, power, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->st()));
-  CK(hipMemcpyAsync(ctx->q_flag, flag, n, hipMemcpyHostToDevice, ctx->st()));
+  CK(hipMemcpyAsync(ctx->qw.a.power, power, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->st()));
+  CK(hipMemcpyAsync(ctx->qw.a.flag, flag, n, hipMemcpyHostToDevice, ctx->st()));
   return 0;
 }
 
@@ -3810,8 +3852,8 @@ static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   } else if ((rc = upload_msgs(ctx, n, msg, n ? msg_off : nullptr))) {
     return rc;
   }
-  if (n) {                  // key indices into q_cidx, which is free until the selection writes it
-    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->q_cidx, ctx->vk, ctx->sig))) return rc;
+  if (n) {                  // key indices into cidx, which is free until the selection writes it
+    if ((rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->qw.cidx, ctx->vk, ctx->sig))) return rc;
     if (!k) {
       launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
       CK(hipGetLastError());
@@ -3821,88 +3863,91 @@ static int quorum_host_inputs(edc_ctx* ctx, size_t nc, const uint32_t* commit_of
   return 0;
 }
 
-// One side's selection, as quorum_select_enqueue and the timing hook both launch it. Side A's writes
-// the skip bytes every back-end reads, or tr_skip_a when a side B follows (pair). Side B's (side_b:
-// d_power / d_flag are tr_power / tr_flag) clears the union's counts, selects against tr_thr into
-// tr_skip_b / tr_planned with side A's commit indices, and runs the union kernel.
-static hipError_t quorum_side_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, int mode, const uint64_t* d_power,
-                                     const uint8_t* d_flag, bool pair, bool side_b) {
-  const uint32_t N = (uint32_t)n, NC = (uint32_t)nc;
-  if (!side_b) {
-    launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, d_power, d_flag, ctx->q_cidx, ctx->q_aggv,
-                         ctx->q_aggf, ctx->q_carry, pair ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), ctx->sc_wg, ctx->q_planned,
-                         ctx->q_err);
-    return hipSuccess;
-  }
-  hipError_t e = hipMemsetAsync(ctx->tr_cnt, 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t), st);
+// One side's selection, as quorum_select_enqueue and the timing hook both launch it, on that side's
+// power / flag (side A's may be the caller's own device arrays) against its thresholds into `skip`
+// (side_skip) and its plan. Side B's (side_b) reads the commit indices side A's has written.
+static void quorum_side_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, int mode, const QuorumSide& s,
+                               const uint64_t* d_power, const uint8_t* d_flag, uint8_t* skip, bool side_b) {
+  const QuorumWs& q = ctx->qw;
+  launch_quorum_select(st, (uint32_t)n, (uint32_t)nc, mode == QUORUM_LIGHT, q.coff, s.thr, d_power, d_flag, q.cidx, q.aggv,
+                       q.aggf, q.carry, skip, ctx->sc_wg, s.planned, q.err, side_b);
+}
+
+// Side B's selection of a pair behind side A's, between the clearing of the union's counts and the
+// union kernel, which writes the skip bytes and tile counts every back-end reads.
+static hipError_t quorum_side_b_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, int mode) {
+  const QuorumWs& q = ctx->qw;
+  const QuorumSide& b = q.b;
+  const hipError_t e = hipMemsetAsync(q.cnt, 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t), st);
   if (e != hipSuccess) return e;
-  launch_quorum_select(st, N, NC, mode == QUORUM_LIGHT, ctx->q_coff, ctx->tr_thr, d_power, d_flag, ctx->q_cidx, ctx->q_aggv,
-                       ctx->q_aggf, ctx->q_carry, ctx->tr_skip_b, ctx->sc_wg, ctx->tr_planned, ctx->q_err, true);
-  launch_quorum_union(st, N, ctx->tr_skip_a, ctx->tr_skip_b, ctx->sc_hit, ctx->tr_side, ctx->sc_wg, ctx->tr_cnt);
+  quorum_side_launch(ctx, st, n, nc, mode, b, b.power, b.flag, b.skip, true);
+  launch_quorum_union(st, (uint32_t)n, q.a.skip, b.skip, ctx->sc_hit, q.sideb, ctx->sc_wg, q.cnt);
   return hipSuccess;
 }
 
 // Workspace, the staged offsets and thresholds, then the selection and the scan of its workgroup
 // counts on device-resident power / flag, all enqueued. A form with work of its own behind the
 // selection (n > 0 only) enqueues it between this and quorum_select_read.
-// tr (a trusting pair; ensure_trust has run and the paired join has written tr_power / tr_flag):
-// side A's selection writes tr_skip_a, side B's runs behind it on tr_power / tr_flag against
-// tr->threshold into tr_skip_b and tr_planned, reading the commit indices and reusing the tile
-// words of side A's (one stream: side A is done with them), and both raise the one error flag; the
-// union kernel then writes the skip bytes and tile counts every back-end reads, so that the scan,
-// the gathers and the lookup see ONE selection, the union's. Its totals {A, B, both} travel to
-// tr_hcnt with the read-back.
+// tr (a trusting pair; ensure_trust has run and the paired join has written side B's power / flag):
+// each side's selection writes its own skip bytes, side B's behind side A's against tr->threshold,
+// reading the commit indices and reusing the tile words of side A's (one stream: side A is done
+// with them), and both raise the one error flag; the union kernel then writes the skip bytes and
+// tile counts every back-end reads, so that the scan, the gathers and the lookup see ONE selection,
+// the union's. Its totals {A, B, both} travel to hcnt with the read-back.
 static int quorum_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                                  int mode, const uint64_t* d_power, const uint8_t* d_flag, const QuorumTrust* tr = nullptr) {
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
   hipStream_t st = ctx->st();
   if ((rc = sc_order_after_inserts(ctx, st))) return rc;
-  CK(hipMemsetAsync(ctx->q_planned, 0, nc * sizeof(uint64_t), st));
+  QuorumWs& q = ctx->qw;
+  QuorumSide &a = q.a, &b = q.b;
+  CK(hipMemsetAsync(a.planned, 0, nc * sizeof(uint64_t), st));
   if (tr) {
-    CK(hipMemsetAsync(ctx->tr_planned, 0, nc * sizeof(uint64_t), st));
-    memset(ctx->tr_hcnt.get(), 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t));
+    CK(hipMemsetAsync(b.planned, 0, nc * sizeof(uint64_t), st));
+    memset(q.hcnt.get(), 0, 3 * QR_UNION_SLOTS * sizeof(uint32_t));
   }
   if (!n) return 0;
   const uint32_t nwg = (uint32_t)quorum_tiles(n);
-  CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(ctx->q_thr, threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  CK(hipMemsetAsync(ctx->q_err, 0, sizeof(int), st));
-  CK(quorum_side_launch(ctx, st, n, nc, mode, d_power, d_flag, tr != nullptr, false));
+  CK(hipMemcpyAsync(q.coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(a.thr, threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  CK(hipMemsetAsync(q.err, 0, sizeof(int), st));
+  quorum_side_launch(ctx, st, n, nc, mode, a, d_power, d_flag, side_skip(ctx, a, tr != nullptr), false);
   if (tr) {
-    CK(hipMemcpyAsync(ctx->tr_thr, tr->threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    CK(quorum_side_launch(ctx, st, n, nc, mode, ctx->tr_power, ctx->tr_flag, true, true));
-    CK(hipMemcpyAsync(ctx->tr_hcnt.get(), ctx->tr_cnt, 3 * QR_UNION_SLOTS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(b.thr, tr->threshold, nc * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    CK(quorum_side_b_launch(ctx, st, n, nc, mode));
+    CK(hipMemcpyAsync(q.hcnt.get(), q.cnt, 3 * QR_UNION_SLOTS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   }
   launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
   CK(hipGetLastError());
-  ctx->q_h[0] = ctx->q_h[1] = ctx->q_h[2] = 0;
+  q.h[0] = q.h[1] = q.h[2] = 0;
   return 0;
 }
 
 // The one read-back behind quorum_select_enqueue: the device checks' flag and the checked count
-// (*n_checked, the size of the gathered list), with whatever else the form sent to q_h. A vote the
+// (*n_checked, the size of the gathered list), with whatever else the form sent to h. A vote the
 // device checks refuse is EDC_ERR_ARG here, before anything is gathered or verified. flag_msg: a
-// templated form's all-n checks raise q_err too (bit 1 for the holes), so it words bit 0 itself.
+// templated form's all-n checks raise err too (bit 1 for the holes), so it words bit 0 itself.
 static int quorum_select_read(edc_ctx* ctx, size_t n, size_t* n_checked, const char* flag_msg = nullptr) {
   *n_checked = 0;
   if (!n) return 0;
   hipStream_t st = ctx->st();
+  QuorumWs& q = ctx->qw;
   const uint32_t nwg = (uint32_t)quorum_tiles(n);
-  CK(hipMemcpyAsync(&ctx->q_h[0], ctx->q_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  CK(hipMemcpyAsync(&ctx->q_h[1], ctx->sc_wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(&q.h[0], q.err, sizeof(int), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(&q.h[1], ctx->sc_wg + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
-  if (ctx->q_h[0] & 2) {
+  if (q.h[0] & 2) {
     ctx->err = "templated items: hole offsets out of range";
     return EDC_ERR_ARG;
   }
-  if (ctx->q_h[0]) {
+  if (q.h[0]) {
     ctx->err = "votes: a flag above 2, a power above 2^63 - 1 or a commit whose counted power passes 2^63 - 1";
     if (flag_msg) ctx->err = flag_msg;
     return EDC_ERR_ARG;
   }
-  if (ctx->q_h[1] > n) { ctx->err = "quorum selection: checked count out of range"; return EDC_ERR_HIP; }
-  *n_checked = ctx->q_h[1];
+  if (q.h[1] > n) { ctx->err = "quorum selection: checked count out of range"; return EDC_ERR_HIP; }
+  *n_checked = q.h[1];
   return 0;
 }
 
@@ -3914,8 +3959,8 @@ static int quorum_select_run(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* 
 }
 
 // Optional stages around the selection (edc_vq_verify): the validator-set join in front of it,
-// writing q_power / q_flag, and the double-vote scan behind it, whose bytes travel to vs_hdv in the
-// selection's read-back. d_vk: the n keys on the device, or null with d_kidx their positions;
+// writing side A's power / flag, and the double-vote scan behind it, whose bytes travel to hdv in
+// the selection's read-back. d_vk: the n keys on the device, or null with d_kidx their positions;
 // d_flag: the caller's flags; cver (host): the commits' versions, null for the one set;
 // host_k: a host form's prehashed k, canonical for the checked votes (quorum_join_check_k).
 // trust: the trusting side of a paired request (needs cver), one more optional input of the same
@@ -3933,16 +3978,13 @@ struct QuorumJoin {
 
 static const char kJoinFlagMsg[] = "votes: a flag above 2 or a commit whose counted power passes 2^63 - 1";
 
-// The join's and the double-vote scan's workspace (edc_valset_* / edc_vhist_* / edc_vq_*, below).
+// join tier: side A's, and the host forms' staging (edc_valset_* / edc_vhist_* / edc_vq_*, below)
 static int ensure_valset(edc_ctx* ctx, size_t n, size_t nc) {
-  hipStream_t st = ctx->st();
-  CK(grow_group(ctx->vs_cap_n, n ? n : 1, item_cap, sync_of(st), [&](size_t cap) {
-    return alloc_all(sized(ctx->vs_who, cap), sized(ctx->vs_kidx, cap), sized(ctx->vs_flag, cap), sized(ctx->vs_set, 2 * cap));
-  }));
-  CK(grow_group(ctx->vs_cap_c, nc, off_cap, sync_of(st), [&](size_t cap) {
-    hipError_t e = ctx->vs_dv.alloc(cap);
-    return e != hipSuccess ? e : ctx->vs_hdv.alloc(cap);
-  }));
+  QuorumWs& q = ctx->qw;
+  GrowSync g{ctx->st()};
+  const int rc = side_join_room(ctx, q.a, n, nc, g);
+  if (rc) return rc;
+  CK(grow_group(q.join_n, n ? n : 1, item_cap, g.n(), [&](size_t cap) { return alloc_all(sized(q.kidx, cap), sized(q.vflag, cap)); }));
   return 0;
 }
 
@@ -3965,72 +4007,70 @@ static int valset_room(edc_ctx* ctx, size_t n, size_t nc, bool hist = false, boo
   int rc = init_slot(ctx, ctx->slot[0]);
   if (rc || (rc = ensure_quorum(ctx, n, nc)) || (rc = ensure_sc(ctx, n ? n : 1))) return rc;
   if (pair && (rc = ensure_trust(ctx, n, nc))) return rc;
-  if (hist) CK(grow_group(ctx->vh_cap_c, nc, off_cap, sync_of(ctx->st()), [&](size_t cap) { return ctx->vh_cver.alloc(cap); }));
+  if (hist) CK(grow(ctx->qw.a.ver, nc, off_cap, sync_of(ctx->st())));
   return ensure_valset(ctx, n, nc);
 }
 
 // The join kernel of jn, as valset_select_enqueue and the timing hooks both launch it: the one
 // set's, the history's (cver) or the paired one (cver and trust), which writes side B's arrays too.
-// The history's read q_coff / vh_cver / tr_ver, which the caller has staged.
+// The history's read coff and each side's ver, which the caller has staged.
 static void valset_join_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, const QuorumJoin& jn) {
   const uint32_t N = (uint32_t)n, NC = (uint32_t)nc;
+  const QuorumWs& q = ctx->qw;
+  const QuorumSide &a = q.a, &b = q.b;
   if (jn.cver && jn.trust)
-    launch_vhist_resolve2(st, N, NC, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, ctx->tr_ver, jn.d_vk, jn.d_kidx,
-                          ctx->kc_reg, jn.d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who, ctx->tr_power, ctx->tr_flag,
-                          ctx->tr_who);
+    launch_vhist_resolve2(st, N, NC, ctx->kc(), ctx->vhv(), q.coff, a.ver, b.ver, jn.d_vk, jn.d_kidx, ctx->kc_reg, jn.d_flag,
+                          a.power, a.flag, a.who, b.power, b.flag, b.who);
   else if (jn.cver)
-    launch_vhist_resolve(st, N, NC, ctx->kc(), ctx->vhv(), ctx->q_coff, ctx->vh_cver, jn.d_vk, jn.d_kidx, ctx->kc_reg,
-                         jn.d_flag, ctx->q_power, ctx->q_flag, ctx->vs_who);
+    launch_vhist_resolve(st, N, NC, ctx->kc(), ctx->vhv(), q.coff, a.ver, jn.d_vk, jn.d_kidx, ctx->kc_reg, jn.d_flag, a.power,
+                         a.flag, a.who);
   else
-    launch_valset_resolve(st, N, ctx->kc(), ctx->vs(), jn.d_vk, jn.d_kidx, ctx->kc_reg, jn.d_flag, ctx->q_power, ctx->q_flag,
-                          ctx->vs_who);
+    launch_valset_resolve(st, N, ctx->kc(), ctx->vs(), jn.d_vk, jn.d_kidx, ctx->kc_reg, jn.d_flag, a.power, a.flag, a.who);
 }
 
-// One side's double-vote scan of n > 0 votes with the clearing of its set and bytes, as every call
-// and the timing hooks run it: side A on its skip bytes (tr_skip_a in a pair) and vs_who, side B on
-// tr_skip_b and tr_who.
-static hipError_t valset_pairs_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, bool pair, bool side_b) {
-  uint8_t* dv = side_b ? ctx->tr_dv.get() : ctx->vs_dv.get();
-  uint64_t* set = side_b ? ctx->tr_set.get() : ctx->vs_set.get();
-  const uint8_t* skip = side_b ? ctx->tr_skip_b.get() : pair ? ctx->tr_skip_a.get() : ctx->sc_hit.get();
-  hipError_t e = hipMemsetAsync(dv, 0, nc, st);
-  if (e != hipSuccess || (e = hipMemsetAsync(set, 0, 2 * n * sizeof(uint64_t), st)) != hipSuccess) return e;
-  launch_valset_pairs(st, (uint32_t)n, ctx->q_coff, ctx->q_cidx, skip, side_b ? ctx->tr_who.get() : ctx->vs_who.get(), set, dv);
+// One side's double-vote scan of n > 0 votes on its skip bytes (side_skip), members and set, with
+// the clearing of its set and bytes, as every call and the timing hooks run it.
+static hipError_t valset_pairs_launch(edc_ctx* ctx, hipStream_t st, size_t n, size_t nc, const QuorumSide& s,
+                                      const uint8_t* skip) {
+  hipError_t e = hipMemsetAsync(s.dv, 0, nc, st);
+  if (e != hipSuccess || (e = hipMemsetAsync(s.set, 0, 2 * n * sizeof(uint64_t), st)) != hipSuccess) return e;
+  launch_valset_pairs(st, (uint32_t)n, ctx->qw.coff, ctx->qw.cidx, skip, s.who, s.set, s.dv);
   return hipSuccess;
 }
 
 // The join, the selection and the double-vote scan of n votes whose keys (jn->d_vk, or jn->d_kidx
 // with d_vk null) and flags are on the device, enqueued with the copies quorum_select_read's one
-// read-back then brings: the commits' double-vote bytes in vs_hdv and, for a host form's prehashed
+// read-back then brings: each side's double-vote bytes in its hdv and, for a host form's prehashed
 // k, the n skip bytes in jn->skip. valset_room has run.
 // jn->trust (a trusting pair, with cver): the paired join writes side B's arrays beside side A's,
 // the selection runs per side and leaves the union's skip bytes (quorum_select_enqueue), and the
-// double-vote scan runs once per side on that side's skip bytes, members and set; side B's bytes
-// travel to tr_hdv in the same read-back.
+// double-vote scan runs once per side.
 static int valset_select_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                                  int mode, QuorumJoin* jn) {
   hipStream_t st = ctx->st();
   const QuorumTrust* tr = jn->trust;
+  QuorumWs& q = ctx->qw;
+  QuorumSide &a = q.a, &b = q.b;
   jn->skip.assign(jn->host_k ? n : 0, 0);
   if (jn->cver && n) {  // the history's join reads the offsets, which the selection stages (again) only behind it
-    CK(hipMemcpyAsync(ctx->q_coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(ctx->vh_cver, jn->cver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (tr) CK(hipMemcpyAsync(ctx->tr_ver, tr->ver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(q.coff, commit_off, (nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(a.ver, jn->cver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (tr) CK(hipMemcpyAsync(b.ver, tr->ver, nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
   valset_join_launch(ctx, st, n, nc, *jn);
   CK(hipGetLastError());
-  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, tr);
+  int rc = quorum_select_enqueue(ctx, n, nc, commit_off, threshold, mode, a.power, a.flag, tr);
   if (rc) return rc;
-  memset(ctx->vs_hdv, 0, nc);
-  if (tr) memset(ctx->tr_hdv, 0, nc);
+  memset(a.hdv, 0, nc);
+  if (tr) memset(b.hdv, 0, nc);
   if (n) {
-    CK(valset_pairs_launch(ctx, st, n, nc, tr != nullptr, false));
+    CK(valset_pairs_launch(ctx, st, n, nc, a, side_skip(ctx, a, tr != nullptr)));
     if (tr) {
-      CK(valset_pairs_launch(ctx, st, n, nc, true, true));
-      CK(hipMemcpyAsync(ctx->tr_hdv, ctx->tr_dv, nc, hipMemcpyDeviceToHost, st));
+      CK(valset_pairs_launch(ctx, st, n, nc, b, b.skip));
+      CK(hipMemcpyAsync(b.hdv, b.dv, nc, hipMemcpyDeviceToHost, st));
     }
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(ctx->vs_hdv, ctx->vs_dv, nc, hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(a.hdv, a.dv, nc, hipMemcpyDeviceToHost, st));
     if (!jn->skip.empty()) CK(hipMemcpyAsync(jn->skip.data(), ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
   }
   return 0;
@@ -4044,7 +4084,7 @@ static int valset_select(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* comm
 }
 
 // quorum_select_enqueue, with the join in front and the double-vote scan behind it when jn is given
-// (d_power / d_flag are then q_power / q_flag, which the join writes)
+// (d_power / d_flag are then side A's, which the join writes)
 static int quorum_front_enqueue(edc_ctx* ctx, size_t n, size_t nc, const uint32_t* commit_off, const uint64_t* threshold,
                                 int mode, const uint64_t* d_power, const uint8_t* d_flag, QuorumJoin* jn) {
   if (jn) return valset_select_enqueue(ctx, n, nc, commit_off, threshold, mode, jn);
@@ -4124,12 +4164,14 @@ struct QuorumCached {
 // dv (a validator-set form, host, nc bytes): the commits that hold a double vote (valset_reduce).
 // tr (a trusting pair): the list is the union of both sides' checked votes. A passing union makes
 // each side's tally its planned[]; a failed one runs the tally kernel for both sides at once, each
-// masked by its bit of the side bytes. Side B is reduced with its own double-vote bytes (tr_hdv),
-// and the return value is taken over both sides.
+// masked by its bit of the side bytes. Side B is reduced with its own double-vote bytes, and the
+// return value is taken over both sides.
 static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, size_t n, const ItemList& list,
                          const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed, const QuorumOut& out,
                          const QuorumCached* cq = nullptr, const uint8_t* dv = nullptr, const QuorumTrust* tr = nullptr) {
   hipStream_t st = ctx->st();
+  QuorumWs& q = ctx->qw;
+  const int sides = tr ? 2 : 1;
   const size_t m = list.count;
   std::vector<uint8_t> mv(m ? m : 1);
   const BatchIn in{list.vk, list.sig, nullptr, nullptr, list.k, z_seed, 0, nullptr, false};
@@ -4143,12 +4185,12 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
     CK(hipGetLastError());
     CK(hipMemcpyAsync(ctx->sc_hctr, ctx->sc_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   }
-  std::vector<uint64_t> tal(nc), tal_b(tr ? nc : 0);
-  std::vector<uint32_t> cor32, cor32_b;
-  std::vector<uint8_t> cor, cor_b;
+  std::vector<uint64_t> tal[2];
+  std::vector<uint8_t> cor[2];
+  for (int j = 0; j < sides; ++j) tal[j].resize(nc);
   if (code == EDC_OK) {                 // every checked item verified: the tally is the plan
-    CK(hipMemcpyAsync(tal.data(), ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (tr) CK(hipMemcpyAsync(tal_b.data(), ctx->tr_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    for (int j = 0; j < sides; ++j)
+      CK(hipMemcpyAsync(tal[j].data(), q.side[j].planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (out.item_verdicts && n) CK(hipMemcpyAsync(out.item_verdicts, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     if (out.item_verdicts)
@@ -4173,66 +4215,64 @@ static int quorum_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold, siz
         d_codes = ctx->sc_verd;
       }
     }
-    CK(hipMemsetAsync(ctx->q_tally, 0, nc * sizeof(uint64_t), st));
-    CK(hipMemsetAsync(ctx->q_cor, 0, nc * sizeof(uint32_t), st));
-    if (tr) {
-      CK(hipMemsetAsync(ctx->tr_tally, 0, nc * sizeof(uint64_t), st));
-      CK(hipMemsetAsync(ctx->tr_cor, 0, nc * sizeof(uint32_t), st));
-      launch_quorum_tally2(st, (uint32_t)n, ctx->q_cidx, ctx->tr_side, d_power, d_flag, ctx->tr_power, ctx->tr_flag, d_codes,
-                           ctx->q_tally, ctx->q_cor, ctx->tr_tally, ctx->tr_cor);
-    } else {
-      launch_quorum_tally(st, (uint32_t)n, ctx->q_cidx, d_power, d_flag, d_codes, ctx->q_tally, ctx->q_cor);
+    const QuorumSide &a = q.a, &b = q.b;
+    for (int j = 0; j < sides; ++j) {
+      CK(hipMemsetAsync(q.side[j].tally, 0, nc * sizeof(uint64_t), st));
+      CK(hipMemsetAsync(q.side[j].cor, 0, nc * sizeof(uint32_t), st));
     }
+    if (tr)
+      launch_quorum_tally2(st, (uint32_t)n, q.cidx, q.sideb, d_power, d_flag, b.power, b.flag, d_codes, a.tally, a.cor, b.tally,
+                           b.cor);
+    else
+      launch_quorum_tally(st, (uint32_t)n, q.cidx, d_power, d_flag, d_codes, a.tally, a.cor);
     CK(hipGetLastError());
-    cor32.resize(nc);
-    CK(hipMemcpyAsync(tal.data(), ctx->q_tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(cor32.data(), ctx->q_cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (tr) {
-      cor32_b.resize(nc);
-      CK(hipMemcpyAsync(tal_b.data(), ctx->tr_tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      CK(hipMemcpyAsync(cor32_b.data(), ctx->tr_cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> cor32[2];
+    for (int j = 0; j < sides; ++j) {
+      cor32[j].resize(nc);
+      CK(hipMemcpyAsync(tal[j].data(), q.side[j].tally, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      CK(hipMemcpyAsync(cor32[j].data(), q.side[j].cor, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     if (out.item_verdicts) CK(hipMemcpyAsync(out.item_verdicts, d_codes, n, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
-    cor.resize(nc);
-    for (size_t c = 0; c < nc; ++c) cor[c] = cor32[c] ? 1 : 0;
-    cor_b.resize(cor32_b.size());
-    for (size_t c = 0; c < cor_b.size(); ++c) cor_b[c] = cor32_b[c] ? 1 : 0;
+    for (int j = 0; j < sides; ++j) {
+      cor[j].resize(nc);
+      for (size_t c = 0; c < nc; ++c) cor[j][c] = cor32[j][c] ? 1 : 0;
+    }
   }
   size_t bad = 0;
-  const uint8_t* corp = cor.empty() ? nullptr : cor.data();
-  int res = dv ? valset_reduce(nc, corp, tal.data(), threshold, dv, out.commit_verdicts, &bad)
-               : quorum_reduce(nc, corp, tal.data(), threshold, out.commit_verdicts, &bad);
+  const uint8_t* corp = cor[0].empty() ? nullptr : cor[0].data();
+  int res = dv ? valset_reduce(nc, corp, tal[0].data(), threshold, dv, out.commit_verdicts, &bad)
+               : quorum_reduce(nc, corp, tal[0].data(), threshold, out.commit_verdicts, &bad);
   if (tr) {
     size_t bad_b = 0;
-    const int res_b = vq_trust_reduce(nc, tr->ver, cor_b.empty() ? nullptr : cor_b.data(), tal_b.data(), tr->threshold,
-                                      ctx->tr_hdv, tr->verdicts, &bad_b);
+    const int res_b = vq_trust_reduce(nc, tr->ver, cor[1].empty() ? nullptr : cor[1].data(), tal[1].data(), tr->threshold,
+                                      q.b.hdv, tr->verdicts, &bad_b);
     res = vq_trust_code(res, res_b);
-    if (tr->tally) memcpy(tr->tally, tal_b.data(), nc * sizeof(uint64_t));
+    if (tr->tally) memcpy(tr->tally, tal[1].data(), nc * sizeof(uint64_t));
     if (tr->n_bad) *tr->n_bad = (int)bad_b;
     uint64_t a = 0, b = 0, ab = 0;        // the union kernel's totals, spread over its slots
     for (uint32_t j = 0; j < QR_UNION_SLOTS; ++j) {
-      a += ctx->tr_hcnt[3 * j];
-      b += ctx->tr_hcnt[3 * j + 1];
-      ab += ctx->tr_hcnt[3 * j + 2];
+      a += q.hcnt[3 * j];
+      b += q.hcnt[3 * j + 1];
+      ab += q.hcnt[3 * j + 2];
     }
     const uint64_t last[4] = {a, b, ab, a + b - ab};
-    memcpy(ctx->vqt_last, last, sizeof(last));
-    ctx->vqt_have = true;
+    memcpy(q.vqt_last, last, sizeof(last));
+    q.vqt_have = true;
   }
-  if (out.tally) memcpy(out.tally, tal.data(), nc * sizeof(uint64_t));
+  if (out.tally) memcpy(out.tally, tal[0].data(), nc * sizeof(uint64_t));
   if (out.n_bad_commits) *out.n_bad_commits = (int)bad;
   if (out.n_checked) *out.n_checked = cq ? cq->n_checked : m;
   if (cq) {
     if (out.n_miss) *out.n_miss = m;
-    ctx->cq_last[3] = m;
-    ctx->cq_last[5] = ctx->sc_hctr[0] - ins0;
+    q.cq_last[3] = m;
+    q.cq_last[5] = ctx->sc_hctr[0] - ins0;
   }
   return res;
 }
 
 // A checked quorum commit set whose items (all: vk, sig, k of the n votes; power, flag) are on the
-// device. jn (a validator-set form): power and flag are q_power / q_flag, which the join writes.
+// device. jn (a validator-set form): power and flag are side A's, which the join writes.
 static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* threshold, int mode,
                       const ItemList& all, const uint64_t* d_power, const uint8_t* d_flag, const uint8_t* z_seed,
                       const QuorumOut& out, QuorumJoin* jn = nullptr) {
@@ -4243,7 +4283,7 @@ static int quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
   if (rc || (rc = quorum_select_read(ctx, n, &m, jn ? kJoinFlagMsg : nullptr)) || (rc = quorum_join_check_k(ctx, jn)) ||
       (rc = quorum_gather(ctx, all, m, ctx->sc_hit, ctx->sc_wg, sc_area(ctx), &list)))
     return rc;
-  return quorum_finish(ctx, nc, threshold, n, list, d_power, d_flag, z_seed, out, nullptr, jn ? ctx->vs_hdv.get() : nullptr,
+  return quorum_finish(ctx, nc, threshold, n, list, d_power, d_flag, z_seed, out, nullptr, jn ? ctx->qw.a.hdv.get() : nullptr,
                        jn ? jn->trust : nullptr);
 }
 
@@ -4261,10 +4301,10 @@ int edc_quorum_plan(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const u
   if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
   CK(hipSetDevice(ctx->device));
   if ((rc = quorum_stage_votes(ctx, n, nc, power, flag)) ||
-      (rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, &m)))
+      (rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, ctx->qw.a.power, ctx->qw.a.flag, &m)))
     return rc;
   hipStream_t st = ctx->st();
-  if (planned) CK(hipMemcpyAsync(planned, ctx->q_planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (planned) CK(hipMemcpyAsync(planned, ctx->qw.a.planned, nc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (checked && n) CK(hipMemcpyAsync(checked, ctx->sc_hit, n, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
   if (checked)
@@ -4301,8 +4341,8 @@ int edc_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const
   size_t n;
   if ((rc = quorum_host_inputs(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, power, flag, threshold, mode, &n)))
     return rc;
-  return quorum_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n}, ctx->q_power,
-                    ctx->q_flag, z_seed, out);
+  return quorum_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n}, ctx->qw.a.power,
+                    ctx->qw.a.flag, z_seed, out);
 }
 
 int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off, const uint64_t* power,
@@ -4315,7 +4355,7 @@ int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
   if (rc || (rc = quorum_check_votes(ctx, nc, commit_off, power, flag))) return rc;
   CK(hipSetDevice(ctx->device));
   if ((rc = quorum_stage_votes(ctx, n, nc, power, flag)) ||
-      (rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, ctx->q_power, ctx->q_flag, &m)))
+      (rc = quorum_select_run(ctx, n, nc, commit_off, threshold, mode, ctx->qw.a.power, ctx->qw.a.flag, &m)))
     return rc;
   if (!n) return EDC_OK;
   hipStream_t st = ctx->st();
@@ -4324,9 +4364,7 @@ int edc_debug_quorum_select(edc_ctx* ctx, size_t nc, const uint32_t* commit_off,
   CK(e1.create());
   CK(hipEventRecord(e0, st));
   for (int r = 0; r < reps; ++r)        // planned is a maximum: repeating the launch leaves it unchanged
-    launch_quorum_select(st, (uint32_t)n, (uint32_t)nc, mode == QUORUM_LIGHT, ctx->q_coff, ctx->q_thr, ctx->q_power,
-                         ctx->q_flag, ctx->q_cidx, ctx->q_aggv, ctx->q_aggf, ctx->q_carry, ctx->sc_hit, ctx->sc_wg,
-                         ctx->q_planned, ctx->q_err);
+    quorum_side_launch(ctx, st, n, nc, mode, ctx->qw.a, ctx->qw.a.power, ctx->qw.a.flag, ctx->sc_hit, false);
   CK(hipGetLastError());
   CK(hipEventRecord(e1, st));
   CK(hipEventSynchronize(e1));
@@ -4379,14 +4417,14 @@ static int tmpl_quorum_stage_holes(edc_ctx* ctx, size_t n, const uint8_t* item_a
                                    const uint32_t* var_off, TmplQuorumItems* it) {
   hipStream_t st = ctx->st();
   const size_t var_bytes = var_off[n], o_alt = up16(4 * (n + 1)), o_var = up16(o_alt + n);
-  int rc = tmpl_room(ctx, st, ctx->tq_in, o_var + var_bytes);
+  int rc = tmpl_room(ctx, st, ctx->qw.tq_in, o_var + var_bytes);
   if (rc) return rc;
-  CK(hipMemcpyAsync(ctx->tq_in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
-  if (item_alt) CK(hipMemcpyAsync(ctx->tq_in + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
-  if (var_bytes) CK(hipMemcpyAsync(ctx->tq_in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
-  it->item_alt = item_alt ? ctx->tq_in + o_alt : nullptr;
-  it->var = ctx->tq_in + o_var;
-  it->var_off = reinterpret_cast<const uint32_t*>(ctx->tq_in.get());
+  CK(hipMemcpyAsync(ctx->qw.tq_in, var_off, 4 * (n + 1), hipMemcpyHostToDevice, st));
+  if (item_alt) CK(hipMemcpyAsync(ctx->qw.tq_in + o_alt, item_alt, n, hipMemcpyHostToDevice, st));
+  if (var_bytes) CK(hipMemcpyAsync(ctx->qw.tq_in + o_var, var, var_bytes, hipMemcpyHostToDevice, st));
+  it->item_alt = item_alt ? ctx->qw.tq_in + o_alt : nullptr;
+  it->var = ctx->qw.tq_in + o_var;
+  it->var_off = reinterpret_cast<const uint32_t*>(ctx->qw.tq_in.get());
   it->var_bytes = var_bytes;
   return 0;
 }
@@ -4408,11 +4446,11 @@ static int tmpl_quorum_host_inputs(edc_ctx* ctx, const edc_templates* ts, size_t
   CK(hipSetDevice(ctx->device));
   if ((rc = quorum_stage_votes(ctx, n, nc, power, flag)) || (rc = ensure_n(ctx, n))) return rc;
   hipStream_t st = ctx->st();
-  TmplQuorumItems it{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->q_power, ctx->q_flag};
+  TmplQuorumItems it{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->qw.a.power, ctx->qw.a.flag};
   if (n) {
-    // key indices into q_cidx, which is free until the selection writes it
+    // key indices into cidx, which is free until the selection writes it
     if ((rc = tmpl_quorum_stage_holes(ctx, n, item_alt, var, var_off, &it)) ||
-        (rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->q_cidx, ctx->vk, ctx->sig)))
+        (rc = stage_keys_sigs(ctx, st, n, vk, key_idx, sig, ctx->qw.cidx, ctx->vk, ctx->sig)))
       return rc;
   }
   *sh_out = sh;
@@ -4437,55 +4475,55 @@ static int tmpl_quorum_list(edc_ctx* ctx, const edc_templates* ts, const TmplSha
   TmplView view;
   if ((rc = tmpl_upload_set(ctx, w, st, ts, sh, &view))) return rc;
   const uint32_t nwg = (uint32_t)quorum_tiles(n);
-  if ((rc = tmpl_room(ctx, st, ctx->tq_tpl, n)) || (rc = tmpl_room(ctx, st, ctx->tq_ctpl, nc)) ||
-      (rc = tmpl_room(ctx, st, ctx->tq_wgh, (size_t)nwg + 1)))
+  if ((rc = tmpl_room(ctx, st, ctx->qw.tq_tpl, n)) || (rc = tmpl_room(ctx, st, ctx->qw.tq_ctpl, nc)) ||
+      (rc = tmpl_room(ctx, st, ctx->qw.tq_wgh, (size_t)nwg + 1)))
     return rc;
-  if (!ctx->tq_harena) CK(ctx->tq_harena.alloc(1));
+  if (!ctx->qw.tq_harena) CK(ctx->qw.tq_harena.alloc(1));
   if ((rc = quorum_front_enqueue(ctx, n, nc, commit_off, threshold, mode, it.power, it.flag, jn))) return rc;
   if (n) {                      // behind the selection: the all-n checks and the checked hole bytes
-    CK(hipMemcpyAsync(ctx->tq_ctpl, commit_tpl, nc * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, ctx->q_coff, ctx->tq_ctpl, alt_span, it.item_alt, ctx->tq_tpl,
-                               ctx->q_err);
-    launch_tmpl_quorum_holes(st, (uint32_t)n, ctx->sc_hit, it.var_off, it.var_bytes, ctx->tq_wgh, ctx->q_err);
-    launch_sc_scan(st, nwg, ctx->tq_wgh, ctx->tq_wgh + nwg);
+    CK(hipMemcpyAsync(ctx->qw.tq_ctpl, commit_tpl, nc * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    launch_tmpl_commit_map_alt(st, (uint32_t)n, (uint32_t)nc, ctx->qw.coff, ctx->qw.tq_ctpl, alt_span, it.item_alt, ctx->qw.tq_tpl,
+                               ctx->qw.err);
+    launch_tmpl_quorum_holes(st, (uint32_t)n, ctx->sc_hit, it.var_off, it.var_bytes, ctx->qw.tq_wgh, ctx->qw.err);
+    launch_sc_scan(st, nwg, ctx->qw.tq_wgh, ctx->qw.tq_wgh + nwg);
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(&ctx->q_h[2], ctx->tq_wgh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CK(hipMemcpyAsync(&ctx->qw.h[2], ctx->qw.tq_wgh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   }
   size_t m = 0;
   rc = quorum_select_read(
       ctx, n, &m,
       "votes: a flag above 2, a power or a commit's counted power above 2^63 - 1, or an item_alt[i] >= alt_span");
   if (rc) return rc;
-  const size_t holes = m ? ctx->q_h[2] : 0;
+  const size_t holes = m ? ctx->qw.h[2] : 0;
   if (holes > it.var_bytes) { ctx->err = "quorum selection: checked hole bytes out of range"; return EDC_ERR_HIP; }
-  ctx->tq_have = true;
-  ctx->tq_last[0] = n;
-  ctx->tq_last[1] = m;
-  ctx->tq_last[2] = ctx->tq_last[3] = 0;
+  ctx->qw.tq_have = true;
+  ctx->qw.tq_last[0] = n;
+  ctx->qw.tq_last[1] = m;
+  ctx->qw.tq_last[2] = ctx->qw.tq_last[3] = 0;
   // an empty list still runs the n = 0 batch, whose k is never read
   *list = ItemList{it.vk, it.sig, reinterpret_cast<const uint32_t*>(ctx->sc_hit.get()), nullptr, m};
-  *ctx->tq_harena = 0;
+  *ctx->qw.tq_harena = 0;
   if (!m) return 0;
-  const uint16_t* e_tpl = ctx->tq_tpl;
+  const uint16_t* e_tpl = ctx->qw.tq_tpl;
   const uint8_t* e_var = it.var;
   const uint32_t* e_voff = it.var_off;
   size_t e_bytes = it.var_bytes;
   if (m < n) {
-    if ((rc = tmpl_room(ctx, st, ctx->tq_gtpl, m)) || (rc = tmpl_room(ctx, st, ctx->tq_gvoff, m + 1)) ||
-        (rc = tmpl_room(ctx, st, ctx->tq_gvar, holes + 16)))
+    if ((rc = tmpl_room(ctx, st, ctx->qw.tq_gtpl, m)) || (rc = tmpl_room(ctx, st, ctx->qw.tq_gvoff, m + 1)) ||
+        (rc = tmpl_room(ctx, st, ctx->qw.tq_gvar, holes + 16)))
       return rc;
     uint8_t* g_vk = ctx->sc_g;
     uint8_t* g_sig = g_vk + ctx->sc_cap_n * 32;
-    launch_tmpl_quorum_gather(st, (uint32_t)n, (uint32_t)m, ctx->sc_hit, ctx->sc_wg, ctx->tq_wgh, it.vk, it.sig,
-                              ctx->tq_tpl, it.var, it.var_off, ctx->sc_idx, g_vk, g_sig, ctx->tq_gtpl, ctx->tq_gvar,
-                              ctx->tq_gvoff);
+    launch_tmpl_quorum_gather(st, (uint32_t)n, (uint32_t)m, ctx->sc_hit, ctx->sc_wg, ctx->qw.tq_wgh, it.vk, it.sig,
+                              ctx->qw.tq_tpl, it.var, it.var_off, ctx->sc_idx, g_vk, g_sig, ctx->qw.tq_gtpl, ctx->qw.tq_gvar,
+                              ctx->qw.tq_gvoff);
     CK(hipGetLastError());
     list->vk = g_vk;
     list->sig = g_sig;
     list->idx = ctx->sc_idx;
-    e_tpl = ctx->tq_gtpl;
-    e_var = ctx->tq_gvar;
-    e_voff = ctx->tq_gvoff;
+    e_tpl = ctx->qw.tq_gtpl;
+    e_var = ctx->qw.tq_gvar;
+    e_voff = ctx->qw.tq_gvoff;
     e_bytes = holes;
   }
   // Item::from (src/batch.rs:82-94) for the m checked votes alone: the arena is sized from m
@@ -4495,19 +4533,19 @@ static int tmpl_quorum_list(edc_ctx* ctx, const edc_templates* ts, const TmplSha
   // k_tmpl_len checks the gathered items again; its flag travels behind the expansion and the
   // batch's wait reads it before it believes a verdict
   CK(hipMemcpyAsync(w.h_flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  CK(hipMemcpyAsync(ctx->tq_harena.get(), w.off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(ctx->qw.tq_harena.get(), w.off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   w.check = true;
   launch_challenge(st, (uint32_t)m, list->vk, list->sig, w.arena, w.off, ctx->kbuf);
   CK(hipGetLastError());
   list->k = ctx->kbuf;
-  ctx->tq_last[2] = m;
+  ctx->qw.tq_last[2] = m;
   return 0;
 }
 
 // behind the batch on tmpl_quorum_list's list; rc: what it returned
 static int tmpl_quorum_done(edc_ctx* ctx, int rc) {
   ctx->slot[0].tw.check = false;        // also when the batch never reached its wait
-  if (rc >= 0) ctx->tq_last[3] = *ctx->tq_harena;
+  if (rc >= 0) ctx->qw.tq_last[3] = *ctx->qw.tq_harena;
   return rc;
 }
 
@@ -4561,8 +4599,8 @@ int edc_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t nc, con
 }
 
 int edc_debug_tmpl_quorum_last(const edc_ctx* ctx, uint64_t out[4]) {
-  if (!ctx || !out || !ctx->tq_have) return EDC_ERR_ARG;
-  memcpy(out, ctx->tq_last, sizeof(ctx->tq_last));
+  if (!ctx || !out || !ctx->qw.tq_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->qw.tq_last, sizeof(ctx->qw.tq_last));
   return EDC_OK;
 }
 
@@ -4581,45 +4619,45 @@ int edc_debug_tmpl_quorum_last(const edc_ctx* ctx, uint64_t out[4]) {
 // and the miss count needs a second read-back; the misses are compacted into a second staging area
 // (the first still holds the gathered list, which the insert and the code scatter index).
 static int ensure_cq(edc_ctx* ctx, size_t n) {
-  CK(grow_group(ctx->cq_cap_n, n ? n : 1, item_cap, sync_of(ctx->st()), [&](size_t cap) {
-    return alloc_all(sized(ctx->cq_leave, cap), sized(ctx->cq_code, cap),
-                     sized(ctx->cq_wg, 2 * (cap / SC_BLOCK + 2)));    // misses + total, hits + total
+  CK(grow_group(ctx->qw.cq_cap_n, n ? n : 1, item_cap, sync_of(ctx->st()), [&](size_t cap) {
+    return alloc_all(sized(ctx->qw.cq_leave, cap), sized(ctx->qw.cq_code, cap),
+                     sized(ctx->qw.cq_wg, 2 * (cap / SC_BLOCK + 2)));    // misses + total, hits + total
   }));
   return 0;
 }
 
 // The lookup of a list (skip: the selection's bytes, null: every item is checked) and the scans of
-// its workgroup counts; the miss and hit totals travel to q_h[3] / q_h[4].
+// its workgroup counts; the miss and hit totals travel to h[3] / h[4].
 static int cq_lookup(edc_ctx* ctx, const ItemList& list, const uint8_t* skip) {
   int rc = ensure_cq(ctx, list.count);
   if (rc) return rc;
   hipStream_t st = ctx->st();
   const uint32_t nwg = (uint32_t)((list.count + SC_BLOCK - 1) / SC_BLOCK);
-  uint32_t *wm = ctx->cq_wg, *wh = ctx->cq_wg + nwg + 1;
-  launch_sc_lookup_masked(st, ctx->sc(), (uint32_t)list.count, skip, list.vk, list.sig, list.k, ctx->cq_leave, ctx->cq_code,
+  uint32_t *wm = ctx->qw.cq_wg, *wh = ctx->qw.cq_wg + nwg + 1;
+  launch_sc_lookup_masked(st, ctx->sc(), (uint32_t)list.count, skip, list.vk, list.sig, list.k, ctx->qw.cq_leave, ctx->qw.cq_code,
                           wm, wh);
   launch_sc_scan(st, nwg, wm, wm + nwg);
   launch_sc_scan(st, nwg, wh, wh + nwg);
   CK(hipGetLastError());
-  ctx->q_h[3] = ctx->q_h[4] = 0;
-  CK(hipMemcpyAsync(&ctx->q_h[3], wm + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  CK(hipMemcpyAsync(&ctx->q_h[4], wh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  ctx->qw.h[3] = ctx->qw.h[4] = 0;
+  CK(hipMemcpyAsync(&ctx->qw.h[3], wm + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CK(hipMemcpyAsync(&ctx->qw.h[4], wh + nwg, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   return 0;
 }
 
 // the counts of a lookup that has been read back: the statistics and the debug record
 static int cq_counts(edc_ctx* ctx, size_t n, size_t m, size_t hashed, size_t* miss) {
-  const size_t c = m ? ctx->q_h[3] : 0, h = m ? ctx->q_h[4] : 0;
+  const size_t c = m ? ctx->qw.h[3] : 0, h = m ? ctx->qw.h[4] : 0;
   if (c + h != m) { ctx->err = "cached quorum: hits and misses do not add up to the checked count"; return EDC_ERR_HIP; }
   ctx->sc_hits += h;
   ctx->sc_misses += c;
-  ctx->cq_have = true;
-  ctx->cq_last[0] = n;
-  ctx->cq_last[1] = m;
-  ctx->cq_last[2] = h;
-  ctx->cq_last[3] = c;
-  ctx->cq_last[4] = hashed;
-  ctx->cq_last[5] = 0;
+  ctx->qw.cq_have = true;
+  ctx->qw.cq_last[0] = n;
+  ctx->qw.cq_last[1] = m;
+  ctx->qw.cq_last[2] = h;
+  ctx->qw.cq_last[3] = c;
+  ctx->qw.cq_last[4] = hashed;
+  ctx->qw.cq_last[5] = 0;
   *miss = c;
   return 0;
 }
@@ -4640,9 +4678,9 @@ static int cached_quorum_run(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
   if ((rc = quorum_select_read(ctx, n, &m, jn ? kJoinFlagMsg : nullptr)) || (rc = quorum_join_check_k(ctx, jn)) ||
       (rc = cq_counts(ctx, n, m, hashed, &c)))
     return rc;
-  if ((rc = quorum_gather(ctx, all, c, ctx->cq_leave, ctx->cq_wg, sc_area(ctx), &miss))) return rc;
-  const QuorumCached cq{m, ctx->cq_code, all};
-  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, jn ? ctx->vs_hdv.get() : nullptr,
+  if ((rc = quorum_gather(ctx, all, c, ctx->qw.cq_leave, ctx->qw.cq_wg, sc_area(ctx), &miss))) return rc;
+  const QuorumCached cq{m, ctx->qw.cq_code, all};
+  return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, jn ? ctx->qw.a.hdv.get() : nullptr,
                        jn ? jn->trust : nullptr);
 }
 
@@ -4665,14 +4703,14 @@ static int cached_tmpl_finish(edc_ctx* ctx, size_t nc, const uint64_t* threshold
   size_t c = 0;
   if ((rc = cq_counts(ctx, n, m, m, &c))) return rc;
   if (c && c < m) {                     // the second staging area, when something is gathered
-    CK(grow_group(ctx->cq_cap_g, m, item_cap, sync_of(st), [&](size_t cap) {
-      return alloc_all(sized(ctx->cq_g, cap * 128), sized(ctx->cq_idx, cap));
+    CK(grow_group(ctx->qw.cq_cap_g, m, item_cap, sync_of(st), [&](size_t cap) {
+      return alloc_all(sized(ctx->qw.cq_g, cap * 128), sized(ctx->qw.cq_idx, cap));
     }));
   }
   ItemList miss;
-  if ((rc = quorum_gather(ctx, list, c, ctx->cq_leave, ctx->cq_wg, GatherArea{ctx->cq_g, ctx->cq_cap_g, ctx->cq_idx}, &miss)))
+  if ((rc = quorum_gather(ctx, list, c, ctx->qw.cq_leave, ctx->qw.cq_wg, GatherArea{ctx->qw.cq_g, ctx->qw.cq_cap_g, ctx->qw.cq_idx}, &miss)))
     return rc;
-  const QuorumCached cq{m, ctx->cq_code, list};
+  const QuorumCached cq{m, ctx->qw.cq_code, list};
   return quorum_finish(ctx, nc, threshold, n, miss, d_power, d_flag, z_seed, out, &cq, dv, tr);
 }
 
@@ -4718,7 +4756,7 @@ int edc_cached_quorum_verify(edc_ctx* ctx, size_t nc, const uint32_t* commit_off
   if ((rc = quorum_host_inputs(ctx, nc, commit_off, vk, key_idx, sig, msg, msg_off, k, power, flag, threshold, mode, &n)))
     return rc;
   return cached_quorum_run(ctx, nc, commit_off, threshold, mode, ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n},
-                           ctx->q_power, ctx->q_flag, z_seed, out, k ? 0 : n);
+                           ctx->qw.a.power, ctx->qw.a.flag, z_seed, out, k ? 0 : n);
 }
 
 int edc_cached_tmpl_quorum_verify_device(edc_ctx* ctx, const edc_templates* ts, size_t nc, const uint32_t* commit_off,
@@ -4761,8 +4799,8 @@ int edc_cached_tmpl_quorum_verify(edc_ctx* ctx, const edc_templates* ts, size_t 
 }
 
 int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
-  if (!ctx || !out || !ctx->cq_have) return EDC_ERR_ARG;
-  memcpy(out, ctx->cq_last, sizeof(ctx->cq_last));
+  if (!ctx || !out || !ctx->qw.cq_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->qw.cq_last, sizeof(ctx->qw.cq_last));
   return EDC_OK;
 }
 
@@ -4771,7 +4809,7 @@ int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
 // ---------------------------------------------------------------- validator-set quorum commit sets
 // edc_valset_*: the quorum entries with the join on the device. The registered list carries its
 // powers (edc_valset_set_powers); the resolve kernel turns every vote's key bytes (or position)
-// into the power and flag the selection reads, in q_power / q_flag where a host form of the quorum
+// into the power and flag the selection reads, in side A's arrays where a host form of the quorum
 // entries stages them; the double-vote scan runs behind the selection on its skip bytes, and its
 // per-commit bytes come back with the selection's one read-back. Everything after that is the
 // quorum entries' own: quorum_gather, then quorum_finish with the double-vote bytes.
@@ -4785,17 +4823,17 @@ int edc_debug_cached_quorum_last(const edc_ctx* ctx, uint64_t out[6]) {
 //   verify   vq_run_plain (messages or k) and, for requests only, vq_run_tmpl
 //   resolve  valset_resolve_body, one side or a trusting pair
 //   timing   valset_debug_select_body, which launches what valset_select_enqueue launches
-// keys (bytes into ctx->vk, or positions into vs_kidx) and flags (vs_flag) of n > 0 host votes
+// keys (bytes into ctx->vk, or positions into kidx) and flags (vflag) of n > 0 host votes
 static int valset_stage_votes(edc_ctx* ctx, size_t n, const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag) {
   hipStream_t st = ctx->st();
   if (key_idx) {
-    CK(hipMemcpyAsync(ctx->vs_kidx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(ctx->qw.kidx, key_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   } else {
     int rc = ensure_n(ctx, n);
     if (rc) return rc;
     CK(hipMemcpyAsync(ctx->vk, vk, n * 32, hipMemcpyHostToDevice, st));
   }
-  CK(hipMemcpyAsync(ctx->vs_flag, flag, n, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(ctx->qw.vflag, flag, n, hipMemcpyHostToDevice, st));
   return 0;
 }
 
@@ -4924,8 +4962,8 @@ static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut&
       return rc;
     }
     if (n) {                  // 4 + 64 + 1 bytes per vote in the key_idx form: the keys are expanded on the device
-      CK(hipMemcpyAsync(ctx->vs_flag, rq->flag, n, hipMemcpyHostToDevice, st));
-      if ((rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->vs_kidx, ctx->vk, ctx->sig))) return rc;
+      CK(hipMemcpyAsync(ctx->qw.vflag, rq->flag, n, hipMemcpyHostToDevice, st));
+      if ((rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->qw.kidx, ctx->vk, ctx->sig))) return rc;
       if (!rq->k) {
         launch_challenge(st, (uint32_t)n, ctx->vk, ctx->sig, ctx->msg, ctx->off, ctx->kbuf);
         CK(hipGetLastError());
@@ -4933,15 +4971,15 @@ static int vq_run_plain(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut&
     }
     all = ItemList{ctx->vk, ctx->sig, ctx->kbuf, nullptr, n};
     jn.d_vk = rq->key_idx ? nullptr : ctx->vk.get();
-    jn.d_kidx = ctx->vs_kidx;
-    jn.d_flag = ctx->vs_flag;
+    jn.d_kidx = ctx->qw.kidx;
+    jn.d_flag = ctx->qw.vflag;
     jn.host_k = n ? rq->k : nullptr;
   }
   *hashed = rq->k ? 0 : n;
   if (rq->cached)
-    return cached_quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->q_power, ctx->q_flag, rq->z_seed,
+    return cached_quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->qw.a.power, ctx->qw.a.flag, rq->z_seed,
                              out, *hashed, &jn);
-  return quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->q_power, ctx->q_flag, rq->z_seed, out, &jn);
+  return quorum_run(ctx, nc, rq->commit_off, rq->threshold, rq->mode, all, ctx->qw.a.power, ctx->qw.a.flag, rq->z_seed, out, &jn);
 }
 
 // The edc_valset_* / edc_vhist_* verify entries: what they accept and refuse before the arrays are
@@ -5002,14 +5040,13 @@ static int valset_resolve_select(edc_ctx* ctx, bool hist, size_t nc, const uint3
   CK(hipSetDevice(ctx->device));
   if ((rc = valset_room(ctx, *n, nc, hist, tr != nullptr)) || (*n && (rc = valset_stage_votes(ctx, *n, vk, key_idx, flag))))
     return rc;
-  QuorumJoin jn{key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, cver, nullptr, {}, tr};
+  QuorumJoin jn{key_idx ? nullptr : ctx->vk.get(), ctx->qw.kidx, ctx->qw.vflag, cver, nullptr, {}, tr};
   return valset_select(ctx, *n, nc, commit_off, threshold, mode, &jn, m);
 }
 
 // edc_valset_resolve, edc_vhist_resolve (hist) and edc_vq_trust_resolve (tr, with b and side): the
 // join, the selection and the double-vote scan as the verify entries run them, and each side's
-// arrays read back. One side's skip bytes are the selection's (sc_hit); a pair's are tr_skip_a /
-// tr_skip_b, sc_hit then holding the union's.
+// arrays read back (side_skip: a pair's sc_hit holds the union's skip bytes).
 static int valset_resolve_body(edc_ctx* ctx, bool hist, size_t nc, const uint32_t* commit_off, const uint32_t* cver,
                                const uint8_t* vk, const uint32_t* key_idx, const uint8_t* flag, const uint64_t* threshold,
                                int mode, const ResolveSide& a, size_t* n_checked, const QuorumTrust* tr = nullptr,
@@ -5022,30 +5059,26 @@ static int valset_resolve_body(edc_ctx* ctx, bool hist, size_t nc, const uint32_
   }
   const std::vector<uint32_t>& posh = hist ? ctx->vh_posh : ctx->vs_posh;
   hipStream_t st = ctx->st();
-  std::vector<uint32_t> who(a.pos ? n : 0), who_b(b.pos ? n : 0);
+  const QuorumWs& q = ctx->qw;
+  const ResolveSide* o[2] = {&a, &b};
+  std::vector<uint32_t> who[2];
   auto back = [&](void* dst, const void* src, size_t bytes) {
     return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
   };
-  CK(back(who.data(), ctx->vs_who, who.size() * sizeof(uint32_t)));
-  CK(back(who_b.data(), ctx->tr_who, who_b.size() * sizeof(uint32_t)));
-  CK(back(a.power, ctx->q_power, n * sizeof(uint64_t)));
-  CK(back(b.power, ctx->tr_power, n * sizeof(uint64_t)));
-  CK(back(a.flag, ctx->q_flag, n));
-  CK(back(b.flag, ctx->tr_flag, n));
-  CK(back(a.planned, ctx->q_planned, nc * sizeof(uint64_t)));
-  CK(back(b.planned, ctx->tr_planned, nc * sizeof(uint64_t)));
-  CK(back(a.checked, tr ? ctx->tr_skip_a.get() : ctx->sc_hit.get(), n));
-  CK(back(b.checked, ctx->tr_skip_b, n));
-  CK(back(side, ctx->tr_side, n));
+  const int sides = tr ? 2 : 1;         // array by array, side A's in front of side B's
+  for (int j = 0; j < sides; ++j) who[j].resize(o[j]->pos ? n : 0);
+  for (int j = 0; j < sides; ++j) CK(back(who[j].data(), q.side[j].who, who[j].size() * sizeof(uint32_t)));
+  for (int j = 0; j < sides; ++j) CK(back(o[j]->power, q.side[j].power, n * sizeof(uint64_t)));
+  for (int j = 0; j < sides; ++j) CK(back(o[j]->flag, q.side[j].flag, n));
+  for (int j = 0; j < sides; ++j) CK(back(o[j]->planned, q.side[j].planned, nc * sizeof(uint64_t)));
+  for (int j = 0; j < sides; ++j) CK(back(o[j]->checked, side_skip(ctx, q.side[j], tr != nullptr), n));
+  CK(back(side, q.sideb, n));
   CK(hipStreamSynchronize(st));
-  for (size_t i = 0; i < who.size(); ++i) a.pos[i] = who[i] == KC_EMPTY ? VALSET_NO_POS : posh[who[i]];
-  for (size_t i = 0; i < who_b.size(); ++i) b.pos[i] = who_b[i] == KC_EMPTY ? VALSET_NO_POS : posh[who_b[i]];
-  for (size_t i = 0; i < n; ++i) {      // the kernels write skip bytes
-    if (a.checked) a.checked[i] = a.checked[i] ? 0 : 1;
-    if (b.checked) b.checked[i] = b.checked[i] ? 0 : 1;
+  for (int j = 0; j < sides; ++j) {
+    for (size_t i = 0; i < who[j].size(); ++i) o[j]->pos[i] = who[j][i] == KC_EMPTY ? VALSET_NO_POS : posh[who[j][i]];
+    for (size_t i = 0; i < n && o[j]->checked; ++i) o[j]->checked[i] = o[j]->checked[i] ? 0 : 1;      // the kernels write skip bytes
+    if (o[j]->dv) memcpy(o[j]->dv, q.side[j].hdv, nc);
   }
-  if (a.dv) memcpy(a.dv, ctx->vs_hdv, nc);
-  if (b.dv) memcpy(b.dv, ctx->tr_hdv, nc);
   if (n_checked) *n_checked = m;
   return EDC_OK;
 }
@@ -5065,7 +5098,8 @@ static int valset_debug_select_body(edc_ctx* ctx, bool hist, size_t nc, const ui
   const int rc = valset_resolve_select(ctx, hist, nc, commit_off, cver, vk, key_idx, flag, threshold, mode, tr, &n, &m);
   if (rc || !n) return rc;
   hipStream_t st = ctx->st();
-  const QuorumJoin jn{key_idx ? nullptr : ctx->vk.get(), ctx->vs_kidx, ctx->vs_flag, cver, nullptr, {}, tr};
+  const QuorumSide &a = ctx->qw.a, &b = ctx->qw.side[1];
+  const QuorumJoin jn{key_idx ? nullptr : ctx->vk.get(), ctx->qw.kidx, ctx->qw.vflag, cver, nullptr, {}, tr};
   const uint32_t nwg = (uint32_t)quorum_tiles(n);
   Event e[4];
   for (int j = 0; j <= intervals; ++j) CK(e[j].create());
@@ -5076,16 +5110,16 @@ static int valset_debug_select_body(edc_ctx* ctx, bool hist, size_t nc, const ui
   CK(hipEventRecord(e[at++], st));
   if (intervals == 3) {
     for (int r = 0; r < reps; ++r) {
-      CK(quorum_side_launch(ctx, st, n, nc, mode, ctx->q_power, ctx->q_flag, tr != nullptr, false));
-      if (tr) CK(quorum_side_launch(ctx, st, n, nc, mode, ctx->tr_power, ctx->tr_flag, true, true));
+      quorum_side_launch(ctx, st, n, nc, mode, a, a.power, a.flag, side_skip(ctx, a, tr != nullptr), false);
+      if (tr) CK(quorum_side_b_launch(ctx, st, n, nc, mode));
       launch_sc_scan(st, nwg, ctx->sc_wg, ctx->sc_wg + nwg);
     }
     CK(hipGetLastError());
     CK(hipEventRecord(e[at++], st));
   }
   for (int r = 0; r < reps; ++r) {
-    CK(valset_pairs_launch(ctx, st, n, nc, tr != nullptr, false));
-    if (tr) CK(valset_pairs_launch(ctx, st, n, nc, true, true));
+    CK(valset_pairs_launch(ctx, st, n, nc, a, side_skip(ctx, a, tr != nullptr)));
+    if (tr) CK(valset_pairs_launch(ctx, st, n, nc, b, b.skip));
   }
   CK(hipGetLastError());
   CK(hipEventRecord(e[at], st));
@@ -5706,29 +5740,29 @@ static int vq_run_tmpl(edc_ctx* ctx, const edc_vq_request* rq, const QuorumOut& 
   CK(hipSetDevice(ctx->device));
   if ((rc = valset_room(ctx, n, nc, rq->commit_ver != nullptr, tr != nullptr))) return rc;
   hipStream_t st = ctx->st();
-  TmplQuorumItems it{rq->vk, rq->sig, rq->item_alt, rq->var, rq->var_off, rq->var_bytes, ctx->q_power, ctx->q_flag};
+  TmplQuorumItems it{rq->vk, rq->sig, rq->item_alt, rq->var, rq->var_off, rq->var_bytes, ctx->qw.a.power, ctx->qw.a.flag};
   QuorumJoin jn{rq->vk, nullptr, rq->flag, rq->commit_ver, nullptr, {}, tr};
   if (!rq->device) {
     if ((rc = ensure_n(ctx, n))) return rc;
-    it = TmplQuorumItems{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->q_power, ctx->q_flag};
+    it = TmplQuorumItems{ctx->vk, ctx->sig, nullptr, nullptr, nullptr, 0, ctx->qw.a.power, ctx->qw.a.flag};
     if (n) {                    // 4 + 64 + 1 bytes per vote and its hole in the key_idx form
-      CK(hipMemcpyAsync(ctx->vs_flag, rq->flag, n, hipMemcpyHostToDevice, st));
+      CK(hipMemcpyAsync(ctx->qw.vflag, rq->flag, n, hipMemcpyHostToDevice, st));
       if ((rc = tmpl_quorum_stage_holes(ctx, n, rq->item_alt, rq->var, rq->var_off, &it)) ||
-          (rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->vs_kidx, ctx->vk, ctx->sig)))
+          (rc = stage_keys_sigs(ctx, st, n, rq->vk, rq->key_idx, rq->sig, ctx->qw.kidx, ctx->vk, ctx->sig)))
         return rc;
     }
     jn.d_vk = rq->key_idx ? nullptr : ctx->vk.get();
-    jn.d_kidx = ctx->vs_kidx;
-    jn.d_flag = ctx->vs_flag;
+    jn.d_kidx = ctx->qw.kidx;
+    jn.d_flag = ctx->qw.vflag;
   }
   ItemList list;
   if ((rc = tmpl_quorum_list(ctx, rq->ts, sh, nc, rq->commit_off, rq->commit_tpl, rq->alt_span, n, it, rq->threshold,
                              rq->mode, &list, &jn)))
     return rc;
   return tmpl_quorum_done(ctx, rq->cached ? cached_tmpl_finish(ctx, nc, rq->threshold, n, list, it.power, it.flag,
-                                                               rq->z_seed, out, ctx->vs_hdv, tr)
+                                                               rq->z_seed, out, ctx->qw.a.hdv, tr)
                                           : quorum_finish(ctx, nc, rq->threshold, n, list, it.power, it.flag, rq->z_seed,
-                                                          out, nullptr, ctx->vs_hdv, tr));
+                                                          out, nullptr, ctx->qw.a.hdv, tr));
 }
 
 extern "C" {
@@ -5761,28 +5795,28 @@ int edc_vq_verify(edc_ctx* ctx, const edc_vq_request* rq_in, edc_vq_result* rs_i
   if (rc < 0) return rc;
   // the debug record, from the records of the stages that ran
   const uint64_t n = rq->commit_off[rq->nc];
-  uint64_t* L = ctx->vq_last;
+  uint64_t* L = ctx->qw.vq_last;
   L[0] = n;
   L[1] = *out.n_checked;
-  L[2] = rq->cached ? ctx->cq_last[2] : 0;
-  L[3] = rq->cached ? ctx->cq_last[3] : 0;
-  L[4] = rq->ts ? ctx->tq_last[2] : hashed;
-  L[5] = rq->cached ? ctx->cq_last[5] : 0;
+  L[2] = rq->cached ? ctx->qw.cq_last[2] : 0;
+  L[3] = rq->cached ? ctx->qw.cq_last[3] : 0;
+  L[4] = rq->ts ? ctx->qw.tq_last[2] : hashed;
+  L[5] = rq->cached ? ctx->qw.cq_last[5] : 0;
   L[6] = 0;     // reserved
-  L[7] = rq->ts ? ctx->tq_last[3] : 0;
-  ctx->vq_have = true;
+  L[7] = rq->ts ? ctx->qw.tq_last[3] : 0;
+  ctx->qw.vq_have = true;
   return rc;
 }
 
 int edc_debug_vq_last(const edc_ctx* ctx, uint64_t out[8]) {
-  if (!ctx || !out || !ctx->vq_have) return EDC_ERR_ARG;
-  memcpy(out, ctx->vq_last, sizeof(ctx->vq_last));
+  if (!ctx || !out || !ctx->qw.vq_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->qw.vq_last, sizeof(ctx->qw.vq_last));
   return EDC_OK;
 }
 
 int edc_debug_vq_trust_last(const edc_ctx* ctx, uint64_t out[4]) {
-  if (!ctx || !out || !ctx->vqt_have) return EDC_ERR_ARG;
-  memcpy(out, ctx->vqt_last, sizeof(ctx->vqt_last));
+  if (!ctx || !out || !ctx->qw.vqt_have) return EDC_ERR_ARG;
+  memcpy(out, ctx->qw.vqt_last, sizeof(ctx->qw.vqt_last));
   return EDC_OK;
 }
 
